@@ -6,11 +6,16 @@ Workload (BASELINE.json configs[1]): batched image multi-hash (pHash + dHash + a
 GRAY8 frames resident in HBM.  One "step" = one pass of the hot path over the whole batch =
 ONE kernel launch reading 26.2 GB.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F] [--dump-outputs DIR] [--full]
 
 N > 1 is launched by torch.distributed.run, one rank per GPU.  The path shards by frame with
 no data-path collective, so every rank hashes its own F frames (weak scaling) and
 only the timing is reduced (MAX over ranks).  Rank 0 prints ONE JSON line.
+
+A plain run measures the headline only: set up, W warm-up steps, K timed steps, the line.
+--full adds every secondary leg (RGB8, ingest to index, CPU baselines, configs[0], search
+batcher, upload mix, ANN, cosine, text, audio) to the same line.  --dump-outputs DIR writes
+the records of the last timed step (dump_outputs) for comparing two builds output for output.
 """
 import argparse
 import json
@@ -49,6 +54,13 @@ def parse():
                     "(BASELINE configs[2]: 10 h); 0 skips")
     ap.add_argument("--traffic-bytes", type=float, default=None,
                     help="HBM bytes per launch from a separate rocprofv3 --pmc pass (profiles/)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement (RGB8 variant, ingest to index, CPU baselines, config 0 "
+                         "PNG / JPEG, search batcher, upload mix, ANN, cosine, text, audio); the options above that "
+                         "size or skip those legs apply only with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (float32 / "
+                         "float64, a fixed sample of rows; rank 0's frames at N > 1)")
     return ap.parse_args()
 
 
@@ -1303,6 +1315,26 @@ def bench_audio(args, rank, world, dev, ctx):
     return res
 
 
+DUMP_ROWS = 16384   # 16384 x 537 x 4 B = 35 MB of float32: under the 64 MB a dump may take
+
+
+def dump_outputs(d, out, status):
+    """What a caller of the timed path receives -- the 536-byte bundles and the per-frame status of the last step -- for a
+    fixed, seeded sample of frames, as float32 (bytes and small integers are exact), plus the per-byte-column sums of the
+    bundles over ALL frames as float64 (exact: at most 255 x frames).  The frames are a function of their index, so the
+    same arguments give the same files on every build."""
+    import numpy as np
+    import torch
+    os.makedirs(d, exist_ok=True)
+    n = out.shape[0]
+    rows = np.sort(np.random.default_rng(0xD0D0).choice(n, min(n, DUMP_ROWS), replace=False))
+    idx = torch.from_numpy(rows).to(out.device)
+    np.save(os.path.join(d, "records.npy"), out[idx].cpu().numpy().astype(np.float32))
+    np.save(os.path.join(d, "status.npy"), status[idx].cpu().numpy().astype(np.float32))
+    np.save(os.path.join(d, "record_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(d, "records_column_sums.npy"), out.sum(0, dtype=torch.int64).cpu().numpy().astype(np.float64))
+
+
 _LINE_FD = None
 
 
@@ -1391,10 +1423,12 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     assert int(status.abs().sum().item()) == 0, "some frames were rejected"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, status)
 
     # ---- RGB8 variant of the same workload ("also report RGB8"): 786 432 B/frame ----
     rgb = None
-    if args.rgb_frames > 0:
+    if args.full and args.rgb_frames > 0:
         nr = args.rgb_frames
         rgbf = torch.empty((nr, FRAME_SIDE, FRAME_SIDE * 3), dtype=torch.uint8, device=dev)
         _lib.check(lib.ucfp_image_synth_dev(ctx.handle, rgbf.data_ptr(), nr, FRAME_SIDE * 3, FRAME_SIDE, 0, stream))
@@ -1419,31 +1453,33 @@ def main():
     # ---- the same launch followed by what an ingest does with the records: the three 64-bit global hashes of every
     # bundle go into per-algorithm Hamming shards, all on the device (hash -> ucfp_image_record_codes_dev ->
     # ucfp_index_append_dev); the main line above stays the bare fingerprint rate BASELINE names ----
-    from ucfp_amd import index as _index
-    shards = [_index.DeviceIndex(_index.HAMMING64, 0, _index.APPEND_ONLY, ctx) for _ in range(3)]
-    codes = torch.empty((3, n), dtype=torch.int64, device=dev)
-    rec_ids = torch.arange(rank * n, (rank + 1) * n, dtype=torch.int64, device=dev)
+    ingest = None
+    if args.full:
+        from ucfp_amd import index as _index
+        shards = [_index.DeviceIndex(_index.HAMMING64, 0, _index.APPEND_ONLY, ctx) for _ in range(3)]
+        codes = torch.empty((3, n), dtype=torch.int64, device=dev)
+        rec_ids = torch.arange(rank * n, (rank + 1) * n, dtype=torch.int64, device=dev)
 
-    def ingest_step():
-        step()
-        for a, which in enumerate((image.AHASH, image.PHASH, image.DHASH)):
-            image.record_codes_dev(out.data_ptr(), n, codes[a].data_ptr(), algo=image.MULTI, which=which, stream=stream,
-                                   ctx=ctx)
-            shards[a].append_dev(0, rec_ids.data_ptr(), codes[a].data_ptr(), n, stream)
-    ingest_step()
-    torch.cuda.synchronize()
-    i0, i1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    i0.record()
-    for _ in range(5):
+        def ingest_step():
+            step()
+            for a, which in enumerate((image.AHASH, image.PHASH, image.DHASH)):
+                image.record_codes_dev(out.data_ptr(), n, codes[a].data_ptr(), algo=image.MULTI, which=which, stream=stream,
+                                       ctx=ctx)
+                shards[a].append_dev(0, rec_ids.data_ptr(), codes[a].data_ptr(), n, stream)
         ingest_step()
-    i1.record()
-    torch.cuda.synchronize()
-    ingest_ms = i0.elapsed_time(i1) / 5
-    ingest = {"ms_per_batch": ingest_ms, "fingerprints_per_s": n / ingest_ms * 1e3 * world,
-              "indexed_codes_per_gpu": int(shards[0].size(0)), "what": "hash + 3 x (record -> code, append to a Hamming shard)"}
-    for sh in shards:
-        sh.close()
-    del shards, codes, rec_ids
+        torch.cuda.synchronize()
+        i0, i1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        i0.record()
+        for _ in range(5):
+            ingest_step()
+        i1.record()
+        torch.cuda.synchronize()
+        ingest_ms = i0.elapsed_time(i1) / 5
+        ingest = {"ms_per_batch": ingest_ms, "fingerprints_per_s": n / ingest_ms * 1e3 * world,
+                  "indexed_codes_per_gpu": int(shards[0].size(0)), "what": "hash + 3 x (record -> code, append to a Hamming shard)"}
+        for sh in shards:
+            sh.close()
+        del shards, codes, rec_ids
     if rank == 0:
         total_frames = n * world * args.steps
         value = total_frames / elapsed
@@ -1479,10 +1515,11 @@ def main():
                 "traffic": traffic_from_profiles(n) if args.traffic_bytes is None else args.traffic_bytes,
             },
         }
-        res["rgb8_variant"] = rgb
-        res["ingest_to_index"] = ingest
-        res["ann"] = None
-        if args.cpu_sample > 0 and world == 1:
+        if args.full:
+            res["rgb8_variant"] = rgb
+            res["ingest_to_index"] = ingest
+            res["ann"] = None
+        if args.full and args.cpu_sample > 0 and world == 1:
             want = min(n, max(args.cpu_sample, 64 * cpu_share()["usable_cpus"]))     # >= 64 frames per thread
             head = out[:want].cpu().numpy()
             res["cpu_baseline"] = cpu_baseline(want, head)
@@ -1492,7 +1529,7 @@ def main():
                 res["upload_mix"] = bench_upload_mix(dev, ctx)
             except Exception as e:   # noqa: BLE001  (a secondary leg: reported, never substituted)
                 res["upload_mix"] = {"error": f"{type(e).__name__}: {e}"}
-        elif args.cpu_sample > 0:
+        elif args.full and args.cpu_sample > 0:
             res["cpu_baseline"] = None  # measured at N=1 only (see BENCH at n_gpus=1)
     else:
         res = None
@@ -1503,7 +1540,7 @@ def main():
     # communicator.  A rank that fails alone would leave the others waiting in a collective for ever and the driver
     # without any line: a watchdog prints what has been measured (the headline above) and ends the rank instead.
     watchdog = None
-    if world > 1:
+    if args.full and world > 1:
         import threading
 
         def _fire():
@@ -1515,7 +1552,7 @@ def main():
         watchdog = threading.Timer(600.0, _fire)
         watchdog.daemon = True
         watchdog.start()
-    if args.ann_corpus > 0:
+    if args.full and args.ann_corpus > 0:
         # a failure of this secondary leg (e.g. the RCCL communicator cannot be created on this node) is REPORTED in
         # the line, it does not take the headline measurement above down with it; nothing is substituted for it
         try:
@@ -1535,17 +1572,17 @@ def main():
             if world == 1:
                 res["ann_shard_12m5"] = ann12
                 res["ann_shard_1m25"] = ann1m
-    if args.cosine_rows > 0:
+    if args.full and args.cosine_rows > 0:
         r = bench_cosine(args, rank, world, dev, ctx)
         if rank == 0:
             res["cosine"] = r
         torch.cuda.empty_cache()
-    if args.text_docs > 0:
+    if args.full and args.text_docs > 0:
         r = bench_text(args, rank, world, dev, ctx)
         if rank == 0:
             res["text"] = r
         torch.cuda.empty_cache()
-    if args.audio_seconds > 0:
+    if args.full and args.audio_seconds > 0:
         r = bench_audio(args, rank, world, dev, ctx)
         if rank == 0:
             res["audio"] = r

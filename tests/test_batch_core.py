@@ -2,6 +2,7 @@
 without a GPU, under ThreadSanitizer.  Every submitter must get ITS result back, no flush may exceed max_batch /
 max_units, and the protocol (claim by compare-and-swap, commit, generation futex, release) must be race-free."""
 import os
+import platform
 import shutil
 import subprocess
 
@@ -20,10 +21,19 @@ def _build(tmp_path, *flags):
     return exe
 
 
+def _no_aslr(cmd):
+    """gcc 11's ThreadSanitizer runtime expects the binary and its libraries in fixed address ranges; a kernel that randomises
+    mmap over more bits than that runtime knows places them elsewhere and the run ends at start-up in "FATAL: ThreadSanitizer:
+    unexpected memory mapping".  The sanitized child therefore runs with its own address randomisation off (setarch -R)."""
+    setarch = shutil.which("setarch")
+    return [setarch, platform.machine(), "-R", *cmd] if setarch else list(cmd)
+
+
 @pytest.mark.parametrize("threads,per_thread,delay_us", [(24, 300, 0), (40, 60, 200), (3, 500, 0)])
 def test_batch_core_under_thread_sanitizer(tmp_path, threads, per_thread, delay_us):
     exe = _build(tmp_path, "-O1", "-g", "-fsanitize=thread")
-    r = subprocess.run([exe, str(threads), str(per_thread), str(delay_us)], capture_output=True, text=True, timeout=300)
+    r = subprocess.run(_no_aslr([exe, str(threads), str(per_thread), str(delay_us)]), capture_output=True, text=True,
+                       timeout=300)
     assert r.returncode == 0 and "ThreadSanitizer" not in r.stderr, r.stdout + r.stderr
 
 

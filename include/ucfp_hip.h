@@ -337,6 +337,52 @@ int ucfp_audio_batcher_submit(ucfp_audio_batcher* b, const float* pcm, size_t n,
                               size_t* n_hashes);
 int ucfp_audio_batcher_stats(ucfp_audio_batcher* b, uint64_t* batches, uint64_t* items);
 
+/* STREAMING Wang: audio::StreamingWangSession::new / push / finalize (src/modality/audio.rs:413-480)
+ * behind POST /v1/ingest/audio/{tid}/{rid}/stream (src/server/handlers.rs:957-1010), with the state on the device and
+ * many streams advanced by one push.  A set holds max_streams slots; a slot is one stream at 8 kHz.  The Wang spec is
+ * local in time, so after a push that brings a stream to n samples the hashes emitted so far are exactly the offline
+ * hashes (ucfp_audio_wang on the same samples) with t_anchor < F(n) (ucfp_wang_stream_frontier), in offline order; a
+ * final push emits the rest.  The concatenation over all pushes equals ucfp_audio_wang of the whole stream byte for
+ * byte, however the stream is cut into chunks.  t_anchor counts frames since the stream was opened (u32, ~795 days;
+ * the 2^23-frame limit of one offline clip does not apply).  With the default config the emission lag is at most
+ * 7 + 62 + 63 = 132 frames (2.1 s).
+ *   - The set serialises its own calls: it is safe to call from several threads.  Consecutive pushes are ordered by
+ *     the set itself (an event), whatever `stream` the caller passes.
+ *   - Device bytes per stream: ucfp_wang_streams_state_bytes(cfg) (about 16.5 KiB with the defaults: 2816 carried
+ *     samples, the open second's <= 320 candidates, the retained peaks), fixed at creation, whatever the stream's
+ *     length.  The push path allocates nothing beyond growing the context's workspace to the largest push seen.
+ *   - Errors are status codes: UCFP_E_INVALID for a slot out of range or not open, a slot twice in one push, a chunk
+ *     above 2^29 samples, a stream that would pass 2^32 frames, cap_hashes below the bound; UCFP_E_MODALITY for a rate
+ *     other than 8000 or a config outside the /v1/algorithms ranges.  A failed call changes no state. */
+typedef struct ucfp_wang_streams ucfp_wang_streams;
+/* sample_rate must be 8000 (audio.rs:425-431 -> UCFP_E_MODALITY); cfg as ucfp_audio_wang, NULL = defaults.  The rate and
+ * the config are checked before anything else.  Fails with UCFP_E_INDEX without a gfx950 device (no CPU fallback). */
+int ucfp_wang_streams_create(ucfp_ctx* ctx, uint32_t sample_rate, const ucfp_wang_config* cfg, uint32_t max_streams,
+                             ucfp_wang_streams** out);
+void ucfp_wang_streams_destroy(ucfp_wang_streams* s);
+int ucfp_wang_streams_open(ucfp_wang_streams* s, uint32_t* slot);      /* fresh stream, t = 0 (audio.rs:413-431) */
+int ucfp_wang_streams_close(ucfp_wang_streams* s, uint32_t slot);      /* discard, emit nothing */
+/* Host-only, no GPU: F(n) of A9 -- frames(n) = n < 1024 ? 0 : (n - 1024) / 128 + 1, J = max(0, frames - 7),
+ * C = the first frame of the second holding frame J, F = max(0, C - target_zone_t). */
+uint64_t ucfp_wang_stream_frontier(uint64_t n_samples, const ucfp_wang_config* cfg);
+/* Host-only: device bytes a set holds per stream (0 for an out-of-range config). */
+size_t ucfp_wang_streams_state_bytes(const ucfp_wang_config* cfg);
+/* Upper bound on the hashes a push can emit; host-computable from the per-slot sample counts (0 for an invalid push). */
+size_t ucfp_wang_streams_max_hashes(ucfp_wang_streams* s, const uint32_t* slots, const uint64_t* n_samples,
+                                    const uint8_t* final, size_t n);
+/* slots / n_samples / final: host arrays of n entries (distinct open slots; final may be NULL = none); d_pcm: the n
+ * chunks concatenated in that order on the device.  Hashes of entry i -> d_out[d_out_offsets[i] .. d_out_offsets[i+1])
+ * (8 B each, t_anchor since the stream was opened; n + 1 device u64 offsets).  final[i] != 0 emits the rest and closes
+ * the slot.  cap_hashes below ucfp_wang_streams_max_hashes -> UCFP_E_INVALID before ANY state changes.  One launch
+ * sequence whatever n is; no host synchronisation (the host waits only for the table copy of the push two back). */
+int ucfp_wang_streams_push_dev(ucfp_wang_streams* s, const uint32_t* slots, const uint64_t* n_samples,
+                               const uint8_t* final, size_t n, const float* d_pcm, uint8_t* d_out, size_t cap_hashes,
+                               uint64_t* d_out_offsets, void* stream);
+/* Host-pointer convenience for one slot (the per-request shape of the reference route, handlers.rs:957-1010);
+ * synchronous.  *n_hashes = hashes of this push. */
+int ucfp_wang_streams_push(ucfp_wang_streams* s, uint32_t slot, const float* pcm, size_t n, int final, uint8_t* out,
+                           size_t cap_hashes, size_t* n_hashes);
+
 size_t ucfp_audio_haitsma_frames(size_t n_samples, uint32_t sample_rate);
 int ucfp_audio_haitsma(ucfp_ctx* ctx, const float* pcm, size_t n, uint32_t sample_rate,
                        const ucfp_haitsma_config* cfg, uint32_t* out, size_t cap_frames, size_t* n_frames);

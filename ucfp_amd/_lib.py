@@ -157,6 +157,18 @@ SIGNATURES = {
     "ucfp_text_batcher_destroy": (None, [C.c_void_p]),
     "ucfp_text_batcher_submit": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_int32)]),
     "ucfp_text_batcher_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "ucfp_wang_streams_create": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(WangConfig), C.c_uint32,
+                                           C.POINTER(C.c_void_p)]),
+    "ucfp_wang_streams_destroy": (None, [C.c_void_p]),
+    "ucfp_wang_streams_open": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "ucfp_wang_streams_close": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "ucfp_wang_stream_frontier": (C.c_uint64, [C.c_uint64, C.POINTER(WangConfig)]),
+    "ucfp_wang_streams_state_bytes": (C.c_size_t, [C.POINTER(WangConfig)]),
+    "ucfp_wang_streams_max_hashes": (C.c_size_t, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "ucfp_wang_streams_push_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                             C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "ucfp_wang_streams_push": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p,
+                                         C.c_size_t, C.POINTER(C.c_size_t)]),
     "ucfp_audio_batcher_create": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(WangConfig), C.c_size_t, C.c_size_t,
                                             C.c_uint32, C.POINTER(C.c_void_p)]),
     "ucfp_audio_batcher_destroy": (None, [C.c_void_p]),

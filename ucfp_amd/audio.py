@@ -215,27 +215,119 @@ def fingerprint_haitsma_with(samples, sample_rate: int, cfg: HaitsmaConfig, tena
     return _record(ALGORITHM_HAITSMA, haitsma_frames(samples, sample_rate, cfg).tobytes(), tenant_id, record_id)
 
 
+class WangStreams:
+    """A set of live Wang streams on the device (ucfp_wang_streams_*): `push` advances any subset of them
+    by one chunk each with one launch sequence and returns the hashes each one emits now -- exactly the offline hashes
+    with t_anchor < frontier(n) so far, the rest on the final push (t_anchor = frames since `open`)."""
+
+    def __init__(self, max_streams: int, cfg: Optional[WangConfig] = None, sample_rate: int = WANG_SR, ctx=None):
+        self._lib = _lib.load()
+        self.ctx = ctx or _lib.current_context()
+        self._cfg = (cfg or WangConfig())._c()
+        h = C.c_void_p()
+        _lib.check(self._lib.ucfp_wang_streams_create(self.ctx.handle, sample_rate, C.byref(self._cfg), max_streams,
+                                                      C.byref(h)))
+        self.handle = h
+        self.max_streams = max_streams
+
+    def open(self) -> int:
+        slot = C.c_uint32(0)
+        _lib.check(self._lib.ucfp_wang_streams_open(self.handle, C.byref(slot)))
+        return int(slot.value)
+
+    def close(self, slot: int) -> None:
+        """Discards the stream; emits nothing."""
+        _lib.check(self._lib.ucfp_wang_streams_close(self.handle, slot))
+
+    def frontier(self, n_samples: int) -> int:
+        """F(n): after a non-final push, every hash with t_anchor < F(n) has been emitted, and no other."""
+        return int(self._lib.ucfp_wang_stream_frontier(n_samples, C.byref(self._cfg)))
+
+    def _arrays(self, slots, counts, final):
+        sl = np.ascontiguousarray(slots, dtype=np.uint32)
+        ns = np.ascontiguousarray(counts, dtype=np.uint64)
+        fi = np.array([1 if s in final else 0 for s in sl.tolist()], np.uint8)
+        return sl, ns, fi
+
+    def max_hashes(self, slots, counts, final=()) -> int:
+        sl, ns, fi = self._arrays(slots, counts, set(final))
+        return int(self._lib.ucfp_wang_streams_max_hashes(self.handle, sl.ctypes.data, ns.ctypes.data, fi.ctypes.data,
+                                                          sl.size))
+
+    def push_dev(self, slots, counts, pcm, out, out_offsets, final=(), cap_hashes: Optional[int] = None,
+                 stream: int = 0) -> None:
+        """Device variant (no sync): `pcm` the chunks of `slots` concatenated (float32 tensor), `out` an int32 [cap, 2]
+        tensor, `out_offsets` an int64 [len(slots) + 1] tensor; hashes of slots[i] = out[out_offsets[i]:out_offsets[i+1]]."""
+        sl, ns, fi = self._arrays(slots, counts, set(final))
+        cap = out.shape[0] if cap_hashes is None else cap_hashes
+        _lib.check(self._lib.ucfp_wang_streams_push_dev(self.handle, sl.ctypes.data, ns.ctypes.data, fi.ctypes.data,
+                                                        sl.size, pcm.data_ptr() if pcm.numel() else None,
+                                                        out.data_ptr() if cap else None, cap, out_offsets.data_ptr(),
+                                                        stream or None))
+
+    def push(self, chunks: dict, final=()) -> dict:
+        """{slot: samples} -> {slot: uint32 [n, 2]} of the hashes emitted now; slots in `final` end (and close)."""
+        import torch
+        final = set(final)
+        slots = list(chunks)
+        arrs = [np.ascontiguousarray(chunks[s], dtype=np.float32).reshape(-1) for s in slots]
+        counts = [a.size for a in arrs]
+        cap = self.max_hashes(slots, counts, final)
+        dev = f"cuda:{self.ctx.device}"
+        blob = np.concatenate(arrs) if sum(counts) else np.zeros(0, np.float32)
+        d_pcm = torch.from_numpy(blob).to(dev)
+        d_out = torch.zeros((max(cap, 1), 2), dtype=torch.int32, device=dev)
+        d_oo = torch.zeros(len(slots) + 1, dtype=torch.int64, device=dev)
+        self.push_dev(slots, counts, d_pcm, d_out, d_oo, final, cap, torch.cuda.current_stream().cuda_stream)
+        oo = d_oo.cpu().numpy()
+        out = d_out.cpu().numpy().view(np.uint32)
+        return {s: out[oo[i]:oo[i + 1]].copy() for i, s in enumerate(slots)}
+
+    def destroy(self):
+        if getattr(self, "handle", None):
+            self._lib.ucfp_wang_streams_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
 class StreamingWangSession:
-    """Push/finalize wrapper (audio.rs:414-480). Hashes are a function of the whole signal (per-second
-    peak caps, forward target zones), so the session buffers PCM and emits at `finalize`; `push`
-    returns no records -- allowed by the reference contract ("typically zero or one")."""
+    """Push/finalize wrapper (audio.rs:414-480) on a one-slot WangStreams: each `push` moves its PCM to the device and
+    advances the stream there; only the hashes emitted so far are held on the host, so memory stays bounded however
+    long the stream runs.  `push` returns no records -- allowed by the reference contract ("typically zero or one");
+    `finalize` returns one record with every hash (the offline hashes of the whole stream, byte for byte)."""
 
     def __init__(self, sample_rate: int, tenant_id: int, record_id: int):
         if sample_rate != WANG_SR:
             raise ModalityError(f"Wang requires 8 kHz mono input (got {sample_rate} Hz); resample upstream")
-        self._chunks: List[np.ndarray] = []
         self.tenant_id, self.record_id = tenant_id, record_id
+        self._set = WangStreams(1)
+        self._slot = self._set.open()
+        self._hashes: List[np.ndarray] = []
+
+    def _push(self, samples, final: bool):
+        x = np.ascontiguousarray(samples, dtype=np.float32).reshape(-1)
+        lib = self._set._lib
+        cap = self._set.max_hashes([self._slot], [x.size], [self._slot] if final else ())
+        out = np.zeros((max(cap, 1), 2), np.uint32)
+        n = C.c_size_t(0)
+        _lib.check(lib.ucfp_wang_streams_push(self._set.handle, self._slot, x.ctypes.data if x.size else None, x.size,
+                                              1 if final else 0, out.ctypes.data, cap, C.byref(n)))
+        if n.value:
+            self._hashes.append(out[: n.value].copy())
 
     def push(self, samples) -> List[Record]:
-        self._chunks.append(np.asarray(samples, dtype=np.float32).reshape(-1))
+        self._push(samples, False)
         return []
 
     def finalize(self) -> List[Record]:
-        if not self._chunks:
+        self._push(np.zeros(0, np.float32), True)
+        self._slot = self._set.open()           # the session may be reused, as before
+        h, self._hashes = self._hashes, []
+        if not h:
             return []
-        x = np.concatenate(self._chunks)
-        self._chunks = []
-        h = wang_hashes(x, WANG_SR)
-        if h.shape[0] == 0:
-            return []
-        return [_record(ALGORITHM_WANG, h.tobytes(), self.tenant_id, self.record_id)]
+        return [_record(ALGORITHM_WANG, np.concatenate(h).tobytes(), self.tenant_id, self.record_id)]

@@ -479,6 +479,7 @@ constexpr int kPrologue = 2560;               // samples staged before round 0: 
 static_assert(kBatch == 2 * kSW * 64 && kPrologue >= (kSW - 1) * kWangHop + kWangN && kPrologue + kBatch <= kSmpRing, "");
 
 struct WangClip {
+    static constexpr bool kStream = false;
     uint64_t src_off;   // first source sample of the clip in the batch buffer
     uint64_t src_n;     // source samples
     uint64_t n8k;       // samples at 8 kHz (= src_n when the input is at 8 kHz)
@@ -487,6 +488,7 @@ struct WangClip {
     uint32_t n_seg;     // workgroup segments
     uint32_t pad;
 };
+
 
 struct WangStreamLds {
     float buf[kSW][Rfft<kWangN>::BUF_FLOATS];   // per wave: transpose 2, untangling exchange, power spectrum, row-maximum scratch
@@ -509,6 +511,16 @@ __device__ __forceinline__ uint32_t smp_swz(uint32_t s) { return s ^ ((s >> 2) &
 // Frames per workgroup segment.  Long inputs: as close to kSegMax as gives a whole number of rounds of 256 workgroups
 // (one per CU) -- 4400 segments of 512 frames would run 17 full rounds and an 18th with 48 workgroups; 4608 of 489 run
 // 18 full ones.  Short inputs get shorter segments so that ~1000 workgroups exist.
+// base[0..n_clips] ascending (exclusive scan of counts); entry g of the map = the clip c with base[c] <= g < base[c+1]
+__device__ __forceinline__ uint32_t clip_of(const uint32_t* __restrict__ base, uint32_t n_clips, uint32_t g) {
+    uint32_t lo = 0, hi = n_clips;                 // first index in (0, n_clips] with base[idx] > g, minus one
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (base[mid + 1] > g) hi = mid;
+        else lo = mid + 1;
+    }
+    return lo;
+}
 inline uint32_t wang_segment(size_t frames) {
     size_t seg = (frames + 1023) / 1024;
     if (seg < 48) seg = 48;
@@ -519,14 +531,16 @@ inline uint32_t wang_segment(size_t frames) {
     return (uint32_t)seg;
 }
 
-template <bool RESAMPLE>
+// Clip = WangClip: the offline ragged batch (segment -> clip by seg_clip, seconds from sec_base).  Clip = WangStreamClip:
+// one push of a stream set (segment -> stream by a search of seg_base over n_clips entries; sec_base unused).
+template <bool RESAMPLE, class Clip>
 __global__ __launch_bounds__(kSW * 64) void wang_stream_kernel(const float* __restrict__ pcm,
-                                                          const WangClip* __restrict__ clips,
+                                                          const Clip* __restrict__ clips,
                                                           const uint32_t* __restrict__ seg_clip,
                                                           const uint32_t* __restrict__ seg_base,
                                                           const uint32_t* __restrict__ sec_base,
                                                           const uint32_t* __restrict__ n_segs_total, uint32_t seg,
-                                                          uint32_t sr_in, uint32_t* __restrict__ cand_cnt,
+                                                          uint32_t sr_in, uint32_t n_clips, uint32_t* __restrict__ cand_cnt,
                                                           uint32_t* __restrict__ cand_t,
                                                           uint32_t* __restrict__ cand_k, float* __restrict__ cand_p) {
     // This kernel is bound by instruction issue (every instruction of any kind costs about the same: measured by
@@ -537,10 +551,11 @@ __global__ __launch_bounds__(kSW * 64) void wang_stream_kernel(const float* __re
     WangStreamLds& L = *reinterpret_cast<WangStreamLds*>(lds_raw);
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // frame and ring arithmetic stays scalar
-    const uint32_t clip = seg_clip[blockIdx.x];
-    const WangClip cl = clips[clip];
+    constexpr bool STREAM = Clip::kStream;
+    const uint32_t clip = STREAM ? clip_of(seg_base, n_clips, blockIdx.x) : seg_clip[blockIdx.x];
+    const Clip cl = clips[clip];
     const float* __restrict__ x = pcm + cl.src_off;
-    const uint32_t sec0 = sec_base[clip];
+    const uint32_t sec0 = STREAM ? 0u : sec_base[clip];
     RfftConst<kWangN> K;
     rfft_consts<kWangN>(lane, K);
     if (wave == 0) {
@@ -550,8 +565,14 @@ __global__ __launch_bounds__(kSW * 64) void wang_stream_kernel(const float* __re
     float* buf = L.buf[wave];
     const float* pw = buf;
     const int total = (int)cl.frames;
-    const int s0 = (int)((blockIdx.x - seg_base[clip]) * seg);     // frames [s0, s1) are this segment's to judge
-    const int s1 = s0 + (int)seg < total ? s0 + (int)seg : total;
+    int s0, s1;                                                    // frames [s0, s1) are this segment's to judge
+    if constexpr (STREAM) {
+        s0 = (int)(cl.j_lo + (blockIdx.x - seg_base[clip]) * seg);
+        s1 = s0 + (int)seg < (int)cl.j_hi ? s0 + (int)seg : (int)cl.j_hi;
+    } else {
+        s0 = (int)((blockIdx.x - seg_base[clip]) * seg);
+        s1 = s0 + (int)seg < total ? s0 + (int)seg : total;
+    }
     const int f_lo = s0 - kRT < 0 ? 0 : s0 - kRT;                  // frames [f_lo, f_hi) are computed
     const int f_hi = s1 + kRT < total ? s1 + kRT : total;
 
@@ -734,10 +755,18 @@ __global__ __launch_bounds__(kSW * 64) void wang_stream_kernel(const float* __re
             // (s_waitcnt vmcnt(0) + v_readfirstlane right behind the atomic), which parks every wave for the trip.
             const uint64_t pm = __ballot(is_peak);
             if (pm) {
-                const uint32_t sec = sec0 + ((uint32_t)t * kWangHop) / kWangSr;
+                uint32_t sec;
+                if constexpr (STREAM) {      // seconds counted from the stream's start (64-bit: a stream may pass 2^25 frames)
+                    const uint32_t ts = (uint32_t)t + cl.t_shift;
+                    const uint32_t rel = (uint32_t)(((uint64_t)(cl.t_org + ts) * kWangHop) / kWangSr) - cl.sec_org;
+                    sec = rel < cl.n_closed ? cl.closed_base + rel : cl.open_slot;
+                    pend_t = ts;
+                } else {
+                    sec = sec0 + ((uint32_t)t * kWangHop) / kWangSr;
+                    pend_t = (uint32_t)t;
+                }
                 pend = is_peak;
                 pend_off = sec * (uint32_t)kCandCap;
-                pend_t = (uint32_t)t;
                 pend_k = pk;
                 pend_v = pv;
                 pend_rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(pm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)pm, 0u));
@@ -1006,6 +1035,45 @@ __global__ void wang_compact_kernel(const uint32_t* __restrict__ sel_cnt, const 
 }
 
 // ---- A6: pairing (src/modality/audio.rs:965-1003) ------------------------------------------------
+// Anchor i's targets among the time-sorted peaks i + 1 .. end - 1 (ptk = t << 9 | k); the hashes go to out[o ..) with
+// t_anchor = t + t_org.  Returns the number of targets taken.
+template <bool EMIT>
+__device__ __forceinline__ uint32_t wang_pair_walk(const uint32_t* __restrict__ ptk, uint32_t i, uint32_t end,
+                                                   uint32_t fan_out, uint32_t zone_t, uint32_t zone_f, uint32_t t_org,
+                                                   size_t o, uint2* __restrict__ out, size_t cap) {
+    const uint32_t a = ptk[i];
+    const int32_t ta = (int32_t)(a >> 9), ka = (int32_t)(a & 511u);
+    uint32_t taken = 0;
+    // the walk is a chain of dependent decisions but not of dependent loads: eight following peaks are fetched at
+    // once (a peak past the clip reads as "infinitely late" and ends the walk)
+    bool done = false;
+    for (uint32_t j0 = i + 1; j0 < end && !done; j0 += 8) {
+        uint32_t bb[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) bb[u] = j0 + u < end ? ptk[j0 + u] : 0xffffffffu;
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+            if (done) continue;
+            const uint32_t b = bb[u];
+            const int32_t dt = (int32_t)(b >> 9) - ta;
+            if (dt <= 0) continue;
+            if (dt > (int32_t)zone_t) {
+                done = true;
+                continue;
+            }
+            const int32_t kb = (int32_t)(b & 511u);
+            int32_t df = kb - ka;
+            df = df < 0 ? -df : df;
+            if (df > (int32_t)zone_f) continue;
+            if (EMIT && o < cap) out[o] = make_uint2(((uint32_t)ka << 23) | ((uint32_t)kb << 14) | ((uint32_t)dt & 0x3fffu), (uint32_t)ta + t_org);
+            o++;
+            taken++;
+            if (taken >= fan_out) done = true;
+        }
+    }
+    return taken;
+}
+
 // ptk = t << 9 | k (t < 2^23 frames = 37 h per clip); the peaks of a clip are contiguous, [.., pend[clip]) ends it
 template <bool EMIT>
 __global__ void wang_pair_kernel(const uint32_t* __restrict__ ptk, const float* __restrict__ pp,
@@ -1019,37 +1087,8 @@ __global__ void wang_pair_kernel(const uint32_t* __restrict__ ptk, const float* 
     if (i >= np) return;
     uint32_t taken = 0;
     if (pp[i] >= floor_p) {
-        const uint32_t a = ptk[i];
-        const int32_t ta = (int32_t)(a >> 9), ka = (int32_t)(a & 511u);
         const uint32_t end = sel_off[sec_base[pc[i] + 1]];         // first peak of the next clip
-        size_t o = EMIT ? offs[i] : 0;
-        // the walk is a chain of dependent decisions but not of dependent loads: eight following peaks are fetched at
-        // once (a peak past the clip reads as "infinitely late" and ends the walk)
-        bool done = false;
-        for (uint32_t j0 = i + 1; j0 < end && !done; j0 += 8) {
-            uint32_t bb[8];
-#pragma unroll
-            for (int u = 0; u < 8; u++) bb[u] = j0 + u < end ? ptk[j0 + u] : 0xffffffffu;
-#pragma unroll
-            for (int u = 0; u < 8; u++) {
-                if (done) continue;
-                const uint32_t b = bb[u];
-                const int32_t dt = (int32_t)(b >> 9) - ta;
-                if (dt <= 0) continue;
-                if (dt > (int32_t)zone_t) {
-                    done = true;
-                    continue;
-                }
-                const int32_t kb = (int32_t)(b & 511u);
-                int32_t df = kb - ka;
-                df = df < 0 ? -df : df;
-                if (df > (int32_t)zone_f) continue;
-                if (EMIT && o < cap) out[o] = make_uint2(((uint32_t)ka << 23) | ((uint32_t)kb << 14) | ((uint32_t)dt & 0x3fffu), (uint32_t)ta);
-                o++;
-                taken++;
-                if (taken >= fan_out) done = true;
-            }
-        }
+        taken = wang_pair_walk<EMIT>(ptk, i, end, fan_out, zone_t, zone_f, 0u, EMIT ? offs[i] : 0, out, cap);
     }
     if (!EMIT) counts[i] = taken;
 }
@@ -1075,16 +1114,6 @@ __global__ void wang_clip_prep_kernel(const uint64_t* __restrict__ offsets, uint
     clips[c] = cl;
     seg_cnt[c] = cl.n_seg;
     sec_cnt[c] = cl.n_sec;
-}
-// base[0..n_clips] ascending (exclusive scan of counts); entry g of the map = the clip c with base[c] <= g < base[c+1]
-__device__ __forceinline__ uint32_t clip_of(const uint32_t* __restrict__ base, uint32_t n_clips, uint32_t g) {
-    uint32_t lo = 0, hi = n_clips;                 // first index in (0, n_clips] with base[idx] > g, minus one
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (base[mid + 1] > g) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo;
 }
 __global__ void wang_clip_map_kernel(const uint32_t* __restrict__ seg_base, const uint32_t* __restrict__ sec_base,
                                      uint32_t n_clips, uint32_t* __restrict__ seg_clip, uint32_t* __restrict__ sec_clip) {
@@ -1219,6 +1248,177 @@ __global__ void haitsma_frame_map_kernel(const uint64_t* __restrict__ offsets, c
 
 inline unsigned blocks_for(size_t n, unsigned bs) { return (unsigned)((n + bs - 1) / bs); }
 
+// ---- streaming Wang (A9): the kernels around wang_stream_kernel<false, WangStreamClip> for one push of a stream set.
+// The host builds the push's table (WangPushWs); every kernel here runs over all the push's streams at once.
+
+// one wave per entry: the open second's carried candidates -> its first list (t relative to the push's origin);
+// every other list of the entry starts empty
+__global__ __launch_bounds__(64) void wang_streams_load_kernel(const WangStreamClip* __restrict__ clips,
+                                                               const WangStreamEntry* __restrict__ ents,
+                                                               WangStreamsDev st, uint32_t* __restrict__ cand_cnt,
+                                                               uint32_t* __restrict__ cand_t, uint32_t* __restrict__ cand_k,
+                                                               float* __restrict__ cand_p) {
+    const WangStreamClip cl = clips[blockIdx.x];
+    const WangStreamEntry e = ents[blockIdx.x];
+    const uint32_t lane = threadIdx.x;
+    const uint32_t first = cl.n_closed ? cl.closed_base : cl.open_slot;
+    const bool has_open = !e.fin;
+    if (!cl.n_closed && !has_open) return;       // nothing judged, nothing open (a final push of a short stream)
+    const uint32_t c = e.fresh ? 0u : st.cand_n[e.slot];
+    for (uint32_t i = lane; i < c; i += 64) {
+        const size_t src = (size_t)e.slot * kCandCap + i, dst = (size_t)first * kCandCap + i;
+        cand_t[dst] = st.cand_t[src] - cl.t_org;
+        cand_k[dst] = st.cand_k[src];
+        cand_p[dst] = st.cand_p[src];
+    }
+    for (uint32_t i = lane; i < cl.n_closed; i += 64) cand_cnt[cl.closed_base + i] = 0;
+    if (lane == 0) {
+        if (has_open) cand_cnt[cl.open_slot] = 0;
+        cand_cnt[first] = c;
+    }
+}
+
+// virtual clip i = the carried samples of its stream, then its chunk
+__global__ void wang_streams_gather_kernel(const float* __restrict__ pcm, const WangStreamEntry* __restrict__ ents,
+                                           const uint32_t* __restrict__ v_base, uint32_t n, const float* __restrict__ smp,
+                                           float* __restrict__ vbuf) {
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= v_base[n]) return;
+    const uint32_t i = clip_of(v_base, n, g);
+    const WangStreamEntry e = ents[i];
+    const uint32_t r = g - v_base[i];
+    vbuf[g] = r < e.carry_in ? smp[(size_t)e.slot * kWangCarry + r] : pcm[e.chunk_off + (r - e.carry_in)];
+}
+
+// one wave per entry: its peak list = the retained peaks, then the selected peaks of its closed seconds (in order)
+__global__ __launch_bounds__(64) void wang_streams_peaks_kernel(const WangStreamClip* __restrict__ clips,
+                                                                const WangStreamEntry* __restrict__ ents,
+                                                                const uint32_t* __restrict__ pk_base, WangStreamsDev st,
+                                                                const uint32_t* __restrict__ sel_cnt,
+                                                                const uint32_t* __restrict__ sel_t,
+                                                                const uint32_t* __restrict__ sel_k,
+                                                                const float* __restrict__ sel_p, uint32_t pps,
+                                                                uint32_t* __restrict__ ptk, float* __restrict__ pp,
+                                                                uint32_t* __restrict__ np) {
+    const WangStreamClip cl = clips[blockIdx.x];
+    const WangStreamEntry e = ents[blockIdx.x];
+    const uint32_t lane = threadIdx.x, base = pk_base[blockIdx.x];
+    const uint32_t r = e.fresh ? 0u : st.ret_n[e.slot];
+    for (uint32_t i = lane; i < r; i += 64) {
+        const size_t src = (size_t)e.slot * st.ret_cap + i;
+        ptk[base + i] = ((st.ret_t[src] - e.o) << 9) | st.ret_k[src];
+        pp[base + i] = st.ret_p[src];
+    }
+    uint32_t pos = base + r;
+    for (uint32_t c0 = 0; c0 < cl.n_closed; c0 += 64) {
+        const uint32_t s = c0 + lane;
+        const uint32_t cnt = s < cl.n_closed ? sel_cnt[cl.closed_base + s] : 0u;
+        uint32_t inc = cnt;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t v = __shfl_up(inc, off, 64);
+            if (lane >= (uint32_t)off) inc += v;
+        }
+        const uint32_t dst = pos + inc - cnt;
+        const size_t src = (size_t)(cl.closed_base + (s < cl.n_closed ? s : 0u)) * pps;
+        for (uint32_t q = 0; q < cnt; q++) {       // sel_t is relative to the push's origin t_org = e.o
+            ptk[dst + q] = (sel_t[src + q] << 9) | sel_k[src + q];
+            pp[dst + q] = sel_p[src + q];
+        }
+        pos += __shfl(inc, 63, 64);
+    }
+    if (lane == 0) np[blockIdx.x] = pos - base;
+}
+
+// one thread per peak position of the push: the anchors inside the entry's emission window pair with the peaks after
+// them (A6, wang_pair_walk); counts / offsets over all positions, like the offline pair kernel
+template <bool EMIT>
+__global__ void wang_streams_pair_kernel(const WangStreamEntry* __restrict__ ents, const uint32_t* __restrict__ pk_base,
+                                         uint32_t n, const uint32_t* __restrict__ np, const uint32_t* __restrict__ ptk,
+                                         const float* __restrict__ pp, uint32_t fan_out, uint32_t zone_t, uint32_t zone_f,
+                                         float floor_p, uint32_t* __restrict__ counts, const uint32_t* __restrict__ offs,
+                                         uint2* __restrict__ out, size_t cap) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= pk_base[n]) return;
+    const uint32_t c = clip_of(pk_base, n, i);
+    const uint32_t end = pk_base[c] + np[c];
+    uint32_t taken = 0;
+    if (i < end && pp[i] >= floor_p) {
+        const WangStreamEntry e = ents[c];
+        const uint32_t t = e.o + (ptk[i] >> 9);
+        if (t >= e.f_lo && (e.fin || t < e.f_hi))
+            taken = wang_pair_walk<EMIT>(ptk, i, end, fan_out, zone_t, zone_f, e.o, EMIT ? offs[i] : 0, out, cap);
+    }
+    if (!EMIT) counts[i] = taken;
+}
+
+// hashes of entry i = out[out_off[i] .. out_off[i + 1])
+__global__ void wang_streams_offsets_kernel(const uint32_t* __restrict__ pk_base, uint32_t n,
+                                            const uint32_t* __restrict__ pair_off, uint64_t* __restrict__ out_off) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i <= n) out_off[i] = pair_off[pk_base[i]];
+}
+
+// one workgroup per entry: what the next push needs goes back into the stream's state (a final push leaves it empty)
+__global__ __launch_bounds__(256) void wang_streams_save_kernel(const WangStreamClip* __restrict__ clips,
+                                                                const WangStreamEntry* __restrict__ ents,
+                                                                const uint32_t* __restrict__ pk_base,
+                                                                const uint32_t* __restrict__ np, WangStreamsDev st,
+                                                                const float* __restrict__ vbuf,
+                                                                const uint32_t* __restrict__ cand_cnt,
+                                                                const uint32_t* __restrict__ cand_t,
+                                                                const uint32_t* __restrict__ cand_k,
+                                                                const float* __restrict__ cand_p,
+                                                                const uint32_t* __restrict__ ptk,
+                                                                const float* __restrict__ pp) {
+    __shared__ uint32_t first;
+    const WangStreamClip cl = clips[blockIdx.x];
+    const WangStreamEntry e = ents[blockIdx.x];
+    const uint32_t tid = threadIdx.x;
+    if (e.fin) {
+        if (tid == 0) {
+            st.cand_n[e.slot] = 0;
+            st.ret_n[e.slot] = 0;
+        }
+        return;
+    }
+    // samples from frame J - 7's first one on
+    for (uint32_t i = tid; i < e.carry_out; i += 256)
+        st.smp[(size_t)e.slot * kWangCarry + i] = vbuf[cl.src_off + e.keep_rel + i];
+    // the open second's candidates (absolute t)
+    uint32_t c = cand_cnt[cl.open_slot];
+    c = c < (uint32_t)kCandCap ? c : (uint32_t)kCandCap;
+    for (uint32_t i = tid; i < c; i += 256) {
+        const size_t src = (size_t)cl.open_slot * kCandCap + i, dst = (size_t)e.slot * kCandCap + i;
+        st.cand_t[dst] = cand_t[src] + cl.t_org;
+        st.cand_k[dst] = cand_k[src];
+        st.cand_p[dst] = cand_p[src];
+    }
+    // peaks at or after ret_from: a time-sorted suffix of the entry's list
+    const uint32_t base = pk_base[blockIdx.x], m = np[blockIdx.x];
+    if (tid == 0) first = m;
+    __syncthreads();
+    for (uint32_t i = tid; i < m; i += 256) {
+        const bool in = e.o + (ptk[base + i] >> 9) >= e.ret_from;
+        const bool prev_in = i > 0 && e.o + (ptk[base + i - 1] >> 9) >= e.ret_from;
+        if (in && !prev_in) first = i;
+    }
+    __syncthreads();
+    uint32_t r = m - first;
+    r = r < st.ret_cap ? r : st.ret_cap;
+    for (uint32_t i = tid; i < r; i += 256) {
+        const uint32_t a = ptk[base + first + i];
+        const size_t dst = (size_t)e.slot * st.ret_cap + i;
+        st.ret_t[dst] = e.o + (a >> 9);
+        st.ret_k[dst] = a & 511u;
+        st.ret_p[dst] = pp[base + first + i];
+    }
+    if (tid == 0) {
+        st.cand_n[e.slot] = c;
+        st.ret_n[e.slot] = r;
+    }
+}
+
 }  // namespace
 
 size_t audio_resample_len(size_t n, uint32_t sr_in, uint32_t sr_out) {
@@ -1310,18 +1510,18 @@ int launch_wang_batch(const float* pcm, const uint64_t* d_offsets, size_t n_src_
     (void)hipMemsetAsync(u32(w.cand_cnt), 0, (size_t)w.n_sec * 4, stream);
     const size_t lds = sizeof(WangStreamLds);
     if (sr_in == (uint32_t)kWangSr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wang_stream_kernel<false>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wang_stream_kernel<false, WangClip>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(wang_stream_kernel<false>, dim3(w.n_seg), dim3(kSW * 64), lds, stream, pcm,
+        hipLaunchKernelGGL((wang_stream_kernel<false, WangClip>), dim3(w.n_seg), dim3(kSW * 64), lds, stream, pcm,
                            (const WangClip*)clips, (const uint32_t*)u32(w.seg_clip), (const uint32_t*)u32(w.seg_base),
-                           (const uint32_t*)u32(w.sec_base), n_segs_total, w.seg, sr_in, u32(w.cand_cnt),
+                           (const uint32_t*)u32(w.sec_base), n_segs_total, w.seg, sr_in, nc, u32(w.cand_cnt),
                            u32(w.cand_t), u32(w.cand_k), f32(w.cand_p));
     } else {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wang_stream_kernel<true>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wang_stream_kernel<true, WangClip>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(wang_stream_kernel<true>, dim3(w.n_seg), dim3(kSW * 64), lds, stream, pcm,
+        hipLaunchKernelGGL((wang_stream_kernel<true, WangClip>), dim3(w.n_seg), dim3(kSW * 64), lds, stream, pcm,
                            (const WangClip*)clips, (const uint32_t*)u32(w.seg_clip), (const uint32_t*)u32(w.seg_base),
-                           (const uint32_t*)u32(w.sec_base), n_segs_total, w.seg, sr_in, u32(w.cand_cnt),
+                           (const uint32_t*)u32(w.sec_base), n_segs_total, w.seg, sr_in, nc, u32(w.cand_cnt),
                            u32(w.cand_t), u32(w.cand_k), f32(w.cand_p));
     }
     hipLaunchKernelGGL(wang_select_kernel, dim3(w.n_sec), dim3(64), 0, stream, u32(w.cand_cnt), u32(w.cand_t),
@@ -1439,6 +1639,103 @@ int launch_haitsma_batch(const float* pcm, const uint64_t* d_offsets, size_t n_t
         hipLaunchKernelGGL(haitsma_bits_kernel, dim3(blocks_for(e1 - e0, 256)), dim3(256), 0, stream, E, e0, e1 - e0,
                            out, (const uint64_t*)src_map, cap_frames);
     }
+    return 0;
+}
+
+// ---- streaming Wang orchestration (A9) ------------------------------------------------------------
+static_assert(kWangCandCap == (uint32_t)kCandCap, "");
+
+WangPushWs wang_push_layout(size_t n, size_t n_slots, size_t n_closed, size_t total_v, size_t total_cap,
+                            size_t judged, uint32_t pps) {
+    auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    WangPushWs w;
+    w.n = n;
+    w.n_slots = n_slots;
+    w.n_closed = n_closed;
+    w.total_v = total_v;
+    w.total_cap = total_cap;
+    w.seg = wang_segment(judged);
+    if (w.seg < 64) w.seg = 64;          // a one-second push judges ~63 frames: one segment per stream
+    size_t off = 0;
+    w.clips = off;      off += n * sizeof(WangStreamClip);
+    w.ents = off;       off += n * sizeof(WangStreamEntry);
+    w.v_base = off;     off += (n + 1) * 4;
+    w.seg_base = off;   off += (n + 1) * 4;
+    w.pk_base = off;    off += (n + 1) * 4;
+    w.n_closed_w = off; off += 4;
+    w.tab_bytes = off;  off = align(off);
+    w.vbuf = off;       off = align(off + total_v * 4);
+    w.cand_cnt = off;   off = align(off + n_slots * 4);
+    w.cand_t = off;     off = align(off + n_slots * kCandCap * 4);
+    w.cand_k = off;     off = align(off + n_slots * kCandCap * 4);
+    w.cand_p = off;     off = align(off + n_slots * kCandCap * 4);
+    w.sel_cnt = off;    off = align(off + (n_closed + 1) * 4);
+    w.sel_t = off;      off = align(off + n_closed * pps * 4);
+    w.sel_k = off;      off = align(off + n_closed * pps * 4);
+    w.sel_p = off;      off = align(off + n_closed * pps * 4);
+    w.pt = off;         off = align(off + total_cap * 4);
+    w.pp = off;         off = align(off + total_cap * 4);
+    w.np = off;         off = align(off + n * 4);
+    w.pair_cnt = off;   off = align(off + (total_cap + 1) * 4);
+    w.pair_off = off;   off = align(off + (total_cap + 1) * 4);
+    w.scan_tmp = off;   off = align(off + 2 * (total_cap / 4096 + 4) * 4);
+    w.total = off + 256;
+    return w;
+}
+
+// The table [ws + w.clips, ws + w.tab_bytes) is on the device already (the caller copies it in front of this).
+// Launches: load, gather, stream, select, peaks, pair count, scan (1 or 3), pair emit, offsets, save -- whatever n is.
+int launch_wang_streams_push(const float* pcm, const WangStreamsDev& st, uint32_t fan_out, uint32_t zone_t,
+                             uint32_t zone_f, uint32_t pps, float floor_power, uint8_t* ws, const WangPushWs& w,
+                             uint32_t* out, size_t cap, uint64_t* d_out_off, hipStream_t stream) {
+    const uint32_t n = (uint32_t)w.n;
+    if (n == 0) {
+        (void)hipMemsetAsync(d_out_off, 0, 8, stream);
+        return 0;
+    }
+    auto f32 = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    auto u32 = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
+    const WangStreamClip* clips = reinterpret_cast<const WangStreamClip*>(ws + w.clips);
+    const WangStreamEntry* ents = reinterpret_cast<const WangStreamEntry*>(ws + w.ents);
+    const uint32_t* v_base = u32(w.v_base);
+    const uint32_t* seg_base = u32(w.seg_base);
+    const uint32_t* pk_base = u32(w.pk_base);
+    hipLaunchKernelGGL(wang_streams_load_kernel, dim3(n), dim3(64), 0, stream, clips, ents, st, u32(w.cand_cnt),
+                       u32(w.cand_t), u32(w.cand_k), f32(w.cand_p));
+    if (w.total_v)
+        hipLaunchKernelGGL(wang_streams_gather_kernel, dim3(blocks_for(w.total_v, 256)), dim3(256), 0, stream, pcm, ents,
+                           v_base, n, (const float*)st.smp, f32(w.vbuf));
+    if (w.n_seg) {
+        const size_t lds = sizeof(WangStreamLds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wang_stream_kernel<false, WangStreamClip>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL((wang_stream_kernel<false, WangStreamClip>), dim3((uint32_t)w.n_seg), dim3(kSW * 64), lds,
+                           stream, (const float*)f32(w.vbuf), clips, (const uint32_t*)nullptr, seg_base,
+                           (const uint32_t*)nullptr, seg_base + n, w.seg, (uint32_t)kWangSr, n, u32(w.cand_cnt),
+                           u32(w.cand_t), u32(w.cand_k), f32(w.cand_p));
+    }
+    if (w.n_closed)
+        hipLaunchKernelGGL(wang_select_kernel, dim3((uint32_t)w.n_closed), dim3(64), 0, stream, u32(w.cand_cnt),
+                           u32(w.cand_t), u32(w.cand_k), f32(w.cand_p), pps, (const uint32_t*)u32(w.n_closed_w),
+                           u32(w.sel_cnt), u32(w.sel_t), u32(w.sel_k), f32(w.sel_p));
+    hipLaunchKernelGGL(wang_streams_peaks_kernel, dim3(n), dim3(64), 0, stream, clips, ents, pk_base, st,
+                       (const uint32_t*)u32(w.sel_cnt), (const uint32_t*)u32(w.sel_t), (const uint32_t*)u32(w.sel_k),
+                       (const float*)f32(w.sel_p), pps, u32(w.pt), f32(w.pp), u32(w.np));
+    const size_t tc = w.total_cap;
+    hipLaunchKernelGGL(wang_streams_pair_kernel<false>, dim3(blocks_for(tc, 256)), dim3(256), 0, stream, ents, pk_base,
+                       n, (const uint32_t*)u32(w.np), (const uint32_t*)u32(w.pt), (const float*)f32(w.pp), fan_out,
+                       zone_t, zone_f, floor_power, u32(w.pair_cnt), (const uint32_t*)nullptr, (uint2*)nullptr, (size_t)0);
+    launch_exclusive_scan(u32(w.pair_cnt), tc, u32(w.pair_off), u32(w.scan_tmp), stream);
+    hipLaunchKernelGGL(wang_streams_pair_kernel<true>, dim3(blocks_for(tc, 256)), dim3(256), 0, stream, ents, pk_base,
+                       n, (const uint32_t*)u32(w.np), (const uint32_t*)u32(w.pt), (const float*)f32(w.pp), fan_out,
+                       zone_t, zone_f, floor_power, (uint32_t*)nullptr, (const uint32_t*)u32(w.pair_off),
+                       reinterpret_cast<uint2*>(out), cap);
+    hipLaunchKernelGGL(wang_streams_offsets_kernel, dim3(blocks_for(n + 1, 256)), dim3(256), 0, stream, pk_base, n,
+                       (const uint32_t*)u32(w.pair_off), d_out_off);
+    hipLaunchKernelGGL(wang_streams_save_kernel, dim3(n), dim3(256), 0, stream, clips, ents, pk_base,
+                       (const uint32_t*)u32(w.np), st, (const float*)f32(w.vbuf), (const uint32_t*)u32(w.cand_cnt),
+                       (const uint32_t*)u32(w.cand_t), (const uint32_t*)u32(w.cand_k), (const float*)f32(w.cand_p),
+                       (const uint32_t*)u32(w.pt), (const float*)f32(w.pp));
     return 0;
 }
 

@@ -285,6 +285,61 @@ int launch_wang_batch(const float* pcm, const uint64_t* d_offsets, size_t n_src_
                       uint32_t fan_out, uint32_t zone_t, uint32_t zone_f, uint32_t pps,
                       float floor_power, uint8_t* ws, const WangWs& w, uint32_t* out, size_t cap, uint64_t* d_out_off,
                       uint64_t* out_count, hipStream_t stream);
+
+// ---- streaming Wang (A9): one push of a stream set (wang_streams.hip plans it, audio.hip runs it) ----
+constexpr uint32_t kWangCarry = 2816;     // carried samples per stream: n - 128 max(0, J - 7) <= 1023 + 14 * 128
+constexpr uint32_t kWangCandCap = 320;    // = kCandCap: candidates of a stream's one open second
+// One stream's share of a push (A9): a "virtual clip" = the stream's carried samples followed by its new chunk, whose
+// frame 0 is frame t_org + t_shift of the stream.  Only frames [j_lo, j_hi) are judged; the window is cut at the clip's
+// edges as usual, which happens only where the stream starts (t_org + t_shift = 0) or ends (the final push).  A judged
+// peak is recorded at t + t_shift (relative to the push's origin t_org, so t << 9 | k stays packable whatever the
+// stream's age) in the candidate list of its second: closed seconds sec_org .. sec_org + n_closed - 1 are lists
+// closed_base .., a later (still open) second is list open_slot.  Segments of the push map to streams via seg_base.
+struct WangStreamClip {
+    static constexpr bool kStream = true;
+    uint64_t src_off, src_n, n8k;   // as WangClip (src_n = n8k: streams are at 8 kHz)
+    uint32_t frames, j_lo, j_hi, t_shift, t_org, sec_org, n_closed, closed_base, open_slot, pad;
+};
+// the rest of a push entry, for the kernels around the stream kernel
+struct WangStreamEntry {
+    uint32_t slot;        // stream slot
+    uint32_t carry_in;    // carried samples at the head of the virtual clip
+    uint32_t keep_rel;    // first sample of the virtual clip carried into the next push
+    uint32_t carry_out;   // samples carried into the next push
+    uint64_t chunk_off;   // the entry's chunk in the caller's buffer
+    uint32_t o;           // origin: peak t = o + (ptk >> 9)
+    uint32_t f_lo, f_hi;  // anchors emitted: f_lo <= t < f_hi (final: t >= f_lo)
+    uint32_t fin;         // final push
+    uint32_t ret_from;    // peaks with t >= ret_from are retained (non-final)
+    uint32_t fresh;       // first push of the stream: its state holds nothing yet
+};
+// device state of a stream set, per slot (sized at creation)
+struct WangStreamsDev {
+    float* smp;           // [slots][kWangCarry]
+    uint32_t* cand_n;     // [slots]: candidates of the open second
+    uint32_t* cand_t;     // [slots][kWangCandCap] absolute frames
+    uint32_t* cand_k;
+    float* cand_p;
+    uint32_t* ret_n;      // [slots]: retained peaks
+    uint32_t* ret_t;      // [slots][ret_cap] absolute frames, time-sorted
+    uint32_t* ret_k;
+    float* ret_p;
+    uint32_t ret_cap;
+};
+// one push in the context's workspace; [tab, tab + tab_bytes) is the host-built table:
+// clips[n], ents[n], v_base[n + 1] (virtual clips in vbuf), seg_base[n + 1], pk_base[n + 1] (peak lists), n_closed
+struct WangPushWs {
+    size_t n = 0, n_slots = 0, n_closed = 0, total_v = 0, total_cap = 0, n_seg = 0;
+    uint32_t seg = 0;
+    size_t clips, ents, v_base, seg_base, pk_base, n_closed_w, tab_bytes, vbuf, cand_cnt, cand_t, cand_k, cand_p,
+        sel_cnt, sel_t, sel_k, sel_p, pt, pp, np, pair_cnt, pair_off, scan_tmp, total = 0;
+};
+WangPushWs wang_push_layout(size_t n, size_t n_slots, size_t n_closed, size_t total_v, size_t total_cap,
+                            size_t judged, uint32_t pps);
+int launch_wang_streams_push(const float* pcm, const WangStreamsDev& st, uint32_t fan_out, uint32_t zone_t,
+                             uint32_t zone_f, uint32_t pps, float floor_power, uint8_t* ws, const WangPushWs& w,
+                             uint32_t* out, size_t cap, uint64_t* d_out_off, hipStream_t stream);
+
 struct HaitsmaBatchWs {
     size_t n5_ub = 0, frames_ub = 0;      // upper bounds (the per-clip lengths of a batch live on the device)
     size_t edges, s5_off, fr_off, src_map, pcm5k, E, total = 0;

@@ -475,6 +475,39 @@ int ucfp_lsh_build_dev(ucfp_lsh* lsh, const uint64_t* d_ids, const uint8_t* d_re
 int ucfp_lsh_query_dev(ucfp_lsh* lsh, const uint8_t* d_query_records, size_t nq, uint32_t k, uint64_t* d_out_ids,
                        float* d_out_scores, uint32_t* d_out_counts, void* stream);
 
+/* ---- landmark index over Wang hashes (the reference has no audio matcher) ----
+ * Records and queries are sets of landmarks: 8 bytes each, u32 LE hash then u32 LE t (UCFP_WANG_HASH_BYTES), t < 2^31.
+ * Item i of a batch is landmarks[offsets[i] .. offsets[i+1]) with BYTE offsets: offsets[0] = 0, non-decreasing,
+ * multiples of 8; n + 1 entries.  Duplicate (hash, t) pairs count once.  Within a tenant, P(h) = distinct (record, t)
+ * postings of hash h; an index with max_postings > 0 ignores every h with P(h) > max_postings (0 = no cap).
+ * votes(r) = max over d of |{(h, t) in Q : (h, t + d) in R_r}|, offset(r) = the smallest d attaining it (the position of
+ * the query's frame 0 in the record, in frames).  Hits: votes >= max(min_votes, 1), ordered (votes desc, id asc), first
+ * k <= UCFP_INDEX_MAX_K; score = (float)votes / (float)|Q|.  Unused output slots: id UINT64_MAX, votes 0, offset 0,
+ * score -1.  An empty query, k = 0 or an unknown tenant gives 0 hits; bad offsets or t >= 2^31 give UCFP_E_INVALID.
+ * Upsert of a known id replaces its set, delete removes it; postings are rebuilt lazily at the next query, size or
+ * flush of a changed tenant.  Queries read the checked sizes and the vote count of each query back to the host (two
+ * synchronisations of `stream`) to size their buffers; the rest of a query is asynchronous.  upsert_dev copies its
+ * inputs to the host record table (it synchronises `stream`).  flags: 0. */
+typedef struct ucfp_landmark_index ucfp_landmark_index;
+int ucfp_landmark_index_create(ucfp_ctx* ctx, uint32_t max_postings, uint32_t flags, ucfp_landmark_index** out);
+void ucfp_landmark_index_destroy(ucfp_landmark_index* ix);
+int ucfp_landmark_index_upsert(ucfp_landmark_index* ix, uint32_t tenant, const uint64_t* ids, const uint8_t* landmarks,
+                               const uint64_t* offsets, size_t n);
+int ucfp_landmark_index_upsert_dev(ucfp_landmark_index* ix, uint32_t tenant, const uint64_t* d_ids,
+                                   const uint8_t* d_landmarks, const uint64_t* d_offsets, size_t n, void* stream);
+int ucfp_landmark_index_delete(ucfp_landmark_index* ix, uint32_t tenant, const uint64_t* ids, size_t n, size_t* n_removed);
+/* records = live records (empty ones included); postings = sum of P(h) (rebuilds a changed tenant). */
+int ucfp_landmark_index_size(ucfp_landmark_index* ix, uint32_t tenant, size_t* records, size_t* postings);
+int ucfp_landmark_index_flush(ucfp_landmark_index* ix);
+/* nq ragged queries; out_ids / out_votes / out_offsets / out_scores are nq x k; out_n[q] = hits of query q. */
+int ucfp_landmark_index_query(ucfp_landmark_index* ix, uint32_t tenant, const uint8_t* landmarks, const uint64_t* offsets,
+                              size_t nq, uint32_t k, uint32_t min_votes, uint64_t* out_ids, uint32_t* out_votes,
+                              int32_t* out_offsets, float* out_scores, uint32_t* out_n);
+int ucfp_landmark_index_query_dev(ucfp_landmark_index* ix, uint32_t tenant, const uint8_t* d_landmarks,
+                                  const uint64_t* d_offsets, size_t nq, uint32_t k, uint32_t min_votes, uint64_t* d_out_ids,
+                                  uint32_t* d_out_votes, int32_t* d_out_offsets, float* d_out_scores, uint32_t* d_out_n,
+                                  void* stream);
+
 /* =============================== INDEX ========================================
  * Replaces `trait IndexBackend` kNN (src/index/mod.rs:29-35) as implemented by
  * EmbeddedBackend::knn (src/index/embedded/mod.rs:268-360): exact brute-force top-k inside

@@ -18,6 +18,7 @@ class HitSource:
     Bm25 = "bm25"
     Fused = "fused"
     Hamming = "hamming"   # new capability behind /v1/query; not in the reference
+    Landmark = "landmark"  # audio identification over Wang landmarks (DESIGN A10); not in the reference
 
 
 @dataclass
@@ -47,6 +48,8 @@ class Hit:
     bm25_rank: Optional[int] = None
     term_hits: list = field(default_factory=list)
     distance: Optional[int] = None    # Hamming distance when source == "hamming"
+    votes: Optional[int] = None       # offset-consistent landmark matches when source == "landmark"
+    offset: Optional[int] = None      # where the query's frame 0 lies in the record (frames) when source == "landmark"
 
 
 FORMAT_VERSION = 1  # src/lib.rs:62
@@ -54,8 +57,9 @@ FORMAT_VERSION = 1  # src/lib.rs:62
 
 # ---- /v1/query wire types (src/server/dto.rs:74-116, handlers.rs:143-187) -----------------------------
 # The reference's request needs `vector`; the Hamming search adds ONE additive, backward-compatible field
-# (SURVEY 8b / 8f N3): `hash` (u64, or 8 little-endian bytes) with `algorithm` naming the hash space.  A body
-# the reference accepts parses to the same query here.
+# (SURVEY 8b / 8f N3): `hash` (u64, or 8 little-endian bytes) with `algorithm` naming the hash space.  Audio
+# identification adds `landmarks` (DESIGN A10): Wang landmark bytes (8 per landmark) or a list of [hash, t] pairs.
+# A body the reference accepts parses to the same query here.
 
 DEFAULT_K = 10   # dto.rs:85-87
 
@@ -68,6 +72,7 @@ class QueryRequest:
     vector: Optional[List[float]] = None
     hash: Optional[int] = None
     algorithm: Optional[str] = None
+    landmarks: Optional[bytes] = None   # 8 bytes per landmark: u32 LE hash, u32 LE t
 
     @classmethod
     def from_json(cls, body: dict) -> "QueryRequest":
@@ -78,9 +83,11 @@ class QueryRequest:
         except (KeyError, TypeError, ValueError) as e:
             raise InvalidArgument(f"bad query body: {e}") from None
         k = int(body.get("k", DEFAULT_K))
-        vector, h = body.get("vector"), body.get("hash")
-        if vector is None and h is None:
+        vector, h, lm = body.get("vector"), body.get("hash"), body.get("landmarks")
+        if vector is None and h is None and lm is None:
             raise InvalidArgument("query needs `vector` (dto.rs:80-82) or `hash`")
+        if lm is not None:
+            lm = _landmark_bytes(lm)
         if isinstance(h, (list, bytes, bytearray)):
             if len(h) != 8:
                 raise InvalidArgument("`hash` bytes must be 8 little-endian bytes")
@@ -89,14 +96,37 @@ class QueryRequest:
             raise InvalidArgument("`hash` must be a u64")
         return cls(tenant_id=tenant_id, modality=modality, k=max(k, 1),       # handlers.rs:153: k.max(1)
                    vector=[float(x) for x in vector] if vector is not None else None,
-                   hash=int(h) if h is not None else None, algorithm=body.get("algorithm"))
+                   hash=int(h) if h is not None else None, algorithm=body.get("algorithm"), landmarks=lm)
+
+
+def _landmark_bytes(lm) -> bytes:
+    """`landmarks` of a query body -> 8 bytes per landmark (u32 LE hash, u32 LE t < 2^31)."""
+    from .errors import InvalidArgument
+    if isinstance(lm, (bytes, bytearray)):
+        if len(lm) % 8:
+            raise InvalidArgument("`landmarks` bytes must be a multiple of 8 (u32 hash, u32 t per landmark)")
+        return bytes(lm)
+    if not isinstance(lm, list):
+        raise InvalidArgument("`landmarks` must be bytes or a list of [hash, t] pairs")
+    out = bytearray()
+    for p in lm:
+        if not isinstance(p, (list, tuple)) or len(p) != 2 or not all(isinstance(x, int) for x in p):
+            raise InvalidArgument("every landmark must be a [hash, t] pair of integers")
+        if not 0 <= p[0] < 1 << 32 or not 0 <= p[1] < 1 << 31:
+            raise InvalidArgument("a landmark needs 0 <= hash < 2^32 and 0 <= t < 2^31")
+        out += int(p[0]).to_bytes(4, "little") + int(p[1]).to_bytes(4, "little")
+    return bytes(out)
 
 
 def hit_to_json(h: Hit) -> dict:
-    """HitOut (dto.rs:94-116); `distance` only appears on Hamming hits, so vector hits stay byte-stable."""
+    """HitOut (dto.rs:94-116); `distance` only appears on Hamming hits and `votes` / `offset` only on landmark hits, so
+    vector hits stay byte-stable."""
     out = {"tenant_id": h.tenant_id, "record_id": h.record_id, "score": h.score, "source": h.source,
            "vector_score": h.vector_score, "bm25_score": h.bm25_score, "vector_rank": h.vector_rank,
            "bm25_rank": h.bm25_rank, "term_hits": list(h.term_hits)}
     if h.distance is not None:
         out["distance"] = h.distance
+    if h.source == HitSource.Landmark:
+        out["votes"] = h.votes
+        out["offset"] = h.offset
     return out

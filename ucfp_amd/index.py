@@ -6,6 +6,7 @@ path, backed by the GPU-resident shard behind the C ABI (ucfp_index_*).
     GpuIndex.knn(tenant, query, k)    IndexBackend::knn      :29-35  (cosine over Record.embedding,
                                       as EmbeddedBackend::knn src/index/embedded/mod.rs:268-360)
     GpuIndex.hamming(tenant, h, k)    the new Hamming search behind /v1/query
+    GpuIndex.identify(tenant, lm, k)  audio identification over Wang landmarks (DESIGN A10; LandmarkIndex)
     GpuIndex.flush()                  IndexBackend::flush    :63
 
 The reference keeps redb as the source of truth; this object is the device mirror of one shard
@@ -18,6 +19,7 @@ from typing import Iterable, List, Optional, Sequence
 import numpy as np
 
 from . import _lib
+from .audio import ALGORITHM_WANG
 from .core import Hit, HitSource, Record
 from .errors import InvalidArgument
 
@@ -158,6 +160,99 @@ class DeviceIndex:
                                                    out_counts_ptr, stream or None))
 
 
+def _pack_landmarks(items):
+    """Sequence of landmark sets (bytes, or uint32 [n, 2] arrays of (hash, t)) -> (u8 blob, u64 byte offsets [n + 1]).
+    Bytes go through unchanged, so a length that is not a multiple of 8 reaches the library (UCFP_E_INVALID)."""
+    parts = []
+    for x in items:
+        if isinstance(x, (bytes, bytearray, memoryview)):
+            parts.append(bytes(x))
+        else:
+            parts.append(np.ascontiguousarray(x, dtype=np.uint32).reshape(-1, 2).tobytes())
+    offs = np.zeros(len(parts) + 1, np.uint64)
+    np.cumsum([len(b) for b in parts], out=offs[1:])
+    blob = np.frombuffer(b"".join(parts) + b"\0" * 8, np.uint8)
+    return blob, offs
+
+
+class LandmarkIndex:
+    """Thin RAII wrapper over one ucfp_landmark_index (DESIGN A10): records and queries are sets of Wang landmarks;
+    a query answers the top-k records by offset-consistent vote count, with the best offset of each."""
+
+    def __init__(self, max_postings: int = 0, flags: int = 0, ctx=None):
+        self._lib = _lib.load()
+        self.ctx = ctx or _lib.current_context()
+        self.max_postings = max_postings
+        h = C.c_void_p()
+        _lib.check(self._lib.ucfp_landmark_index_create(self.ctx.handle, max_postings, flags, C.byref(h)))
+        self.handle = h
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self._lib.ucfp_landmark_index_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def upsert(self, tenant: int, ids, landmarks) -> None:
+        """ids [n]; landmarks: n landmark sets (bytes or uint32 [m, 2] of (hash, t))."""
+        ids = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        landmarks = list(landmarks)
+        if len(landmarks) != ids.shape[0]:
+            raise InvalidArgument("ids and landmark sets disagree on the number of records")
+        blob, offs = _pack_landmarks(landmarks)
+        _lib.check(self._lib.ucfp_landmark_index_upsert(self.handle, tenant, ids.ctypes.data, blob.ctypes.data,
+                                                        offs.ctypes.data, ids.shape[0]))
+
+    def upsert_dev(self, tenant: int, ids_ptr: int, landmarks_ptr: int, offsets_ptr: int, n: int, stream: int = 0) -> None:
+        _lib.check(self._lib.ucfp_landmark_index_upsert_dev(self.handle, tenant, ids_ptr, landmarks_ptr or None,
+                                                            offsets_ptr, n, stream or None))
+
+    def delete(self, tenant: int, ids) -> int:
+        ids = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        removed = C.c_size_t(0)
+        _lib.check(self._lib.ucfp_landmark_index_delete(self.handle, tenant, ids.ctypes.data, ids.shape[0],
+                                                        C.byref(removed)))
+        return int(removed.value)
+
+    def size(self, tenant: int):
+        """-> (records, postings) of a tenant."""
+        r, p = C.c_size_t(0), C.c_size_t(0)
+        _lib.check(self._lib.ucfp_landmark_index_size(self.handle, tenant, C.byref(r), C.byref(p)))
+        return int(r.value), int(p.value)
+
+    def flush(self) -> None:
+        _lib.check(self._lib.ucfp_landmark_index_flush(self.handle))
+
+    def query(self, tenant: int, queries, k: int, min_votes: int = 1):
+        """queries: landmark sets (bytes or uint32 [m, 2]).  -> (ids [nq,k] u64, votes [nq,k] u32, offsets [nq,k] i32,
+        scores [nq,k] f32, counts [nq] u32)."""
+        blob, offs = _pack_landmarks(list(queries))
+        nq = offs.size - 1
+        kk = max(int(k), 1)
+        ids = np.full((nq, kk), INVALID_ID, np.uint64)
+        votes = np.zeros((nq, kk), np.uint32)
+        offsets = np.zeros((nq, kk), np.int32)
+        scores = np.zeros((nq, kk), np.float32)
+        counts = np.zeros(nq, np.uint32)
+        _lib.check(self._lib.ucfp_landmark_index_query(self.handle, tenant, blob.ctypes.data, offs.ctypes.data, nq, int(k),
+                                                       int(min_votes), ids.ctypes.data, votes.ctypes.data,
+                                                       offsets.ctypes.data, scores.ctypes.data, counts.ctypes.data))
+        return ids[:, :k], votes[:, :k], offsets[:, :k], scores[:, :k], counts
+
+    def query_dev(self, tenant: int, landmarks_ptr: int, offsets_ptr: int, nq: int, k: int, min_votes: int,
+                  out_ids_ptr: int, out_votes_ptr: int, out_offsets_ptr: int, out_scores_ptr: int, out_n_ptr: int,
+                  stream: int = 0) -> None:
+        _lib.check(self._lib.ucfp_landmark_index_query_dev(self.handle, tenant, landmarks_ptr or None, offsets_ptr, nq, k,
+                                                           min_votes, out_ids_ptr or None, out_votes_ptr or None,
+                                                           out_offsets_ptr or None, out_scores_ptr or None, out_n_ptr,
+                                                           stream or None))
+
+
 def topk_merge_dev(kind: int, part_ids_ptr: int, part_keys_ptr: int, parts: int, nq: int, k: int,
                    out_ids_ptr: int, out_scores_ptr: int, out_keys_ptr: int, out_counts_ptr: int,
                    stream: int = 0, ctx=None) -> None:
@@ -177,6 +272,7 @@ class GpuIndex:
         self.ctx = ctx or _lib.current_context()
         self._cos = {}        # dim -> DeviceIndex
         self._ham = {}        # hash space name -> DeviceIndex
+        self._lm = None       # LandmarkIndex of the audiofp-wang-v1 records (DESIGN A10)
         self._sidecar = sidecar   # ucfp_amd.store.Sidecar: the stored-table mirror written at upsert
 
     def attach_sidecar(self, sidecar) -> None:
@@ -194,22 +290,32 @@ class GpuIndex:
             ix = self._ham[space] = DeviceIndex(HAMMING64, 0, 0, self.ctx)
         return ix
 
+    def _landmarks(self) -> LandmarkIndex:
+        if self._lm is None:
+            self._lm = LandmarkIndex(0, 0, self.ctx)
+        return self._lm
+
     def upsert(self, records: Sequence[Record]) -> None:
         """Embeddings go to the cosine index of their dimension; image records also feed the
-        Hamming spaces `<algorithm>` with their 64-bit global hashes (SURVEY 8f N2 offsets).
+        Hamming spaces `<algorithm>` with their 64-bit global hashes (SURVEY 8f N2 offsets);
+        `audiofp-wang-v1` records feed the landmark index with their landmarks.
 
         Overwrite semantics are the reference's: everything is keyed by (tenant_id, record_id), a re-ingested record
         REPLACES the old one -- "Drop any stale vector for this key" when the new record has no embedding
         (src/index/embedded/mod.rs:184-191), a new dimension or algorithm replaces the old row.  So before inserting,
-        the key is removed from every cosine index of another dimension and every hash space the new record does not
-        feed.  Within one batch the last record of a key wins, as successive `insert`s in one redb transaction do."""
+        the key is removed from every cosine index of another dimension, every hash space and the landmark index when
+        the new record does not feed them.  Within one batch the last record of a key wins, as successive `insert`s in one redb transaction do."""
         if self._sidecar is not None:     # the log first (the host does this right after its redb commit), then the mirror
             self._sidecar.append(records)
         last = {}
         for r in records:
             last[(r.tenant_id, r.record_id)] = r
-        by_cos, by_ham, stale_cos, stale_ham = {}, {}, {}, {}
+        by_cos, by_ham, stale_cos, stale_ham, by_lm, stale_lm = {}, {}, {}, {}, {}, {}
         for r in last.values():
+            if r.algorithm == ALGORITHM_WANG:
+                by_lm.setdefault(r.tenant_id, []).append(r)
+            elif self._lm is not None:
+                stale_lm.setdefault(r.tenant_id, []).append(r.record_id)
             dim = len(r.embedding) if r.embedding is not None else 0
             if dim > 0:
                 by_cos.setdefault((r.tenant_id, dim), []).append(r)
@@ -227,6 +333,11 @@ class GpuIndex:
             self._cos[d].delete(tenant, np.array(ids, np.uint64))
         for (tenant, space), ids in stale_ham.items():
             self._ham[space].delete(tenant, np.array(ids, np.uint64))
+        for tenant, ids in stale_lm.items():
+            self._lm.delete(tenant, np.array(ids, np.uint64))
+        for tenant, recs in by_lm.items():
+            self._landmarks().upsert(tenant, np.array([r.record_id for r in recs], np.uint64),
+                                     [bytes(r.fingerprint) for r in recs])
         for (tenant, dim), recs in by_cos.items():
             ids = np.array([r.record_id for r in recs], np.uint64)
             rows = np.array([r.embedding for r in recs], np.float32)
@@ -240,7 +351,7 @@ class GpuIndex:
         ids = np.array(list(record_ids), np.uint64)
         if self._sidecar is not None:
             self._sidecar.delete(tenant_id, ids.tolist())
-        for ix in list(self._cos.values()) + list(self._ham.values()):
+        for ix in list(self._cos.values()) + list(self._ham.values()) + ([self._lm] if self._lm is not None else []):
             ix.delete(tenant_id, ids)
 
     def knn(self, tenant_id: int, query: Sequence[float], k: int, _filter: Optional[bytes] = None) -> List[Hit]:
@@ -263,10 +374,21 @@ class GpuIndex:
         return [Hit(tenant_id=tenant_id, record_id=int(ids[0, i]), score=float(scores[0, i]),
                     source=HitSource.Hamming, distance=int(dist[0, i])) for i in range(int(counts[0]))]
 
+    def identify(self, tenant_id: int, landmarks, k: int, min_votes: int = 1) -> List[Hit]:
+        """Which recording is this clip, and where in it: landmarks = bytes (8 per landmark) or uint32 [n, 2] of
+        (hash, t).  Hits by offset-consistent votes (DESIGN A10); `offset` = the clip's frame 0 in the record."""
+        if k == 0 or self._lm is None:
+            return []
+        ids, votes, offs, scores, counts = self._lm.query(tenant_id, [landmarks], min(k, MAX_K), min_votes)
+        return [Hit(tenant_id=tenant_id, record_id=int(ids[0, i]), score=float(scores[0, i]), source=HitSource.Landmark,
+                    votes=int(votes[0, i]), offset=int(offs[0, i])) for i in range(int(counts[0]))]
+
     def query(self, req) -> List[Hit]:
         """POST /v1/query (handlers.rs:143-187) with the additive `hash` field: a vector goes to the cosine kNN,
-        a hash to the Hamming space `algorithm` (default: the only hash space present)."""
-        if req.hash is not None:
+        a hash to the Hamming space `algorithm` (default: the only hash space present), `landmarks` to identify."""
+        if getattr(req, "landmarks", None) is not None:
+            hits = self.identify(req.tenant_id, req.landmarks, req.k)
+        elif req.hash is not None:
             space = req.algorithm
             if space is None:
                 if len(self._ham) != 1:
@@ -283,7 +405,7 @@ class GpuIndex:
     def flush(self) -> None:
         if self._sidecar is not None:
             self._sidecar.sync()
-        for ix in list(self._cos.values()) + list(self._ham.values()):
+        for ix in list(self._cos.values()) + list(self._ham.values()) + ([self._lm] if self._lm is not None else []):
             ix.flush()
 
 

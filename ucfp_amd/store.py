@@ -9,7 +9,8 @@ host right after its redb transaction commits) and rebuilds the shards from it:
 
     Sidecar(path).append(records) / .delete(tenant, ids) / .sync()      the writer, one call per upsert / delete
     Snapshot(path)                                                      live rows after replay, redb range-scan order
-    rebuild(path, ctx) -> GpuIndex                                      start-up: every hash space and cosine index
+    rebuild(path, ctx) -> GpuIndex                                      start-up: every hash space, cosine index and
+                                                                        the landmark index of the Wang records
 
 Hash spaces are keyed by the catalog's `algorithm` tag, so only comparable 64-bit hashes share an index; the 64-bit
 global hashes are cut out of the stored 168 / 536-byte records ON THE DEVICE (ucfp_image_record_codes_dev, offsets
@@ -164,6 +165,7 @@ def rebuild(path: str, ctx=None, sidecar: bool = False):
     """Start-up: replay the sidecar at `path` into a fresh GpuIndex (every hash space, every cosine dimension).
     `sidecar=True` keeps the log attached, so later upserts / deletes are appended to it."""
     import torch
+    from .audio import ALGORITHM_WANG
     from .index import GpuIndex
     ctx = ctx or _lib.current_context()
     lib = _lib.load()
@@ -190,6 +192,13 @@ def rebuild(path: str, ctx=None, sidecar: bool = False):
             for tenant in np.unique(tenants):
                 sel = tenants == tenant
                 gi._hamming(algorithm).upsert(int(tenant), ids[sel], np.ascontiguousarray(blobs[sel]).view(np.uint64).reshape(-1))
+        # Wang records are variable length: walk the rows (the landmark index keeps its record table on the host)
+        wang = {}
+        for r in snap:
+            if r.algorithm == ALGORITHM_WANG:
+                wang.setdefault(r.tenant_id, []).append(r)
+        for tenant, recs in wang.items():
+            gi._landmarks().upsert(tenant, np.array([r.record_id for r in recs], np.uint64), [r.fingerprint for r in recs])
         for dim in snap.dims():
             tenants, ids, rows = snap.gather_vectors(dim)
             for tenant in np.unique(tenants):

@@ -508,6 +508,45 @@ int ucfp_landmark_index_query_dev(ucfp_landmark_index* ix, uint32_t tenant, cons
                                   uint32_t* d_out_votes, int32_t* d_out_offsets, float* d_out_scores, uint32_t* d_out_n,
                                   void* stream);
 
+/* ---- BM25 keyword index (src/index/embedded/bm25.rs:79-628) ----
+ * A document is a list of (key u64, tf u32) pairs: item i of a batch is keys/tfs[offsets[i] .. offsets[i+1]) with
+ * ELEMENT offsets (offsets[0] = 0, non-decreasing, n + 1 entries); dl = sum tf < 2^32.  Keys are the caller's: equal
+ * terms of a tenant must map to equal keys (the Python mirror numbers its terms; the Rust host can pass FST term ids).
+ * A key twice in one document, tf = 0 or bad offsets give UCFP_E_INVALID before anything changes.  A document without
+ * pairs still counts in N.  Upsert of a known id replaces the document, delete removes it; postings are rebuilt lazily
+ * at the next query or flush of a changed tenant.
+ * A query is a list of keys (order and duplicates kept; an unknown key matches nothing).  With N live documents,
+ * T = sum dl, avgdl = (float)T / (float)N, df_j = documents holding key j, idf_j = logf((N - df_j + 0.5f) /
+ * (df_j + 0.5f) + 1.0f) by the HOST's logf, c = (idf_j * (tf * (K1 + 1))) / fmaxf(tf + K1 * ((1 - B) + (B * dl) /
+ * fmaxf(avgdl, 1)), 1e-6f) with K1 = 1.2f, B = 0.75f, all f32 one operation at a time; score = sum of c in key order
+ * from 0.  Hits: every document holding some query key, ordered (score desc, id asc), first k <= UCFP_INDEX_MAX_K.
+ * Unused output slots: id UINT64_MAX, score -1.  k = 0, an empty query or an unknown / empty tenant gives 0 hits.
+ * Optional explain outputs (NULL = not written): out_idf[offsets[q] + j] = idf of position j (0 for an unknown key);
+ * out_tf / out_contrib[k * offsets[q] + h * m_q + j] = tf and c of hit h at position j of query q (m_q keys; 0 when the
+ * hit does not hold the key or h >= out_n[q]).  A query reads df of its keys back to the host once (one synchronisation
+ * of `stream`; query_dev also reads the offsets); the rest is asynchronous.  A query with more than
+ * UCFP_BM25_LDS_POSTINGS postings in all is scored by ordinal ranges instead of in one LDS table; both give the same
+ * bits.  upsert_dev copies its inputs to the host document table (it synchronises `stream`).  flags: 0. */
+#define UCFP_BM25_LDS_POSTINGS 6144u
+typedef struct ucfp_bm25_index ucfp_bm25_index;
+int ucfp_bm25_index_create(ucfp_ctx* ctx, uint32_t flags, ucfp_bm25_index** out);
+void ucfp_bm25_index_destroy(ucfp_bm25_index* ix);
+int ucfp_bm25_index_upsert(ucfp_bm25_index* ix, uint32_t tenant, const uint64_t* ids, const uint64_t* keys,
+                           const uint32_t* tfs, const uint64_t* offsets, size_t n);
+int ucfp_bm25_index_upsert_dev(ucfp_bm25_index* ix, uint32_t tenant, const uint64_t* d_ids, const uint64_t* d_keys,
+                               const uint32_t* d_tfs, const uint64_t* d_offsets, size_t n, void* stream);
+int ucfp_bm25_index_delete(ucfp_bm25_index* ix, uint32_t tenant, const uint64_t* ids, size_t n, size_t* n_removed);
+/* docs = live documents (empty ones included); postings = (key, document) pairs. */
+int ucfp_bm25_index_size(ucfp_bm25_index* ix, uint32_t tenant, size_t* docs, size_t* postings);
+int ucfp_bm25_index_flush(ucfp_bm25_index* ix);
+/* nq ragged queries; out_ids / out_scores are nq x k; out_n[q] = hits of query q. */
+int ucfp_bm25_index_query(ucfp_bm25_index* ix, uint32_t tenant, const uint64_t* keys, const uint64_t* offsets, size_t nq,
+                          uint32_t k, uint64_t* out_ids, float* out_scores, uint32_t* out_n, float* out_idf,
+                          uint32_t* out_tf, float* out_contrib);
+int ucfp_bm25_index_query_dev(ucfp_bm25_index* ix, uint32_t tenant, const uint64_t* d_keys, const uint64_t* d_offsets,
+                              size_t nq, uint32_t k, uint64_t* d_out_ids, float* d_out_scores, uint32_t* d_out_n,
+                              float* d_out_idf, uint32_t* d_out_tf, float* d_out_contrib, void* stream);
+
 /* =============================== INDEX ========================================
  * Replaces `trait IndexBackend` kNN (src/index/mod.rs:29-35) as implemented by
  * EmbeddedBackend::knn (src/index/embedded/mod.rs:268-360): exact brute-force top-k inside

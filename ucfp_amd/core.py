@@ -37,6 +37,15 @@ class Record:
 
 
 @dataclass
+class TermHit:
+    """One matched query term of a BM25 hit (src/core/mod.rs:191-205): filled when the query asks to explain."""
+    term: str
+    idf: float
+    tf: int
+    contribution: float
+
+
+@dataclass
 class Hit:
     tenant_id: int
     record_id: int
@@ -59,6 +68,8 @@ FORMAT_VERSION = 1  # src/lib.rs:62
 # The reference's request needs `vector`; the Hamming search adds ONE additive, backward-compatible field
 # (SURVEY 8b / 8f N3): `hash` (u64, or 8 little-endian bytes) with `algorithm` naming the hash space.  Audio
 # identification adds `landmarks` (DESIGN A10): Wang landmark bytes (8 per landmark) or a list of [hash, t] pairs.
+# Keyword search adds `terms` (the reference's Query::terms, src/core/mod.rs:163-164; BM25, DESIGN A11) and `explain`
+# (the reference's `?explain=1`, handlers.rs:133-140): terms alone give a BM25 query, vector + terms the hybrid one.
 # A body the reference accepts parses to the same query here.
 
 DEFAULT_K = 10   # dto.rs:85-87
@@ -73,6 +84,8 @@ class QueryRequest:
     hash: Optional[int] = None
     algorithm: Optional[str] = None
     landmarks: Optional[bytes] = None   # 8 bytes per landmark: u32 LE hash, u32 LE t
+    terms: List[str] = field(default_factory=list)
+    explain: bool = False
 
     @classmethod
     def from_json(cls, body: dict) -> "QueryRequest":
@@ -84,8 +97,11 @@ class QueryRequest:
             raise InvalidArgument(f"bad query body: {e}") from None
         k = int(body.get("k", DEFAULT_K))
         vector, h, lm = body.get("vector"), body.get("hash"), body.get("landmarks")
-        if vector is None and h is None and lm is None:
-            raise InvalidArgument("query needs `vector` (dto.rs:80-82) or `hash`")
+        terms = body.get("terms") or []
+        if not isinstance(terms, list) or not all(isinstance(t, str) for t in terms):
+            raise InvalidArgument("`terms` must be a list of strings")
+        if vector is None and h is None and lm is None and not terms:
+            raise InvalidArgument("query needs `vector` (dto.rs:80-82), `terms`, `hash` or `landmarks`")
         if lm is not None:
             lm = _landmark_bytes(lm)
         if isinstance(h, (list, bytes, bytearray)):
@@ -96,7 +112,15 @@ class QueryRequest:
             raise InvalidArgument("`hash` must be a u64")
         return cls(tenant_id=tenant_id, modality=modality, k=max(k, 1),       # handlers.rs:153: k.max(1)
                    vector=[float(x) for x in vector] if vector is not None else None,
-                   hash=int(h) if h is not None else None, algorithm=body.get("algorithm"), landmarks=lm)
+                   hash=int(h) if h is not None else None, algorithm=body.get("algorithm"), landmarks=lm,
+                   terms=list(terms), explain=_flag(body.get("explain", False)))
+
+
+def _flag(v) -> bool:
+    """`explain`: a JSON bool, or the reference's query-string forms "1" | "true" | "yes" (handlers.rs:139-141)."""
+    if isinstance(v, str):
+        return v in ("1", "true", "yes")
+    return bool(v)
 
 
 def _landmark_bytes(lm) -> bytes:
@@ -120,10 +144,12 @@ def _landmark_bytes(lm) -> bytes:
 
 def hit_to_json(h: Hit) -> dict:
     """HitOut (dto.rs:94-116); `distance` only appears on Hamming hits and `votes` / `offset` only on landmark hits, so
-    vector hits stay byte-stable."""
+    vector hits stay byte-stable.  `term_hits` are TermHitOut objects {term, idf, tf, contribution} (dto.rs:118-124)."""
     out = {"tenant_id": h.tenant_id, "record_id": h.record_id, "score": h.score, "source": h.source,
            "vector_score": h.vector_score, "bm25_score": h.bm25_score, "vector_rank": h.vector_rank,
-           "bm25_rank": h.bm25_rank, "term_hits": list(h.term_hits)}
+           "bm25_rank": h.bm25_rank,
+           "term_hits": [{"term": t.term, "idf": t.idf, "tf": t.tf, "contribution": t.contribution}
+                         if isinstance(t, TermHit) else t for t in h.term_hits]}
     if h.distance is not None:
         out["distance"] = h.distance
     if h.source == HitSource.Landmark:

@@ -7,6 +7,7 @@ path, backed by the GPU-resident shard behind the C ABI (ucfp_index_*).
                                       as EmbeddedBackend::knn src/index/embedded/mod.rs:268-360)
     GpuIndex.hamming(tenant, h, k)    the new Hamming search behind /v1/query
     GpuIndex.identify(tenant, lm, k)  audio identification over Wang landmarks (DESIGN A10; LandmarkIndex)
+    GpuIndex.bm25(tenant, terms, k)   IndexBackend::bm25 / bm25_explain :37-50 over Record.text (DESIGN A11; Bm25Index)
     GpuIndex.flush()                  IndexBackend::flush    :63
 
 The reference keeps redb as the source of truth; this object is the device mirror of one shard
@@ -20,13 +21,16 @@ import numpy as np
 
 from . import _lib
 from .audio import ALGORITHM_WANG
-from .core import Hit, HitSource, Record
-from .errors import InvalidArgument
+from .core import Hit, HitSource, Record, TermHit
+from .errors import InvalidArgument, UnsupportedError
+from .terms import query_terms, tokenize
 
 HAMMING64, COSINE_F32 = 1, 2
 APPEND_ONLY = 1
 MAX_K = 128
 INVALID_ID = 0xFFFFFFFFFFFFFFFF
+BM25_LDS_POSTINGS = 6144   # UCFP_BM25_LDS_POSTINGS: a query with more postings is scored by ordinal ranges
+TERM_HITS_PER_DOC = 16     # bm25.rs:503
 
 
 class SearchBatcher:
@@ -253,6 +257,136 @@ class LandmarkIndex:
                                                            stream or None))
 
 
+class Bm25Index:
+    """Thin RAII wrapper over one ucfp_bm25_index (DESIGN A11): BM25 over documents of (key, tf) pairs.  It keeps the
+    term -> key dictionary of the index (keys number the terms in order of first sight); query terms it has never
+    seen are dropped on the host."""
+
+    def __init__(self, flags: int = 0, ctx=None):
+        self._lib = _lib.load()
+        self.ctx = ctx or _lib.current_context()
+        self.keys = {}     # term -> key
+        h = C.c_void_p()
+        _lib.check(self._lib.ucfp_bm25_index_create(self.ctx.handle, flags, C.byref(h)))
+        self.handle = h
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self._lib.ucfp_bm25_index_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _key(self, term: str) -> int:
+        k = self.keys.get(term)
+        if k is None:
+            k = self.keys[term] = len(self.keys)
+        return k
+
+    def upsert_pairs(self, tenant: int, ids, keys, tfs, offsets) -> None:
+        """The ABI form: document i is (keys, tfs)[offsets[i] .. offsets[i + 1])."""
+        ids = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        keys = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1)
+        tfs = np.ascontiguousarray(tfs, dtype=np.uint32).reshape(-1)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+        if offsets.size != ids.size + 1:
+            raise InvalidArgument("offsets needs one entry more than ids")
+        if keys.size != tfs.size:
+            raise InvalidArgument("keys and tfs disagree on the number of pairs")
+        _lib.check(self._lib.ucfp_bm25_index_upsert(self.handle, tenant, ids.ctypes.data, keys.ctypes.data,
+                                                    tfs.ctypes.data, offsets.ctypes.data, ids.size))
+
+    def upsert(self, tenant: int, ids, texts: Sequence[str]) -> None:
+        """Tokenize each text (terms.tokenize) and store its term counts; a text without tokens is an empty document."""
+        ids = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        texts = list(texts)
+        if len(texts) != ids.size:
+            raise InvalidArgument("ids and texts disagree on the number of documents")
+        keys, tfs, offs = [], [], [0]
+        for t in texts:
+            counts = {}
+            for tok in tokenize(t):
+                counts[tok] = counts.get(tok, 0) + 1
+            keys.extend(self._key(tok) for tok in counts)
+            tfs.extend(counts.values())
+            offs.append(len(keys))
+        self.upsert_pairs(tenant, ids, np.array(keys, np.uint64), np.array(tfs, np.uint32), np.array(offs, np.uint64))
+
+    def upsert_dev(self, tenant: int, ids_ptr: int, keys_ptr: int, tfs_ptr: int, offsets_ptr: int, n: int,
+                   stream: int = 0) -> None:
+        _lib.check(self._lib.ucfp_bm25_index_upsert_dev(self.handle, tenant, ids_ptr, keys_ptr or None, tfs_ptr or None,
+                                                        offsets_ptr, n, stream or None))
+
+    def delete(self, tenant: int, ids) -> int:
+        ids = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        removed = C.c_size_t(0)
+        _lib.check(self._lib.ucfp_bm25_index_delete(self.handle, tenant, ids.ctypes.data, ids.shape[0], C.byref(removed)))
+        return int(removed.value)
+
+    def size(self, tenant: int):
+        """-> (documents, postings) of a tenant."""
+        d, p = C.c_size_t(0), C.c_size_t(0)
+        _lib.check(self._lib.ucfp_bm25_index_size(self.handle, tenant, C.byref(d), C.byref(p)))
+        return int(d.value), int(p.value)
+
+    def flush(self) -> None:
+        _lib.check(self._lib.ucfp_bm25_index_flush(self.handle))
+
+    def query_keys(self, tenant: int, queries, k: int, explain: bool = False):
+        """queries: key lists.  -> (ids [nq,k] u64, scores [nq,k] f32, counts [nq] u32) and, with explain, (idf [total] f32,
+        tf [total * k] u32, contributions [total * k] f32) laid out as ucfp_hip.h says."""
+        qs = [np.ascontiguousarray(q, dtype=np.uint64).reshape(-1) for q in queries]
+        offs = np.zeros(len(qs) + 1, np.uint64)
+        np.cumsum([q.size for q in qs], out=offs[1:])
+        keys = np.concatenate(qs + [np.zeros(1, np.uint64)])
+        nq, total, kk = len(qs), int(offs[-1]), max(int(k), 1)
+        ids = np.full((nq, kk), INVALID_ID, np.uint64)
+        scores = np.zeros((nq, kk), np.float32)
+        counts = np.zeros(nq, np.uint32)
+        idf = np.zeros(max(total, 1), np.float32)
+        tf = np.zeros(max(total * kk, 1), np.uint32)
+        con = np.zeros(max(total * kk, 1), np.float32)
+        x = (idf.ctypes.data, tf.ctypes.data, con.ctypes.data) if explain else (None, None, None)
+        _lib.check(self._lib.ucfp_bm25_index_query(self.handle, tenant, keys.ctypes.data, offs.ctypes.data, nq, int(k),
+                                                   ids.ctypes.data, scores.ctypes.data, counts.ctypes.data, *x))
+        out = (ids[:, :k], scores[:, :k], counts)
+        return out + (idf[:total], tf[:total * k], con[:total * k]) if explain else out
+
+    def query_dev(self, tenant: int, keys_ptr: int, offsets_ptr: int, nq: int, k: int, out_ids_ptr: int,
+                  out_scores_ptr: int, out_n_ptr: int, out_idf_ptr: int = 0, out_tf_ptr: int = 0, out_contrib_ptr: int = 0,
+                  stream: int = 0) -> None:
+        _lib.check(self._lib.ucfp_bm25_index_query_dev(self.handle, tenant, keys_ptr or None, offsets_ptr, nq, k,
+                                                       out_ids_ptr or None, out_scores_ptr or None, out_n_ptr,
+                                                       out_idf_ptr or None, out_tf_ptr or None, out_contrib_ptr or None,
+                                                       stream or None))
+
+    def search(self, tenant: int, terms: Sequence[str], k: int, explain: bool = False) -> List[Hit]:
+        """bm25.rs `search_explain`: the query terms are re-tokenized and flattened; each hit explains at most 16
+        matched positions, sorted stably by contribution, descending."""
+        toks = [t for t in query_terms(terms) if t in self.keys]
+        if k == 0 or not toks:
+            return []
+        k = min(k, MAX_K)
+        res = self.query_keys(tenant, [[self.keys[t] for t in toks]], k, explain)
+        ids, scores, counts = res[:3]
+        hits = []
+        m = len(toks)
+        for h in range(int(counts[0])):
+            th = []
+            if explain:
+                idf, tf, con = res[3:]
+                th = [TermHit(term=toks[j], idf=float(idf[j]), tf=int(tf[h * m + j]), contribution=float(con[h * m + j]))
+                      for j in range(m) if tf[h * m + j]]
+                th = sorted(th, key=lambda t: t.contribution, reverse=True)[:TERM_HITS_PER_DOC]
+            hits.append(Hit(tenant_id=tenant, record_id=int(ids[0, h]), score=float(scores[0, h]), source=HitSource.Bm25,
+                            term_hits=th))
+        return hits
+
+
 def topk_merge_dev(kind: int, part_ids_ptr: int, part_keys_ptr: int, parts: int, nq: int, k: int,
                    out_ids_ptr: int, out_scores_ptr: int, out_keys_ptr: int, out_counts_ptr: int,
                    stream: int = 0, ctx=None) -> None:
@@ -273,6 +407,7 @@ class GpuIndex:
         self._cos = {}        # dim -> DeviceIndex
         self._ham = {}        # hash space name -> DeviceIndex
         self._lm = None       # LandmarkIndex of the audiofp-wang-v1 records (DESIGN A10)
+        self._bm = None       # Bm25Index of the records with text (DESIGN A11)
         self._sidecar = sidecar   # ucfp_amd.store.Sidecar: the stored-table mirror written at upsert
 
     def attach_sidecar(self, sidecar) -> None:
@@ -295,10 +430,20 @@ class GpuIndex:
             self._lm = LandmarkIndex(0, 0, self.ctx)
         return self._lm
 
+    def _bm25(self) -> Bm25Index:
+        if self._bm is None:
+            self._bm = Bm25Index(0, self.ctx)
+        return self._bm
+
+    def _all(self):
+        return (list(self._cos.values()) + list(self._ham.values()) + ([self._lm] if self._lm is not None else [])
+                + ([self._bm] if self._bm is not None else []))
+
     def upsert(self, records: Sequence[Record]) -> None:
         """Embeddings go to the cosine index of their dimension; image records also feed the
         Hamming spaces `<algorithm>` with their 64-bit global hashes (SURVEY 8f N2 offsets);
-        `audiofp-wang-v1` records feed the landmark index with their landmarks.
+        `audiofp-wang-v1` records feed the landmark index with their landmarks; every record with `text`, whatever its
+        modality, feeds BM25, and a record without text leaves it (src/index/embedded/mod.rs:208-219).
 
         Overwrite semantics are the reference's: everything is keyed by (tenant_id, record_id), a re-ingested record
         REPLACES the old one -- "Drop any stale vector for this key" when the new record has no embedding
@@ -310,8 +455,12 @@ class GpuIndex:
         last = {}
         for r in records:
             last[(r.tenant_id, r.record_id)] = r
-        by_cos, by_ham, stale_cos, stale_ham, by_lm, stale_lm = {}, {}, {}, {}, {}, {}
+        by_cos, by_ham, stale_cos, stale_ham, by_lm, stale_lm, by_bm, stale_bm = {}, {}, {}, {}, {}, {}, {}, {}
         for r in last.values():
+            if r.text is not None:
+                by_bm.setdefault(r.tenant_id, []).append(r)
+            elif self._bm is not None:
+                stale_bm.setdefault(r.tenant_id, []).append(r.record_id)
             if r.algorithm == ALGORITHM_WANG:
                 by_lm.setdefault(r.tenant_id, []).append(r)
             elif self._lm is not None:
@@ -335,6 +484,10 @@ class GpuIndex:
             self._ham[space].delete(tenant, np.array(ids, np.uint64))
         for tenant, ids in stale_lm.items():
             self._lm.delete(tenant, np.array(ids, np.uint64))
+        for tenant, ids in stale_bm.items():
+            self._bm.delete(tenant, np.array(ids, np.uint64))
+        for tenant, recs in by_bm.items():
+            self._bm25().upsert(tenant, np.array([r.record_id for r in recs], np.uint64), [r.text for r in recs])
         for tenant, recs in by_lm.items():
             self._landmarks().upsert(tenant, np.array([r.record_id for r in recs], np.uint64),
                                      [bytes(r.fingerprint) for r in recs])
@@ -351,7 +504,7 @@ class GpuIndex:
         ids = np.array(list(record_ids), np.uint64)
         if self._sidecar is not None:
             self._sidecar.delete(tenant_id, ids.tolist())
-        for ix in list(self._cos.values()) + list(self._ham.values()) + ([self._lm] if self._lm is not None else []):
+        for ix in self._all():
             ix.delete(tenant_id, ids)
 
     def knn(self, tenant_id: int, query: Sequence[float], k: int, _filter: Optional[bytes] = None) -> List[Hit]:
@@ -383,9 +536,27 @@ class GpuIndex:
         return [Hit(tenant_id=tenant_id, record_id=int(ids[0, i]), score=float(scores[0, i]), source=HitSource.Landmark,
                     votes=int(votes[0, i]), offset=int(offs[0, i])) for i in range(int(counts[0]))]
 
+    def bm25(self, tenant_id: int, terms: Sequence[str], k: int, filter: Optional[bytes] = None,
+             explain: bool = False) -> List[Hit]:
+        """IndexBackend::bm25 / bm25_explain (src/index/embedded/mod.rs:127-150): "bm25" hits by BM25 score (DESIGN
+        A11); with `explain`, each hit's term_hits.  A metadata filter is not supported, as in the reference."""
+        if filter is not None:
+            raise UnsupportedError("BM25 filter pre-filtering is not yet supported")
+        if k == 0 or self._bm is None:
+            return []
+        return self._bm.search(tenant_id, terms, k, explain)
+
     def query(self, req) -> List[Hit]:
         """POST /v1/query (handlers.rs:143-187) with the additive `hash` field: a vector goes to the cosine kNN,
-        a hash to the Hamming space `algorithm` (default: the only hash space present), `landmarks` to identify."""
+        a hash to the Hamming space `algorithm` (default: the only hash space present), `landmarks` to identify;
+        `terms` go through the matcher (BM25, or vector + BM25 fused by RRF: src/matcher/mod.rs:140-207)."""
+        if getattr(req, "landmarks", None) is None and req.hash is None and getattr(req, "terms", None):
+            from . import matcher
+            hits = matcher.search(self, req)
+            for rank, h in enumerate(hits):
+                if h.source == HitSource.Bm25:
+                    h.bm25_score, h.bm25_rank = h.score, rank + 1
+            return hits
         if getattr(req, "landmarks", None) is not None:
             hits = self.identify(req.tenant_id, req.landmarks, req.k)
         elif req.hash is not None:
@@ -405,7 +576,7 @@ class GpuIndex:
     def flush(self) -> None:
         if self._sidecar is not None:
             self._sidecar.sync()
-        for ix in list(self._cos.values()) + list(self._ham.values()) + ([self._lm] if self._lm is not None else []):
+        for ix in self._all():
             ix.flush()
 
 

@@ -19,8 +19,6 @@
 #include "common.h"
 
 namespace ucfp {
-int capi_fail(int code, const char* fmt, ...);
-int ctx_device(const ucfp_ctx* ctx);
 int image_hash_ordered(ucfp_ctx* ctx, uint32_t algo, const uint8_t* frames, size_t n, uint32_t w, uint32_t h,
                        size_t row_stride, size_t frame_stride, int pixfmt, uint32_t min_dim, uint32_t max_dim,
                        const uint8_t* exact, uint8_t* out, int32_t* status, hipStream_t stream);

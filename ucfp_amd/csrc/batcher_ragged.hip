@@ -17,10 +17,6 @@
 #include "batch_core.h"
 #include "common.h"
 
-namespace ucfp {
-int capi_fail(int code, const char* fmt, ...);
-int ctx_device(const ucfp_ctx* ctx);
-}  // namespace ucfp
 using ucfp::capi_fail;
 
 namespace {

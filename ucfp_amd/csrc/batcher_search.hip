@@ -20,7 +20,6 @@
 #include "common.h"
 
 namespace ucfp {
-int capi_fail(int code, const char* fmt, ...);
 int index_kind(const ucfp_index* ix);
 int index_device(const ucfp_index* ix);
 uint32_t index_dim(const ucfp_index* ix);

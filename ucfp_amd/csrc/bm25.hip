@@ -12,7 +12,10 @@
 // Layout of a tenant after a (lazy) rebuild: postings u64 [P] (ordinal | tf << 32) sorted by (key, ordinal) -- one run
 // P_j per distinct key -- with the distinct keys u64 [U], their run starts u32 [U + 1], a directory dir[b] = first
 // distinct key with key >> shift >= b (shift puts the largest key in 18 bits), the id of each ordinal and norm per
-// ordinal.  Ordinals follow ascending record id, so (score desc, ordinal asc) is the spec's (score desc, id asc).
+// ordinal.  Ordinals follow ascending record id, so (score desc, ordinal asc) is the spec's (score desc, id asc).  The
+// rebuild is postings.h's: rocPRIM's stable radix sort of (key, ordinal | tf << 32), the compaction post_count /
+// post_scan_tiles / post_compact with BmHead (a key's first posting) and BmEmit (ukeys, ustart), post_directory on
+// key >> shift; bm_norm computes norm.
 //
 // Query (one launch sequence for a ragged batch of key lists):
 //   bm_lookup    one thread per query key: its run (start, df)
@@ -21,8 +24,8 @@
 //                added in order with a barrier between them (within one term an ordinal occurs once: no atomic add);
 //                then a bitonic sort of the packed candidates (~bits(score) << 32 | ordinal) in LDS
 //   bm_range     larger V: block (r, q) owns ordinals [r R, (r + 1) R) of query q and keeps their scores dense in LDS,
-//                walking the terms in order with a binary search into each P_j; a running top-k of the range goes to
-//                a parts buffer (k u64 candidate keys per range)
+//                walking the terms in order with a binary search into each P_j; a running top-k of the range
+//                (topk_offer) goes to a parts buffer (k u64 candidate keys per range)
 //   bm_merge     one block per large query: running top-k over its parts
 //   bm_explain   optional: tf and the contribution of every (hit, position), by binary search in P_j
 // Scores are >= 0, so ~bits(score) is monotone decreasing in the score and a zero score still sorts before the empty
@@ -30,85 +33,27 @@
 
 #include <hip/hip_runtime.h>
 
-#include <cstring>  // rocPRIM's texture iterator calls the host memset without including it
-
-#include <rocprim/rocprim.hpp>
-
 #include <algorithm>
 #include <cmath>
 #include <map>
-#include <mutex>
-#include <new>
 #include <unordered_map>
 #include <vector>
 
-#include "../../include/ucfp_hip.h"
-#include "common.h"
-
-namespace ucfp {
-int capi_fail(int code, const char* fmt, ...);
-int ctx_device(const ucfp_ctx* ctx);
-}  // namespace ucfp
-using ucfp::capi_fail;
-
-#define HIP_TRY(expr)                                                                           \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess)                                                                   \
-            return capi_fail(UCFP_E_INDEX, "%s failed: %s", #expr, hipGetErrorString(e_));      \
-    } while (0)
+#include "postings.h"
 
 namespace {
 
 constexpr float K1 = 1.2f;
 constexpr float B = 0.75f;
-constexpr int kThreads = 256;
 constexpr uint32_t kDirBits = 18;
 constexpr uint32_t kSlots = 8192;                   // bm_small LDS table: 64 KiB of (ordinal, score)
 constexpr uint32_t kSlotsPerThread = kSlots / kThreads;
 constexpr uint64_t kLdsPostings = UCFP_BM25_LDS_POSTINGS;   // at most 75 % load; a query with more takes bm_range
 constexpr uint32_t kRange = 8192;                   // bm_range: ordinals per block (32 KiB of scores)
-constexpr uint64_t kEmpty64 = ~0ull;
-constexpr uint32_t kEmpty32 = 0xffffffffu;
-constexpr uint32_t kCompactTile = 1024;
 constexpr uint32_t kSmall = 0xffffffffu;            // path[q] of a query on bm_small
 constexpr size_t kPartsBudget = (size_t)32 << 20;   // bm_range candidates per launch (256 MiB of u64)
 
 static_assert(kLdsPostings * 4 <= (uint64_t)kSlots * 3, "bm_small needs a free slot for every posting");
-
-// ---------------------------------------------------------------- block helpers (256 threads)
-
-__device__ __forceinline__ uint64_t block_scan_incl(uint64_t v, uint64_t* s_w) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint64_t t = __shfl_up(v, o, 64);
-        if (lane >= o) v += t;
-    }
-    if (lane == 63) s_w[w] = v;
-    __syncthreads();
-    uint64_t add = 0;
-    for (int i = 0; i < w; i++) add += s_w[i];
-    __syncthreads();
-    return v + add;
-}
-
-// ascending bitonic sort of n (a power of two) keys; ends with a barrier
-__device__ void bitonic_sort(uint64_t* s_key, uint32_t n) {
-    for (uint32_t k2 = 2; k2 <= n; k2 <<= 1)
-        for (uint32_t j = k2 >> 1; j > 0; j >>= 1) {
-            for (uint32_t i = threadIdx.x; i < n; i += kThreads) {
-                const uint32_t p = i ^ j;
-                if (p > i) {
-                    const uint64_t a = s_key[i], b = s_key[p];
-                    if ((a > b) == ((i & k2) == 0)) {
-                        s_key[i] = b;
-                        s_key[p] = a;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-}
 
 __device__ __forceinline__ uint64_t cand_key(float score, uint32_t ord) {
     return ((uint64_t)(~__float_as_uint(score)) << 32) | ord;
@@ -120,17 +65,6 @@ __host__ __device__ __forceinline__ float contribution(float idf, uint32_t tf, f
     const float den = ftf + norm;
     const float num = idf * (ftf * (K1 + 1.0f));
     return num / fmaxf(den, 1e-6f);
-}
-
-// [0, k) of s_top holds the best k so far (k <= 128 < 256); a chunk of 256 candidates goes to [256, 512) and the 512
-// are sorted when one of them beats the current k-th
-__device__ __forceinline__ void topk_offer(uint64_t* s_top, uint32_t k, uint64_t key) {
-    const bool better = key < s_top[k - 1];
-    if (__syncthreads_or(better)) {
-        s_top[kThreads + threadIdx.x] = key;
-        __syncthreads();
-        bitonic_sort(s_top, 2 * kThreads);
-    }
 }
 
 // s_key[0, n) sorted ascending (entries past n are not read); one block writes query q's first k
@@ -162,74 +96,22 @@ __device__ __forceinline__ uint32_t lower_ord(const uint64_t* __restrict__ post,
 
 // ---------------------------------------------------------------- rebuild
 
-__global__ void bm_start_count(const uint64_t* __restrict__ keys, size_t n, uint32_t* __restrict__ block_counts) {
-    const size_t base = (size_t)blockIdx.x * kCompactTile;
-    uint32_t c = 0;
-    for (uint32_t j = threadIdx.x; j < kCompactTile; j += kThreads) {
-        const size_t i = base + j;
-        if (i < n) c += (i == 0 || keys[i] != keys[i - 1]) ? 1u : 0u;
-    }
-    __shared__ uint64_t s_w[4];
-    const uint64_t tot = block_scan_incl(c, s_w);
-    if (threadIdx.x == kThreads - 1) block_counts[blockIdx.x] = (uint32_t)tot;
-}
+// postings sorted by (key, ordinal): a head is the start of a key's run
+struct BmHead {
+    const uint64_t* keys;
+    __device__ bool operator()(size_t i) const { return i == 0 || keys[i] != keys[i - 1]; }
+};
 
-// exclusive scan of nb block counts (one block); out[nb] = total
-__global__ void bm_scan_blocks(const uint32_t* __restrict__ counts, size_t nb, uint64_t* __restrict__ out) {
-    __shared__ uint64_t s_w[4];
-    __shared__ uint64_t s_tot;
-    uint64_t carry = 0;
-    for (size_t base = 0; base < nb; base += kThreads) {
-        const size_t i = base + threadIdx.x;
-        const uint64_t v = i < nb ? counts[i] : 0;
-        const uint64_t inc = block_scan_incl(v, s_w);
-        if (i < nb) out[i] = carry + inc - v;
-        if (threadIdx.x == kThreads - 1) s_tot = inc;
-        __syncthreads();
-        carry += s_tot;
-        __syncthreads();
+// the distinct keys and where their runs start
+struct BmEmit {
+    const uint64_t* keys;
+    uint64_t* ukeys;
+    uint32_t* ustart;
+    __device__ void operator()(size_t i, uint64_t o) const {
+        ukeys[o] = keys[i];
+        ustart[o] = (uint32_t)i;
     }
-    if (threadIdx.x == 0) out[nb] = carry;
-}
-
-// the distinct keys and where their runs start; ustart[U] = n
-__global__ void bm_compact(const uint64_t* __restrict__ keys, size_t n, const uint64_t* __restrict__ block_off,
-                           uint64_t* __restrict__ ukeys, uint32_t* __restrict__ ustart) {
-    __shared__ uint64_t s_w[4];
-    const size_t base = (size_t)blockIdx.x * kCompactTile;
-    constexpr uint32_t kPer = kCompactTile / kThreads;
-    bool start[kPer];
-    uint32_t c = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < kPer; j++) {
-        const size_t i = base + threadIdx.x * kPer + j;
-        start[j] = i < n && (i == 0 || keys[i] != keys[i - 1]);
-        c += start[j] ? 1u : 0u;
-    }
-    uint64_t o = block_off[blockIdx.x] + block_scan_incl(c, s_w) - c;
-#pragma unroll
-    for (uint32_t j = 0; j < kPer; j++) {
-        const size_t i = base + threadIdx.x * kPer + j;
-        if (start[j]) {
-            ukeys[o] = keys[i];
-            ustart[o] = (uint32_t)i;
-            o++;
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) ustart[block_off[gridDim.x]] = (uint32_t)n;
-}
-
-// dir[b] = first distinct key with key >> shift >= b, for b in [0, nb]
-__global__ void bm_directory(const uint64_t* __restrict__ ukeys, size_t u, uint32_t shift, uint32_t nb,
-                             uint32_t* __restrict__ dir) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= u) return;
-    const uint32_t b = (uint32_t)(ukeys[i] >> shift);
-    const uint32_t from = i == 0 ? 0u : (uint32_t)(ukeys[i - 1] >> shift) + 1u;
-    for (uint32_t x = from; x <= b; x++) dir[x] = (uint32_t)i;
-    if (i + 1 == u)
-        for (uint32_t x = b + 1; x <= nb; x++) dir[x] = (uint32_t)u;
-}
+};
 
 __global__ void bm_norm(const uint32_t* __restrict__ dl, size_t n, float avgdl, float* __restrict__ norm) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -428,27 +310,6 @@ __global__ void bm_empty(size_t nq, uint32_t k, uint64_t* __restrict__ out_ids, 
     if (i < nq) out_n[i] = 0;
 }
 
-struct DevArr {
-    void* p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t bytes) {
-        if (p && cap >= bytes) return 0;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        HIP_TRY(hipMalloc(&p, bytes + 256));
-        cap = bytes + 256;
-        return 0;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-    template <class T>
-    T* as() const { return reinterpret_cast<T*>(p); }
-};
-
 struct Doc {
     std::vector<uint64_t> keys;
     std::vector<uint32_t> tfs;
@@ -467,12 +328,7 @@ struct Tenant {
 
 }  // namespace
 
-struct ucfp_bm25_index {
-    ucfp_ctx* ctx = nullptr;
-    int device = 0;
-    std::mutex mu;
-    hipStream_t own = nullptr;
-    hipEvent_t done = nullptr;   // the previous call's last work: the workspace is free after it
+struct ucfp_bm25_index : ucfp::IndexCore {
     std::unordered_map<uint32_t, Tenant> tenants;
     // rebuild workspace
     DevArr b_keys_a, b_keys_b, b_vals_a, b_dl, b_cnt, b_off, b_tmp;
@@ -570,40 +426,23 @@ int rebuild(ucfp_bm25_index* ix, Tenant& T, hipStream_t st) {
     }
     size_t u = 0;
     if (n) {
-        const size_t nb = (n + kCompactTile - 1) / kCompactTile;
-        if ((rc = ix->b_keys_a.ensure(n * 8)) || (rc = ix->b_keys_b.ensure(n * 8)) || (rc = ix->b_vals_a.ensure(n * 8)) ||
-            (rc = ix->b_cnt.ensure(nb * 4)) || (rc = ix->b_off.ensure((nb + 1) * 8)))
+        if ((rc = ix->b_keys_a.ensure(n * 8)) || (rc = ix->b_keys_b.ensure(n * 8)) || (rc = ix->b_vals_a.ensure(n * 8)))
             return rc;
         HIP_TRY(hipMemcpyAsync(ix->b_keys_a.p, h_keys.data(), n * 8, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(ix->b_vals_a.p, h_vals.data(), n * 8, hipMemcpyHostToDevice, st));
-        size_t tmp = 0;
-        const int end_bit = bits ? (int)bits : 1;
-        HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp, ix->b_keys_a.as<uint64_t>(), ix->b_keys_b.as<uint64_t>(),
-                                          ix->b_vals_a.as<uint64_t>(), T.post.as<uint64_t>(), n, 0, end_bit, st));
-        if ((rc = ix->b_tmp.ensure(tmp))) return rc;
         // stable: the documents of one key keep ascending ordinals
-        HIP_TRY(rocprim::radix_sort_pairs(ix->b_tmp.p, tmp, ix->b_keys_a.as<uint64_t>(), ix->b_keys_b.as<uint64_t>(),
-                                          ix->b_vals_a.as<uint64_t>(), T.post.as<uint64_t>(), n, 0, end_bit, st));
-        hipLaunchKernelGGL(bm_start_count, dim3((unsigned)nb), dim3(kThreads), 0, st, ix->b_keys_b.as<uint64_t>(), n,
-                           ix->b_cnt.as<uint32_t>());
-        hipLaunchKernelGGL(bm_scan_blocks, dim3(1), dim3(kThreads), 0, st, ix->b_cnt.as<uint32_t>(), nb,
-                           ix->b_off.as<uint64_t>());
-        HIP_TRY(hipGetLastError());
-        uint64_t total = 0;
-        HIP_TRY(hipMemcpyAsync(&total, ix->b_off.as<uint64_t>() + nb, 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        u = (size_t)total;
-        if ((rc = T.ukeys.ensure(u * 8)) || (rc = T.ustart.ensure((u + 1) * 4))) return rc;
-        hipLaunchKernelGGL(bm_compact, dim3((unsigned)nb), dim3(kThreads), 0, st, ix->b_keys_b.as<uint64_t>(), n,
-                           ix->b_off.as<uint64_t>(), T.ukeys.as<uint64_t>(), T.ustart.as<uint32_t>());
-        hipLaunchKernelGGL(bm_directory, dim3((unsigned)((u + 255) / 256)), dim3(256), 0, st, T.ukeys.as<uint64_t>(), u,
-                           T.shift, T.nb, T.dir.as<uint32_t>());
-        HIP_TRY(hipGetLastError());
-    } else {
-        if ((rc = T.ukeys.ensure(0)) || (rc = T.ustart.ensure(4))) return rc;
-        HIP_TRY(hipMemsetAsync(T.ustart.p, 0, 4, st));
-        HIP_TRY(hipMemsetAsync(T.dir.p, 0, ((size_t)T.nb + 1) * 4, st));
+        uint64_t* keys = ix->b_keys_b.as<uint64_t>();
+        if ((rc = sort_pairs(ix->b_tmp, ix->b_keys_a.as<uint64_t>(), keys, ix->b_vals_a.as<uint64_t>(), T.post.as<uint64_t>(),
+                             n, bits ? (int)bits : 1, st)) ||
+            (rc = count_heads(BmHead{keys}, n, ix->b_cnt, ix->b_off, st, &u)) || (rc = T.ukeys.ensure(u * 8)) ||
+            (rc = T.ustart.ensure((u + 1) * 4)) ||
+            (rc = compact_heads(BmHead{keys}, BmEmit{keys, T.ukeys.as<uint64_t>(), T.ustart.as<uint32_t>()}, n, ix->b_off, st)))
+            return rc;
+    } else if ((rc = T.ukeys.ensure(0)) || (rc = T.ustart.ensure(4))) {
+        return rc;
     }
+    HIP_TRY(hipMemsetD32Async(T.ustart.as<uint32_t>() + u, (int)n, 1, st));   // ustart[U] = n
+    if ((rc = build_directory(T.ukeys.as<uint64_t>(), u, T.shift, T.nb, T.dir.as<uint32_t>(), st))) return rc;
     HIP_TRY(hipStreamSynchronize(st));   // the host vectors above go out of scope
     T.n_keys = u;
     T.dirty = false;
@@ -736,27 +575,12 @@ int ucfp_bm25_index_create(ucfp_ctx* ctx, uint32_t flags, ucfp_bm25_index** out)
     if (!ctx || !out) return capi_fail(UCFP_E_INVALID, "ctx/out is NULL");
     *out = nullptr;
     if (flags != 0) return capi_fail(UCFP_E_INVALID, "no BM25 index flags are defined (got %u)", flags);
-    ucfp_bm25_index* ix = new (std::nothrow) ucfp_bm25_index();
-    if (!ix) return capi_fail(UCFP_E_INDEX, "out of host memory");
-    ix->ctx = ctx;
-    ix->device = ucfp::ctx_device(ctx);
-    hipError_t e = hipSetDevice(ix->device);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&ix->own, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&ix->done, hipEventDisableTiming);
-    if (e != hipSuccess) {
-        if (ix->own) (void)hipStreamDestroy(ix->own);
-        delete ix;
-        return capi_fail(UCFP_E_INDEX, "BM25 index setup failed: %s", hipGetErrorString(e));
-    }
-    HIP_TRY(hipEventRecord(ix->done, ix->own));
-    *out = ix;
-    return UCFP_OK;
+    return ucfp::create_index(ctx, "BM25 index", out);
 }
 
 void ucfp_bm25_index_destroy(ucfp_bm25_index* ix) {
     if (!ix) return;
-    (void)hipSetDevice(ix->device);
-    (void)hipDeviceSynchronize();
+    ix->quiesce();
     for (auto& kv : ix->tenants)
         for (DevArr* a : {&kv.second.post, &kv.second.ukeys, &kv.second.ustart, &kv.second.dir, &kv.second.ids,
                           &kv.second.norm})
@@ -765,8 +589,6 @@ void ucfp_bm25_index_destroy(ucfp_bm25_index* ix) {
                       &ix->b_tmp, &ix->q_keys, &ix->q_off, &ix->q_lo, &ix->q_df, &ix->q_idf, &ix->q_path, &ix->q_lq,
                       &ix->q_parts, &ix->q_hord, &ix->q_out})
         a->release();
-    (void)hipEventDestroy(ix->done);
-    (void)hipStreamDestroy(ix->own);
     delete ix;
 }
 
@@ -790,9 +612,8 @@ int ucfp_bm25_index_upsert_dev(ucfp_bm25_index* ix, uint32_t tenant, const uint6
     HIP_TRY(hipMemcpyAsync(ids.data(), d_ids, n * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(offs.data(), d_offsets, (n + 1) * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    if (offs[0] != 0) return capi_fail(UCFP_E_INVALID, "offsets[0] must be 0");
-    for (size_t i = 0; i < n; i++)
-        if (offs[i + 1] < offs[i]) return capi_fail(UCFP_E_INVALID, "offsets decrease at %zu", i);
+    int rc = check_offsets(offs, n);
+    if (rc) return rc;
     const size_t m = offs[n];
     std::vector<uint64_t> keys(m);
     std::vector<uint32_t> tfs(m);
@@ -836,20 +657,7 @@ int ucfp_bm25_index_size(ucfp_bm25_index* ix, uint32_t tenant, size_t* docs, siz
     return UCFP_OK;
 }
 
-int ucfp_bm25_index_flush(ucfp_bm25_index* ix) {
-    if (!ix) return capi_fail(UCFP_E_INVALID, "index is NULL");
-    std::lock_guard<std::mutex> lk(ix->mu);
-    HIP_TRY(hipSetDevice(ix->device));
-    HIP_TRY(hipEventSynchronize(ix->done));
-    for (auto& kv : ix->tenants)
-        if (kv.second.dirty) {
-            int rc = rebuild(ix, kv.second, ix->own);
-            if (rc) return rc;
-        }
-    HIP_TRY(hipStreamSynchronize(ix->own));
-    HIP_TRY(hipEventRecord(ix->done, ix->own));
-    return UCFP_OK;
-}
+int ucfp_bm25_index_flush(ucfp_bm25_index* ix) { return ucfp::flush_dirty(ix, rebuild); }
 
 int ucfp_bm25_index_query_dev(ucfp_bm25_index* ix, uint32_t tenant, const uint64_t* d_keys, const uint64_t* d_offsets,
                               size_t nq, uint32_t k, uint64_t* d_out_ids, float* d_out_scores, uint32_t* d_out_n,
@@ -857,17 +665,15 @@ int ucfp_bm25_index_query_dev(ucfp_bm25_index* ix, uint32_t tenant, const uint64
     int rc = query_args(ix, d_offsets, nq, k, d_out_ids, d_out_scores, d_out_n);
     if (rc || nq == 0) return rc;
     std::lock_guard<std::mutex> lk(ix->mu);
-    HIP_TRY(hipSetDevice(ix->device));
+    if ((rc = ix->begin())) return rc;
     hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(hipEventSynchronize(ix->done));   // the workspace is shared by every call
     ix->h_off.resize(nq + 1);
     HIP_TRY(hipMemcpyAsync(ix->h_off.data(), d_offsets, (nq + 1) * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if ((rc = check_offsets(ix->h_off, nq))) return rc;
     rc = query_impl(ix, tenant, d_keys, d_offsets, nq, k, d_out_ids, d_out_scores, d_out_n, d_out_idf, d_out_tf,
                     d_out_contrib, st);
-    HIP_TRY(hipEventRecord(ix->done, st));
-    return rc;
+    return ix->end(st, rc);
 }
 
 int ucfp_bm25_index_query(ucfp_bm25_index* ix, uint32_t tenant, const uint64_t* keys, const uint64_t* offsets, size_t nq,
@@ -880,9 +686,8 @@ int ucfp_bm25_index_query(ucfp_bm25_index* ix, uint32_t tenant, const uint64_t* 
     if ((rc = check_offsets(ix->h_off, nq))) return rc;
     const size_t total = offsets[nq], nk = nq * k;
     if (total && !keys) return capi_fail(UCFP_E_INVALID, "keys is NULL");
-    HIP_TRY(hipSetDevice(ix->device));
+    if ((rc = ix->begin())) return rc;
     hipStream_t st = ix->own;
-    HIP_TRY(hipEventSynchronize(ix->done));
     // outputs: ids [nk] u64, scores [nk], n [nq], idf [total], tf [total k], contributions [total k]
     const size_t o_sc = nk * 8, o_n = o_sc + nk * 4, o_idf = o_n + nq * 4, o_tf = o_idf + total * 4,
                  o_c = o_tf + total * k * 4, o_end = o_c + total * k * 4;
@@ -894,11 +699,7 @@ int ucfp_bm25_index_query(ucfp_bm25_index* ix, uint32_t tenant, const uint64_t* 
     rc = query_impl(ix, tenant, ix->q_keys.as<uint64_t>(), ix->q_off.as<uint64_t>(), nq, k, (uint64_t*)ob,
                     (float*)(ob + o_sc), (uint32_t*)(ob + o_n), out_idf ? (float*)(ob + o_idf) : nullptr,
                     out_tf ? (uint32_t*)(ob + o_tf) : nullptr, out_contrib ? (float*)(ob + o_c) : nullptr, st);
-    if (rc) {
-        (void)hipStreamSynchronize(st);
-        (void)hipEventRecord(ix->done, st);
-        return rc;
-    }
+    if (rc) return ix->end_sync(rc);
     if (nk) {
         HIP_TRY(hipMemcpyAsync(out_ids, ob, nk * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(out_scores, ob + o_sc, nk * 4, hipMemcpyDeviceToHost, st));
@@ -907,9 +708,7 @@ int ucfp_bm25_index_query(ucfp_bm25_index* ix, uint32_t tenant, const uint64_t* 
     if (total && out_idf) HIP_TRY(hipMemcpyAsync(out_idf, ob + o_idf, total * 4, hipMemcpyDeviceToHost, st));
     if (total && nk && out_tf) HIP_TRY(hipMemcpyAsync(out_tf, ob + o_tf, total * k * 4, hipMemcpyDeviceToHost, st));
     if (total && nk && out_contrib) HIP_TRY(hipMemcpyAsync(out_contrib, ob + o_c, total * k * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipEventRecord(ix->done, st));
-    return UCFP_OK;
+    return ix->end_sync(UCFP_OK);
 }
 
 }  // extern "C"

@@ -4,7 +4,48 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "../../include/ucfp_hip.h"
+
 namespace ucfp {
+
+// capi.hip: sets the thread's last error message and returns `code`
+int capi_fail(int code, const char* fmt, ...);
+int ctx_device(const ucfp_ctx* ctx);
+
+}  // namespace ucfp
+
+// returns UCFP_E_INDEX from the enclosing function when a HIP call fails
+#define HIP_TRY(expr)                                                                                \
+    do {                                                                                             \
+        hipError_t e_ = (expr);                                                                      \
+        if (e_ != hipSuccess)                                                                        \
+            return ucfp::capi_fail(UCFP_E_INDEX, "%s failed: %s", #expr, hipGetErrorString(e_));     \
+    } while (0)
+
+namespace ucfp {
+
+// A device buffer that only grows (contents are not kept).  A zero-byte ensure still allocates, so a pointer handed to a
+// kernel is never null.
+struct DevArr {
+    void* p = nullptr;
+    size_t cap = 0;
+    int ensure(size_t bytes) {
+        if (p && cap >= bytes) return 0;
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+        HIP_TRY(hipMalloc(&p, bytes + 256));
+        cap = bytes + 256;
+        return 0;
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    template <class T>
+    T* as() const { return reinterpret_cast<T*>(p); }
+};
 
 // Intra-wave LDS hand-off: the DS unit executes one wave's LDS instructions in issue order, so a
 // later read sees an earlier write of another lane; what is needed is that the COMPILER keeps the

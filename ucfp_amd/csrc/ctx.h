@@ -5,17 +5,7 @@
 #include <mutex>
 
 #include "../../include/ucfp_hip.h"
-
-namespace ucfp {
-int capi_fail(int code, const char* fmt, ...);
-}
-
-#define HIP_TRY(expr)                                                                                \
-    do {                                                                                             \
-        hipError_t e_ = (expr);                                                                      \
-        if (e_ != hipSuccess)                                                                        \
-            return ucfp::capi_fail(UCFP_E_INDEX, "%s failed: %s", #expr, hipGetErrorString(e_));     \
-    } while (0)
+#include "common.h"
 
 struct ucfp_ctx {
     int device = 0;

@@ -24,19 +24,7 @@
 #include "../../include/ucfp_hip.h"
 #include "common.h"
 
-namespace ucfp {
-int capi_fail(int code, const char* fmt, ...);  // capi.hip
-int ctx_device(const ucfp_ctx* ctx);            // capi.hip
-}  // namespace ucfp
-
 using ucfp::capi_fail;
-
-#define HIP_TRY(expr)                                                                           \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess)                                                                   \
-            return capi_fail(UCFP_E_INDEX, "%s failed: %s", #expr, hipGetErrorString(e_));      \
-    } while (0)
 
 namespace {
 

@@ -12,7 +12,9 @@
 // Layout of a tenant after a (lazy) rebuild: postings sorted by (hash, t, ordinal), deduplicated, as two arrays --
 // hashes u32 [P] and entries u64 [P] (ordinal | t << 32) -- plus a directory dir[b] = first posting whose hash >> 14
 // is >= b (b < 2^18 + 1: the f_a|f_b bits) and the id of each ordinal.  Ordinals follow ascending record id, so the
-// (votes desc, ordinal asc) order is the (votes desc, id asc) order of the spec.
+// (votes desc, ordinal asc) order is the (votes desc, id asc) order of the spec.  The rebuild is postings.h's: rocPRIM's
+// stable radix sort of (hash << 32 | t, ordinal), the compaction post_count / post_scan_tiles / post_compact with
+// LmHead (a new (key, ordinal) pair) and LmEmit (hashes, entries), and post_directory on hash >> 14.
 //
 // Query (one launch sequence for a ragged batch):
 //   lm_qprep / lm_qkeys   check the offsets and t < 2^31, pack keys = hash << 32 | t
@@ -28,89 +30,27 @@
 //   spill path            rocPRIM segmented sort of the spilled votes; lm_spill_best: every run end of equal
 //                         (ordinal, offset) keys takes its count from a binary search for the run start and folds
 //                         (count, -offset) into a dense per-(query, ordinal) best with atomicMax; lm_spill_topk scans
-//                         that row 256 ordinals at a time and merges candidates into an LDS top-k by bitonic sort.
+//                         that row 256 ordinals at a time and merges candidates into an LDS top-k (topk_offer).
 // The host reads two small arrays per query batch (the checked sizes, then V per query) to size the sort and the
 // spill buffers; everything else is asynchronous.
 
 #include <hip/hip_runtime.h>
 
-#include <cstring>  // rocPRIM's texture iterator calls the host memset without including it
-
-#include <rocprim/rocprim.hpp>
-
 #include <map>
-#include <mutex>
-#include <new>
 #include <unordered_map>
 #include <vector>
 
-#include "../../include/ucfp_hip.h"
-#include "common.h"
-
-namespace ucfp {
-int capi_fail(int code, const char* fmt, ...);
-int ctx_device(const ucfp_ctx* ctx);
-}  // namespace ucfp
-using ucfp::capi_fail;
-
-#define HIP_TRY(expr)                                                                           \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess)                                                                   \
-            return capi_fail(UCFP_E_INDEX, "%s failed: %s", #expr, hipGetErrorString(e_));      \
-    } while (0)
+#include "postings.h"
 
 namespace {
 
-constexpr int kThreads = 256;
 constexpr uint32_t kDirBits = 14;                  // hash >> 14 = f_a | f_b
 constexpr uint32_t kDirSize = 1u << 18;
 constexpr uint32_t kSlots = 4096;                  // LDS vote table (48 KiB with the counts)
 constexpr uint32_t kSlotsPerThread = kSlots / kThreads;
 constexpr uint64_t kLdsVotes = 3072;               // at most 75 % load: a query with more votes spills
-constexpr uint64_t kEmpty64 = ~0ull;
-constexpr uint32_t kEmpty32 = 0xffffffffu;
 constexpr uint32_t kBias = 0x80000000u;            // offset d stored as d + 2^31 (monotone in d)
 constexpr uint64_t kNoSpill = ~0ull;
-constexpr uint32_t kCompactTile = 1024;            // rebuild compaction: elements per block
-
-// ---------------------------------------------------------------- block helpers (256 threads)
-
-__device__ __forceinline__ uint64_t block_scan_incl(uint64_t v, uint64_t* s_w) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint64_t t = __shfl_up(v, o, 64);
-        if (lane >= o) v += t;
-    }
-    if (lane == 63) s_w[w] = v;
-    __syncthreads();
-    uint64_t add = 0;
-    for (int i = 0; i < w; i++) add += s_w[i];
-    __syncthreads();   // s_w may be reused by the next call
-    return v + add;
-}
-
-// ascending bitonic sort of n (a power of two) keys with a u32 payload; ends with a barrier
-__device__ void bitonic_sort(uint64_t* s_key, uint32_t* s_val, uint32_t n) {
-    for (uint32_t k2 = 2; k2 <= n; k2 <<= 1)
-        for (uint32_t j = k2 >> 1; j > 0; j >>= 1) {
-            for (uint32_t i = threadIdx.x; i < n; i += kThreads) {
-                const uint32_t p = i ^ j;
-                if (p > i) {
-                    const uint64_t a = s_key[i], b = s_key[p];
-                    const bool asc = (i & k2) == 0;
-                    if ((a > b) == asc) {
-                        s_key[i] = b;
-                        s_key[p] = a;
-                        const uint32_t t = s_val[i];
-                        s_val[i] = s_val[p];
-                        s_val[p] = t;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-}
 
 // candidate sort key: (votes desc, ordinal asc); kEmpty64 sorts last
 __device__ __forceinline__ uint64_t cand_key(uint32_t votes, uint32_t ord) {
@@ -164,75 +104,24 @@ __device__ __forceinline__ void find_run(const uint32_t* __restrict__ hashes, co
 
 // ---------------------------------------------------------------- rebuild
 
-__global__ void lm_keep_count(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ ords, size_t n,
-                              uint32_t* __restrict__ block_counts) {
-    const size_t base = (size_t)blockIdx.x * kCompactTile;
-    uint32_t c = 0;
-    for (uint32_t j = threadIdx.x; j < kCompactTile; j += kThreads) {
-        const size_t i = base + j;
-        if (i < n) c += (i == 0 || keys[i] != keys[i - 1] || ords[i] != ords[i - 1]) ? 1u : 0u;
-    }
-    __shared__ uint64_t s_w[4];
-    const uint64_t tot = block_scan_incl(c, s_w);
-    if (threadIdx.x == kThreads - 1) block_counts[blockIdx.x] = (uint32_t)tot;
-}
+// postings sorted by (hash, t, ordinal): a head is a new (key, ordinal) -- duplicates of one record are dropped
+struct LmHead {
+    const uint64_t* keys;
+    const uint32_t* ords;
+    __device__ bool operator()(size_t i) const { return i == 0 || keys[i] != keys[i - 1] || ords[i] != ords[i - 1]; }
+};
 
-// exclusive scan of nb block counts (one block); out[nb] = total
-__global__ void lm_scan_blocks(const uint32_t* __restrict__ counts, size_t nb, uint64_t* __restrict__ out) {
-    __shared__ uint64_t s_w[4];
-    __shared__ uint64_t s_tot;
-    uint64_t carry = 0;
-    for (size_t base = 0; base < nb; base += kThreads) {
-        const size_t i = base + threadIdx.x;
-        const uint64_t v = i < nb ? counts[i] : 0;
-        const uint64_t inc = block_scan_incl(v, s_w);
-        if (i < nb) out[i] = carry + inc - v;
-        if (threadIdx.x == kThreads - 1) s_tot = inc;
-        __syncthreads();
-        carry += s_tot;
-        __syncthreads();
+struct LmEmit {
+    const uint64_t* keys;
+    const uint32_t* ords;
+    uint32_t* hashes;
+    uint64_t* entries;
+    __device__ void operator()(size_t i, uint64_t o) const {
+        const uint64_t key = keys[i];
+        hashes[o] = (uint32_t)(key >> 32);
+        entries[o] = (uint64_t)ords[i] | ((key & 0xffffffffull) << 32);
     }
-    if (threadIdx.x == 0) out[nb] = carry;
-}
-
-__global__ void lm_compact(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ ords, size_t n,
-                           const uint64_t* __restrict__ block_off, uint32_t* __restrict__ hashes,
-                           uint64_t* __restrict__ entries) {
-    __shared__ uint64_t s_w[4];
-    const size_t base = (size_t)blockIdx.x * kCompactTile;
-    constexpr uint32_t kPer = kCompactTile / kThreads;
-    // thread t owns elements [t * kPer, (t + 1) * kPer) of the tile, so the output keeps the input order
-    bool keep[kPer];
-    uint32_t c = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < kPer; j++) {
-        const size_t i = base + threadIdx.x * kPer + j;
-        keep[j] = i < n && (i == 0 || keys[i] != keys[i - 1] || ords[i] != ords[i - 1]);
-        c += keep[j] ? 1u : 0u;
-    }
-    uint64_t o = block_off[blockIdx.x] + block_scan_incl(c, s_w) - c;
-#pragma unroll
-    for (uint32_t j = 0; j < kPer; j++) {
-        const size_t i = base + threadIdx.x * kPer + j;
-        if (keep[j]) {
-            const uint64_t key = keys[i];
-            hashes[o] = (uint32_t)(key >> 32);
-            entries[o] = (uint64_t)ords[i] | ((key & 0xffffffffull) << 32);
-            o++;
-        }
-    }
-}
-
-// dir[b] = first posting with hash >> 14 >= b, for b in [0, 2^18]
-__global__ void lm_directory(const uint32_t* __restrict__ hashes, size_t p, uint32_t* __restrict__ dir) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= p) return;
-    const uint32_t b = hashes[i] >> kDirBits;
-    const uint32_t from = i == 0 ? 0u : (hashes[i - 1] >> kDirBits) + 1u;
-    for (uint32_t x = from; x <= b; x++) dir[x] = (uint32_t)i;
-    if (i + 1 == p)
-        for (uint32_t x = b + 1; x <= kDirSize; x++) dir[x] = (uint32_t)p;
-}
+};
 
 // ---------------------------------------------------------------- query
 
@@ -426,7 +315,7 @@ __global__ __launch_bounds__(kThreads) void lm_vote(const uint64_t* __restrict__
     while (n < nc) n <<= 1;
     for (uint32_t i = nc + threadIdx.x; i < n; i += kThreads) s_key[i] = kEmpty64;
     __syncthreads();
-    bitonic_sort(s_key, s_db, n);
+    bitonic_sort(s_key, n, s_db);
     write_hits(s_key, s_db, n, q, k, qn[q], ids, out_ids, out_votes, out_offsets, out_scores, out_n);
 }
 
@@ -466,19 +355,11 @@ __global__ __launch_bounds__(kThreads) void lm_spill_topk(const uint64_t* __rest
         s_db[i] = 0;
     }
     __syncthreads();
-    // [0, k) holds the best so far (k <= 128 < 256); a chunk's candidates go to [256, 512) and are merged by a sort
     for (uint32_t b = 0; b < n_ord; b += kThreads) {
         const uint32_t o = b + threadIdx.x;
         const uint64_t v = o < n_ord ? row[o] : 0;
         const uint32_t cnt = (uint32_t)(v >> 32);
-        const uint64_t ck = cnt >= minv ? cand_key(cnt, o) : kEmpty64;
-        const bool better = ck < s_key[k - 1];
-        if (__syncthreads_or(better)) {
-            s_key[kThreads + threadIdx.x] = ck;
-            s_db[kThreads + threadIdx.x] = 0xffffffffu - (uint32_t)v;
-            __syncthreads();
-            bitonic_sort(s_key, s_db, 2 * kThreads);
-        }
+        topk_offer(s_key, k, cnt >= minv ? cand_key(cnt, o) : kEmpty64, s_db, 0xffffffffu - (uint32_t)v);
     }
     const uint32_t q = spill_q[s];
     write_hits(s_key, s_db, k, q, k, qn[q], ids, out_ids, out_votes, out_offsets, out_scores, out_n);
@@ -497,27 +378,6 @@ __global__ void lm_empty(size_t nq, uint32_t k, uint64_t* __restrict__ out_ids, 
     if (i < nq) out_n[i] = 0;
 }
 
-struct DevArr {
-    void* p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t bytes) {
-        if (p && cap >= bytes) return 0;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        HIP_TRY(hipMalloc(&p, bytes + 256));
-        cap = bytes + 256;
-        return 0;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-    template <class T>
-    T* as() const { return reinterpret_cast<T*>(p); }
-};
-
 struct Tenant {
     std::map<uint64_t, std::vector<uint64_t>> recs;   // id -> landmarks as hash << 32 | t (ascending id = ordinal order)
     bool dirty = true;
@@ -527,13 +387,8 @@ struct Tenant {
 
 }  // namespace
 
-struct ucfp_landmark_index {
-    ucfp_ctx* ctx = nullptr;
-    int device = 0;
+struct ucfp_landmark_index : ucfp::IndexCore {
     uint32_t max_postings = 0;
-    std::mutex mu;
-    hipStream_t own = nullptr;
-    hipEvent_t done = nullptr;       // the previous call's last work: the workspace is free after it
     std::unordered_map<uint32_t, Tenant> tenants;
     // rebuild workspace
     DevArr b_keys_a, b_keys_b, b_ords_a, b_ords_b, b_cnt, b_off, b_tmp;
@@ -585,39 +440,25 @@ int rebuild(ucfp_landmark_index* ix, Tenant& T, hipStream_t st) {
     if (!h_ids.empty()) HIP_TRY(hipMemcpyAsync(T.ids.p, h_ids.data(), h_ids.size() * 8, hipMemcpyHostToDevice, st));
     size_t p = 0;
     if (n) {
-        const size_t nb = (n + kCompactTile - 1) / kCompactTile;
         if ((rc = ix->b_keys_a.ensure(n * 8)) || (rc = ix->b_keys_b.ensure(n * 8)) || (rc = ix->b_ords_a.ensure(n * 4)) ||
-            (rc = ix->b_ords_b.ensure(n * 4)) || (rc = ix->b_cnt.ensure(nb * 4)) || (rc = ix->b_off.ensure((nb + 1) * 8)))
+            (rc = ix->b_ords_b.ensure(n * 4)))
             return rc;
         HIP_TRY(hipMemcpyAsync(ix->b_keys_a.p, h_keys.data(), n * 8, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(ix->b_ords_a.p, h_ords.data(), n * 4, hipMemcpyHostToDevice, st));
-        size_t tmp = 0;
-        HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp, ix->b_keys_a.as<uint64_t>(), ix->b_keys_b.as<uint64_t>(),
-                                          ix->b_ords_a.as<uint32_t>(), ix->b_ords_b.as<uint32_t>(), n, 0, 64, st));
-        if ((rc = ix->b_tmp.ensure(tmp))) return rc;
         // stable: equal (hash, t) keep ascending ordinals, so duplicates of one record are adjacent
-        HIP_TRY(rocprim::radix_sort_pairs(ix->b_tmp.p, tmp, ix->b_keys_a.as<uint64_t>(), ix->b_keys_b.as<uint64_t>(),
-                                          ix->b_ords_a.as<uint32_t>(), ix->b_ords_b.as<uint32_t>(), n, 0, 64, st));
-        hipLaunchKernelGGL(lm_keep_count, dim3((unsigned)nb), dim3(kThreads), 0, st, ix->b_keys_b.as<uint64_t>(),
-                           ix->b_ords_b.as<uint32_t>(), n, ix->b_cnt.as<uint32_t>());
-        hipLaunchKernelGGL(lm_scan_blocks, dim3(1), dim3(kThreads), 0, st, ix->b_cnt.as<uint32_t>(), nb,
-                           ix->b_off.as<uint64_t>());
-        HIP_TRY(hipGetLastError());
-        uint64_t total = 0;
-        HIP_TRY(hipMemcpyAsync(&total, ix->b_off.as<uint64_t>() + nb, 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        p = (size_t)total;
-        if ((rc = T.hashes.ensure(p * 4)) || (rc = T.entries.ensure(p * 8))) return rc;
-        hipLaunchKernelGGL(lm_compact, dim3((unsigned)nb), dim3(kThreads), 0, st, ix->b_keys_b.as<uint64_t>(),
-                           ix->b_ords_b.as<uint32_t>(), n, ix->b_off.as<uint64_t>(), T.hashes.as<uint32_t>(),
-                           T.entries.as<uint64_t>());
-        hipLaunchKernelGGL(lm_directory, dim3((unsigned)((p + 255) / 256)), dim3(256), 0, st, T.hashes.as<uint32_t>(), p,
-                           T.dir.as<uint32_t>());
-        HIP_TRY(hipGetLastError());
-    } else {
-        if ((rc = T.hashes.ensure(0)) || (rc = T.entries.ensure(0))) return rc;
-        HIP_TRY(hipMemsetAsync(T.dir.p, 0, (kDirSize + 1) * 4, st));
+        uint64_t* keys = ix->b_keys_b.as<uint64_t>();
+        uint32_t* ords = ix->b_ords_b.as<uint32_t>();
+        const LmHead head{keys, ords};
+        if ((rc = sort_pairs(ix->b_tmp, ix->b_keys_a.as<uint64_t>(), keys, ix->b_ords_a.as<uint32_t>(), ords, n, 64, st)) ||
+            (rc = count_heads(head, n, ix->b_cnt, ix->b_off, st, &p)) || (rc = T.hashes.ensure(p * 4)) ||
+            (rc = T.entries.ensure(p * 8)) ||
+            (rc = compact_heads(head, LmEmit{keys, ords, T.hashes.as<uint32_t>(), T.entries.as<uint64_t>()}, n, ix->b_off,
+                                st)))
+            return rc;
+    } else if ((rc = T.hashes.ensure(0)) || (rc = T.entries.ensure(0))) {
+        return rc;
     }
+    if ((rc = build_directory(T.hashes.as<uint32_t>(), p, kDirBits, kDirSize, T.dir.as<uint32_t>(), st))) return rc;
     HIP_TRY(hipStreamSynchronize(st));   // the host vectors above go out of scope
     T.postings = p;
     T.dirty = false;
@@ -686,13 +527,9 @@ int query_impl(ucfp_landmark_index* ix, uint32_t tenant, const uint8_t* d_lm, co
     Tenant& T = it->second;
     if (T.dirty && (rc = rebuild(ix, T, st))) return rc;
     // 2. sort each query, runs, |Q| and V
-    size_t tmp = 0;
     const uint64_t* lo = ix->q_loff.as<uint64_t>();
-    HIP_TRY(rocprim::segmented_radix_sort_keys(nullptr, tmp, ix->q_keys_a.as<uint64_t>(), ix->q_keys_b.as<uint64_t>(),
-                                               (unsigned)total, (unsigned)nq, lo, lo + 1, 0, 64, st));
-    if ((rc = ix->q_tmp.ensure(tmp))) return rc;
-    HIP_TRY(rocprim::segmented_radix_sort_keys(ix->q_tmp.p, tmp, ix->q_keys_a.as<uint64_t>(), ix->q_keys_b.as<uint64_t>(),
-                                               (unsigned)total, (unsigned)nq, lo, lo + 1, 0, 64, st));
+    if ((rc = sort_segments(ix->q_tmp, ix->q_keys_a.as<uint64_t>(), ix->q_keys_b.as<uint64_t>(), total, nq, lo, st)))
+        return rc;
     if ((rc = ix->q_lo.ensure(total * 4)) || (rc = ix->q_len.ensure(total * 4)) || (rc = ix->q_qn.ensure(nq * 4)) ||
         (rc = ix->q_votes.ensure(nq * 8)) || (rc = ix->q_sbase.ensure(nq * 8)))
         return rc;
@@ -734,13 +571,9 @@ int query_impl(ucfp_landmark_index* ix, uint32_t tenant, const uint8_t* d_lm, co
     HIP_TRY(hipGetLastError());
     if (n_spill) {
         const uint64_t* so = ix->q_soff.as<uint64_t>();
-        size_t stmp = 0;
-        HIP_TRY(rocprim::segmented_radix_sort_keys(nullptr, stmp, ix->q_spill_a.as<uint64_t>(), ix->q_spill_b.as<uint64_t>(),
-                                                   (unsigned)n_votes, (unsigned)n_spill, so, so + 1, 0, 64, st));
-        if ((rc = ix->q_tmp.ensure(stmp))) return rc;
-        HIP_TRY(rocprim::segmented_radix_sort_keys(ix->q_tmp.p, stmp, ix->q_spill_a.as<uint64_t>(),
-                                                   ix->q_spill_b.as<uint64_t>(), (unsigned)n_votes, (unsigned)n_spill, so,
-                                                   so + 1, 0, 64, st));
+        if ((rc = sort_segments(ix->q_tmp, ix->q_spill_a.as<uint64_t>(), ix->q_spill_b.as<uint64_t>(), n_votes, n_spill, so,
+                                st)))
+            return rc;
         HIP_TRY(hipMemsetAsync(ix->q_best.p, 0, n_spill * n_ord * 8, st));
         hipLaunchKernelGGL(lm_spill_best, dim3((unsigned)n_spill), dim3(kThreads), 0, st, ix->q_spill_b.as<uint64_t>(), so,
                            n_ord, ix->q_best.as<uint64_t>());
@@ -771,41 +604,21 @@ int ucfp_landmark_index_create(ucfp_ctx* ctx, uint32_t max_postings, uint32_t fl
     if (!ctx || !out) return capi_fail(UCFP_E_INVALID, "ctx/out is NULL");
     *out = nullptr;
     if (flags != 0) return capi_fail(UCFP_E_INVALID, "no landmark index flags are defined (got %u)", flags);
-    ucfp_landmark_index* ix = new (std::nothrow) ucfp_landmark_index();
-    if (!ix) return capi_fail(UCFP_E_INDEX, "out of host memory");
-    ix->ctx = ctx;
-    ix->device = ucfp::ctx_device(ctx);
-    ix->max_postings = max_postings;
-    hipError_t e = hipSetDevice(ix->device);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&ix->own, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&ix->done, hipEventDisableTiming);
-    if (e != hipSuccess) {
-        if (ix->own) (void)hipStreamDestroy(ix->own);
-        delete ix;
-        return capi_fail(UCFP_E_INDEX, "landmark index setup failed: %s", hipGetErrorString(e));
-    }
-    HIP_TRY(hipEventRecord(ix->done, ix->own));
-    *out = ix;
-    return UCFP_OK;
+    const int rc = ucfp::create_index(ctx, "landmark index", out);
+    if (!rc) (*out)->max_postings = max_postings;
+    return rc;
 }
 
 void ucfp_landmark_index_destroy(ucfp_landmark_index* ix) {
     if (!ix) return;
-    (void)hipSetDevice(ix->device);
-    (void)hipDeviceSynchronize();
-    for (auto& kv : ix->tenants) {
-        kv.second.hashes.release();
-        kv.second.entries.release();
-        kv.second.dir.release();
-        kv.second.ids.release();
-    }
+    ix->quiesce();
+    for (auto& kv : ix->tenants)
+        for (DevArr* a : {&kv.second.hashes, &kv.second.entries, &kv.second.dir, &kv.second.ids}) a->release();
     for (DevArr* a : {&ix->b_keys_a, &ix->b_keys_b, &ix->b_ords_a, &ix->b_ords_b, &ix->b_cnt, &ix->b_off, &ix->b_tmp,
                       &ix->q_lm, &ix->q_off, &ix->q_loff, &ix->q_info, &ix->q_keys_a, &ix->q_keys_b, &ix->q_tmp, &ix->q_lo,
                       &ix->q_len, &ix->q_qn, &ix->q_votes, &ix->q_sbase, &ix->q_soff, &ix->q_sq, &ix->q_spill_a,
                       &ix->q_spill_b, &ix->q_best, &ix->q_out})
         a->release();
-    (void)hipEventDestroy(ix->done);
-    (void)hipStreamDestroy(ix->own);
     delete ix;
 }
 
@@ -861,11 +674,8 @@ int ucfp_landmark_index_size(ucfp_landmark_index* ix, uint32_t tenant, size_t* r
     if (it != ix->tenants.end()) {
         Tenant& T = it->second;
         if (T.dirty) {
-            HIP_TRY(hipSetDevice(ix->device));
-            HIP_TRY(hipEventSynchronize(ix->done));
-            int rc = rebuild(ix, T, ix->own);
-            if (rc) return rc;
-            HIP_TRY(hipEventRecord(ix->done, ix->own));
+            int rc = ix->begin();
+            if (rc || (rc = rebuild(ix, T, ix->own)) || (rc = ix->end(ix->own))) return rc;
         }
         r = T.recs.size();
         p = T.postings;
@@ -875,20 +685,7 @@ int ucfp_landmark_index_size(ucfp_landmark_index* ix, uint32_t tenant, size_t* r
     return UCFP_OK;
 }
 
-int ucfp_landmark_index_flush(ucfp_landmark_index* ix) {
-    if (!ix) return capi_fail(UCFP_E_INVALID, "index is NULL");
-    std::lock_guard<std::mutex> lk(ix->mu);
-    HIP_TRY(hipSetDevice(ix->device));
-    HIP_TRY(hipEventSynchronize(ix->done));
-    for (auto& kv : ix->tenants)
-        if (kv.second.dirty) {
-            int rc = rebuild(ix, kv.second, ix->own);
-            if (rc) return rc;
-        }
-    HIP_TRY(hipStreamSynchronize(ix->own));
-    HIP_TRY(hipEventRecord(ix->done, ix->own));
-    return UCFP_OK;
-}
+int ucfp_landmark_index_flush(ucfp_landmark_index* ix) { return ucfp::flush_dirty(ix, rebuild); }
 
 int ucfp_landmark_index_query_dev(ucfp_landmark_index* ix, uint32_t tenant, const uint8_t* d_landmarks,
                                   const uint64_t* d_offsets, size_t nq, uint32_t k, uint32_t min_votes, uint64_t* d_out_ids,
@@ -897,13 +694,11 @@ int ucfp_landmark_index_query_dev(ucfp_landmark_index* ix, uint32_t tenant, cons
     int rc = query_args(ix, d_offsets, nq, k, d_out_ids, d_out_votes, d_out_offsets, d_out_scores, d_out_n);
     if (rc || nq == 0) return rc;
     std::lock_guard<std::mutex> lk(ix->mu);
-    HIP_TRY(hipSetDevice(ix->device));
+    if ((rc = ix->begin())) return rc;
     hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(hipEventSynchronize(ix->done));   // the workspace is shared by every call
     rc = query_impl(ix, tenant, d_landmarks, d_offsets, nq, k, min_votes, d_out_ids, d_out_votes, d_out_offsets,
                     d_out_scores, d_out_n, st);
-    HIP_TRY(hipEventRecord(ix->done, st));
-    return rc;
+    return ix->end(st, rc);
 }
 
 int ucfp_landmark_index_query(ucfp_landmark_index* ix, uint32_t tenant, const uint8_t* landmarks, const uint64_t* offsets,
@@ -913,9 +708,8 @@ int ucfp_landmark_index_query(ucfp_landmark_index* ix, uint32_t tenant, const ui
     if (rc || nq == 0) return rc;
     if ((rc = check_batch_host(landmarks, offsets, nq))) return rc;
     std::lock_guard<std::mutex> lk(ix->mu);
-    HIP_TRY(hipSetDevice(ix->device));
+    if ((rc = ix->begin())) return rc;
     hipStream_t st = ix->own;
-    HIP_TRY(hipEventSynchronize(ix->done));
     const size_t bytes = offsets[nq], nk = nq * k;
     const size_t o_votes = nk * 8, o_offs = o_votes + nk * 4, o_sc = o_offs + nk * 4, o_n = o_sc + nk * 4;
     if ((rc = ix->q_lm.ensure(bytes)) || (rc = ix->q_off.ensure((nq + 1) * 8)) || (rc = ix->q_out.ensure(o_n + nq * 4)))
@@ -925,11 +719,7 @@ int ucfp_landmark_index_query(ucfp_landmark_index* ix, uint32_t tenant, const ui
     uint8_t* ob = ix->q_out.as<uint8_t>();
     rc = query_impl(ix, tenant, ix->q_lm.as<uint8_t>(), ix->q_off.as<uint64_t>(), nq, k, min_votes, (uint64_t*)ob,
                     (uint32_t*)(ob + o_votes), (int32_t*)(ob + o_offs), (float*)(ob + o_sc), (uint32_t*)(ob + o_n), st);
-    if (rc) {
-        (void)hipStreamSynchronize(st);
-        (void)hipEventRecord(ix->done, st);
-        return rc;
-    }
+    if (rc) return ix->end_sync(rc);
     if (nk) {
         HIP_TRY(hipMemcpyAsync(out_ids, ob, nk * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(out_votes, ob + o_votes, nk * 4, hipMemcpyDeviceToHost, st));
@@ -937,9 +727,7 @@ int ucfp_landmark_index_query(ucfp_landmark_index* ix, uint32_t tenant, const ui
         HIP_TRY(hipMemcpyAsync(out_scores, ob + o_sc, nk * 4, hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(hipMemcpyAsync(out_n, ob + o_n, nq * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipEventRecord(ix->done, st));
-    return UCFP_OK;
+    return ix->end_sync(UCFP_OK);
 }
 
 }  // extern "C"

@@ -25,18 +25,8 @@
 #include "../../include/ucfp_hip.h"
 #include "common.h"
 
-namespace ucfp {
-int capi_fail(int code, const char* fmt, ...);
-int ctx_device(const ucfp_ctx* ctx);
-}  // namespace ucfp
 using ucfp::capi_fail;
-
-#define HIP_TRY(expr)                                                                           \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess)                                                                   \
-            return capi_fail(UCFP_E_INDEX, "%s failed: %s", #expr, hipGetErrorString(e_));      \
-    } while (0)
+using ucfp::DevArr;
 
 namespace {
 
@@ -181,25 +171,6 @@ __global__ __launch_bounds__(64) void lsh_query_kernel(const uint8_t* __restrict
     }
     if (lane == 0) out_counts[q] = kept;
 }
-
-struct DevArr {
-    void* p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t bytes) {
-        if (cap >= bytes) return 0;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        HIP_TRY(hipMalloc(&p, bytes + 256));
-        cap = bytes + 256;
-        return 0;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
 
 }  // namespace
 

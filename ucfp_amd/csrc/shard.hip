@@ -26,20 +26,11 @@
 #include "common.h"
 
 namespace ucfp {
-int capi_fail(int code, const char* fmt, ...);  // capi.hip
-int ctx_device(const ucfp_ctx* ctx);            // capi.hip
 int index_kind(const ucfp_index* ix);           // index.hip
 int index_device(const ucfp_index* ix);         // index.hip
 }  // namespace ucfp
 
 using ucfp::capi_fail;
-
-#define HIP_TRY(expr)                                                                           \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess)                                                                   \
-            return capi_fail(UCFP_E_INDEX, "%s failed: %s", #expr, hipGetErrorString(e_));      \
-    } while (0)
 
 namespace {
 

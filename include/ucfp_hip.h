@@ -508,6 +508,50 @@ int ucfp_landmark_index_query_dev(ucfp_landmark_index* ix, uint32_t tenant, cons
                                   uint32_t* d_out_votes, int32_t* d_out_offsets, float* d_out_scores, uint32_t* d_out_n,
                                   void* stream);
 
+/* ---- Haitsma-Kalker sub-fingerprint index (the reference has no audio matcher) ----
+ * A record r is a sequence F_r[0 .. n_r) of u32 sub-fingerprints (the bytes of an audiofp-haitsma-v1 record, 4 per
+ * frame, little endian); a query is a sequence Q[0 .. m), m <= UCFP_HAITSMA_MAX_QUERY_FRAMES.  Item i of a batch is
+ * frames[offsets[i] .. offsets[i+1]) with ELEMENT offsets (frames): offsets[0] = 0, non-decreasing, n + 1 entries --
+ * the shape ucfp_audio_haitsma_batch_dev writes as d_out_offsets.
+ * Within a tenant, P(v) = positions (r, t) with F_r[t] == v; an index with max_postings > 0 stops every v with
+ * P(v) > max_postings (0 = no cap).  An alignment (r, d) is admissible iff 0 <= d and d + m <= n_r; it is a candidate
+ * iff some j < m has popcount(F_r[d+j] ^ Q[j]) <= flip_bits with F_r[d+j] not stopped (flip_bits 0, 1 or 2: 1, 33 or
+ * 529 probe values per query frame).  dist(r, d) = sum over j of popcount(F_r[d+j] ^ Q[j]); dist(r) = the minimum over
+ * the candidates of r, offset(r) = the smallest d attaining it (the position of the query's frame 0 in the record).
+ * Hits: dist(r) * 1000000 <= max_ber_ppm * 32 * m in 64-bit integers (max_ber_ppm <= 1000000), ordered (dist asc,
+ * id asc), first k <= UCFP_INDEX_MAX_K; score = 1.0f - (float)dist / (float)(32 * m).  Unused output slots: id
+ * UINT64_MAX, dist UINT32_MAX, offset 0, score -1.  k = 0, m = 0 or an unknown / empty tenant gives 0 hits; bad offsets,
+ * m > UCFP_HAITSMA_MAX_QUERY_FRAMES, flip_bits > 2 or max_ber_ppm > 1000000 give UCFP_E_INVALID before anything runs.
+ * Upsert of a known id replaces its frames, delete removes it, a record with 0 frames counts in `size`; postings are
+ * rebuilt lazily at the next query, size or flush of a changed tenant.  Limits: a record below 2^31 frames, a tenant
+ * below 2^32 - 1 frames in all, one query below 2^32 - 1 seeds (positions its probes find).  Queries read the checked
+ * sizes back to the host once and the seed count of each query once per pass of 1024 queries (synchronisations of
+ * `stream`) to size their buffers; queries whose seeds exceed the workspace are processed in slices, with the same
+ * answers.  upsert_dev copies
+ * its inputs to the host record table (it synchronises `stream`).  flags: 0. */
+#define UCFP_HAITSMA_MAX_QUERY_FRAMES 4096u
+typedef struct ucfp_haitsma_index ucfp_haitsma_index;
+/* probe values per query frame: 1, 33, 529 for flip_bits 0, 1, 2; 0 for anything else.  Host only. */
+size_t ucfp_haitsma_index_probes(uint32_t flip_bits);
+int ucfp_haitsma_index_create(ucfp_ctx* ctx, uint32_t max_postings, uint32_t flags, ucfp_haitsma_index** out);
+void ucfp_haitsma_index_destroy(ucfp_haitsma_index* ix);
+int ucfp_haitsma_index_upsert(ucfp_haitsma_index* ix, uint32_t tenant, const uint64_t* ids, const uint32_t* frames,
+                              const uint64_t* offsets, size_t n);
+int ucfp_haitsma_index_upsert_dev(ucfp_haitsma_index* ix, uint32_t tenant, const uint64_t* d_ids, const uint32_t* d_frames,
+                                  const uint64_t* d_offsets, size_t n, void* stream);
+int ucfp_haitsma_index_delete(ucfp_haitsma_index* ix, uint32_t tenant, const uint64_t* ids, size_t n, size_t* n_removed);
+/* records = live records (empty ones included); frames = their frames in all (rebuilds a changed tenant). */
+int ucfp_haitsma_index_size(ucfp_haitsma_index* ix, uint32_t tenant, size_t* records, size_t* frames);
+int ucfp_haitsma_index_flush(ucfp_haitsma_index* ix);
+/* nq ragged queries; out_ids / out_dist / out_offsets / out_scores are nq x k; out_n[q] = hits of query q. */
+int ucfp_haitsma_index_query(ucfp_haitsma_index* ix, uint32_t tenant, const uint32_t* frames, const uint64_t* offsets,
+                             size_t nq, uint32_t k, uint32_t flip_bits, uint32_t max_ber_ppm, uint64_t* out_ids,
+                             uint32_t* out_dist, int32_t* out_offsets, float* out_scores, uint32_t* out_n);
+int ucfp_haitsma_index_query_dev(ucfp_haitsma_index* ix, uint32_t tenant, const uint32_t* d_frames, const uint64_t* d_offsets,
+                                 size_t nq, uint32_t k, uint32_t flip_bits, uint32_t max_ber_ppm, uint64_t* d_out_ids,
+                                 uint32_t* d_out_dist, int32_t* d_out_offsets, float* d_out_scores, uint32_t* d_out_n,
+                                 void* stream);
+
 /* ---- BM25 keyword index (src/index/embedded/bm25.rs:79-628) ----
  * A document is a list of (key u64, tf u32) pairs: item i of a batch is keys/tfs[offsets[i] .. offsets[i+1]) with
  * ELEMENT offsets (offsets[0] = 0, non-decreasing, n + 1 entries); dl = sum tf < 2^32.  Keys are the caller's: equal

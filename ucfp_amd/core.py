@@ -19,6 +19,7 @@ class HitSource:
     Fused = "fused"
     Hamming = "hamming"   # new capability behind /v1/query; not in the reference
     Landmark = "landmark"  # audio identification over Wang landmarks (DESIGN A10); not in the reference
+    Haitsma = "haitsma"    # audio identification over Haitsma sub-fingerprints (DESIGN A12); not in the reference
 
 
 @dataclass
@@ -56,9 +57,9 @@ class Hit:
     vector_rank: Optional[int] = None
     bm25_rank: Optional[int] = None
     term_hits: list = field(default_factory=list)
-    distance: Optional[int] = None    # Hamming distance when source == "hamming"
+    distance: Optional[int] = None    # Hamming distance when source == "hamming"; bit errors of the block when "haitsma"
     votes: Optional[int] = None       # offset-consistent landmark matches when source == "landmark"
-    offset: Optional[int] = None      # where the query's frame 0 lies in the record (frames) when source == "landmark"
+    offset: Optional[int] = None      # where the query's frame 0 lies in the record (frames) when source == "landmark" / "haitsma"
 
 
 FORMAT_VERSION = 1  # src/lib.rs:62
@@ -70,6 +71,8 @@ FORMAT_VERSION = 1  # src/lib.rs:62
 # identification adds `landmarks` (DESIGN A10): Wang landmark bytes (8 per landmark) or a list of [hash, t] pairs.
 # Keyword search adds `terms` (the reference's Query::terms, src/core/mod.rs:163-164; BM25, DESIGN A11) and `explain`
 # (the reference's `?explain=1`, handlers.rs:133-140): terms alone give a BM25 query, vector + terms the hybrid one.
+# Identification by bit-error rate adds `subfingerprints` (DESIGN A12): Haitsma frames as bytes (4 per frame, u32 LE) or a
+# list of integers.
 # A body the reference accepts parses to the same query here.
 
 DEFAULT_K = 10   # dto.rs:85-87
@@ -84,6 +87,7 @@ class QueryRequest:
     hash: Optional[int] = None
     algorithm: Optional[str] = None
     landmarks: Optional[bytes] = None   # 8 bytes per landmark: u32 LE hash, u32 LE t
+    subfingerprints: Optional[bytes] = None   # 4 bytes per frame: u32 LE (an audiofp-haitsma-v1 block)
     terms: List[str] = field(default_factory=list)
     explain: bool = False
 
@@ -97,11 +101,14 @@ class QueryRequest:
             raise InvalidArgument(f"bad query body: {e}") from None
         k = int(body.get("k", DEFAULT_K))
         vector, h, lm = body.get("vector"), body.get("hash"), body.get("landmarks")
+        sub = body.get("subfingerprints")
         terms = body.get("terms") or []
         if not isinstance(terms, list) or not all(isinstance(t, str) for t in terms):
             raise InvalidArgument("`terms` must be a list of strings")
-        if vector is None and h is None and lm is None and not terms:
-            raise InvalidArgument("query needs `vector` (dto.rs:80-82), `terms`, `hash` or `landmarks`")
+        if vector is None and h is None and lm is None and sub is None and not terms:
+            raise InvalidArgument("query needs `vector` (dto.rs:80-82), `terms`, `hash`, `landmarks` or `subfingerprints`")
+        if sub is not None:
+            sub = _subfingerprint_bytes(sub)
         if lm is not None:
             lm = _landmark_bytes(lm)
         if isinstance(h, (list, bytes, bytearray)):
@@ -112,7 +119,7 @@ class QueryRequest:
             raise InvalidArgument("`hash` must be a u64")
         return cls(tenant_id=tenant_id, modality=modality, k=max(k, 1),       # handlers.rs:153: k.max(1)
                    vector=[float(x) for x in vector] if vector is not None else None,
-                   hash=int(h) if h is not None else None, algorithm=body.get("algorithm"), landmarks=lm,
+                   hash=int(h) if h is not None else None, algorithm=body.get("algorithm"), landmarks=lm, subfingerprints=sub,
                    terms=list(terms), explain=_flag(body.get("explain", False)))
 
 
@@ -142,8 +149,23 @@ def _landmark_bytes(lm) -> bytes:
     return bytes(out)
 
 
+def _subfingerprint_bytes(sub) -> bytes:
+    """`subfingerprints` of a query body -> 4 bytes per frame (u32 LE)."""
+    from .errors import InvalidArgument
+    if isinstance(sub, (bytes, bytearray)):
+        if len(sub) % 4:
+            raise InvalidArgument("`subfingerprints` bytes must be a multiple of 4 (one u32 per frame)")
+        return bytes(sub)
+    if not isinstance(sub, list) or not all(isinstance(x, int) and not isinstance(x, bool) for x in sub):
+        raise InvalidArgument("`subfingerprints` must be bytes or a list of integers")
+    if not all(0 <= x < 1 << 32 for x in sub):
+        raise InvalidArgument("a sub-fingerprint needs 0 <= value < 2^32")
+    return b"".join(int(x).to_bytes(4, "little") for x in sub)
+
+
 def hit_to_json(h: Hit) -> dict:
-    """HitOut (dto.rs:94-116); `distance` only appears on Hamming hits and `votes` / `offset` only on landmark hits, so
+    """HitOut (dto.rs:94-116); `distance` only appears on Hamming and Haitsma hits, `votes` only on landmark hits and
+    `offset` only on landmark and Haitsma hits, so
     vector hits stay byte-stable.  `term_hits` are TermHitOut objects {term, idf, tf, contribution} (dto.rs:118-124)."""
     out = {"tenant_id": h.tenant_id, "record_id": h.record_id, "score": h.score, "source": h.source,
            "vector_score": h.vector_score, "bm25_score": h.bm25_score, "vector_rank": h.vector_rank,
@@ -154,5 +176,7 @@ def hit_to_json(h: Hit) -> dict:
         out["distance"] = h.distance
     if h.source == HitSource.Landmark:
         out["votes"] = h.votes
+        out["offset"] = h.offset
+    if h.source == HitSource.Haitsma:
         out["offset"] = h.offset
     return out

@@ -7,6 +7,7 @@ path, backed by the GPU-resident shard behind the C ABI (ucfp_index_*).
                                       as EmbeddedBackend::knn src/index/embedded/mod.rs:268-360)
     GpuIndex.hamming(tenant, h, k)    the new Hamming search behind /v1/query
     GpuIndex.identify(tenant, lm, k)  audio identification over Wang landmarks (DESIGN A10; LandmarkIndex)
+    GpuIndex.identify_frames(tenant, frames, k)  the same over Haitsma sub-fingerprints (DESIGN A12; HaitsmaIndex)
     GpuIndex.bm25(tenant, terms, k)   IndexBackend::bm25 / bm25_explain :37-50 over Record.text (DESIGN A11; Bm25Index)
     GpuIndex.flush()                  IndexBackend::flush    :63
 
@@ -20,7 +21,7 @@ from typing import Iterable, List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from .audio import ALGORITHM_WANG
+from .audio import ALGORITHM_HAITSMA, ALGORITHM_WANG
 from .core import Hit, HitSource, Record, TermHit
 from .errors import InvalidArgument, UnsupportedError
 from .terms import query_terms, tokenize
@@ -31,6 +32,7 @@ MAX_K = 128
 INVALID_ID = 0xFFFFFFFFFFFFFFFF
 BM25_LDS_POSTINGS = 6144   # UCFP_BM25_LDS_POSTINGS: a query with more postings is scored by ordinal ranges
 TERM_HITS_PER_DOC = 16     # bm25.rs:503
+HAITSMA_MAX_QUERY_FRAMES = 4096   # UCFP_HAITSMA_MAX_QUERY_FRAMES
 
 
 class SearchBatcher:
@@ -257,6 +259,99 @@ class LandmarkIndex:
                                                            stream or None))
 
 
+def _pack_frames(items):
+    """Sequence of sub-fingerprint blocks (bytes, or uint32 [m] arrays) -> (u32 frames, u64 element offsets [n + 1])."""
+    parts = []
+    for x in items:
+        if isinstance(x, (bytes, bytearray, memoryview)):
+            if len(x) % 4:
+                raise InvalidArgument("sub-fingerprint bytes must be a multiple of 4 (one u32 per frame)")
+            parts.append(np.frombuffer(bytes(x), "<u4"))
+        else:
+            parts.append(np.ascontiguousarray(x, dtype=np.uint32).reshape(-1))
+    offs = np.zeros(len(parts) + 1, np.uint64)
+    np.cumsum([p.size for p in parts], out=offs[1:])
+    frames = np.ascontiguousarray(np.concatenate(parts + [np.zeros(1, np.uint32)]), dtype=np.uint32)
+    return frames, offs
+
+
+class HaitsmaIndex:
+    """Thin RAII wrapper over one ucfp_haitsma_index (DESIGN A12): records and queries are sequences of Haitsma
+    sub-fingerprints; a query answers the top-k records by bit errors over the whole block at the best alignment."""
+
+    def __init__(self, max_postings: int = 0, flags: int = 0, ctx=None):
+        self._lib = _lib.load()
+        self.ctx = ctx or _lib.current_context()
+        self.max_postings = max_postings
+        h = C.c_void_p()
+        _lib.check(self._lib.ucfp_haitsma_index_create(self.ctx.handle, max_postings, flags, C.byref(h)))
+        self.handle = h
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self._lib.ucfp_haitsma_index_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def upsert(self, tenant: int, ids, frames) -> None:
+        """ids [n]; frames: n blocks (bytes, 4 per frame, or uint32 [m])."""
+        ids = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        frames = list(frames)
+        if len(frames) != ids.shape[0]:
+            raise InvalidArgument("ids and frame blocks disagree on the number of records")
+        flat, offs = _pack_frames(frames)
+        _lib.check(self._lib.ucfp_haitsma_index_upsert(self.handle, tenant, ids.ctypes.data, flat.ctypes.data,
+                                                       offs.ctypes.data, ids.shape[0]))
+
+    def upsert_dev(self, tenant: int, ids_ptr: int, frames_ptr: int, offsets_ptr: int, n: int, stream: int = 0) -> None:
+        _lib.check(self._lib.ucfp_haitsma_index_upsert_dev(self.handle, tenant, ids_ptr, frames_ptr or None, offsets_ptr, n,
+                                                           stream or None))
+
+    def delete(self, tenant: int, ids) -> int:
+        ids = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        removed = C.c_size_t(0)
+        _lib.check(self._lib.ucfp_haitsma_index_delete(self.handle, tenant, ids.ctypes.data, ids.shape[0], C.byref(removed)))
+        return int(removed.value)
+
+    def size(self, tenant: int):
+        """-> (records, frames) of a tenant."""
+        r, f = C.c_size_t(0), C.c_size_t(0)
+        _lib.check(self._lib.ucfp_haitsma_index_size(self.handle, tenant, C.byref(r), C.byref(f)))
+        return int(r.value), int(f.value)
+
+    def flush(self) -> None:
+        _lib.check(self._lib.ucfp_haitsma_index_flush(self.handle))
+
+    def query(self, tenant: int, queries, k: int, flip_bits: int = 2, max_ber_ppm: int = 350_000):
+        """queries: blocks (bytes or uint32 [m]).  -> (ids [nq,k] u64, dist [nq,k] u32, offsets [nq,k] i32,
+        scores [nq,k] f32, counts [nq] u32)."""
+        flat, offs = _pack_frames(list(queries))
+        nq = offs.size - 1
+        kk = max(int(k), 1)
+        ids = np.full((nq, kk), INVALID_ID, np.uint64)
+        dist = np.full((nq, kk), 0xFFFFFFFF, np.uint32)
+        offsets = np.zeros((nq, kk), np.int32)
+        scores = np.full((nq, kk), -1.0, np.float32)
+        counts = np.zeros(nq, np.uint32)
+        _lib.check(self._lib.ucfp_haitsma_index_query(self.handle, tenant, flat.ctypes.data, offs.ctypes.data, nq, int(k),
+                                                      int(flip_bits), int(max_ber_ppm), ids.ctypes.data, dist.ctypes.data,
+                                                      offsets.ctypes.data, scores.ctypes.data, counts.ctypes.data))
+        return ids[:, :k], dist[:, :k], offsets[:, :k], scores[:, :k], counts
+
+    def query_dev(self, tenant: int, frames_ptr: int, offsets_ptr: int, nq: int, k: int, flip_bits: int, max_ber_ppm: int,
+                  out_ids_ptr: int, out_dist_ptr: int, out_offsets_ptr: int, out_scores_ptr: int, out_n_ptr: int,
+                  stream: int = 0) -> None:
+        _lib.check(self._lib.ucfp_haitsma_index_query_dev(self.handle, tenant, frames_ptr or None, offsets_ptr, nq, k,
+                                                          flip_bits, max_ber_ppm, out_ids_ptr or None, out_dist_ptr or None,
+                                                          out_offsets_ptr or None, out_scores_ptr or None, out_n_ptr,
+                                                          stream or None))
+
+
 class Bm25Index:
     """Thin RAII wrapper over one ucfp_bm25_index (DESIGN A11): BM25 over documents of (key, tf) pairs.  It keeps the
     term -> key dictionary of the index (keys number the terms in order of first sight); query terms it has never
@@ -407,6 +502,7 @@ class GpuIndex:
         self._cos = {}        # dim -> DeviceIndex
         self._ham = {}        # hash space name -> DeviceIndex
         self._lm = None       # LandmarkIndex of the audiofp-wang-v1 records (DESIGN A10)
+        self._hx = None       # HaitsmaIndex of the audiofp-haitsma-v1 records (DESIGN A12)
         self._bm = None       # Bm25Index of the records with text (DESIGN A11)
         self._sidecar = sidecar   # ucfp_amd.store.Sidecar: the stored-table mirror written at upsert
 
@@ -430,6 +526,11 @@ class GpuIndex:
             self._lm = LandmarkIndex(0, 0, self.ctx)
         return self._lm
 
+    def _haitsma(self) -> HaitsmaIndex:
+        if self._hx is None:
+            self._hx = HaitsmaIndex(0, 0, self.ctx)
+        return self._hx
+
     def _bm25(self) -> Bm25Index:
         if self._bm is None:
             self._bm = Bm25Index(0, self.ctx)
@@ -437,18 +538,20 @@ class GpuIndex:
 
     def _all(self):
         return (list(self._cos.values()) + list(self._ham.values()) + ([self._lm] if self._lm is not None else [])
+                + ([self._hx] if self._hx is not None else [])
                 + ([self._bm] if self._bm is not None else []))
 
     def upsert(self, records: Sequence[Record]) -> None:
         """Embeddings go to the cosine index of their dimension; image records also feed the
         Hamming spaces `<algorithm>` with their 64-bit global hashes (SURVEY 8f N2 offsets);
-        `audiofp-wang-v1` records feed the landmark index with their landmarks; every record with `text`, whatever its
+        `audiofp-wang-v1` records feed the landmark index with their landmarks and `audiofp-haitsma-v1` records the
+        sub-fingerprint index with their frames; every record with `text`, whatever its
         modality, feeds BM25, and a record without text leaves it (src/index/embedded/mod.rs:208-219).
 
         Overwrite semantics are the reference's: everything is keyed by (tenant_id, record_id), a re-ingested record
         REPLACES the old one -- "Drop any stale vector for this key" when the new record has no embedding
         (src/index/embedded/mod.rs:184-191), a new dimension or algorithm replaces the old row.  So before inserting,
-        the key is removed from every cosine index of another dimension, every hash space and the landmark index when
+        the key is removed from every cosine index of another dimension, every hash space, the landmark index and the sub-fingerprint index when
         the new record does not feed them.  Within one batch the last record of a key wins, as successive `insert`s in one redb transaction do."""
         if self._sidecar is not None:     # the log first (the host does this right after its redb commit), then the mirror
             self._sidecar.append(records)
@@ -456,6 +559,7 @@ class GpuIndex:
         for r in records:
             last[(r.tenant_id, r.record_id)] = r
         by_cos, by_ham, stale_cos, stale_ham, by_lm, stale_lm, by_bm, stale_bm = {}, {}, {}, {}, {}, {}, {}, {}
+        by_hx, stale_hx = {}, {}
         for r in last.values():
             if r.text is not None:
                 by_bm.setdefault(r.tenant_id, []).append(r)
@@ -465,6 +569,10 @@ class GpuIndex:
                 by_lm.setdefault(r.tenant_id, []).append(r)
             elif self._lm is not None:
                 stale_lm.setdefault(r.tenant_id, []).append(r.record_id)
+            if r.algorithm == ALGORITHM_HAITSMA:
+                by_hx.setdefault(r.tenant_id, []).append(r)
+            elif self._hx is not None:
+                stale_hx.setdefault(r.tenant_id, []).append(r.record_id)
             dim = len(r.embedding) if r.embedding is not None else 0
             if dim > 0:
                 by_cos.setdefault((r.tenant_id, dim), []).append(r)
@@ -484,6 +592,8 @@ class GpuIndex:
             self._ham[space].delete(tenant, np.array(ids, np.uint64))
         for tenant, ids in stale_lm.items():
             self._lm.delete(tenant, np.array(ids, np.uint64))
+        for tenant, ids in stale_hx.items():
+            self._hx.delete(tenant, np.array(ids, np.uint64))
         for tenant, ids in stale_bm.items():
             self._bm.delete(tenant, np.array(ids, np.uint64))
         for tenant, recs in by_bm.items():
@@ -491,6 +601,9 @@ class GpuIndex:
         for tenant, recs in by_lm.items():
             self._landmarks().upsert(tenant, np.array([r.record_id for r in recs], np.uint64),
                                      [bytes(r.fingerprint) for r in recs])
+        for tenant, recs in by_hx.items():
+            self._haitsma().upsert(tenant, np.array([r.record_id for r in recs], np.uint64),
+                                   [bytes(r.fingerprint) for r in recs])
         for (tenant, dim), recs in by_cos.items():
             ids = np.array([r.record_id for r in recs], np.uint64)
             rows = np.array([r.embedding for r in recs], np.float32)
@@ -536,6 +649,18 @@ class GpuIndex:
         return [Hit(tenant_id=tenant_id, record_id=int(ids[0, i]), score=float(scores[0, i]), source=HitSource.Landmark,
                     votes=int(votes[0, i]), offset=int(offs[0, i])) for i in range(int(counts[0]))]
 
+    def identify_frames(self, tenant_id: int, frames, k: int, flip_bits: int = 2, max_ber: float = 0.35) -> List[Hit]:
+        """Which recording is this clip, and where in it: frames = Haitsma sub-fingerprints as bytes (4 per frame) or
+        uint32 [m], m <= HAITSMA_MAX_QUERY_FRAMES.  Hits by bit errors over the whole block at the best alignment found
+        within `flip_bits` of some frame, under the bit-error rate `max_ber` (DESIGN A12); `distance` = the bit errors,
+        `offset` = the clip's frame 0 in the record."""
+        if k == 0 or self._hx is None:
+            return []
+        ids, dist, offs, scores, counts = self._hx.query(tenant_id, [frames], min(k, MAX_K), flip_bits,
+                                                         int(round(max_ber * 1_000_000)))
+        return [Hit(tenant_id=tenant_id, record_id=int(ids[0, i]), score=float(scores[0, i]), source=HitSource.Haitsma,
+                    distance=int(dist[0, i]), offset=int(offs[0, i])) for i in range(int(counts[0]))]
+
     def bm25(self, tenant_id: int, terms: Sequence[str], k: int, filter: Optional[bytes] = None,
              explain: bool = False) -> List[Hit]:
         """IndexBackend::bm25 / bm25_explain (src/index/embedded/mod.rs:127-150): "bm25" hits by BM25 score (DESIGN
@@ -548,9 +673,10 @@ class GpuIndex:
 
     def query(self, req) -> List[Hit]:
         """POST /v1/query (handlers.rs:143-187) with the additive `hash` field: a vector goes to the cosine kNN,
-        a hash to the Hamming space `algorithm` (default: the only hash space present), `landmarks` to identify;
+        a hash to the Hamming space `algorithm` (default: the only hash space present), `landmarks` to identify, `subfingerprints` to identify_frames;
         `terms` go through the matcher (BM25, or vector + BM25 fused by RRF: src/matcher/mod.rs:140-207)."""
-        if getattr(req, "landmarks", None) is None and req.hash is None and getattr(req, "terms", None):
+        if (getattr(req, "landmarks", None) is None and getattr(req, "subfingerprints", None) is None and req.hash is None
+                and getattr(req, "terms", None)):
             from . import matcher
             hits = matcher.search(self, req)
             for rank, h in enumerate(hits):
@@ -559,6 +685,8 @@ class GpuIndex:
             return hits
         if getattr(req, "landmarks", None) is not None:
             hits = self.identify(req.tenant_id, req.landmarks, req.k)
+        elif getattr(req, "subfingerprints", None) is not None:
+            hits = self.identify_frames(req.tenant_id, req.subfingerprints, req.k)
         elif req.hash is not None:
             space = req.algorithm
             if space is None:

@@ -474,6 +474,25 @@ int ucfp_lsh_build_dev(ucfp_lsh* lsh, const uint64_t* d_ids, const uint8_t* d_re
  * 1024 in total); score = equal slots / 128; best k by (score desc, id asc). */
 int ucfp_lsh_query_dev(ucfp_lsh* lsh, const uint8_t* d_query_records, size_t nq, uint32_t k, uint64_t* d_out_ids,
                        float* d_out_scores, uint32_t* d_out_counts, void* stream);
+/* Near-duplicate clusters of the rows 0 .. n-1 of the last ucfp_lsh_build_dev, all on the device.
+ * agree(a, c) = number of i < 128 with slot_i(a) == slot_i(c) (all 128 slots, also those no band covers).
+ *   candidates  per band, per maximal run of equal keys in the sorted table (rows r_0 < r_1 < ... < r_{m-1}, the sort
+ *               is stable): the pairs (r_i, r_j) with 0 < j - i <= span.  span = 0 means 16, span = UINT32_MAX every
+ *               pair of the run.  Runs are runs of equal KEYS, so a 64-bit key collision makes a run as well.
+ *   edges       candidates with agree >= min_agree, 1 <= min_agree <= 128
+ *   clusters    connected components of the edge graph: labels[row] = smallest row of the component,
+ *               keep[row] = (labels[row] == row), rep_ids[row] = ids[labels[row]]
+ *   stats       [0] pairs = candidates summed over bands (a pair counts once per band it appears in),
+ *               [1] clusters = rows with keep, [2] duplicates = n - clusters, [3] largest = size of the largest cluster
+ * Every output is a function of the build's input alone.  Stream-ordered; the only synchronisation is what growing the
+ * workspace needs.  The workspace lives in the object: one dedup in flight per ucfp_lsh.  An index never built or built
+ * empty: UCFP_OK, stats all zero. */
+int ucfp_lsh_dedup_dev(ucfp_lsh* lsh, uint32_t min_agree, uint32_t span,
+                       uint32_t* d_out_labels,   /* n, required            */
+                       uint64_t* d_out_rep_ids,  /* n, may be NULL         */
+                       uint8_t*  d_out_keep,     /* n, may be NULL         */
+                       uint64_t* d_out_stats,    /* 4, may be NULL         */
+                       void* stream);
 
 /* ---- landmark index over Wang hashes (the reference has no audio matcher) ----
  * Records and queries are sets of landmarks: 8 bytes each, u32 LE hash then u32 LE t (UCFP_WANG_HASH_BYTES), t < 2^31.

@@ -12,9 +12,15 @@
 // One wave per query: binary search is wave-uniform, candidates are gathered 64 at a time, the
 // agreement count is two 64-bit compares per lane and a ballot popcount.  The sort is rocPRIM's
 // device radix sort (a plain library primitive); everything else is hand-written.
+//   dedup   (L5-L7) self-join over the band runs: rows r_i < r_j of one run with j - i <= span are candidates, a
+//           candidate with agree >= min_agree is an edge, clusters are the connected components, labelled by their
+//           smallest row.  One streaming pass over the sorted keys finds the live positions by ballot; a wave
+//           verifies a live position's partners (two slots per lane, two ballots) and hooks the roots lock-free
+//           (union_find.h); a second launch flattens the forest into labels, keep flags and the counts.
 
 #include <hip/hip_runtime.h>
 
+#include <cstdlib>
 #include <cstring>  // rocPRIM's texture iterator calls the host memset without including it
 
 #include <rocprim/rocprim.hpp>
@@ -24,6 +30,7 @@
 
 #include "../../include/ucfp_hip.h"
 #include "common.h"
+#include "union_find.h"
 
 using ucfp::capi_fail;
 using ucfp::DevArr;
@@ -172,6 +179,190 @@ __global__ __launch_bounds__(64) void lsh_query_kernel(const uint8_t* __restrict
     if (lane == 0) out_counts[q] = kept;
 }
 
+// ---- de-duplication ----
+
+constexpr uint32_t kDedupDefaultSpan = 16;
+constexpr int kLinkBlock = 256;   // 4 waves; no LDS, no barrier: every wave works on its own
+
+__global__ void dedup_init_kernel(uint32_t* __restrict__ parent, uint32_t* __restrict__ sizes, size_t n,
+                                  uint64_t* __restrict__ stats) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < 4) stats[i] = i == 3;   // largest: a cluster has its own row at least (n > 0 here)
+    if (i < n) {
+        parent[i] = (uint32_t)i;
+        sizes[i] = 0;
+    }
+}
+
+// Verifies the partners named by `vm` (lane t holds partner row q) against row r, four at a time: 1 KiB of slots each,
+// two per lane, all loads issued before the first compare; lane 0 hooks the edges.  Row r's own slots are loaded on
+// first use (have / qa / qb).  Everything but q is wave-uniform.
+__device__ __forceinline__ void dedup_verify(uint64_t vm, uint32_t q, uint32_t r, const uint64_t* __restrict__ sigs,
+                                             uint32_t* parent, uint32_t min_agree, int lane, bool& have, uint64_t& qa,
+                                             uint64_t& qb) {
+    if (vm && !have) {
+        const uint64_t* sg = sigs + (size_t)r * 128;
+        qa = sg[lane];
+        qb = sg[lane + 64];
+        have = true;
+    }
+    while (vm) {
+        uint32_t qs[4];
+        int nq = 0;
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            qs[u] = r;
+            if (vm) {
+                qs[u] = (uint32_t)__shfl((int)q, __ffsll((unsigned long long)vm) - 1, 64);
+                vm &= vm - 1;
+                nq = u + 1;
+            }
+        }
+        uint64_t xa[4], xb[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const uint64_t* sg = sigs + (size_t)qs[u] * 128;
+            xa[u] = sg[lane];
+            xb[u] = sg[lane + 64];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const uint32_t agree = (uint32_t)__popcll(__ballot(xa[u] == qa)) + (uint32_t)__popcll(__ballot(xb[u] == qb));
+            if (u < nq && agree >= min_agree && lane == 0) ucfp::uf_unite(parent, r, qs[u]);
+        }
+    }
+}
+
+// One wave per tile of 64 positions of one band's sorted table (coalesced: the scan over bands * n keys is a streaming
+// pass).  Position p is live iff key[p + 1] == key[p]; a tile without a live position costs its two key loads.  A tile
+// with one loads, once and coalesced, the keys and rows of the next 64 positions too and (with `skip`) the root of
+// every row that lies in a run, lane-parallel; the wave then walks its live positions by ballot, and a position's first
+// 64 partners -- all of them at the default span -- come out of registers by shuffle.  A partner whose root (as of the
+// tile's start) equals the position's is in its tree already and is skipped without touching memory; for the others
+// the roots are read afresh, and those still apart are verified (dedup_verify).  Partners beyond 64 places (span > 64)
+// are read from the table, 64 at a time.  Roots only merge, so a stale "equal" stays true and a stale "apart" costs a
+// look, never a result.
+__global__ __launch_bounds__(kLinkBlock) void dedup_link_kernel(const uint64_t* __restrict__ skeys,
+                                                                const uint32_t* __restrict__ srows, size_t n,
+                                                                uint32_t bands, const uint64_t* __restrict__ sigs,
+                                                                uint32_t* parent, uint64_t span, uint32_t min_agree,
+                                                                int skip, uint64_t* stats) {
+    const int lane = threadIdx.x & 63;
+    const size_t tiles_per_band = (n + 63) / 64;
+    const size_t ntiles = tiles_per_band * bands;
+    const size_t nwaves = (size_t)gridDim.x * (kLinkBlock / 64);
+    uint64_t pairs = 0;   // wave-uniform
+    for (size_t tile = (size_t)blockIdx.x * (kLinkBlock / 64) + (threadIdx.x >> 6); tile < ntiles; tile += nwaves) {
+        const size_t b = tile / tiles_per_band;
+        const size_t i0 = (tile - b * tiles_per_band) * 64;
+        const uint64_t* kb = skeys + b * n;
+        const uint32_t* rb = srows + b * n;
+        const size_t i = i0 + lane;
+        const uint64_t key = i < n ? kb[i] : 0;
+        uint64_t live = __ballot(i + 1 < n && kb[i + 1] == key);
+        if (!live) continue;
+        // the tile and the 64 positions after it, in registers
+        const size_t i2 = i + 64;
+        const uint64_t key2 = i2 < n ? kb[i2] : 0;
+        const uint32_t row1 = i < n ? rb[i] : 0, row2 = i2 < n ? rb[i2] : 0;
+        uint32_t root1 = row1, root2 = row2;
+        if (skip) {
+            // rows of this tile that are a live position or follow one; rows of the next 64 that continue the last run
+            if (((live | (live << 1)) >> lane) & 1) root1 = ucfp::uf_find(parent, row1);
+            if ((live >> 63) && i2 < n && key2 == __shfl(key, 63, 64)) root2 = ucfp::uf_find(parent, row2);
+        }
+        while (live) {
+            const int s = __ffsll((unsigned long long)live) - 1;
+            live &= live - 1;
+            const size_t p = i0 + s;
+            const uint64_t k0 = __shfl(key, s, 64);
+            const uint32_t r = (uint32_t)__shfl((int)row1, s, 64);
+            const uint32_t root_r = (uint32_t)__shfl((int)root1, s, 64);
+            bool have = false;
+            uint64_t qa = 0, qb = 0;
+            // partners p + 1 .. p + 64: position s + 1 + lane of the 128 held in registers
+            const int t = s + 1 + lane;
+            const uint64_t k1 = __shfl(key, t & 63, 64), k2 = __shfl(key2, t & 63, 64);
+            const uint32_t q1 = (uint32_t)__shfl((int)row1, t & 63, 64), q2 = (uint32_t)__shfl((int)row2, t & 63, 64);
+            const uint32_t t1 = (uint32_t)__shfl((int)root1, t & 63, 64), t2 = (uint32_t)__shfl((int)root2, t & 63, 64);
+            const bool ok = (uint64_t)lane < span && p + 1 + lane < n && (t < 64 ? k1 : k2) == k0;   // a prefix of the lanes
+            const uint32_t q = ok ? (t < 64 ? q1 : q2) : r;
+            const uint64_t m = __ballot(ok);
+            pairs += (uint64_t)__popcll(m);
+            bool need = ok;
+            if (skip) {
+                need = ok && (t < 64 ? t1 : t2) != root_r;
+                if (__ballot(need)) {   // apart when the tile began: look again
+                    const uint32_t now_r = ucfp::uf_find(parent, r);
+                    need = need && ucfp::uf_find(parent, q) != now_r;
+                }
+            }
+            dedup_verify(__ballot(need), q, r, sigs, parent, min_agree, lane, have, qa, qb);
+            if (__popcll(m) < 64) continue;   // the run (or the span) ended inside these 64
+            for (uint64_t off = 64; off < span; off += 64) {
+                const uint64_t o = off + lane;
+                const size_t idx = p + 1 + o;
+                const bool okf = o < span && idx < n && kb[idx] == k0;
+                const uint64_t mf = __ballot(okf);
+                if (!mf) break;
+                pairs += (uint64_t)__popcll(mf);
+                const uint32_t qf = okf ? rb[idx] : r;
+                bool needf = okf;
+                if (skip && okf) needf = ucfp::uf_find(parent, qf) != ucfp::uf_find(parent, r);
+                dedup_verify(__ballot(needf), qf, r, sigs, parent, min_agree, lane, have, qa, qb);
+                if (__popcll(mf) < 64) break;
+            }
+        }
+    }
+    if (lane == 0 && pairs) __hip_atomic_fetch_add(stats + 0, pairs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// a launch of its own: every hook of the link pass is visible.  sizes[l] counts the rows of cluster l other than l
+// itself, one atomic per wave and label (a corpus without duplicates issues none).
+__global__ void dedup_flatten_kernel(uint32_t* parent, size_t n, const uint64_t* __restrict__ ids,
+                                     uint32_t* __restrict__ labels, uint64_t* __restrict__ rep_ids,
+                                     uint8_t* __restrict__ keep, uint32_t* sizes, uint64_t* stats) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const bool in = i < n;
+    uint32_t l = 0;
+    if (in) {
+        l = ucfp::uf_find(parent, (uint32_t)i);
+        labels[i] = l;
+        if (rep_ids) rep_ids[i] = ids[l];
+        if (keep) keep[i] = l == (uint32_t)i;
+    }
+    const bool dup = in && l != (uint32_t)i;
+    const uint64_t roots = __ballot(in && !dup), rest = __ballot(dup);
+    uint64_t todo = rest;
+    while (todo) {
+        const int s = __ffsll((unsigned long long)todo) - 1;
+        const uint32_t l0 = (uint32_t)__shfl((int)l, s, 64);
+        const uint64_t same = __ballot(dup && l == l0);
+        if (lane == s) __hip_atomic_fetch_add(sizes + l0, (uint32_t)__popcll(same), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        todo &= ~same;
+    }
+    if (lane == 0) {
+        if (roots) __hip_atomic_fetch_add(stats + 1, (uint64_t)__popcll(roots), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (rest) __hip_atomic_fetch_add(stats + 2, (uint64_t)__popcll(rest), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// largest = 1 + the largest count of other rows (stats[3] starts at 1)
+__global__ void dedup_largest_kernel(const uint32_t* __restrict__ sizes, size_t n, uint64_t* stats) {
+    uint32_t m = 0;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const uint32_t v = sizes[i];
+        m = v > m ? v : m;
+    }
+    for (int d = 32; d; d >>= 1) {
+        const uint32_t o = (uint32_t)__shfl_xor((int)m, d, 64);
+        m = o > m ? o : m;
+    }
+    if ((threadIdx.x & 63) == 0 && m)
+        __hip_atomic_fetch_max(stats + 3, (uint64_t)m + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 }  // namespace
 
 struct ucfp_lsh {
@@ -181,6 +372,7 @@ struct ucfp_lsh {
     size_t n = 0;
     std::mutex mu;
     DevArr keys_a, keys_b, rows_a, rows_b, sigs, ids, tmp;
+    DevArr parent, sizes, stats;   // dedup workspace: the forest, per-label counts, stats of a call without d_out_stats
     uint64_t* skeys = nullptr;   // sorted keys, band-major
     uint32_t* srows = nullptr;   // rows in sorted order
 };
@@ -228,6 +420,9 @@ void ucfp_lsh_destroy(ucfp_lsh* l) {
     l->sigs.release();
     l->ids.release();
     l->tmp.release();
+    l->parent.release();
+    l->sizes.release();
+    l->stats.release();
     delete l;
 }
 
@@ -279,6 +474,45 @@ int ucfp_lsh_query_dev(ucfp_lsh* l, const uint8_t* d_query_records, size_t nq, u
     hipLaunchKernelGGL(lsh_query_kernel, dim3((unsigned)nq), dim3(64), 0, st, d_query_records, (uint32_t)nq, l->skeys,
                        l->srows, l->n, l->bands, l->rows, l->cand_per_band, (const uint64_t*)l->sigs.p,
                        (const uint64_t*)l->ids.p, k, d_out_ids, d_out_scores, d_out_counts);
+    HIP_TRY(hipGetLastError());
+    return UCFP_OK;
+}
+
+int ucfp_lsh_dedup_dev(ucfp_lsh* l, uint32_t min_agree, uint32_t span, uint32_t* d_out_labels, uint64_t* d_out_rep_ids,
+                       uint8_t* d_out_keep, uint64_t* d_out_stats, void* stream) {
+    if (!l) return capi_fail(UCFP_E_INVALID, "lsh is NULL");
+    if (min_agree == 0 || min_agree > 128)
+        return capi_fail(UCFP_E_INVALID, "min_agree must be in [1, 128] (got %u)", min_agree);
+    std::lock_guard<std::mutex> lk(l->mu);
+    const size_t n = l->n;
+    if (n && !d_out_labels) return capi_fail(UCFP_E_INVALID, "labels buffer is NULL");
+    HIP_TRY(hipSetDevice(l->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) {
+        if (d_out_stats) HIP_TRY(hipMemsetAsync(d_out_stats, 0, 4 * sizeof(uint64_t), st));
+        return UCFP_OK;
+    }
+    int rc;
+    if ((rc = l->parent.ensure(n * 4)) || (rc = l->sizes.ensure(n * 4)) || (rc = l->stats.ensure(4 * 8))) return rc;
+    uint32_t* parent = l->parent.as<uint32_t>();
+    uint32_t* sizes = l->sizes.as<uint32_t>();
+    uint64_t* stats = d_out_stats ? d_out_stats : l->stats.as<uint64_t>();
+    const unsigned row_blocks = (unsigned)((n + 255) / 256);
+    hipLaunchKernelGGL(dedup_init_kernel, dim3(row_blocks), dim3(256), 0, st, parent, sizes, n, stats);
+    // UCFP_LSH_DEDUP_NO_SKIP=1 verifies every candidate, also those whose rows share a root already (same results;
+    // for measurements and tests)
+    const char* ns = getenv("UCFP_LSH_DEDUP_NO_SKIP");
+    const int skip = !(ns && ns[0] == '1');
+    const size_t ntiles = ((n + 63) / 64) * l->bands;
+    const size_t want = (ntiles + kLinkBlock / 64 - 1) / (kLinkBlock / 64);
+    const unsigned link_blocks = (unsigned)(want < 8192 ? want : 8192);   // the rest by grid stride
+    hipLaunchKernelGGL(dedup_link_kernel, dim3(link_blocks), dim3(kLinkBlock), 0, st, l->skeys, l->srows, n, l->bands,
+                       (const uint64_t*)l->sigs.p, parent, (uint64_t)(span ? span : kDedupDefaultSpan), min_agree, skip,
+                       stats);
+    hipLaunchKernelGGL(dedup_flatten_kernel, dim3(row_blocks), dim3(256), 0, st, parent, n, (const uint64_t*)l->ids.p,
+                       d_out_labels, d_out_rep_ids, d_out_keep, sizes, stats);
+    hipLaunchKernelGGL(dedup_largest_kernel, dim3(row_blocks < 256 ? row_blocks : 256), dim3(256), 0, st, sizes, n,
+                       stats);
     HIP_TRY(hipGetLastError());
     return UCFP_OK;
 }

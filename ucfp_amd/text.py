@@ -12,6 +12,7 @@ characters is canonicalised (NFKC + case fold + Bidi/Cf stripping, text.rs:112-1
 host business (SURVEY "hard parts").
 """
 import ctypes as C
+import math
 import unicodedata
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence, Tuple
@@ -20,7 +21,7 @@ import numpy as np
 
 from . import _lib
 from .core import Modality, Record
-from .errors import ModalityError, UnsupportedError
+from .errors import InvalidArgument, ModalityError, UnsupportedError
 
 DEFAULT_K = 5        # text.rs:39
 DEFAULT_H = 128      # text.rs:41
@@ -318,9 +319,34 @@ def lsh_band_keys(records, bands: int = 16, rows: int = 8, ctx=None) -> np.ndarr
     return d_k[:, :n].t().contiguous().cpu().numpy().view(np.uint64)
 
 
+def min_agree_for(threshold: float) -> int:
+    """Smallest slot agreement whose Jaccard estimate (agree / 128) reaches `threshold`, 0 < threshold <= 1:
+    max(1, ceil(threshold * 128)); the product by 128 is exact in binary floating point."""
+    t = float(threshold)
+    if not 0.0 < t <= 1.0:      # also rejects NaN
+        raise InvalidArgument(f"threshold must be in (0, 1] (got {threshold!r})")
+    return max(1, math.ceil(t * 128.0))
+
+
+SPAN_ALL = 0xFFFFFFFF   # dedup: every pair of a run of equal band keys
+
+
+@dataclass
+class DedupResult:
+    """`LshIndex.dedup`: per row the smallest row of its cluster, that row's record id and whether the row is it."""
+    labels: np.ndarray      # uint32 [n]
+    rep_ids: np.ndarray     # uint64 [n]
+    keep: np.ndarray        # bool [n]
+    pairs: int              # candidate pairs over all bands (a pair counts once per band it appears in)
+    clusters: int
+    duplicates: int
+    largest: int
+
+
 class LshIndex:
     """Banded MinHash LSH shard on the GPU: `build` sorts (band key, row) per band, `query` returns
-    the best k candidates by slot agreement (the MinHash Jaccard estimate)."""
+    the best k candidates by slot agreement (the MinHash Jaccard estimate), `dedup` the near-duplicate
+    clusters of the built rows."""
 
     def __init__(self, bands: int = 16, rows: int = 8, cand_per_band: int = 64, ctx=None):
         self._lib = _lib.load()
@@ -367,6 +393,30 @@ class LshIndex:
         return (o_ids[:nq].cpu().numpy().view(np.uint64), o_sc[:nq].cpu().numpy(),
                 o_ct[:nq].cpu().numpy().view(np.uint32))
 
+    def dedup_dev(self, min_agree: int, span: int, labels_ptr: int, rep_ids_ptr: int = 0, keep_ptr: int = 0,
+                  stats_ptr: int = 0, stream: int = 0) -> None:
+        """Stream-ordered: labels uint32 [n] (required), rep_ids uint64 [n], keep uint8 [n], stats uint64 [4]."""
+        _lib.check(self._lib.ucfp_lsh_dedup_dev(self.handle, min_agree, span, labels_ptr or None, rep_ids_ptr or None,
+                                                keep_ptr or None, stats_ptr or None, stream or None))
+
+    def dedup(self, threshold: float = 0.8, *, min_agree: Optional[int] = None, span: int = 16) -> DedupResult:
+        """Near-duplicate clusters of the rows of the last build: rows that share a band key, lie within `span`
+        places of each other in that key's run (SPAN_ALL: the whole run) and agree in at least `min_agree` slots
+        (default: min_agree_for(threshold)) are joined; clusters are the connected components."""
+        import torch
+        if min_agree is None:
+            min_agree = min_agree_for(threshold)
+        n = self.n
+        d_lab = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")
+        d_rep = torch.empty(max(n, 1), dtype=torch.int64, device="cuda")
+        d_keep = torch.empty(max(n, 1), dtype=torch.uint8, device="cuda")
+        d_st = torch.empty(4, dtype=torch.int64, device="cuda")
+        self.dedup_dev(min_agree, span, d_lab.data_ptr(), d_rep.data_ptr(), d_keep.data_ptr(), d_st.data_ptr(),
+                       torch.cuda.current_stream().cuda_stream)
+        st = d_st.cpu().numpy().view(np.uint64)
+        return DedupResult(d_lab[:n].cpu().numpy().view(np.uint32), d_rep[:n].cpu().numpy().view(np.uint64),
+                           d_keep[:n].cpu().numpy().astype(bool), int(st[0]), int(st[1]), int(st[2]), int(st[3]))
+
     def close(self):
         if getattr(self, "handle", None):
             self._lib.ucfp_lsh_destroy(self.handle)
@@ -377,3 +427,30 @@ class LshIndex:
             self.close()
         except Exception:
             pass
+
+
+def dedup_corpus(texts: Sequence[str], threshold: float = 0.8, opts: Optional[TextOpts] = None, bands: int = 16,
+                 rows: int = 8, span: int = 16, ctx=None):
+    """The de-duplication recipe end to end: MinHash-128 of every document, a band index over the documents that
+    hashed (status 0) with their position in `texts` as id, near-duplicate clusters at `threshold`.
+    -> (keep bool [n], labels int64 [n] = position of the kept representative, status int32 [n]).
+    A document whose status is not 0 (no tokens, oversized token) is its own cluster: kept, its own label, never
+    the representative of another."""
+    min_agree = min_agree_for(threshold)
+    n = len(texts)
+    keep = np.ones(n, bool)
+    labels = np.arange(n, dtype=np.int64)
+    if n == 0:
+        return keep, labels, np.zeros(0, np.int32)
+    rec, status = minhash_batch(texts, opts, ctx)
+    pos = np.flatnonzero(status == 0)
+    if pos.size:
+        idx = LshIndex(bands, rows, ctx=ctx)
+        try:
+            idx.build(pos.astype(np.uint64), rec[pos])
+            res = idx.dedup(min_agree=min_agree, span=span)
+        finally:
+            idx.close()
+        keep[pos] = res.keep
+        labels[pos] = res.rep_ids.astype(np.int64)
+    return keep, labels, status

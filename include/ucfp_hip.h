@@ -417,13 +417,29 @@ int ucfp_audio_resample_linear_dev(ucfp_ctx* ctx, const float* d_in, size_t n, u
  *                           to ASCII).  A document holding a byte >= 0x80 gets status
  *                           UCFP_TEXT_NEEDS_HOST: the host canonicalises + tokenises it
  *                           (Unicode tables live there) and resubmits it as
- *   UCFP_TEXT_PRETOKENIZED  tokens already canonical, separated by single spaces.
- * status[i]: 0, UCFP_TEXT_NEEDS_HOST, UCFP_E_MODALITY (no tokens), UCFP_E_UNSUPPORTED (one token,
- * or a run of fewer than k tokens, longer than the ~1.4 KiB LDS batch).
+ *   UCFP_TEXT_PRETOKENIZED  tokens already canonical, separated by single spaces.  Every byte other
+ *                           than ' ' is a token byte, 0x00 included.
+ * status[i]: 0, UCFP_TEXT_NEEDS_HOST, UCFP_E_MODALITY (no tokens), UCFP_E_UNSUPPORTED (k - 1 tokens
+ * plus the token being read do not fit the LDS batch, see UCFP_TEXT_MAX_WINDOW_BYTES).
  */
 #define UCFP_TEXT_RAW_ASCII 0
 #define UCFP_TEXT_PRETOKENIZED 1
 #define UCFP_TEXT_NEEDS_HOST 1
+/* A document is ALWAYS hashed (never UCFP_E_UNSUPPORTED) when every window of k consecutive tokens -- the whole
+ * document when it has fewer than k tokens, the single token for SimHash -- has a canonical length (token bytes plus
+ * the k - 1 separating spaces) of at most this many bytes.  Longer windows are hashed or refused depending on where
+ * the 64-byte steps fall; a window longer than the 1536-byte batch is always refused.  A refused document's record is
+ * all zero.
+ * Derivation (text.hip): a wave keeps the canonical stream of the current batch in kCanonCap = 1536 bytes of LDS.
+ * Before each 64-byte step it demands room for the step, `cbase + ntok + 130 <= kCanonCap`, where cbase + ntok is the
+ * canonical length in use plus 1 (cbase token bytes, ntok - 1 separators).  When that fails the batch is flushed:
+ * everything is consumed except the last k - 1 complete tokens and the unfinished token, i.e. a PREFIX of one k-token
+ * window, which moves to the front.  The document is refused exactly when the check fails again right after a flush
+ * (or the flush could consume nothing because fewer than k tokens are complete -- the batch is then itself such a
+ * prefix): prefix + 1 + 130 > 1536, i.e. prefix >= 1406.  A prefix is no longer than its window, so windows of at
+ * most 1536 - 130 - 1 = 1405 bytes are never refused.  (The token cap, ntok + 33 <= 256, cannot fail after a flush:
+ * at most k <= 64 tokens are kept.) */
+#define UCFP_TEXT_MAX_WINDOW_BYTES 1405
 #define UCFP_MINHASH_BYTES 1032 /* txtfp::MinHashSig<128>: u16 schema = 1, 6 pad, 128 x u64 LE */
 /* COMPATIBILITY: the LAYOUT is txtfp's, the 128 slot VALUES are not -- txtfp 0.2.0's slot derivation could not be
  * recovered offline (the reference's golden slot 0, src/server/tests.rs:1153-1157, is not

@@ -66,13 +66,17 @@ def test_shingle_width(gpu_ctx, oracle, k):
 
 
 def test_status_codes(gpu_ctx, oracle):
-    docs = [b"", b"   ...  !!! ", b"caf\xc3\xa9 au lait", b"fine text here", b"x" * 5000 + b" tail"]
+    from ucfp_amd import text
+    docs = [b"", b"   ...  !!! ", b"caf\xc3\xa9 au lait", b"fine text here", b"x" * 5000 + b" tail",
+            b"x" * text.MAX_WINDOW_BYTES]
     g, gs = _gpu("minhash", docs)
     o, os_ = oracle.text_minhash_batch(docs)
     assert list(gs[:4]) == [-1, -1, 1, 0] == list(os_[:4])
     assert gs[4] == -2                       # one token longer than the tile: unsupported on the HIP path
     assert not g[0].any() and not g[1].any() and not g[2].any()
     assert np.array_equal(g[3], o[3])
+    assert gs[5] == 0 == os_[5] and np.array_equal(g[5], o[5])   # the longest window that is always supported
+    assert not g[4].any()
 
 
 def test_pretokenized_and_unicode_host_path(gpu_ctx, oracle):

@@ -36,6 +36,9 @@ constexpr int kWavesPerBlock = 4;
 constexpr int kTokCap = 256;        // tokens per LDS batch
 constexpr int kCanonCap = 1536;     // canonical bytes per LDS batch
 constexpr int kStepTok = 33;        // a 64-byte step can open at most 32 (+1 carried) tokens
+constexpr int kStepRoom = 130;      // canonical bytes a step may add (64 + 32 separators), with margin
+// what survives a flush is a prefix of one k-token window: it must leave room for the next step (derivation in ucfp_hip.h)
+static_assert(kCanonCap - kStepRoom - 1 == UCFP_TEXT_MAX_WINDOW_BYTES, "the documented -2 limit follows these constants");
 
 struct WaveLds {
     uint8_t stage[256 + 8];
@@ -60,7 +63,7 @@ __device__ __forceinline__ int cls(uint32_t c) {
 }
 
 __device__ __forceinline__ bool inword(uint32_t p, uint32_t c, uint32_t q, bool pretok) {
-    if (pretok) return c != ' ' && c != 0;
+    if (pretok) return c != ' ';   // every other byte, 0x00 included (the caller's `pos < len` guards the padding)
     const int cc = cls(c), pc = cls(p), qc = cls(q);
     const bool mid_l = (cc == C_ML || cc == C_MNL) && pc == C_L && qc == C_L;   // WB6/7
     const bool mid_n = (cc == C_MN || cc == C_MNL) && pc == C_N && qc == C_N;   // WB11/12
@@ -227,9 +230,9 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void text_hash_kernel(
             const size_t pos = base + 64 * sub + lane;
             if (base + 64 * sub >= len) break;
             // make room: a step opens at most 32 tokens and writes at most 64 + 32 bytes
-            if (ntok + kStepTok > (uint32_t)kTokCap || cbase + ntok + 130 > (uint32_t)kCanonCap) {
+            if (ntok + kStepTok > (uint32_t)kTokCap || cbase + ntok + kStepRoom > (uint32_t)kCanonCap) {
                 flush(false);
-                if (ntok + kStepTok > (uint32_t)kTokCap || cbase + ntok + 130 > (uint32_t)kCanonCap) too_long = true;
+                if (ntok + kStepTok > (uint32_t)kTokCap || cbase + ntok + kStepRoom > (uint32_t)kCanonCap) too_long = true;
                 if (too_long) break;
             }
             const uint32_t c = L.stage[64 * sub + lane];

@@ -39,6 +39,10 @@ FORMAT_VERSION_MINHASH_HIP = 0x48500001
 RAW_ASCII, PRETOKENIZED = 0, 1
 NEEDS_HOST = 1
 MINHASH_BYTES, SIMHASH_BYTES = 1032, 8
+# UCFP_TEXT_MAX_WINDOW_BYTES (include/ucfp_hip.h, derived there): a document is always hashed when every window of k
+# consecutive tokens (the whole document below k tokens, the single token for SimHash) has at most this many
+# canonical bytes, separators included; longer windows may get status -2.
+MAX_WINDOW_BYTES = 1405
 
 # txtfp::config_hash is not available offline and could not be reconstructed (DESIGN section 2 lists what was
 # tried).  The ONE value the reference's tests show (src/server/tests.rs:1158-1161: default canonicalizer,
@@ -220,7 +224,8 @@ def _raise_for(status: int):
     if status == -1:
         raise ModalityError("text has no tokens after canonicalisation")
     if status == -2:
-        raise UnsupportedError("a token (or a run of fewer than k tokens) exceeds the ~1.4 KiB LDS batch")
+        raise UnsupportedError(f"k - 1 tokens plus the token being read do not fit the LDS batch: every window of k "
+                               f"consecutive tokens of up to {MAX_WINDOW_BYTES} bytes (separators included) is supported")
     if status != 0:
         raise ModalityError(f"text fingerprint failed with status {status}")
 

@@ -684,7 +684,8 @@ int ucfp_index_search(ucfp_index* idx, uint32_t tenant, const void* queries, siz
                       uint64_t* out_ids, float* out_scores, uint32_t* out_dist, uint32_t* out_counts);
 /* Same with device pointers, enqueued on `stream` (no synchronisation).  Searches enqueued on different streams are ordered
  * only where they share a workspace: a HAMMING64 index alternates between two, so two batches may be in flight at once
- * (the short staging kernels of one run under the matrix-core scan of the other); cosine searches run one at a time. */
+ * (the short staging kernels of one run under the matrix-core scan of the other); cosine searches run one at a time.
+ * COSINE_F32: any 4-byte-aligned d_queries pointer is accepted; a pointer that is not 16-byte aligned costs one device copy. */
 int ucfp_index_search_dev(ucfp_index* idx, uint32_t tenant, const void* d_queries, size_t nq, uint32_t k,
                           uint64_t* d_out_ids, float* d_out_scores, uint32_t* d_out_dist,
                           uint32_t* d_out_counts, void* stream);

@@ -1004,3 +1004,167 @@ def test_hamming_few_tiles_pipeline_drain(gpu_ctx, oracle):
             g_ids, _, g_d, g_c = ix.search(0, queries, k)
             assert np.array_equal(g_c, o_c) and np.array_equal(g_d, o_d) and np.array_equal(g_ids, o_ids), (nq, k)
     ix.close()
+
+
+# ---- small shards: every key kernel of cosine.hip's dispatch against the float64 reference (tests/cosine_ref.py) ----
+# (n, dim, nq, k, kernel family, the branch the case is aimed at)
+COSINE_SMALL_SHARD_CASES = [
+    # cosine_keys, the VALU kernel: dim % 4 != 0, or a dim whose MFMA query image does not fit LDS (dim >= 2481)
+    (3001, 101, 16, 10, "valu", "one full pass of kQT = 16 queries, scalar row loads, ragged last row block"),
+    (2000, 67, 37, 5, "valu", "passes of 16 + 16 + 5 written at keymat + p0 * n"),
+    (600, 2305, 31, 10, "valu", "pass cut to 15 by LDS fit (15 + 15 + 1), 135 KiB of LDS: the attribute branch"),
+    (500, 2496, 20, 10, "valu", "dim % 4 == 0 without MFMA room: the vector-load branch, passes of 14 + 6"),
+    (200, 9001, 9, 3, "valu", "pass cut to 4 (4 + 4 + 1)"),
+    (96, 18436, 3, 5, "valu", "one query per pass from dim 18433, vector loads"),
+    (64, 36864, 2, 4, "valu", "the widest supported dim: one query row fills the 144 KiB"),
+    (1, 33, 5, 3, "valu", "a single row"),
+    (31, 33, 16, 128, "valu", "one partial 32-row block, k above n"),
+    (33, 35, 16, 8, "valu", "a second block with one live row"),
+    (4097, 10, 3, 10, "valu", "n >= 4096 and <= 4 queries, but dim % 4 != 0: not the stream kernel"),
+    (1500, 3, 16, 10, "valu", "dim below one float4, 16 queries"),
+    # cosine_keys_mfma<G, FULL, dense>
+    (3000, 256, 20, 10, "mfma", "G = 2, FULL"),
+    (3000, 256, 48, 10, "mfma", "G = 3, FULL, nq = 16 * groups"),
+    (2100, 512, 33, 7, "mfma", "G = 3, FULL, one query in the third group"),
+    (1500, 768, 48, 10, "mfma", "G = 3, FULL, dim 768"),
+    (1000, 816, 49, 10, "mfma", "the last dim with 3 groups (dim % 32 != 0: no GEMM): passes of 48 + 1"),
+    (700, 1232, 33, 5, "mfma", "the last dim with 2 groups: passes of 32 + 1"),
+    (400, 2480, 17, 10, "mfma", "the last dim with 1 group, the largest LDS image: passes of 16 + 1"),
+    (1, 256, 20, 1, "mfma", "a single row: one partial tile, G = 2 FULL"),
+    (15, 512, 17, 128, "mfma", "one partial tile, k above n"),
+    (17, 768, 5, 20, "mfma", "a second tile with one live row, k above n"),
+    # n = 4096 switches the 1 .. 4-query stream kernel and the 5 .. 16-query 4x4x1 kernel on; 512 <= dim <= 1024 the latter
+    (4095, 512, 4, 10, "mfma", "one row short of the stream kernel"),
+    (4096, 512, 4, 10, "stream", "the first n of the stream kernel"),
+    (4095, 512, 5, 10, "mfma", "one row short of the 4x4x1 kernel"),
+    (4096, 512, 5, 10, "blocks", "the first n of the 4x4x1 kernel"),
+    (4200, 508, 8, 10, "mfma", "one float4 below the 4x4x1 kernel's dims"),
+    (4200, 1028, 8, 10, "mfma", "one float4 above the 4x4x1 kernel's dims"),
+    # cosine_keys_gemm<NG>: dim % 32 == 0 and more queries than the LDS image holds
+    (1200, 832, 33, 10, "gemm", "the first dim with 2 groups, 33 queries: NG = 4"),
+    (900, 1248, 17, 10, "gemm", "the first dim with 1 group, 17 queries: NG = 4"),
+    (500, 2304, 17, 5, "gemm", "72 K slices"),
+    (17, 64, 70, 10, "gemm", "NG = 8 over two row tiles, the second with one live row"),
+]
+COSINE_BOUNDARY_NQ = [48, 49, 64, 65, 128, 129, 256, 257, 304, 305]
+COSINE_BOUNDARY_SHAPE = (2000, 64, 128)                   # n, dim, largest k
+COSINE_UNALIGNED_CASES = [(2000, 64, 300), (1500, 768, 60), (3000, 256, 20), (5000, 768, 3), (20000, 768, 12),
+                          (131_200, 64, 20)]
+COSINE_UNALIGNED_K = 10
+
+
+def _cosine_case_seed(n, dim, nq, k):
+    return n * 1_000_003 + dim * 1009 + nq * 31 + k
+
+
+_cosine_boundary_cache = []
+
+
+def _cosine_boundary_case():
+    """The pass-boundary corpus, its 305 queries and their reference (best 129), made once for all ten batch sizes."""
+    from cosine_ref import CosineRef, make_case
+    if not _cosine_boundary_cache:
+        n, dim, kmax = COSINE_BOUNDARY_SHAPE
+        ids, rows, queries = make_case(n, dim, max(COSINE_BOUNDARY_NQ), _cosine_case_seed(n, dim, 0, kmax))
+        _cosine_boundary_cache.append((ids, rows, queries, CosineRef(ids, rows, queries, kmax)))
+    return _cosine_boundary_cache[0]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,dim,nq,k,family,aim", COSINE_SMALL_SHARD_CASES,
+                         ids=[f"{c[4]}-{c[0]}x{c[1]}-q{c[2]}-k{c[3]}" for c in COSINE_SMALL_SHARD_CASES])
+def test_cosine_small_shard_dispatch(gpu_ctx, n, dim, nq, k, family, aim):
+    """Every key kernel launch_cosine_keys can pick on a small shard, at the shapes where its branches change (the table above),
+    against the float64 reference: counts, scores within COS_TOL, ids wherever the reference's gaps decide them (the k-th
+    place included unless it really ties with the (k+1)-th), copies of one row with bit-equal scores in id order, and never
+    a zero, NaN or Inf row -- each case plants those beside query 0's best match (cosine_ref.make_case).
+    Largest |score - reference| seen on an MI355X, per kernel family (COS_TOL is 1e-5; each case prints its own figure as
+    `COSDEV family (case) deviation`):
+      valu   7.2e-7 at (64, 36864, 2, 4); 2.4e-7 at dim 18436, 1.2e-7 at dims 2305 .. 9001
+      mfma   1.1e-6 at (400, 2480, 17, 10)            gemm      1.6e-6 at (500, 2304, 17, 5)
+      stream 1.2e-7 at (4096, 512, 4, 10)             blocks    1.2e-7 at (4096, 512, 5, 10)
+      test_cosine_pass_boundaries 2.0e-7 (every batch size)    test_cosine_unaligned_device_queries 7.7e-7 at (1500, 768, 60)"""
+    from cosine_ref import CosineRef, make_case
+    from ucfp_amd import index
+    ids, rows, queries = make_case(n, dim, nq, _cosine_case_seed(n, dim, nq, k))
+    ref = CosineRef(ids, rows, queries, k)
+    ix = index.DeviceIndex(index.COSINE_F32, dim, ctx=gpu_ctx)
+    ix.upsert(0, ids, rows)
+    assert ix.size(0) == n
+    g_ids, g_sc, _, g_c = ix.search(0, queries, k)
+    ix.close()
+    dev = ref.check(g_ids, g_sc, g_c, k, COS_TOL)
+    print(f"COSDEV {family} ({n}, {dim}, {nq}, {k}) {dev:.3e}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nq", COSINE_BOUNDARY_NQ)
+def test_cosine_pass_boundaries(gpu_ctx, nq):
+    """Batch sizes on both sides of every pass boundary over one 2000 x 64 corpus (3 query groups fit LDS): 48 = 16 * groups
+    (the MFMA kernel) and 49 (GEMM), the GEMM instances at 64 / 65 and 128 / 129, a full pass of 256, and last passes of 1
+    and 48 (MFMA again) and 49 (GEMM again) behind it; k = 10 and the largest k."""
+    from ucfp_amd import index
+    ids, rows, queries, ref = _cosine_boundary_case()
+    n, dim, kmax = COSINE_BOUNDARY_SHAPE
+    ix = index.DeviceIndex(index.COSINE_F32, dim, ctx=gpu_ctx)
+    ix.upsert(0, ids, rows)
+    for k in (10, kmax):
+        g_ids, g_sc, _, g_c = ix.search(0, queries[:nq], k)
+        dev = ref.check(g_ids, g_sc, g_c, k, COS_TOL)
+        print(f"COSDEV boundary ({n}, {dim}, {nq}, {k}) {dev:.3e}")
+    ix.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,dim,nq", COSINE_UNALIGNED_CASES)
+def test_cosine_unaligned_device_queries(gpu_ctx, torch_cuda, n, dim, nq):
+    """ucfp_index_search_dev takes any 4-byte-aligned query pointer: queries one float into a device buffer must give, bit for
+    bit, the answer of the same queries at the buffer's start, and the reference's.  (The pass size and most key kernels
+    assume 16-byte alignment; index.hip copies such queries once.  Before that, 300 queries over dim 64 asked the 3-group
+    MFMA kernel for 16 groups and most of the key matrix was never written.)  GEMM passes, the MFMA kernel, the stream and
+    4x4x1 kernels, and the f16-minima pruned pass at 131 200 rows."""
+    torch = torch_cuda
+    from cosine_ref import CosineRef, make_case
+    from ucfp_amd import index
+    k = COSINE_UNALIGNED_K
+    ids, rows, queries = make_case(n, dim, nq, _cosine_case_seed(n, dim, nq, k))
+    ref = CosineRef(ids, rows, queries, k)
+    ix = index.DeviceIndex(index.COSINE_F32, dim, ctx=gpu_ctx)
+    ix.upsert(0, ids, rows)
+    buf = torch.zeros(nq * dim + 4, dtype=torch.float32, device="cuda")
+    assert buf.data_ptr() % 16 == 0
+    stream = torch.cuda.current_stream().cuda_stream
+    answers = []
+    for shift in (0, 1):
+        buf.zero_()
+        buf[shift:shift + nq * dim] = torch.from_numpy(queries.reshape(-1)).cuda()
+        o_ids = torch.full((nq, k), -1, dtype=torch.int64, device="cuda")
+        o_sc = torch.zeros((nq, k), dtype=torch.float32, device="cuda")
+        o_c = torch.zeros((nq,), dtype=torch.int32, device="cuda")
+        ix.search_dev(0, buf.data_ptr() + 4 * shift, nq, k, o_ids.data_ptr(), o_sc.data_ptr(), 0, o_c.data_ptr(), stream)
+        torch.cuda.synchronize()
+        answers.append((o_ids.cpu().numpy().view(np.uint64), o_sc.cpu().numpy(), o_c.cpu().numpy().view(np.uint32)))
+    ix.close()
+    (a_ids, a_sc, a_c), (u_ids, u_sc, u_c) = answers
+    dev = ref.check(u_ids, u_sc, u_c, k, COS_TOL)
+    print(f"COSDEV unaligned ({n}, {dim}, {nq}, {k}) {dev:.3e}")
+    ref.check(a_ids, a_sc, a_c, k, COS_TOL)
+    assert np.array_equal(a_c, u_c) and np.array_equal(a_ids, u_ids) and np.array_equal(a_sc.view(np.uint32), u_sc.view(np.uint32))
+
+
+@pytest.mark.gpu
+def test_cosine_dim_beyond_lds_is_unsupported(gpu_ctx):
+    """Index creation accepts dims up to 65536, but a search needs one query row in 144 KiB of LDS: from dim 36865 on it is
+    refused with UCFP_E_UNSUPPORTED naming the dim, while create, upsert and size work (dim 36864 is searched above)."""
+    from ucfp_amd import index
+    from ucfp_amd.errors import UnsupportedError
+    dim, n = 36868, 8
+    rng = np.random.default_rng(dim)
+    rows = rng.standard_normal((n, dim), dtype=np.float32)
+    ix = index.DeviceIndex(index.COSINE_F32, dim, ctx=gpu_ctx)
+    ix.upsert(0, np.arange(n, dtype=np.uint64), rows)
+    assert ix.size(0) == n
+    with pytest.raises(UnsupportedError, match=str(dim)):
+        ix.search(0, rows[:2], 3)
+    assert ix.size(0) == n
+    ix.close()

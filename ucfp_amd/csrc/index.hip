@@ -223,6 +223,13 @@ int search_shard_dev(ucfp_index* ix, const Shard* s, const void* d_queries, size
     }
     const int qpp = ucfp::cosine_queries_per_pass(dim, nq);
     if (qpp < 1) return capi_fail(UCFP_E_UNSUPPORTED, "cosine dim %u does not fit one query row in LDS", dim);
+    // The key kernels pick their form from the query pointer's alignment, and the pass size above assumes the aligned forms:
+    // queries that are not 16-byte aligned are copied once into the workspace (o_qal, below) and every pass reads the copy.
+    // Until the workspace exists, `q_shape` stands for that copy in the shape predicates below: they ask only how the
+    // pointer is aligned, and kAligned16 is aligned as the copy will be.
+    alignas(16) static const float kAligned16[4] = {0.f, 0.f, 0.f, 0.f};
+    const bool q_copy = (reinterpret_cast<uintptr_t>(d_queries) & 15u) != 0;
+    const float* q_shape = q_copy ? kAligned16 : reinterpret_cast<const float*>(d_queries);
     // chunk the query batch so the key matrix stays under ~2 GiB
     size_t chunk = (size_t)2048 * 1024 * 1024 / (4 * n);
     if (chunk < (size_t)qpp) chunk = qpp;
@@ -275,11 +282,11 @@ int search_shard_dev(ucfp_index* ix, const Shard* s, const void* d_queries, size
     // cosine_mins_eps of the exact score, the thresholds widened by as much), else from the f32 tile (<= 48 queries)
     // (larger batches: passes of at most 64 queries, each its own chain)
     const bool prune_f16 = !getenv("UCFP_COSINE_NO_F16") &&
-                           ucfp::cosine_mins_f16_ok(reinterpret_cast<const float*>(s->rows), dim,
-                                                    reinterpret_cast<const float*>(d_queries), (uint32_t)(nq < 64 ? nq : 64), n, k);
+                           ucfp::cosine_mins_f16_ok(reinterpret_cast<const float*>(s->rows), dim, q_shape,
+                                                    (uint32_t)(nq < 64 ? nq : 64), n, k);
     const bool may_prune = prune_f16 || (nq <= 48 && nq <= (size_t)qpp &&
-                                         ucfp::cosine_prune_ok(reinterpret_cast<const float*>(s->rows), dim,
-                                                               reinterpret_cast<const float*>(d_queries), (uint32_t)nq, n, k));
+                                         ucfp::cosine_prune_ok(reinterpret_cast<const float*>(s->rows), dim, q_shape, (uint32_t)nq,
+                                                               n, k));
     const uint32_t p_capq = ucfp::cosine_prune_plan(n, (uint32_t)fq, k, true).capq;
     const size_t o_pmin = off;
     off = align256(off + (may_prune ? (n / 16 + 1) * 64 * 4 + 64 : 0));
@@ -299,13 +306,16 @@ int search_shard_dev(ucfp_index* ix, const Shard* s, const void* d_queries, size
     off = align256(off + fq * p_capq * 16 * 4);
     const size_t o_pflag = off;   // [0] fallback flag, [1] listed chunks
     off = align256(off + 256);
+    const size_t o_qal = off;     // the aligned copy of the queries
+    off = align256(off + (q_copy ? nq * dim * 4 : 0));
     int rc = ix->ws_slot[ix->ws_cur].ensure(off);
     if (rc) return rc;
     uint8_t* w = ix->ws_slot[ix->ws_cur].p;
+    if (q_copy) HIP_TRY(hipMemcpyAsync(w + o_qal, d_queries, nq * dim * 4, hipMemcpyDeviceToDevice, st));
     float* qn = reinterpret_cast<float*>(w + o_qn);
     uint32_t* keymat = reinterpret_cast<uint32_t*>(w + o_keys);
     uint32_t* okeys = d_out_keys ? d_out_keys : reinterpret_cast<uint32_t*>(w + o_ok);
-    const float* q = reinterpret_cast<const float*>(d_queries);
+    const float* q = q_copy ? reinterpret_cast<const float*>(w + o_qal) : reinterpret_cast<const float*>(d_queries);
     const float* rows = reinterpret_cast<const float*>(s->rows);
     uint64_t* pid = reinterpret_cast<uint64_t*>(w + o_pid);
     uint32_t* pk = reinterpret_cast<uint32_t*>(w + o_pk);

@@ -324,6 +324,43 @@ int ucfp_audio_wang_batch_dev(ucfp_ctx* ctx, const float* d_pcm, const uint64_t*
                               uint32_t sample_rate, const ucfp_wang_config* cfg, uint8_t* d_out, size_t cap_hashes,
                               uint64_t* d_out_offsets, void* stream);
 
+/* PANAKO triplets: audio::fingerprint_panako / fingerprint_panako_with (src/modality/audio.rs:106-156,
+ * the seam is the extract call at audio.rs:136-139) behind ?algorithm=panako (src/server/handlers.rs:778-836).  The
+ * front end is Wang's (8 kHz, 1024 / 128 STFT, 62.5 frames/s, peaks_per_sec strongest peaks per second); an anchor above
+ * the magnitude floor joins PAIRS of peaks of its target zone into triplets (a, b, c), at most fan_out per anchor.
+ * A record is 16 bytes, little-endian: u32 hash = f_a(9) | f_b(9) | f_c(9) | r(5) with r = min(31, 32 (t_b - t_a) /
+ * (t_c - t_a)), then u32 t_anchor, u32 t_b, u32 t_c in frames (LandmarkScatter.svelte:5, :31-35).  Output buffers
+ * must be 16-byte aligned (UCFP_E_INVALID otherwise).  The entries mirror the Wang ones: same limits, same errors. */
+typedef struct ucfp_panako_config { /* audiofp PanakoConfig; defaults and ranges algorithms_manifest.rs:601-650 */
+    uint32_t fan_out;          /* 5   (1 .. 64)   triplets per anchor */
+    uint32_t target_zone_t;    /* 96  (1 .. 512)  frames */
+    uint32_t target_zone_f;    /* 96  (1 .. 1024) bins */
+    uint32_t peaks_per_sec;    /* 30  (1 .. 256) */
+    float min_anchor_mag_db;   /* -50 (-120 .. 0, dB re full-scale sine) */
+} ucfp_panako_config;
+
+#define UCFP_PANAKO_HASH_BYTES 16 /* u32 LE hash, t_anchor, t_b, t_c (LandmarkScatter.svelte:5, AlgorithmView.svelte:134) */
+
+/* Upper bound on the records n samples at 8 kHz can produce: seconds * peaks_per_sec * fan_out. */
+size_t ucfp_audio_panako_max_hashes(size_t n_samples, const ucfp_panako_config* cfg);
+/* Host buffers, 8 kHz only (UCFP_E_MODALITY otherwise, src/server/tests.rs:391); *n_hashes receives the number produced
+ * (if it exceeds cap_hashes the output is truncated and UCFP_E_INVALID is returned). cfg NULL = defaults. */
+int ucfp_audio_panako(ucfp_ctx* ctx, const float* pcm, size_t n, uint32_t sample_rate, const ucfp_panako_config* cfg,
+                      uint8_t* out, size_t cap_hashes, size_t* n_hashes);
+/* Device buffers; d_n_hashes is a device u64 (total produced, may exceed cap). No sync. */
+int ucfp_audio_panako_dev(ucfp_ctx* ctx, const float* d_pcm, size_t n, uint32_t sample_rate,
+                          const ucfp_panako_config* cfg, uint8_t* d_out, size_t cap_hashes, uint64_t* d_n_hashes,
+                          void* stream);
+/* Ragged batch, as ucfp_audio_wang_batch_dev: clip i = d_pcm[d_offsets[i] .. d_offsets[i+1]) at `sample_rate`
+ * (1 000 .. 384 000 Hz; resampled to 8 kHz inside the kernel unless it is 8000).  Records of clip i land in
+ * d_out[d_out_offsets[i] .. d_out_offsets[i+1]) (16 B each, times relative to the clip); a triplet never crosses a clip
+ * boundary.  d_out_offsets[n_clips] > cap_hashes: truncated at cap_hashes.  No synchronisation. */
+size_t ucfp_audio_panako_batch_max_hashes(size_t n_total, size_t n_clips, uint32_t sample_rate,
+                                          const ucfp_panako_config* cfg);
+int ucfp_audio_panako_batch_dev(ucfp_ctx* ctx, const float* d_pcm, const uint64_t* d_offsets, size_t n_total,
+                                size_t n_clips, uint32_t sample_rate, const ucfp_panako_config* cfg, uint8_t* d_out,
+                                size_t cap_hashes, uint64_t* d_out_offsets, void* stream);
+
 /* Host micro-batcher for clips (audio): one clip per request thread (handlers.rs:704-918); concurrent
  * submit() calls become ONE ucfp_audio_wang_batch_dev call over at most max_batch clips / max_samples samples, flushed
  * no later than max_delay_us after the first pending clip.  All clips at `sample_rate` (resampled to 8 kHz in the

@@ -1,6 +1,7 @@
 """Audio leg on its own: Wang over 44.1 kHz PCM (BASELINE config 3) -- fused (the stream kernel resamples) vs two-pass
 (ucfp_audio_resample_linear_dev + ucfp_audio_wang_dev) -- the 8 kHz stream alone, and a batch of 4-second clips
-(benches/end_to_end.rs:55-75) in clips/s.  One JSON line per case on stdout."""
+(benches/end_to_end.rs:55-75) in clips/s; then the Panako triplets (DESIGN A13) over the same 44.1 kHz stream and the
+same clip batch.  One JSON line per case on stdout."""
 import argparse
 import json
 import sys
@@ -67,6 +68,18 @@ def main():
         nh = int(oo[1].item())
         print(json.dumps({"case": "wang 44.1k fused resample", "seconds": secs, "ms": ms, "x_real_time": secs / ms * 1e3,
                           "hashes": nh, "algorithmic_GBs": (n * 4 + nh * 8) / ms / 1e6}), flush=True)
+    if a.only in ("", "panako"):
+        capp = int(lib.ucfp_audio_panako_batch_max_hashes(n, 1, sr, None))
+        outp = torch.empty((capp, 4), dtype=torch.int32, device=dev)
+
+        def panako_fused():
+            _lib.check(lib.ucfp_audio_panako_batch_dev(ctx.handle, x.data_ptr(), one.data_ptr(), n, 1, sr, None, outp.data_ptr(),
+                                                       capp, oo.data_ptr(), st))
+        msp = timeit(panako_fused, a.steps)
+        nhp = int(oo[1].item())
+        print(json.dumps({"case": "panako 44.1k fused resample", "seconds": secs, "ms": msp, "x_real_time": secs / msp * 1e3,
+                          "hashes": nhp, "algorithmic_GBs": (n * 4 + nhp * 16) / msp / 1e6}), flush=True)
+        del outp
     m = int(lib.ucfp_audio_resample_len(n, sr, 8000))
     x8 = torch.empty(m, dtype=torch.float32, device=dev)
 
@@ -85,7 +98,7 @@ def main():
         ms3 = timeit(only8k, a.steps)
         print(json.dumps({"case": "wang 8k stream alone", "seconds": secs, "ms": ms3}), flush=True)
     del x8
-    if a.only in ("", "clips"):
+    if a.only in ("", "clips", "panako"):
         # batch of 4 s clips at 8 kHz (the reference's bench clip) cut from the stream
         clip_n = 4 * 8000
         nc = a.clips
@@ -98,15 +111,26 @@ def main():
         def clips():
             _lib.check(lib.ucfp_audio_wang_batch_dev(ctx.handle, xc.data_ptr(), offs.data_ptr(), nc * clip_n, nc, 8000, None,
                                                      outc.data_ptr(), capc, ooc.data_ptr(), st))
-        msc = timeit(clips, a.steps)
-        print(json.dumps({"case": "wang batch of 4 s clips @ 8 kHz", "clips": nc, "ms": msc, "clips_per_s": nc / msc * 1e3,
-                          "hashes": int(ooc[-1].item())}), flush=True)
+        if a.only in ("", "clips"):
+            msc = timeit(clips, a.steps)
+            print(json.dumps({"case": "wang batch of 4 s clips @ 8 kHz", "clips": nc, "ms": msc, "clips_per_s": nc / msc * 1e3,
+                              "hashes": int(ooc[-1].item())}), flush=True)
 
-        def single():
-            _lib.check(lib.ucfp_audio_wang_dev(ctx.handle, xc.data_ptr(), clip_n, 8000, None, outc.data_ptr(), capc,
-                                               cnt.data_ptr(), st))
-        mss = timeit(single, 50)
-        print(json.dumps({"case": "wang ONE 4 s clip per call", "ms": mss, "clips_per_s": 1e3 / mss}), flush=True)
+            def single():
+                _lib.check(lib.ucfp_audio_wang_dev(ctx.handle, xc.data_ptr(), clip_n, 8000, None, outc.data_ptr(), capc,
+                                                   cnt.data_ptr(), st))
+            mss = timeit(single, 50)
+            print(json.dumps({"case": "wang ONE 4 s clip per call", "ms": mss, "clips_per_s": 1e3 / mss}), flush=True)
+        if a.only in ("", "panako"):
+            cappc = int(lib.ucfp_audio_panako_batch_max_hashes(nc * clip_n, nc, 8000, None))
+            outpc = torch.empty((cappc, 4), dtype=torch.int32, device=dev)
+
+            def panako_clips():
+                _lib.check(lib.ucfp_audio_panako_batch_dev(ctx.handle, xc.data_ptr(), offs.data_ptr(), nc * clip_n, nc, 8000,
+                                                           None, outpc.data_ptr(), cappc, ooc.data_ptr(), st))
+            mspc = timeit(panako_clips, a.steps)
+            print(json.dumps({"case": "panako batch of 4 s clips @ 8 kHz", "clips": nc, "ms": mspc,
+                              "clips_per_s": nc / mspc * 1e3, "hashes": int(ooc[-1].item())}), flush=True)
 
 
 if __name__ == "__main__":

@@ -1,15 +1,19 @@
 #!/usr/bin/env python3
 """Randomised differential soak of the audio fingerprints against the CPU oracle: random lengths (one frame to
-minutes), signal kinds and Wang configurations; Wang hashes and Haitsma frames must be bit-identical.
+minutes), signal kinds and Wang / Panako configurations; Wang hashes, Panako triplets (against the numpy restatement
+in tests/panako_ref.py over the oracle's peaks) and Haitsma frames must be bit-identical.
     python tools/soak_audio.py --seconds 90 --seed 1"""
 import argparse
 import os
 import sys
 import time
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(1, os.path.join(ROOT, "tests"))
 import numpy as np  # noqa: E402
 import oracle  # noqa: E402
+import panako_ref  # noqa: E402
 from ucfp_amd import _lib, audio  # noqa: E402
 
 
@@ -57,6 +61,16 @@ def main():
         g = audio.wang_hashes(x, 8000, cfg, ctx=ctx) if cfg else audio.wang_hashes(x, 8000, ctx=ctx)
         o = oracle.wang(x, ocfg, cap=max(64, g.shape[0] + 1000)) if ocfg else oracle.wang(x)
         assert g.shape == o.shape and np.array_equal(g, o), ("wang", n, rounds)
+        # Panako over the same input: the defaults, or a config drawn from the whole range of /v1/algorithms
+        pc = panako_ref.Cfg()
+        if rng.random() < 0.5:
+            pc = panako_ref.Cfg(int(rng.integers(1, 65)), int(rng.integers(1, 513)), int(rng.integers(1, 1025)),
+                                int(rng.integers(1, 257)), float(np.float32(rng.uniform(-120, 0))))
+        pcfg = audio.PanakoConfig(*pc.astuple())
+        xp = x[: 60 * 8000]                      # the restatement walks the peaks in Python: a minute is enough
+        gp = audio.panako_hashes(xp, 8000, pcfg, ctx=ctx)
+        op = panako_ref.panako_ref(oracle, xp, pc)
+        assert gp.shape == op.shape and gp.tobytes() == op.tobytes(), ("panako", xp.size, pc, rounds)
         if rounds % 4 == 1:
             # the ragged-batch entries: a mix of clip lengths (empty, under one frame, seconds, a minute) at a random source
             # rate, Wang (resampler fused into the stream kernel) and Haitsma (batched 5 kHz resample + frame map)
@@ -70,6 +84,11 @@ def main():
                 r8 = c_ if sr == 8000 else oracle.resample_linear(c_, sr, 8000)
                 o_ = oracle.wang(r8, ocfg, cap=max(64, g_.shape[0] + 1000)) if ocfg else oracle.wang(r8)
                 assert g_.shape == o_.shape and np.array_equal(g_, o_), ("wang batch", sr, c_.size, rounds)
+            gotp = audio.panako_hashes_batch(clips, sr, pcfg, ctx=ctx)
+            for c_, g_ in zip(clips, gotp):
+                r8 = c_ if sr == 8000 else oracle.resample_linear(c_, sr, 8000)
+                o_ = panako_ref.panako_ref(oracle, r8, pc)
+                assert g_.shape == o_.shape and g_.tobytes() == o_.tobytes(), ("panako batch", sr, c_.size, pc, rounds)
             goth = audio.haitsma_frames_batch(clips, sr, ctx=ctx)
             for c_, g_ in zip(clips, goth):
                 o_ = oracle.haitsma(c_, sr)

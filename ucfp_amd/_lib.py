@@ -16,6 +16,12 @@ _lib = None
 _lock = threading.Lock()
 
 
+class PanakoConfig(C.Structure):
+    """ucfp_panako_config (audiofp PanakoConfig; defaults src/server/algorithms_manifest.rs:601-650)."""
+    _fields_ = [("fan_out", C.c_uint32), ("target_zone_t", C.c_uint32), ("target_zone_f", C.c_uint32),
+                ("peaks_per_sec", C.c_uint32), ("min_anchor_mag_db", C.c_float)]
+
+
 class WangConfig(C.Structure):
     """ucfp_wang_config (audiofp WangConfig; defaults src/server/algorithms_manifest.rs:553-592)."""
     _fields_ = [("fan_out", C.c_uint32), ("target_zone_t", C.c_uint32), ("target_zone_f", C.c_uint32),
@@ -80,6 +86,14 @@ SIGNATURES = {
     "ucfp_audio_wang_batch_max_hashes": (C.c_size_t, [C.c_size_t, C.c_size_t, C.c_uint32, C.POINTER(WangConfig)]),
     "ucfp_audio_wang_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32,
                                             C.POINTER(WangConfig), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "ucfp_audio_panako_max_hashes": (C.c_size_t, [C.c_size_t, C.POINTER(PanakoConfig)]),
+    "ucfp_audio_panako": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(PanakoConfig), C.c_void_p,
+                                    C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ucfp_audio_panako_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(PanakoConfig),
+                                        C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "ucfp_audio_panako_batch_max_hashes": (C.c_size_t, [C.c_size_t, C.c_size_t, C.c_uint32, C.POINTER(PanakoConfig)]),
+    "ucfp_audio_panako_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32,
+                                              C.POINTER(PanakoConfig), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "ucfp_audio_haitsma_frames": (C.c_size_t, [C.c_size_t, C.c_uint32]),
     "ucfp_audio_haitsma": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(HaitsmaConfig),
                                      C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),

@@ -2,6 +2,7 @@
 
     fingerprint_wang(samples, sample_rate, tenant_id, record_id)              audio.rs:46-60
     fingerprint_wang_with(samples, sample_rate, cfg, tenant_id, record_id)    audio.rs:64-98
+    fingerprint_panako / fingerprint_panako_with                              audio.rs:106-156
     fingerprint_haitsma / fingerprint_haitsma_with                            audio.rs:164-224
     StreamingWangSession(sample_rate, tenant_id, record_id).push/.finalize    audio.rs:414-480
 
@@ -19,6 +20,7 @@ from .core import Modality, Record
 from .errors import ModalityError
 
 ALGORITHM_WANG = "audiofp-wang-v1"
+ALGORITHM_PANAKO = "audiofp-panako-v1"
 ALGORITHM_HAITSMA = "audiofp-haitsma-v1"
 WANG_SR, HAITSMA_SR = 8000, 5000
 
@@ -35,6 +37,20 @@ class WangConfig:
     def _c(self):
         return _lib.WangConfig(self.fan_out, self.target_zone_t, self.target_zone_f, self.peaks_per_sec,
                                self.min_anchor_mag_db)
+
+
+@dataclass
+class PanakoConfig:
+    """audiofp::classical::PanakoConfig; defaults and ranges src/server/algorithms_manifest.rs:601-650."""
+    fan_out: int = 5
+    target_zone_t: int = 96
+    target_zone_f: int = 96
+    peaks_per_sec: int = 30
+    min_anchor_mag_db: float = -50.0
+
+    def _c(self):
+        return _lib.PanakoConfig(self.fan_out, self.target_zone_t, self.target_zone_f, self.peaks_per_sec,
+                                 self.min_anchor_mag_db)
 
 
 @dataclass
@@ -150,6 +166,80 @@ class WangBatcher:
             pass
 
 
+def _aligned_records(cap: int) -> np.ndarray:
+    """uint32 [cap, 4] whose data is 16-byte aligned (the Panako entries require it)."""
+    raw = np.zeros(cap * 16 + 16, np.uint8)
+    skip = -raw.ctypes.data % 16
+    return raw[skip: skip + cap * 16].view(np.uint32).reshape(cap, 4)
+
+
+def panako_hashes(samples, sample_rate: int, cfg: Optional[PanakoConfig] = None, ctx=None) -> np.ndarray:
+    """-> uint32 [n, 4]: (hash, t_anchor, t_b, t_c) -- the byte image of audiofp's [PanakoHash] (DESIGN A13)."""
+    ctx = ctx or _lib.current_context()
+    _check_rate(sample_rate)
+    x = np.ascontiguousarray(samples, dtype=np.float32).reshape(-1)
+    c = (cfg or PanakoConfig())._c()
+    lib = _lib.load()
+    cap = max(1, int(lib.ucfp_audio_panako_max_hashes(x.size, C.byref(c))))
+    out = _aligned_records(cap)
+    n = C.c_size_t(0)
+    _lib.check(lib.ucfp_audio_panako(ctx.handle, x.ctypes.data, x.size, sample_rate, C.byref(c), out.ctypes.data,
+                                     cap, C.byref(n)))
+    return out[: n.value].copy()
+
+
+def panako_hashes_batch_dev(pcm_ptr: int, offsets_ptr: int, n_total: int, n_clips: int, sample_rate: int, out_ptr: int,
+                            cap_hashes: int, out_offsets_ptr: int, cfg: Optional[PanakoConfig] = None, stream: int = 0,
+                            ctx=None) -> None:
+    """Ragged batch of clips, device pointers, no sync (ucfp_audio_panako_batch_dev): clip i = pcm[offsets[i] ..
+    offsets[i+1]) at `sample_rate` (resampled to 8 kHz in the kernel unless it is 8000); `out_ptr` 16-byte aligned."""
+    ctx = ctx or _lib.current_context()
+    c = (cfg or PanakoConfig())._c()
+    _lib.check(_lib.load().ucfp_audio_panako_batch_dev(ctx.handle, pcm_ptr or None, offsets_ptr or None, n_total, n_clips,
+                                                       sample_rate, C.byref(c), out_ptr or None, cap_hashes,
+                                                       out_offsets_ptr, stream or None))
+
+
+def panako_hashes_batch(clips, sample_rate: int, cfg: Optional[PanakoConfig] = None, ctx=None) -> List[np.ndarray]:
+    """Host convenience over the batch entry: a list of mono f32 clips (all at `sample_rate`) -> one uint32 [n_i, 4]
+    array per clip.  One launch sequence for the whole batch."""
+    import torch
+    ctx = ctx or _lib.current_context()
+    _check_rate(sample_rate)
+    arrs = [np.ascontiguousarray(c, dtype=np.float32).reshape(-1) for c in clips]
+    if not arrs:
+        return []
+    offs = np.zeros(len(arrs) + 1, np.uint64)
+    np.cumsum([a.size for a in arrs], out=offs[1:])
+    blob = np.concatenate(arrs) if offs[-1] else np.zeros(1, np.float32)
+    c = (cfg or PanakoConfig())._c()
+    cap = max(1, int(_lib.load().ucfp_audio_panako_batch_max_hashes(int(offs[-1]), len(arrs), sample_rate, C.byref(c))))
+    dev = f"cuda:{ctx.device}"
+    d_pcm = torch.from_numpy(blob).to(dev)
+    d_off = torch.from_numpy(offs.view(np.int64)).to(dev)
+    d_out = torch.zeros((cap, 4), dtype=torch.int32, device=dev)
+    d_oo = torch.zeros(len(arrs) + 1, dtype=torch.int64, device=dev)
+    panako_hashes_batch_dev(d_pcm.data_ptr(), d_off.data_ptr(), int(offs[-1]), len(arrs), sample_rate, d_out.data_ptr(),
+                            cap, d_oo.data_ptr(), cfg, torch.cuda.current_stream().cuda_stream, ctx)
+    oo = d_oo.cpu().numpy()
+    out = d_out.cpu().numpy().view(np.uint32)
+    if oo[-1] > cap:
+        raise ModalityError(f"Panako batch produced {oo[-1]} hashes, buffer holds {cap}")
+    return [out[oo[i]:oo[i + 1]].copy() for i in range(len(arrs))]
+
+
+def panako_landmarks(record_bytes) -> np.ndarray:
+    """The identification projection of a Panako record (DESIGN A13, P7): its (hash, t_anchor) pairs, 8 bytes out of
+    each 16, as uint32 [n, 2] -- what a LandmarkIndex stores and is queried with."""
+    if isinstance(record_bytes, (bytes, bytearray, memoryview)):
+        if len(record_bytes) % 16:
+            raise ModalityError("a Panako record is a multiple of 16 bytes (u32 hash, t_anchor, t_b, t_c)")
+        rec = np.frombuffer(bytes(record_bytes), "<u4")
+    else:
+        rec = np.ascontiguousarray(record_bytes, dtype=np.uint32)
+    return np.ascontiguousarray(rec.reshape(-1, 4)[:, :2])
+
+
 def haitsma_frames(samples, sample_rate: int, cfg: Optional[HaitsmaConfig] = None, ctx=None) -> np.ndarray:
     ctx = ctx or _lib.current_context()
     _check_rate(sample_rate)
@@ -205,6 +295,15 @@ def fingerprint_wang(samples, sample_rate: int, tenant_id: int, record_id: int) 
 
 def fingerprint_wang_with(samples, sample_rate: int, cfg: WangConfig, tenant_id: int, record_id: int) -> Record:
     return _record(ALGORITHM_WANG, wang_hashes(samples, sample_rate, cfg).tobytes(), tenant_id, record_id)
+
+
+def fingerprint_panako(samples, sample_rate: int, tenant_id: int, record_id: int) -> Record:
+    return fingerprint_panako_with(samples, sample_rate, PanakoConfig(), tenant_id, record_id)
+
+
+def fingerprint_panako_with(samples, sample_rate: int, cfg: PanakoConfig, tenant_id: int, record_id: int) -> Record:
+    # tag, format_version 1, config_hash 0: audio.rs:141-155
+    return _record(ALGORITHM_PANAKO, panako_hashes(samples, sample_rate, cfg).tobytes(), tenant_id, record_id)
 
 
 def fingerprint_haitsma(samples, sample_rate: int, tenant_id: int, record_id: int) -> Record:

@@ -68,7 +68,8 @@ FORMAT_VERSION = 1  # src/lib.rs:62
 # ---- /v1/query wire types (src/server/dto.rs:74-116, handlers.rs:143-187) -----------------------------
 # The reference's request needs `vector`; the Hamming search adds ONE additive, backward-compatible field
 # (SURVEY 8b / 8f N3): `hash` (u64, or 8 little-endian bytes) with `algorithm` naming the hash space.  Audio
-# identification adds `landmarks` (DESIGN A10): Wang landmark bytes (8 per landmark) or a list of [hash, t] pairs.
+# identification adds `landmarks` (DESIGN A10): Wang landmark bytes (8 per landmark) or a list of [hash, t] pairs; with
+# `algorithm` = "audiofp-panako-v1" they are the (hash, t_anchor) pairs of Panako triplets and search that index (A13).
 # Keyword search adds `terms` (the reference's Query::terms, src/core/mod.rs:163-164; BM25, DESIGN A11) and `explain`
 # (the reference's `?explain=1`, handlers.rs:133-140): terms alone give a BM25 query, vector + terms the hybrid one.
 # Identification by bit-error rate adds `subfingerprints` (DESIGN A12): Haitsma frames as bytes (4 per frame, u32 LE) or a

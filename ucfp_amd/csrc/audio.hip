@@ -1093,6 +1093,85 @@ __global__ void wang_pair_kernel(const uint32_t* __restrict__ ptk, const float* 
     if (!EMIT) counts[i] = taken;
 }
 
+// ---- A13: Panako triplets over the same peaks (replaces the arithmetic behind audio.rs:106-156) --------------------
+// Anchor i walks its target zone exactly as wang_pair_walk does (P3); when the m-th qualifying target c arrives it
+// closes a triplet with every earlier target b = q_0 .. q_{m-1} (P4), until fan_out triplets exist.  C(12, 2) = 66 >=
+// 64, so the 12th target always ends the anchor and only 11 earlier ones are ever kept: q[] is indexed by unrolled
+// constants only and stays in registers.  One 16-byte record per triplet (P5): hash, t_a, t_b, t_c.
+constexpr int kPanakoKeep = 11;
+template <bool EMIT>
+__device__ __forceinline__ uint32_t panako_triplet_walk(const uint32_t* __restrict__ ptk, uint32_t i, uint32_t end,
+                                                        uint32_t fan_out, uint32_t zone_t, uint32_t zone_f, size_t o,
+                                                        uint4* __restrict__ out, size_t cap) {
+    const uint32_t a = ptk[i];
+    const int32_t ta = (int32_t)(a >> 9), ka = (int32_t)(a & 511u);
+    uint32_t q[kPanakoKeep];
+#pragma unroll
+    for (int s = 0; s < kPanakoKeep; s++) q[s] = 0;
+    uint32_t m = 0, taken = 0;
+    bool done = false;
+    for (uint32_t j0 = i + 1; j0 < end && !done; j0 += 8) {
+        uint32_t bb[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) bb[u] = j0 + u < end ? ptk[j0 + u] : 0xffffffffu;
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+            if (done) continue;
+            const uint32_t c = bb[u];
+            const int32_t dtc = (int32_t)(c >> 9) - ta;
+            if (dtc <= 0) continue;
+            if (dtc > (int32_t)zone_t) {
+                done = true;
+                continue;
+            }
+            const int32_t kc = (int32_t)(c & 511u);
+            int32_t df = kc - ka;
+            df = df < 0 ? -df : df;
+            if (df > (int32_t)zone_f) continue;
+#pragma unroll
+            for (int s = 0; s < kPanakoKeep; s++) {
+                if ((uint32_t)s < m && taken < fan_out) {
+                    if (EMIT && o < cap) {
+                        const uint32_t b = q[s];
+                        const uint32_t dtb = (b >> 9) - (uint32_t)ta;
+                        uint32_t r = (32u * dtb) / (uint32_t)dtc;
+                        r = r > 31u ? 31u : r;
+                        out[o] = make_uint4(((uint32_t)ka << 23) | ((b & 511u) << 14) | ((uint32_t)kc << 5) | r,
+                                            (uint32_t)ta, b >> 9, c >> 9);
+                    }
+                    o++;
+                    taken++;
+                }
+            }
+#pragma unroll
+            for (int s = 0; s < kPanakoKeep; s++)
+                if ((uint32_t)s == m) q[s] = c;
+            m++;
+            if (taken >= fan_out) done = true;
+        }
+    }
+    return taken;
+}
+
+// one thread per peak, as wang_pair_kernel: a count pass, the exclusive scan, an emit pass
+template <bool EMIT>
+__global__ void panako_triplet_kernel(const uint32_t* __restrict__ ptk, const float* __restrict__ pp,
+                                      const uint32_t* __restrict__ pc, const uint32_t* __restrict__ sec_base,
+                                      const uint32_t* __restrict__ sel_off, const uint32_t* __restrict__ np_ptr,
+                                      uint32_t fan_out, uint32_t zone_t, uint32_t zone_f, float floor_p,
+                                      uint32_t* __restrict__ counts, const uint32_t* __restrict__ offs,
+                                      uint4* __restrict__ out, size_t cap) {
+    const uint32_t np = *np_ptr;
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= np) return;
+    uint32_t taken = 0;
+    if (pp[i] >= floor_p) {
+        const uint32_t end = sel_off[sec_base[pc[i] + 1]];         // first peak of the next clip
+        taken = panako_triplet_walk<EMIT>(ptk, i, end, fan_out, zone_t, zone_f, EMIT ? offs[i] : 0, out, cap);
+    }
+    if (!EMIT) counts[i] = taken;
+}
+
 __global__ void copy_u32_kernel(const uint32_t* __restrict__ src, uint64_t* __restrict__ dst) { *dst = *src; }
 
 // ---- the ragged batch: clip table, segment -> clip and second -> clip maps, per-clip hash offsets ----
@@ -1481,18 +1560,11 @@ WangWs wang_ws_layout(size_t n_src_total, size_t n_clips, uint32_t sr_in, uint32
     return w;
 }
 
-// pcm: the batch buffer; d_offsets: n_clips + 1 device offsets into it (nullptr: one clip [0, n_src_total)); sr_in: the
-// clips' sample rate (8000: taken as is; anything else: resampled to 8 kHz inside the stream kernel, A1);
-// d_out_off: n_clips + 1 hash offsets (may be nullptr); out_count: total hashes produced (may be nullptr)
-int launch_wang_batch(const float* pcm, const uint64_t* d_offsets, size_t n_src_total, size_t n_clips, uint32_t sr_in,
-                      uint32_t fan_out, uint32_t zone_t, uint32_t zone_f, uint32_t pps,
-                      float floor_power, uint8_t* ws, const WangWs& w, uint32_t* out, size_t cap, uint64_t* d_out_off,
-                      uint64_t* out_count, hipStream_t stream) {
-    if (n_clips == 0 || pps == 0) {
-        if (out_count) (void)hipMemsetAsync(out_count, 0, 8, stream);
-        if (d_out_off) (void)hipMemsetAsync(d_out_off, 0, (n_clips + 1) * 8, stream);
-        return 0;
-    }
+// The front end shared by Wang (A6) and Panako (A13): clip table, the stream kernel (A1 + A3 + A5 candidates), the
+// per-second selection and the compaction into time-sorted peaks (pt = t << 9 | k, pp, pc).  The two back ends below
+// differ only in what an anchor emits.
+static void launch_wang_front(const float* pcm, const uint64_t* d_offsets, size_t n_src_total, size_t n_clips,
+                              uint32_t sr_in, uint32_t pps, uint8_t* ws, const WangWs& w, hipStream_t stream) {
     auto f32 = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
     auto u32 = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
     WangClip* clips = reinterpret_cast<WangClip*>(ws + w.clips);
@@ -1531,6 +1603,40 @@ int launch_wang_batch(const float* pcm, const uint64_t* d_offsets, size_t n_src_
     hipLaunchKernelGGL(wang_compact_kernel, dim3(blocks_for((size_t)w.n_sec * pps, 256)), dim3(256), 0, stream,
                        u32(w.sel_cnt), u32(w.sel_off), u32(w.sel_t), u32(w.sel_k), f32(w.sel_p),
                        (const uint32_t*)u32(w.sec_clip), w.n_sec, pps, u32(w.pt), f32(w.pp), u32(w.pc));
+}
+
+// empty batch: no hashes, all offsets zero
+static bool wang_batch_empty(size_t n_clips, uint32_t pps, uint64_t* d_out_off, uint64_t* out_count, hipStream_t stream) {
+    if (n_clips != 0 && pps != 0) return false;
+    if (out_count) (void)hipMemsetAsync(out_count, 0, 8, stream);
+    if (d_out_off) (void)hipMemsetAsync(d_out_off, 0, (n_clips + 1) * 8, stream);
+    return true;
+}
+
+// total and per-clip offsets of either back end's output, from the scanned per-peak counts
+static void launch_wang_totals(uint8_t* ws, const WangWs& w, size_t maxp, size_t n_clips, uint64_t* d_out_off,
+                               uint64_t* out_count, hipStream_t stream) {
+    auto u32 = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
+    if (out_count)
+        hipLaunchKernelGGL(copy_u32_kernel, dim3(1), dim3(1), 0, stream, (const uint32_t*)(u32(w.pair_off) + maxp),
+                           out_count);
+    if (d_out_off)
+        hipLaunchKernelGGL(wang_clip_offsets_kernel, dim3(blocks_for(n_clips + 1, 256)), dim3(256), 0, stream,
+                           (const uint32_t*)u32(w.sec_base), (const uint32_t*)u32(w.sel_off),
+                           (const uint32_t*)u32(w.pair_off), (uint32_t)n_clips, d_out_off);
+}
+
+// pcm: the batch buffer; d_offsets: n_clips + 1 device offsets into it (nullptr: one clip [0, n_src_total)); sr_in: the
+// clips' sample rate (8000: taken as is; anything else: resampled to 8 kHz inside the stream kernel, A1);
+// d_out_off: n_clips + 1 hash offsets (may be nullptr); out_count: total hashes produced (may be nullptr)
+int launch_wang_batch(const float* pcm, const uint64_t* d_offsets, size_t n_src_total, size_t n_clips, uint32_t sr_in,
+                      uint32_t fan_out, uint32_t zone_t, uint32_t zone_f, uint32_t pps,
+                      float floor_power, uint8_t* ws, const WangWs& w, uint32_t* out, size_t cap, uint64_t* d_out_off,
+                      uint64_t* out_count, hipStream_t stream) {
+    if (wang_batch_empty(n_clips, pps, d_out_off, out_count, stream)) return 0;
+    launch_wang_front(pcm, d_offsets, n_src_total, n_clips, sr_in, pps, ws, w, stream);
+    auto f32 = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    auto u32 = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
     const size_t maxp = (size_t)w.n_sec * pps;
     const uint32_t* np_ptr = u32(w.sel_off) + w.n_sec;  // total peaks
     (void)hipMemsetAsync(u32(w.pair_cnt), 0, (maxp + 1) * 4, stream);
@@ -1543,13 +1649,32 @@ int launch_wang_batch(const float* pcm, const uint64_t* d_offsets, size_t n_src_
                        (const uint32_t*)u32(w.pt), (const float*)f32(w.pp), (const uint32_t*)u32(w.pc),
                        (const uint32_t*)u32(w.sec_base), (const uint32_t*)u32(w.sel_off), np_ptr, fan_out, zone_t, zone_f,
                        floor_power, (uint32_t*)nullptr, (const uint32_t*)u32(w.pair_off), reinterpret_cast<uint2*>(out), cap);
-    if (out_count)
-        hipLaunchKernelGGL(copy_u32_kernel, dim3(1), dim3(1), 0, stream, (const uint32_t*)(u32(w.pair_off) + maxp),
-                           out_count);
-    if (d_out_off)
-        hipLaunchKernelGGL(wang_clip_offsets_kernel, dim3(blocks_for(n_clips + 1, 256)), dim3(256), 0, stream,
-                           (const uint32_t*)u32(w.sec_base), (const uint32_t*)u32(w.sel_off),
-                           (const uint32_t*)u32(w.pair_off), nc, d_out_off);
+    launch_wang_totals(ws, w, maxp, n_clips, d_out_off, out_count, stream);
+    return 0;
+}
+
+// A13: the same front end, then one thread per peak counts and emits its triplets (16-byte records, out 16-byte aligned)
+int launch_panako_batch(const float* pcm, const uint64_t* d_offsets, size_t n_src_total, size_t n_clips, uint32_t sr_in,
+                        uint32_t fan_out, uint32_t zone_t, uint32_t zone_f, uint32_t pps, float floor_power,
+                        uint8_t* ws, const WangWs& w, uint32_t* out, size_t cap, uint64_t* d_out_off,
+                        uint64_t* out_count, hipStream_t stream) {
+    if (wang_batch_empty(n_clips, pps, d_out_off, out_count, stream)) return 0;
+    launch_wang_front(pcm, d_offsets, n_src_total, n_clips, sr_in, pps, ws, w, stream);
+    auto f32 = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    auto u32 = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
+    const size_t maxp = (size_t)w.n_sec * pps;
+    const uint32_t* np_ptr = u32(w.sel_off) + w.n_sec;  // total peaks
+    (void)hipMemsetAsync(u32(w.pair_cnt), 0, (maxp + 1) * 4, stream);
+    hipLaunchKernelGGL(panako_triplet_kernel<false>, dim3(blocks_for(maxp, 256)), dim3(256), 0, stream,
+                       (const uint32_t*)u32(w.pt), (const float*)f32(w.pp), (const uint32_t*)u32(w.pc),
+                       (const uint32_t*)u32(w.sec_base), (const uint32_t*)u32(w.sel_off), np_ptr, fan_out, zone_t, zone_f,
+                       floor_power, u32(w.pair_cnt), (const uint32_t*)nullptr, (uint4*)nullptr, (size_t)0);
+    launch_exclusive_scan(u32(w.pair_cnt), maxp, u32(w.pair_off), u32(w.scan_tmp), stream);
+    hipLaunchKernelGGL(panako_triplet_kernel<true>, dim3(blocks_for(maxp, 256)), dim3(256), 0, stream,
+                       (const uint32_t*)u32(w.pt), (const float*)f32(w.pp), (const uint32_t*)u32(w.pc),
+                       (const uint32_t*)u32(w.sec_base), (const uint32_t*)u32(w.sel_off), np_ptr, fan_out, zone_t, zone_f,
+                       floor_power, (uint32_t*)nullptr, (const uint32_t*)u32(w.pair_off), reinterpret_cast<uint4*>(out), cap);
+    launch_wang_totals(ws, w, maxp, n_clips, d_out_off, out_count, stream);
     return 0;
 }
 

@@ -571,6 +571,128 @@ int ucfp_audio_wang(ucfp_ctx* ctx, const float* pcm, size_t n, uint32_t sample_r
     return UCFP_OK;
 }
 
+// ---- Panako triplets (DESIGN A13): audio::fingerprint_panako_with, src/modality/audio.rs:106-156 ----
+static ucfp_panako_config panako_defaults() { return ucfp_panako_config{5u, 96u, 96u, 30u, -50.0f}; }
+
+static int panako_cfg_check(const ucfp_panako_config& c) {      // ranges: algorithms_manifest.rs:601-650
+    if (c.fan_out < 1 || c.fan_out > 64 || c.target_zone_t < 1 || c.target_zone_t > 512 || c.target_zone_f < 1 ||
+        c.target_zone_f > 1024 || c.peaks_per_sec < 1 || c.peaks_per_sec > 256 ||
+        !(c.min_anchor_mag_db >= -120.0f && c.min_anchor_mag_db <= 0.0f))
+        return fail(UCFP_E_MODALITY, "PanakoConfig outside the ranges of /v1/algorithms");
+    return UCFP_OK;
+}
+
+size_t ucfp_audio_panako_max_hashes(size_t n_samples, const ucfp_panako_config* cfg) {
+    const ucfp_panako_config c = cfg ? *cfg : panako_defaults();
+    const size_t frames = ucfp::audio_stft_frames(n_samples, 1024, 128);
+    if (!frames) return 0;
+    const size_t n_sec = ((frames - 1) * 128) / 8000 + 1;
+    return n_sec * c.peaks_per_sec * c.fan_out;
+}
+
+size_t ucfp_audio_panako_batch_max_hashes(size_t n_total, size_t n_clips, uint32_t sample_rate,
+                                          const ucfp_panako_config* cfg) {
+    if (!sample_rate || !n_clips) return 0;
+    const ucfp_panako_config c = cfg ? *cfg : panako_defaults();
+    const ucfp::WangWs w = ucfp::wang_ws_layout(n_total, n_clips, sample_rate, c.peaks_per_sec);
+    return (size_t)w.n_sec * c.peaks_per_sec * c.fan_out;
+}
+
+// shared by the single-clip and the batch entry point; the workspace and the audio_done event are Wang's
+static int panako_batch_impl(ucfp_ctx* ctx, const float* d_pcm, const uint64_t* d_offsets, size_t n_total, size_t n_clips,
+                             uint32_t sample_rate, const ucfp_panako_config* cfg, uint8_t* d_out, size_t cap_hashes,
+                             uint64_t* d_out_offsets, uint64_t* d_n_hashes, hipStream_t st) {
+    const ucfp_panako_config c = cfg ? *cfg : panako_defaults();
+    int rc = panako_cfg_check(c);
+    if (rc) return rc;
+    if (n_clips > 0x7fffffffu || n_total > ((size_t)1 << 46))
+        return fail(UCFP_E_INVALID, "audio batch too large for one call");
+    const ucfp::WangWs w = ucfp::wang_ws_layout(n_total, n_clips, sample_rate, c.peaks_per_sec);
+    if (n_clips == 1 && w.frames >= ((size_t)1 << 23))
+        return fail(UCFP_E_INVALID, "a clip of %zu frames exceeds 2^23 (37 h at 8 kHz): split it", w.frames);
+    if (cap_hashes && ((uintptr_t)d_out & 15u)) return fail(UCFP_E_INVALID, "the hash buffer must be 16-byte aligned");
+    if (w.n_seg > 0x7fffffffu || (size_t)w.n_sec * c.peaks_per_sec > 0x7fffffffu || w.n_sec > 3000000u ||
+        (size_t)w.n_sec * c.peaks_per_sec * c.fan_out > 0xffffffffu)   // per-peak output offsets are 32-bit
+        return fail(UCFP_E_INVALID, "audio batch too large for one call");
+    const float floor_p = (float)(65536.0 * pow(10.0, (double)c.min_anchor_mag_db / 10.0));
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    HIP_TRY(hipSetDevice(ctx->device));
+    rc = grow(&ctx->audio_ws, &ctx->audio_ws_cap, w.total);
+    if (rc) return rc;
+    HIP_TRY(hipStreamWaitEvent(st, ctx->audio_done, 0));
+    ucfp::launch_panako_batch(d_pcm, d_offsets, n_total, n_clips, sample_rate, c.fan_out, c.target_zone_t,
+                              c.target_zone_f, c.peaks_per_sec, floor_p, ctx->audio_ws, w,
+                              reinterpret_cast<uint32_t*>(d_out), cap_hashes, d_out_offsets, d_n_hashes, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ctx->audio_done, st));
+    return UCFP_OK;
+}
+
+int ucfp_audio_panako_dev(ucfp_ctx* ctx, const float* d_pcm, size_t n, uint32_t sample_rate,
+                          const ucfp_panako_config* cfg, uint8_t* d_out, size_t cap_hashes, uint64_t* d_n_hashes,
+                          void* stream) {
+    if (!ctx) return fail(UCFP_E_INVALID, "ctx is NULL");
+    if (!d_n_hashes || (n && !d_pcm) || (cap_hashes && !d_out)) return fail(UCFP_E_INVALID, "NULL buffer");
+    if (sample_rate != 8000)
+        return fail(UCFP_E_MODALITY, "Panako requires 8 kHz mono input (got %u Hz); resample upstream", sample_rate);
+    return panako_batch_impl(ctx, d_pcm, nullptr, n, 1, sample_rate, cfg, d_out, cap_hashes, nullptr, d_n_hashes,
+                             (hipStream_t)stream);
+}
+
+int ucfp_audio_panako_batch_dev(ucfp_ctx* ctx, const float* d_pcm, const uint64_t* d_offsets, size_t n_total,
+                                size_t n_clips, uint32_t sample_rate, const ucfp_panako_config* cfg, uint8_t* d_out,
+                                size_t cap_hashes, uint64_t* d_out_offsets, void* stream) {
+    if (!ctx) return fail(UCFP_E_INVALID, "ctx is NULL");
+    if (!d_out_offsets || (n_clips && !d_offsets) || (n_total && !d_pcm) || (cap_hashes && !d_out))
+        return fail(UCFP_E_INVALID, "NULL buffer");
+    if (sample_rate < 1000 || sample_rate > 384000)
+        return fail(UCFP_E_MODALITY, "invalid sample rate %u (1 000 .. 384 000 Hz)", sample_rate);
+    return panako_batch_impl(ctx, d_pcm, d_offsets, n_total, n_clips, sample_rate, cfg, d_out, cap_hashes,
+                             d_out_offsets, nullptr, (hipStream_t)stream);
+}
+
+int ucfp_audio_panako(ucfp_ctx* ctx, const float* pcm, size_t n, uint32_t sample_rate, const ucfp_panako_config* cfg,
+                      uint8_t* out, size_t cap_hashes, size_t* n_hashes) {
+    if (!ctx || !n_hashes) return fail(UCFP_E_INVALID, "ctx/n_hashes is NULL");
+    *n_hashes = 0;
+    if (n && !pcm) return fail(UCFP_E_INVALID, "pcm is NULL");
+    if (cap_hashes && !out) return fail(UCFP_E_INVALID, "out is NULL");
+    if (sample_rate != 8000)
+        return fail(UCFP_E_MODALITY, "Panako requires 8 kHz mono input (got %u Hz); resample upstream", sample_rate);
+    if (cap_hashes && ((uintptr_t)out & 15u)) return fail(UCFP_E_INVALID, "the hash buffer must be 16-byte aligned");
+    HIP_TRY(hipSetDevice(ctx->device));
+    float* d_pcm = nullptr;
+    uint8_t* d_out = nullptr;
+    uint64_t* d_cnt = nullptr;
+    HIP_TRY(hipMalloc((void**)&d_pcm, (n ? n : 1) * 4));
+    hipError_t e = hipMalloc((void**)&d_out, (cap_hashes ? cap_hashes : 1) * UCFP_PANAKO_HASH_BYTES);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_cnt, 8);
+    int rc = UCFP_OK;
+    uint64_t cnt = 0;
+    hipStream_t st = ctx->host_stream;
+    if (e == hipSuccess && n) e = hipMemcpyAsync(d_pcm, pcm, n * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        rc = ucfp_audio_panako_dev(ctx, d_pcm, n, sample_rate, cfg, d_out, cap_hashes, d_cnt, st);
+        if (rc == UCFP_OK) {
+            e = hipMemcpyAsync(&cnt, d_cnt, 8, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+            if (e == hipSuccess && cnt) {
+                const size_t m = cnt < cap_hashes ? (size_t)cnt : cap_hashes;
+                if (m) e = hipMemcpy(out, d_out, m * UCFP_PANAKO_HASH_BYTES, hipMemcpyDeviceToHost);
+            }
+        }
+    }
+    (void)hipStreamSynchronize(st);
+    (void)hipFree(d_pcm);
+    if (d_out) (void)hipFree(d_out);
+    if (d_cnt) (void)hipFree(d_cnt);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(UCFP_E_INDEX, "panako failed: %s", hipGetErrorString(e));
+    *n_hashes = (size_t)cnt;
+    if (cnt > cap_hashes) return fail(UCFP_E_INVALID, "output holds %zu hashes, %llu produced", cap_hashes, (unsigned long long)cnt);
+    return UCFP_OK;
+}
+
 size_t ucfp_audio_resample_len(size_t n, uint32_t sr_in, uint32_t sr_out) {
     return sr_in ? ucfp::audio_resample_len(n, sr_in, sr_out) : 0;
 }

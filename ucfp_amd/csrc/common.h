@@ -326,6 +326,11 @@ int launch_wang_batch(const float* pcm, const uint64_t* d_offsets, size_t n_src_
                       uint32_t fan_out, uint32_t zone_t, uint32_t zone_f, uint32_t pps,
                       float floor_power, uint8_t* ws, const WangWs& w, uint32_t* out, size_t cap, uint64_t* d_out_off,
                       uint64_t* out_count, hipStream_t stream);
+// A13: Panako triplets behind the same front end, workspace and arguments; out holds 16-byte records (16-byte aligned)
+int launch_panako_batch(const float* pcm, const uint64_t* d_offsets, size_t n_src_total, size_t n_clips, uint32_t sr_in,
+                        uint32_t fan_out, uint32_t zone_t, uint32_t zone_f, uint32_t pps, float floor_power,
+                        uint8_t* ws, const WangWs& w, uint32_t* out, size_t cap, uint64_t* d_out_off,
+                        uint64_t* out_count, hipStream_t stream);
 
 // ---- streaming Wang (A9): one push of a stream set (wang_streams.hip plans it, audio.hip runs it) ----
 constexpr uint32_t kWangCarry = 2816;     // carried samples per stream: n - 128 max(0, J - 7) <= 1023 + 14 * 128

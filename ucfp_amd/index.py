@@ -6,7 +6,8 @@ path, backed by the GPU-resident shard behind the C ABI (ucfp_index_*).
     GpuIndex.knn(tenant, query, k)    IndexBackend::knn      :29-35  (cosine over Record.embedding,
                                       as EmbeddedBackend::knn src/index/embedded/mod.rs:268-360)
     GpuIndex.hamming(tenant, h, k)    the new Hamming search behind /v1/query
-    GpuIndex.identify(tenant, lm, k)  audio identification over Wang landmarks (DESIGN A10; LandmarkIndex)
+    GpuIndex.identify(tenant, lm, k)  audio identification over Wang landmarks (DESIGN A10; LandmarkIndex), or with
+                                      algorithm=ALGORITHM_PANAKO over Panako (hash, t_anchor) pairs (DESIGN A13)
     GpuIndex.identify_frames(tenant, frames, k)  the same over Haitsma sub-fingerprints (DESIGN A12; HaitsmaIndex)
     GpuIndex.bm25(tenant, terms, k)   IndexBackend::bm25 / bm25_explain :37-50 over Record.text (DESIGN A11; Bm25Index)
     GpuIndex.flush()                  IndexBackend::flush    :63
@@ -21,7 +22,7 @@ from typing import Iterable, List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from .audio import ALGORITHM_HAITSMA, ALGORITHM_WANG
+from .audio import ALGORITHM_HAITSMA, ALGORITHM_PANAKO, ALGORITHM_WANG, panako_landmarks
 from .core import Hit, HitSource, Record, TermHit
 from .errors import InvalidArgument, UnsupportedError
 from .terms import query_terms, tokenize
@@ -502,6 +503,7 @@ class GpuIndex:
         self._cos = {}        # dim -> DeviceIndex
         self._ham = {}        # hash space name -> DeviceIndex
         self._lm = None       # LandmarkIndex of the audiofp-wang-v1 records (DESIGN A10)
+        self._pk = None       # LandmarkIndex of the audiofp-panako-v1 records' (hash, t_anchor) pairs (DESIGN A13)
         self._hx = None       # HaitsmaIndex of the audiofp-haitsma-v1 records (DESIGN A12)
         self._bm = None       # Bm25Index of the records with text (DESIGN A11)
         self._sidecar = sidecar   # ucfp_amd.store.Sidecar: the stored-table mirror written at upsert
@@ -526,6 +528,11 @@ class GpuIndex:
             self._lm = LandmarkIndex(0, 0, self.ctx)
         return self._lm
 
+    def _panako(self) -> LandmarkIndex:
+        if self._pk is None:
+            self._pk = LandmarkIndex(0, 0, self.ctx)
+        return self._pk
+
     def _haitsma(self) -> HaitsmaIndex:
         if self._hx is None:
             self._hx = HaitsmaIndex(0, 0, self.ctx)
@@ -538,20 +545,22 @@ class GpuIndex:
 
     def _all(self):
         return (list(self._cos.values()) + list(self._ham.values()) + ([self._lm] if self._lm is not None else [])
+                + ([self._pk] if self._pk is not None else [])
                 + ([self._hx] if self._hx is not None else [])
                 + ([self._bm] if self._bm is not None else []))
 
     def upsert(self, records: Sequence[Record]) -> None:
         """Embeddings go to the cosine index of their dimension; image records also feed the
         Hamming spaces `<algorithm>` with their 64-bit global hashes (SURVEY 8f N2 offsets);
-        `audiofp-wang-v1` records feed the landmark index with their landmarks and `audiofp-haitsma-v1` records the
-        sub-fingerprint index with their frames; every record with `text`, whatever its
+        `audiofp-wang-v1` records feed the landmark index with their landmarks, `audiofp-panako-v1` records a second
+        landmark index with their (hash, t_anchor) pairs (the two never share postings) and `audiofp-haitsma-v1` records
+        the sub-fingerprint index with their frames; every record with `text`, whatever its
         modality, feeds BM25, and a record without text leaves it (src/index/embedded/mod.rs:208-219).
 
         Overwrite semantics are the reference's: everything is keyed by (tenant_id, record_id), a re-ingested record
         REPLACES the old one -- "Drop any stale vector for this key" when the new record has no embedding
         (src/index/embedded/mod.rs:184-191), a new dimension or algorithm replaces the old row.  So before inserting,
-        the key is removed from every cosine index of another dimension, every hash space, the landmark index and the sub-fingerprint index when
+        the key is removed from every cosine index of another dimension, every hash space, both landmark indexes and the sub-fingerprint index when
         the new record does not feed them.  Within one batch the last record of a key wins, as successive `insert`s in one redb transaction do."""
         if self._sidecar is not None:     # the log first (the host does this right after its redb commit), then the mirror
             self._sidecar.append(records)
@@ -559,7 +568,7 @@ class GpuIndex:
         for r in records:
             last[(r.tenant_id, r.record_id)] = r
         by_cos, by_ham, stale_cos, stale_ham, by_lm, stale_lm, by_bm, stale_bm = {}, {}, {}, {}, {}, {}, {}, {}
-        by_hx, stale_hx = {}, {}
+        by_hx, stale_hx, by_pk, stale_pk = {}, {}, {}, {}
         for r in last.values():
             if r.text is not None:
                 by_bm.setdefault(r.tenant_id, []).append(r)
@@ -569,6 +578,10 @@ class GpuIndex:
                 by_lm.setdefault(r.tenant_id, []).append(r)
             elif self._lm is not None:
                 stale_lm.setdefault(r.tenant_id, []).append(r.record_id)
+            if r.algorithm == ALGORITHM_PANAKO:
+                by_pk.setdefault(r.tenant_id, []).append(r)
+            elif self._pk is not None:
+                stale_pk.setdefault(r.tenant_id, []).append(r.record_id)
             if r.algorithm == ALGORITHM_HAITSMA:
                 by_hx.setdefault(r.tenant_id, []).append(r)
             elif self._hx is not None:
@@ -592,6 +605,8 @@ class GpuIndex:
             self._ham[space].delete(tenant, np.array(ids, np.uint64))
         for tenant, ids in stale_lm.items():
             self._lm.delete(tenant, np.array(ids, np.uint64))
+        for tenant, ids in stale_pk.items():
+            self._pk.delete(tenant, np.array(ids, np.uint64))
         for tenant, ids in stale_hx.items():
             self._hx.delete(tenant, np.array(ids, np.uint64))
         for tenant, ids in stale_bm.items():
@@ -601,6 +616,9 @@ class GpuIndex:
         for tenant, recs in by_lm.items():
             self._landmarks().upsert(tenant, np.array([r.record_id for r in recs], np.uint64),
                                      [bytes(r.fingerprint) for r in recs])
+        for tenant, recs in by_pk.items():
+            self._panako().upsert(tenant, np.array([r.record_id for r in recs], np.uint64),
+                                  [panako_landmarks(bytes(r.fingerprint)) for r in recs])
         for tenant, recs in by_hx.items():
             self._haitsma().upsert(tenant, np.array([r.record_id for r in recs], np.uint64),
                                    [bytes(r.fingerprint) for r in recs])
@@ -640,12 +658,17 @@ class GpuIndex:
         return [Hit(tenant_id=tenant_id, record_id=int(ids[0, i]), score=float(scores[0, i]),
                     source=HitSource.Hamming, distance=int(dist[0, i])) for i in range(int(counts[0]))]
 
-    def identify(self, tenant_id: int, landmarks, k: int, min_votes: int = 1) -> List[Hit]:
+    def identify(self, tenant_id: int, landmarks, k: int, min_votes: int = 1, algorithm: str = ALGORITHM_WANG) -> List[Hit]:
         """Which recording is this clip, and where in it: landmarks = bytes (8 per landmark) or uint32 [n, 2] of
-        (hash, t).  Hits by offset-consistent votes (DESIGN A10); `offset` = the clip's frame 0 in the record."""
-        if k == 0 or self._lm is None:
+        (hash, t).  Hits by offset-consistent votes (DESIGN A10); `offset` = the clip's frame 0 in the record.
+        `algorithm` picks the index: Wang landmarks, or the (hash, t_anchor) pairs of Panako records
+        (audio.panako_landmarks, DESIGN A13)."""
+        if algorithm not in (ALGORITHM_WANG, ALGORITHM_PANAKO):
+            raise InvalidArgument(f"no landmark index for algorithm {algorithm!r}")
+        ix = self._pk if algorithm == ALGORITHM_PANAKO else self._lm
+        if k == 0 or ix is None:
             return []
-        ids, votes, offs, scores, counts = self._lm.query(tenant_id, [landmarks], min(k, MAX_K), min_votes)
+        ids, votes, offs, scores, counts = ix.query(tenant_id, [landmarks], min(k, MAX_K), min_votes)
         return [Hit(tenant_id=tenant_id, record_id=int(ids[0, i]), score=float(scores[0, i]), source=HitSource.Landmark,
                     votes=int(votes[0, i]), offset=int(offs[0, i])) for i in range(int(counts[0]))]
 
@@ -673,7 +696,8 @@ class GpuIndex:
 
     def query(self, req) -> List[Hit]:
         """POST /v1/query (handlers.rs:143-187) with the additive `hash` field: a vector goes to the cosine kNN,
-        a hash to the Hamming space `algorithm` (default: the only hash space present), `landmarks` to identify, `subfingerprints` to identify_frames;
+        a hash to the Hamming space `algorithm` (default: the only hash space present), `landmarks` to identify (the Panako
+        index when `algorithm` is "audiofp-panako-v1", the Wang one otherwise), `subfingerprints` to identify_frames;
         `terms` go through the matcher (BM25, or vector + BM25 fused by RRF: src/matcher/mod.rs:140-207)."""
         if (getattr(req, "landmarks", None) is None and getattr(req, "subfingerprints", None) is None and req.hash is None
                 and getattr(req, "terms", None)):
@@ -684,7 +708,9 @@ class GpuIndex:
                     h.bm25_score, h.bm25_rank = h.score, rank + 1
             return hits
         if getattr(req, "landmarks", None) is not None:
-            hits = self.identify(req.tenant_id, req.landmarks, req.k)
+            panako = getattr(req, "algorithm", None) == ALGORITHM_PANAKO
+            hits = self.identify(req.tenant_id, req.landmarks, req.k,
+                                 algorithm=ALGORITHM_PANAKO if panako else ALGORITHM_WANG)
         elif getattr(req, "subfingerprints", None) is not None:
             hits = self.identify_frames(req.tenant_id, req.subfingerprints, req.k)
         elif req.hash is not None:

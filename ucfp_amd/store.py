@@ -165,7 +165,7 @@ def rebuild(path: str, ctx=None, sidecar: bool = False):
     """Start-up: replay the sidecar at `path` into a fresh GpuIndex (every hash space, every cosine dimension).
     `sidecar=True` keeps the log attached, so later upserts / deletes are appended to it."""
     import torch
-    from .audio import ALGORITHM_HAITSMA, ALGORITHM_WANG
+    from .audio import ALGORITHM_HAITSMA, ALGORITHM_PANAKO, ALGORITHM_WANG, panako_landmarks
     from .index import GpuIndex
     ctx = ctx or _lib.current_context()
     lib = _lib.load()
@@ -194,14 +194,19 @@ def rebuild(path: str, ctx=None, sidecar: bool = False):
                 gi._hamming(algorithm).upsert(int(tenant), ids[sel], np.ascontiguousarray(blobs[sel]).view(np.uint64).reshape(-1))
         # Wang records are variable length: walk the rows (the landmark index keeps its record table on the host)
         # (so are Haitsma records: the sub-fingerprint index does the same)
-        wang, haitsma = {}, {}
+        wang, haitsma, panako = {}, {}, {}
         for r in snap:
             if r.algorithm == ALGORITHM_WANG:
                 wang.setdefault(r.tenant_id, []).append(r)
             elif r.algorithm == ALGORITHM_HAITSMA:
                 haitsma.setdefault(r.tenant_id, []).append(r)
+            elif r.algorithm == ALGORITHM_PANAKO:
+                panako.setdefault(r.tenant_id, []).append(r)
         for tenant, recs in wang.items():
             gi._landmarks().upsert(tenant, np.array([r.record_id for r in recs], np.uint64), [r.fingerprint for r in recs])
+        for tenant, recs in panako.items():     # their (hash, t_anchor) pairs, in a landmark index of their own (A13)
+            gi._panako().upsert(tenant, np.array([r.record_id for r in recs], np.uint64),
+                                [panako_landmarks(bytes(r.fingerprint)) for r in recs])
         for tenant, recs in haitsma.items():
             gi._haitsma().upsert(tenant, np.array([r.record_id for r in recs], np.uint64), [r.fingerprint for r in recs])
         for dim in snap.dims():

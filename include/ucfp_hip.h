@@ -580,6 +580,69 @@ int ucfp_landmark_index_query_dev(ucfp_landmark_index* ix, uint32_t tenant, cons
                                   uint32_t* d_out_votes, int32_t* d_out_offsets, float* d_out_scores, uint32_t* d_out_n,
                                   void* stream);
 
+/* ---- Panako triplet index with a (scale, offset) vote (the reference has no audio matcher) ----
+ * Identification that survives a change of tempo.  Records and queries are sequences of Panako records: 16 bytes each,
+ * u32 LE hash, t_a, t_b, t_c (UCFP_PANAKO_HASH_BYTES).  Item i of a batch is records[offsets[i] .. offsets[i+1]) with BYTE
+ * offsets: offsets[0] = 0, non-decreasing, multiples of 16; n + 1 entries.  The set of an item is its distinct triples
+ * (h, a, d) with a = t_a and d = t_c - t_a; t_b is not used (r = h & 31 stands for it).  UCFP_E_INVALID before anything
+ * runs: bad offsets, d outside 1 ... 1023, t_a >= 2^31 in a record, t_a >= 2^28 in a query (every offset then fits an
+ * int32), a match config out of range.  |Q| = the distinct triples of a query.  All arithmetic below is in signed
+ * 64-bit integers; scales are in units of 1/256.
+ *   hypotheses  s = scale_min + j * scale_step <= scale_max, 64 <= scale_min <= scale_max <= 1024, scale_step >= 1, at
+ *               most 64 of them; window W in 1 ... 256; slack in 0 ... 8; r_slack 0 or 1.  config NULL = 204, 320, 4,
+ *               16, 2, 1.
+ *   probes      a query triple with hash h probes (h & ~31) | r' for r' = max(0, r - r_slack) ... min(31, r + r_slack).
+ *               Within a tenant P(h') = distinct (record, a', d') postings of h' over the live records; an index with
+ *               max_postings > 0 ignores every probed h' with P(h') > max_postings (0 = no cap).
+ *   votes       a match is a pair (query triple (h, a, d), posting (r, h', a', d')) with h' probed and not ignored.  It
+ *               supports s iff |256 d' - s d| <= 256 slack; its offset under s is a' - ((s a + 128) >> 8).
+ *               count(r, s, o) = matches of record r that support s with o <= offset < o + W; PAIRS are counted: a
+ *               query triple that meets several postings counts once for each.  votes(r) = the maximum over the
+ *               hypotheses s and over every o that is the offset of some supporting match; (scale(r), offset(r)) = the
+ *               maximiser with the smallest (|s - 256|, s, o), compared in that order.
+ *   hits        votes >= max(min_votes, 1), ordered (votes desc, id asc), first k <= UCFP_INDEX_MAX_K;
+ *               score = (float)votes / (float)|Q|, which may exceed 1 because pairs are counted.  Unused output slots:
+ *               id UINT64_MAX, votes 0, offset 0, scale 0, score -1.  An empty query, k = 0 or an unknown tenant gives
+ *               0 hits.
+ * Upsert of a known id replaces its set, delete removes it, an empty record is stored and counted; postings are rebuilt
+ * lazily at the next query, size or flush of a changed tenant.  Limits: at most 2^23 records per tenant (the ordinal
+ * bits of a posting; UCFP_E_INVALID at the rebuild), a tenant below 2^32 - 1 triples.  UCFP_E_UNSUPPORTED: a query whose
+ * expanded votes (matches x supported hypotheses) reach 2^32, a batch whose queries above
+ * ucfp_panako_index_lds_votes() expand to 2^32 - 1 votes or more in all, a single window that holds 2^26 votes or more.
+ * A query with at most ucfp_panako_index_lds_votes() expanded votes is answered in on-chip memory, a larger one through
+ * global memory; the answers do not depend on the path.  Queries read the checked sizes, the input flags and the vote
+ * count of each query back to the host (three synchronisations of `stream`); upsert_dev copies its inputs to the host
+ * record table (it synchronises `stream`).  flags: 0. */
+typedef struct ucfp_panako_match_config {
+    uint32_t scale_min, scale_max; /* 64 <= min <= max <= 1024, units of 1/256 */
+    uint32_t scale_step;           /* >= 1; (max - min) / step + 1 <= 64 */
+    uint32_t window;               /* 1 ... 256 frames */
+    uint32_t slack;                /* 0 ... 8 frames on d' */
+    uint32_t r_slack;              /* 0 or 1 on the ratio bits of the hash */
+} ucfp_panako_match_config;
+typedef struct ucfp_panako_index ucfp_panako_index;
+/* expanded votes up to which a query stays in on-chip memory.  Host only. */
+uint32_t ucfp_panako_index_lds_votes(void);
+int ucfp_panako_index_create(ucfp_ctx* ctx, uint32_t max_postings, uint32_t flags, ucfp_panako_index** out);
+void ucfp_panako_index_destroy(ucfp_panako_index* ix);
+int ucfp_panako_index_upsert(ucfp_panako_index* ix, uint32_t tenant, const uint64_t* ids, const uint8_t* records,
+                             const uint64_t* offsets, size_t n);
+int ucfp_panako_index_upsert_dev(ucfp_panako_index* ix, uint32_t tenant, const uint64_t* d_ids, const uint8_t* d_records,
+                                 const uint64_t* d_offsets, size_t n, void* stream);
+int ucfp_panako_index_delete(ucfp_panako_index* ix, uint32_t tenant, const uint64_t* ids, size_t n, size_t* n_removed);
+/* records = live records (empty ones included); postings = sum of P(h) (rebuilds a changed tenant). */
+int ucfp_panako_index_size(ucfp_panako_index* ix, uint32_t tenant, size_t* records, size_t* postings);
+int ucfp_panako_index_flush(ucfp_panako_index* ix);
+/* nq ragged queries; out_ids / out_votes / out_offsets / out_scales / out_scores are nq x k; out_n[q] = hits of query q. */
+int ucfp_panako_index_query(ucfp_panako_index* ix, uint32_t tenant, const uint8_t* records, const uint64_t* offsets, size_t nq,
+                            uint32_t k, uint32_t min_votes, const ucfp_panako_match_config* cfg, uint64_t* out_ids,
+                            uint32_t* out_votes, int32_t* out_offsets, uint32_t* out_scales, float* out_scores,
+                            uint32_t* out_n);
+int ucfp_panako_index_query_dev(ucfp_panako_index* ix, uint32_t tenant, const uint8_t* d_records, const uint64_t* d_offsets,
+                                size_t nq, uint32_t k, uint32_t min_votes, const ucfp_panako_match_config* cfg,
+                                uint64_t* d_out_ids, uint32_t* d_out_votes, int32_t* d_out_offsets, uint32_t* d_out_scales,
+                                float* d_out_scores, uint32_t* d_out_n, void* stream);
+
 /* ---- Haitsma-Kalker sub-fingerprint index (the reference has no audio matcher) ----
  * A record r is a sequence F_r[0 .. n_r) of u32 sub-fingerprints (the bytes of an audiofp-haitsma-v1 record, 4 per
  * frame, little endian); a query is a sequence Q[0 .. m), m <= UCFP_HAITSMA_MAX_QUERY_FRAMES.  Item i of a batch is

@@ -22,6 +22,12 @@ class PanakoConfig(C.Structure):
                 ("peaks_per_sec", C.c_uint32), ("min_anchor_mag_db", C.c_float)]
 
 
+class PanakoMatchConfig(C.Structure):
+    """ucfp_panako_match_config: the (scale, offset) vote of the Panako index (DESIGN A14); scales in units of 1/256."""
+    _fields_ = [("scale_min", C.c_uint32), ("scale_max", C.c_uint32), ("scale_step", C.c_uint32), ("window", C.c_uint32),
+                ("slack", C.c_uint32), ("r_slack", C.c_uint32)]
+
+
 class WangConfig(C.Structure):
     """ucfp_wang_config (audiofp WangConfig; defaults src/server/algorithms_manifest.rs:553-592)."""
     _fields_ = [("fan_out", C.c_uint32), ("target_zone_t", C.c_uint32), ("target_zone_f", C.c_uint32),
@@ -132,6 +138,21 @@ SIGNATURES = {
     "ucfp_landmark_index_query_dev": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32,
                                                 C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_void_p]),
+    "ucfp_panako_index_lds_votes": (C.c_uint32, []),
+    "ucfp_panako_index_create": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "ucfp_panako_index_destroy": (None, [C.c_void_p]),
+    "ucfp_panako_index_upsert": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "ucfp_panako_index_upsert_dev": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                               C.c_void_p]),
+    "ucfp_panako_index_delete": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ucfp_panako_index_size": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "ucfp_panako_index_flush": (C.c_int, [C.c_void_p]),
+    "ucfp_panako_index_query": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32,
+                                          C.c_uint32, C.POINTER(PanakoMatchConfig), C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ucfp_panako_index_query_dev": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32,
+                                              C.c_uint32, C.POINTER(PanakoMatchConfig), C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ucfp_haitsma_index_probes": (C.c_size_t, [C.c_uint32]),
     "ucfp_haitsma_index_create": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
     "ucfp_haitsma_index_destroy": (None, [C.c_void_p]),

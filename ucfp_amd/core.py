@@ -60,6 +60,7 @@ class Hit:
     distance: Optional[int] = None    # Hamming distance when source == "hamming"; bit errors of the block when "haitsma"
     votes: Optional[int] = None       # offset-consistent landmark matches when source == "landmark"
     offset: Optional[int] = None      # where the query's frame 0 lies in the record (frames) when source == "landmark" / "haitsma"
+    scale: Optional[float] = None     # record frames per query frame, from the (scale, offset) vote over Panako triplets (DESIGN A14)
 
 
 FORMAT_VERSION = 1  # src/lib.rs:62
@@ -72,6 +73,9 @@ FORMAT_VERSION = 1  # src/lib.rs:62
 # `algorithm` = "audiofp-panako-v1" they are the (hash, t_anchor) pairs of Panako triplets and search that index (A13).
 # Keyword search adds `terms` (the reference's Query::terms, src/core/mod.rs:163-164; BM25, DESIGN A11) and `explain`
 # (the reference's `?explain=1`, handlers.rs:133-140): terms alone give a BM25 query, vector + terms the hybrid one.
+# `triplets` (DESIGN A14) are whole Panako records, 16 bytes per triplet or a list of [hash, t_a, t_b, t_c], and with
+# `algorithm` = "audiofp-panako-v1" go to the (scale, offset) vote, which also finds a time-stretched copy; its hits carry
+# `scale`.
 # Identification by bit-error rate adds `subfingerprints` (DESIGN A12): Haitsma frames as bytes (4 per frame, u32 LE) or a
 # list of integers.
 # A body the reference accepts parses to the same query here.
@@ -89,6 +93,7 @@ class QueryRequest:
     algorithm: Optional[str] = None
     landmarks: Optional[bytes] = None   # 8 bytes per landmark: u32 LE hash, u32 LE t
     subfingerprints: Optional[bytes] = None   # 4 bytes per frame: u32 LE (an audiofp-haitsma-v1 block)
+    triplets: Optional[bytes] = None    # 16 bytes per Panako triplet: u32 LE hash, t_a, t_b, t_c (DESIGN A14)
     terms: List[str] = field(default_factory=list)
     explain: bool = False
 
@@ -102,12 +107,14 @@ class QueryRequest:
             raise InvalidArgument(f"bad query body: {e}") from None
         k = int(body.get("k", DEFAULT_K))
         vector, h, lm = body.get("vector"), body.get("hash"), body.get("landmarks")
-        sub = body.get("subfingerprints")
+        sub, tri = body.get("subfingerprints"), body.get("triplets")
         terms = body.get("terms") or []
         if not isinstance(terms, list) or not all(isinstance(t, str) for t in terms):
             raise InvalidArgument("`terms` must be a list of strings")
-        if vector is None and h is None and lm is None and sub is None and not terms:
+        if vector is None and h is None and lm is None and sub is None and tri is None and not terms:
             raise InvalidArgument("query needs `vector` (dto.rs:80-82), `terms`, `hash`, `landmarks` or `subfingerprints`")
+        if tri is not None:
+            tri = _triplet_bytes(tri)
         if sub is not None:
             sub = _subfingerprint_bytes(sub)
         if lm is not None:
@@ -121,6 +128,7 @@ class QueryRequest:
         return cls(tenant_id=tenant_id, modality=modality, k=max(k, 1),       # handlers.rs:153: k.max(1)
                    vector=[float(x) for x in vector] if vector is not None else None,
                    hash=int(h) if h is not None else None, algorithm=body.get("algorithm"), landmarks=lm, subfingerprints=sub,
+                   triplets=tri,
                    terms=list(terms), explain=_flag(body.get("explain", False)))
 
 
@@ -147,6 +155,24 @@ def _landmark_bytes(lm) -> bytes:
         if not 0 <= p[0] < 1 << 32 or not 0 <= p[1] < 1 << 31:
             raise InvalidArgument("a landmark needs 0 <= hash < 2^32 and 0 <= t < 2^31")
         out += int(p[0]).to_bytes(4, "little") + int(p[1]).to_bytes(4, "little")
+    return bytes(out)
+
+
+def _triplet_bytes(tri) -> bytes:
+    """`triplets` of a query body -> 16 bytes per Panako triplet (u32 LE hash, t_a, t_b, t_c)."""
+    from .errors import InvalidArgument
+    if isinstance(tri, (bytes, bytearray)):
+        if len(tri) % 16:
+            raise InvalidArgument("`triplets` bytes must be a multiple of 16 (u32 hash, t_a, t_b, t_c per triplet)")
+        return bytes(tri)
+    if not isinstance(tri, list):
+        raise InvalidArgument("`triplets` must be bytes or a list of [hash, t_a, t_b, t_c]")
+    out = bytearray()
+    for p in tri:
+        if (not isinstance(p, (list, tuple)) or len(p) != 4
+                or not all(isinstance(x, int) and not isinstance(x, bool) and 0 <= x < 1 << 32 for x in p)):
+            raise InvalidArgument("every triplet must be [hash, t_a, t_b, t_c], integers below 2^32")
+        out += b"".join(int(x).to_bytes(4, "little") for x in p)
     return bytes(out)
 
 
@@ -178,6 +204,8 @@ def hit_to_json(h: Hit) -> dict:
     if h.source == HitSource.Landmark:
         out["votes"] = h.votes
         out["offset"] = h.offset
+        if h.scale is not None:
+            out["scale"] = h.scale
     if h.source == HitSource.Haitsma:
         out["offset"] = h.offset
     return out

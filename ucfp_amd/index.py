@@ -8,6 +8,8 @@ path, backed by the GPU-resident shard behind the C ABI (ucfp_index_*).
     GpuIndex.hamming(tenant, h, k)    the new Hamming search behind /v1/query
     GpuIndex.identify(tenant, lm, k)  audio identification over Wang landmarks (DESIGN A10; LandmarkIndex), or with
                                       algorithm=ALGORITHM_PANAKO over Panako (hash, t_anchor) pairs (DESIGN A13)
+    GpuIndex.identify_stretched(tenant, records, k)  the same over whole Panako triplets, by a (scale, offset) vote that
+                                      survives a change of tempo (DESIGN A14; PanakoIndex)
     GpuIndex.identify_frames(tenant, frames, k)  the same over Haitsma sub-fingerprints (DESIGN A12; HaitsmaIndex)
     GpuIndex.bm25(tenant, terms, k)   IndexBackend::bm25 / bm25_explain :37-50 over Record.text (DESIGN A11; Bm25Index)
     GpuIndex.flush()                  IndexBackend::flush    :63
@@ -260,6 +262,122 @@ class LandmarkIndex:
                                                            stream or None))
 
 
+def _pack_triplets(items):
+    """Sequence of Panako records (bytes, or uint32 [n, 4] arrays of (hash, t_a, t_b, t_c)) -> (u8 blob, u64 byte
+    offsets [n + 1]).  Bytes go through unchanged, so a length that is not a multiple of 16 reaches the library
+    (UCFP_E_INVALID)."""
+    parts = []
+    for x in items:
+        if isinstance(x, (bytes, bytearray, memoryview)):
+            parts.append(bytes(x))
+        else:
+            parts.append(np.ascontiguousarray(x, dtype=np.uint32).reshape(-1, 4).tobytes())
+    offs = np.zeros(len(parts) + 1, np.uint64)
+    np.cumsum([len(b) for b in parts], out=offs[1:])
+    blob = np.frombuffer(b"".join(parts) + b"\0" * 16, np.uint8)
+    return blob, offs
+
+
+PANAKO_MATCH_DEFAULTS = dict(scale_min=204, scale_max=320, scale_step=4, window=16, slack=2, r_slack=1)
+
+
+def panako_match_config(**match) -> "_lib.PanakoMatchConfig":
+    """ucfp_panako_match_config from keyword arguments over PANAKO_MATCH_DEFAULTS (scales in units of 1/256)."""
+    unknown = set(match) - set(PANAKO_MATCH_DEFAULTS)
+    if unknown:
+        raise InvalidArgument(f"unknown match parameters: {sorted(unknown)}")
+    v = {**PANAKO_MATCH_DEFAULTS, **match}
+    if not all(isinstance(x, (int, np.integer)) and 0 <= int(x) < 1 << 32 for x in v.values()):
+        raise InvalidArgument("match parameters are integers in 0 ... 2^32 - 1")
+    return _lib.PanakoMatchConfig(*(int(v[name]) for name in PANAKO_MATCH_DEFAULTS))
+
+
+class PanakoIndex:
+    """Thin RAII wrapper over one ucfp_panako_index (DESIGN A14): records and queries are Panako records; a query
+    answers the top-k records by votes that agree on a (scale, offset) pair, so a time-stretched copy still matches."""
+
+    def __init__(self, max_postings: int = 0, flags: int = 0, ctx=None):
+        self._lib = _lib.load()
+        self.ctx = ctx or _lib.current_context()
+        self.max_postings = max_postings
+        h = C.c_void_p()
+        _lib.check(self._lib.ucfp_panako_index_create(self.ctx.handle, max_postings, flags, C.byref(h)))
+        self.handle = h
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self._lib.ucfp_panako_index_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def lds_votes() -> int:
+        """Expanded votes up to which a query is answered in on-chip memory."""
+        return int(_lib.load().ucfp_panako_index_lds_votes())
+
+    def upsert(self, tenant: int, ids, records) -> None:
+        """ids [n]; records: n Panako records (bytes or uint32 [m, 4] of (hash, t_a, t_b, t_c))."""
+        ids = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        records = list(records)
+        if len(records) != ids.shape[0]:
+            raise InvalidArgument("ids and records disagree on the number of records")
+        blob, offs = _pack_triplets(records)
+        _lib.check(self._lib.ucfp_panako_index_upsert(self.handle, tenant, ids.ctypes.data, blob.ctypes.data,
+                                                      offs.ctypes.data, ids.shape[0]))
+
+    def upsert_dev(self, tenant: int, ids_ptr: int, records_ptr: int, offsets_ptr: int, n: int, stream: int = 0) -> None:
+        _lib.check(self._lib.ucfp_panako_index_upsert_dev(self.handle, tenant, ids_ptr, records_ptr or None, offsets_ptr, n,
+                                                          stream or None))
+
+    def delete(self, tenant: int, ids) -> int:
+        ids = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        removed = C.c_size_t(0)
+        _lib.check(self._lib.ucfp_panako_index_delete(self.handle, tenant, ids.ctypes.data, ids.shape[0], C.byref(removed)))
+        return int(removed.value)
+
+    def size(self, tenant: int):
+        """-> (records, postings) of a tenant."""
+        r, p = C.c_size_t(0), C.c_size_t(0)
+        _lib.check(self._lib.ucfp_panako_index_size(self.handle, tenant, C.byref(r), C.byref(p)))
+        return int(r.value), int(p.value)
+
+    def flush(self) -> None:
+        _lib.check(self._lib.ucfp_panako_index_flush(self.handle))
+
+    def query(self, tenant: int, queries, k: int, min_votes: int = 1, **match):
+        """queries: Panako records (bytes or uint32 [m, 4]); match: fields of PANAKO_MATCH_DEFAULTS.  -> (ids [nq,k] u64,
+        votes [nq,k] u32, offsets [nq,k] i32, scales [nq,k] u32 in 1/256, scores [nq,k] f32, counts [nq] u32)."""
+        cfg = panako_match_config(**match)
+        blob, offs = _pack_triplets(list(queries))
+        nq = offs.size - 1
+        kk = max(int(k), 1)
+        ids = np.full((nq, kk), INVALID_ID, np.uint64)
+        votes = np.zeros((nq, kk), np.uint32)
+        offsets = np.zeros((nq, kk), np.int32)
+        scales = np.zeros((nq, kk), np.uint32)
+        scores = np.zeros((nq, kk), np.float32)
+        counts = np.zeros(nq, np.uint32)
+        _lib.check(self._lib.ucfp_panako_index_query(self.handle, tenant, blob.ctypes.data, offs.ctypes.data, nq, int(k),
+                                                     int(min_votes), C.byref(cfg), ids.ctypes.data, votes.ctypes.data,
+                                                     offsets.ctypes.data, scales.ctypes.data, scores.ctypes.data,
+                                                     counts.ctypes.data))
+        return ids[:, :k], votes[:, :k], offsets[:, :k], scales[:, :k], scores[:, :k], counts
+
+    def query_dev(self, tenant: int, records_ptr: int, offsets_ptr: int, nq: int, k: int, min_votes: int, out_ids_ptr: int,
+                  out_votes_ptr: int, out_offsets_ptr: int, out_scales_ptr: int, out_scores_ptr: int, out_n_ptr: int,
+                  stream: int = 0, **match) -> None:
+        cfg = panako_match_config(**match)
+        _lib.check(self._lib.ucfp_panako_index_query_dev(self.handle, tenant, records_ptr or None, offsets_ptr, nq, k,
+                                                         min_votes, C.byref(cfg), out_ids_ptr or None, out_votes_ptr or None,
+                                                         out_offsets_ptr or None, out_scales_ptr or None,
+                                                         out_scores_ptr or None, out_n_ptr, stream or None))
+
+
 def _pack_frames(items):
     """Sequence of sub-fingerprint blocks (bytes, or uint32 [m] arrays) -> (u32 frames, u64 element offsets [n + 1])."""
     parts = []
@@ -504,6 +622,7 @@ class GpuIndex:
         self._ham = {}        # hash space name -> DeviceIndex
         self._lm = None       # LandmarkIndex of the audiofp-wang-v1 records (DESIGN A10)
         self._pk = None       # LandmarkIndex of the audiofp-panako-v1 records' (hash, t_anchor) pairs (DESIGN A13)
+        self._ps = None       # PanakoIndex of the same records' triples: the (scale, offset) vote (DESIGN A14)
         self._hx = None       # HaitsmaIndex of the audiofp-haitsma-v1 records (DESIGN A12)
         self._bm = None       # Bm25Index of the records with text (DESIGN A11)
         self._sidecar = sidecar   # ucfp_amd.store.Sidecar: the stored-table mirror written at upsert
@@ -533,6 +652,11 @@ class GpuIndex:
             self._pk = LandmarkIndex(0, 0, self.ctx)
         return self._pk
 
+    def _panako_stretch(self) -> PanakoIndex:
+        if self._ps is None:
+            self._ps = PanakoIndex(0, 0, self.ctx)
+        return self._ps
+
     def _haitsma(self) -> HaitsmaIndex:
         if self._hx is None:
             self._hx = HaitsmaIndex(0, 0, self.ctx)
@@ -546,6 +670,7 @@ class GpuIndex:
     def _all(self):
         return (list(self._cos.values()) + list(self._ham.values()) + ([self._lm] if self._lm is not None else [])
                 + ([self._pk] if self._pk is not None else [])
+                + ([self._ps] if self._ps is not None else [])
                 + ([self._hx] if self._hx is not None else [])
                 + ([self._bm] if self._bm is not None else []))
 
@@ -607,6 +732,7 @@ class GpuIndex:
             self._lm.delete(tenant, np.array(ids, np.uint64))
         for tenant, ids in stale_pk.items():
             self._pk.delete(tenant, np.array(ids, np.uint64))
+            self._ps.delete(tenant, np.array(ids, np.uint64))
         for tenant, ids in stale_hx.items():
             self._hx.delete(tenant, np.array(ids, np.uint64))
         for tenant, ids in stale_bm.items():
@@ -619,6 +745,8 @@ class GpuIndex:
         for tenant, recs in by_pk.items():
             self._panako().upsert(tenant, np.array([r.record_id for r in recs], np.uint64),
                                   [panako_landmarks(bytes(r.fingerprint)) for r in recs])
+            self._panako_stretch().upsert(tenant, np.array([r.record_id for r in recs], np.uint64),
+                                          [bytes(r.fingerprint) for r in recs])
         for tenant, recs in by_hx.items():
             self._haitsma().upsert(tenant, np.array([r.record_id for r in recs], np.uint64),
                                    [bytes(r.fingerprint) for r in recs])
@@ -672,6 +800,19 @@ class GpuIndex:
         return [Hit(tenant_id=tenant_id, record_id=int(ids[0, i]), score=float(scores[0, i]), source=HitSource.Landmark,
                     votes=int(votes[0, i]), offset=int(offs[0, i])) for i in range(int(counts[0]))]
 
+    def identify_stretched(self, tenant_id: int, records, k: int, min_votes: int = 1, **match) -> List[Hit]:
+        """Which recording is this clip, where in it and at what tempo: records = Panako records as bytes (16 per
+        triplet) or uint32 [n, 4] of (hash, t_a, t_b, t_c).  Hits by votes that agree on a scale and an offset window
+        (DESIGN A14; `match` overrides PANAKO_MATCH_DEFAULTS): `offset` = the clip's frame 0 in the record, `scale` =
+        the record's frames per frame of the clip."""
+        if self._ps is None:
+            panako_match_config(**match)
+            return []
+        ids, votes, offs, scales, scores, counts = self._ps.query(tenant_id, [records], min(k, MAX_K), min_votes, **match)
+        return [Hit(tenant_id=tenant_id, record_id=int(ids[0, i]), score=float(scores[0, i]), source=HitSource.Landmark,
+                    votes=int(votes[0, i]), offset=int(offs[0, i]), scale=int(scales[0, i]) / 256.0)
+                for i in range(int(counts[0]))]
+
     def identify_frames(self, tenant_id: int, frames, k: int, flip_bits: int = 2, max_ber: float = 0.35) -> List[Hit]:
         """Which recording is this clip, and where in it: frames = Haitsma sub-fingerprints as bytes (4 per frame) or
         uint32 [m], m <= HAITSMA_MAX_QUERY_FRAMES.  Hits by bit errors over the whole block at the best alignment found
@@ -697,17 +838,22 @@ class GpuIndex:
     def query(self, req) -> List[Hit]:
         """POST /v1/query (handlers.rs:143-187) with the additive `hash` field: a vector goes to the cosine kNN,
         a hash to the Hamming space `algorithm` (default: the only hash space present), `landmarks` to identify (the Panako
-        index when `algorithm` is "audiofp-panako-v1", the Wang one otherwise), `subfingerprints` to identify_frames;
+        index when `algorithm` is "audiofp-panako-v1", the Wang one otherwise), `triplets` to identify_stretched,
+        `subfingerprints` to identify_frames;
         `terms` go through the matcher (BM25, or vector + BM25 fused by RRF: src/matcher/mod.rs:140-207)."""
         if (getattr(req, "landmarks", None) is None and getattr(req, "subfingerprints", None) is None and req.hash is None
-                and getattr(req, "terms", None)):
+                and getattr(req, "triplets", None) is None and getattr(req, "terms", None)):
             from . import matcher
             hits = matcher.search(self, req)
             for rank, h in enumerate(hits):
                 if h.source == HitSource.Bm25:
                     h.bm25_score, h.bm25_rank = h.score, rank + 1
             return hits
-        if getattr(req, "landmarks", None) is not None:
+        if getattr(req, "triplets", None) is not None:
+            if getattr(req, "algorithm", None) != ALGORITHM_PANAKO:
+                raise InvalidArgument(f"`triplets` need `algorithm` = {ALGORITHM_PANAKO!r}")
+            hits = self.identify_stretched(req.tenant_id, req.triplets, req.k)
+        elif getattr(req, "landmarks", None) is not None:
             panako = getattr(req, "algorithm", None) == ALGORITHM_PANAKO
             hits = self.identify(req.tenant_id, req.landmarks, req.k,
                                  algorithm=ALGORITHM_PANAKO if panako else ALGORITHM_WANG)

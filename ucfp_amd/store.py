@@ -207,6 +207,8 @@ def rebuild(path: str, ctx=None, sidecar: bool = False):
         for tenant, recs in panako.items():     # their (hash, t_anchor) pairs, in a landmark index of their own (A13)
             gi._panako().upsert(tenant, np.array([r.record_id for r in recs], np.uint64),
                                 [panako_landmarks(bytes(r.fingerprint)) for r in recs])
+            gi._panako_stretch().upsert(tenant, np.array([r.record_id for r in recs], np.uint64),   # and their triples (A14)
+                                        [bytes(r.fingerprint) for r in recs])
         for tenant, recs in haitsma.items():
             gi._haitsma().upsert(tenant, np.array([r.record_id for r in recs], np.uint64), [r.fingerprint for r in recs])
         for dim in snap.dims():

@@ -496,6 +496,56 @@ int ucfp_text_simhash_batch_dev(ucfp_ctx* ctx, const uint8_t* d_utf8, const uint
 int ucfp_text_simhash_batch(ucfp_ctx* ctx, const uint8_t* utf8, const uint64_t* offsets, size_t n, int mode,
                             uint8_t* out, int32_t* status);
 
+/* ---- TLSH 128/1 (the `tlsh` arm of the text route, src/modality/text.rs:452-484, tag "tlsh-128-1") ----
+ * The digest of a BYTE STRING: for a text record the UTF-8 of the canonicalised, preprocessed text (the reference's
+ * tokenizer tag "tlsh-bytes"); there is no `mode`, bytes are bytes, 0x00 and 0xff included.  Same blob + n + 1 byte
+ * offsets shape as the MinHash calls.  A record is UCFP_TLSH_BYTES bytes in the order of the published hex string:
+ * swap(checksum), swap(L), (Q1 << 4) | Q2, code[31] .. code[0] (swap exchanges the nibbles); the reference stores
+ * "T1" + the 70 upper-case hex digits of these bytes.
+ * status[i] (may be NULL): 0, or UCFP_E_MODALITY for a document that TLSH refuses -- shorter than 50 bytes, at most 64
+ * of the 128 buckets non-zero, or 2^31 bytes and longer; its record is all zero.  n = 0 is a no-op.  One wave hashes
+ * one document whatever its length.
+ * PARITY: bit-exact against the restatement of the published algorithm in tests/tlsh_ref.py only; no digest made by
+ * another implementation was available. */
+#define UCFP_TLSH_BYTES 35u
+#define UCFP_TLSH_MAX_DISTANCE 2473u /* 1536 (L) + 84 + 84 (Q1, Q2) + 1 (checksum) + 768 (body) */
+/* src/modality/text.rs:452-484 */
+int ucfp_text_tlsh_batch_dev(ucfp_ctx* ctx, const uint8_t* d_bytes, const uint64_t* d_offsets, size_t n, uint8_t* d_out,
+                             int32_t* d_status, void* stream);
+/* src/modality/text.rs:452-484; host pointers */
+int ucfp_text_tlsh_batch(ucfp_ctx* ctx, const uint8_t* bytes, const uint64_t* offsets, size_t n, uint8_t* out,
+                         int32_t* status);
+/* Host-only (no device needed).  The L byte of a document of n bytes, from the committed table of class boundaries
+ * (include/ucfp_tlsh_ltab.h); the TLSH distance of two 35-byte digests, 0 .. UCFP_TLSH_MAX_DISTANCE (a NULL argument
+ * gives UCFP_TLSH_MAX_DISTANCE). */
+uint32_t ucfp_tlsh_lvalue(uint64_t n);
+uint32_t ucfp_tlsh_distance(const uint8_t* a, const uint8_t* b);
+
+/* TLSH-distance search: the k <= UCFP_INDEX_MAX_K rows of a tenant nearest to each query digest, EXACT, ties included.
+ *   rows / queries   packed 35-byte digests; any 35 bytes are a valid row
+ *   upsert           a known id replaces its row; tenants are isolated; delete reports how many ids it removed
+ *   query            rows with distance > max_distance are left out (UINT32_MAX: no cut); order (distance ascending,
+ *                    id ascending); score = (float)(2473 - distance) / 2473.0f.  out_ids / out_dist / out_scores: nq x k,
+ *                    unused slots UCFP_INVALID_ID / UINT32_MAX / -1; out_n: nq.  An unknown tenant, k = 0 or nq = 0
+ *                    gives 0 hits.
+ * Mutations are host bookkeeping; the device rows of a tenant are rebuilt at its next query (or by flush).  The
+ * *_dev calls take device pointers and a stream and are stream-ordered.  Not built: sharding over GPUs, a search
+ * micro-batcher, save / load. */
+typedef struct ucfp_tlsh_index ucfp_tlsh_index;
+int ucfp_tlsh_index_create(ucfp_ctx* ctx, uint32_t flags, ucfp_tlsh_index** out);
+void ucfp_tlsh_index_destroy(ucfp_tlsh_index* ix);
+int ucfp_tlsh_index_upsert(ucfp_tlsh_index* ix, uint32_t tenant, const uint64_t* ids, const uint8_t* digests, size_t n);
+int ucfp_tlsh_index_upsert_dev(ucfp_tlsh_index* ix, uint32_t tenant, const uint64_t* d_ids, const uint8_t* d_digests,
+                               size_t n, void* stream);
+int ucfp_tlsh_index_delete(ucfp_tlsh_index* ix, uint32_t tenant, const uint64_t* ids, size_t n, size_t* n_removed);
+int ucfp_tlsh_index_size(ucfp_tlsh_index* ix, uint32_t tenant, size_t* rows);
+int ucfp_tlsh_index_flush(ucfp_tlsh_index* ix);
+int ucfp_tlsh_index_query(ucfp_tlsh_index* ix, uint32_t tenant, const uint8_t* digests, size_t nq, uint32_t k,
+                          uint32_t max_distance, uint64_t* out_ids, uint32_t* out_dist, float* out_scores, uint32_t* out_n);
+int ucfp_tlsh_index_query_dev(ucfp_tlsh_index* ix, uint32_t tenant, const uint8_t* d_digests, size_t nq, uint32_t k,
+                              uint32_t max_distance, uint64_t* d_out_ids, uint32_t* d_out_dist, float* d_out_scores,
+                              uint32_t* d_out_n, void* stream);
+
 /* Host micro-batcher for documents: the caller side of handlers::ingest_text
  * (src/server/handlers.rs:304-460) fingerprints one document per request thread, up to 512 in flight
  * (src/bin/ucfp.rs:267).  submit() is BLOCKING and thread-safe: concurrent calls are packed back to back into one

@@ -20,6 +20,7 @@ class HitSource:
     Hamming = "hamming"   # new capability behind /v1/query; not in the reference
     Landmark = "landmark"  # audio identification over Wang landmarks (DESIGN A10); not in the reference
     Haitsma = "haitsma"    # audio identification over Haitsma sub-fingerprints (DESIGN A12); not in the reference
+    Tlsh = "tlsh"          # nearest `tlsh-128-1` records by TLSH distance (DESIGN A15); not in the reference
 
 
 @dataclass
@@ -57,7 +58,7 @@ class Hit:
     vector_rank: Optional[int] = None
     bm25_rank: Optional[int] = None
     term_hits: list = field(default_factory=list)
-    distance: Optional[int] = None    # Hamming distance when source == "hamming"; bit errors of the block when "haitsma"
+    distance: Optional[int] = None    # Hamming distance when source == "hamming"; bit errors of the block when "haitsma"; TLSH distance when "tlsh"
     votes: Optional[int] = None       # offset-consistent landmark matches when source == "landmark"
     offset: Optional[int] = None      # where the query's frame 0 lies in the record (frames) when source == "landmark" / "haitsma"
     scale: Optional[float] = None     # record frames per query frame, from the (scale, offset) vote over Panako triplets (DESIGN A14)
@@ -78,6 +79,8 @@ FORMAT_VERSION = 1  # src/lib.rs:62
 # `scale`.
 # Identification by bit-error rate adds `subfingerprints` (DESIGN A12): Haitsma frames as bytes (4 per frame, u32 LE) or a
 # list of integers.
+# TLSH-distance search adds `tlsh` (DESIGN A15): the digest string a `tlsh-128-1` record stores ("T1" + 70 hex digits; the
+# prefix may be left out) or the 35 digest bytes (bytes, or a list of 35 integers); valid with `algorithm` = "tlsh-128-1" or none.
 # A body the reference accepts parses to the same query here.
 
 DEFAULT_K = 10   # dto.rs:85-87
@@ -94,6 +97,7 @@ class QueryRequest:
     landmarks: Optional[bytes] = None   # 8 bytes per landmark: u32 LE hash, u32 LE t
     subfingerprints: Optional[bytes] = None   # 4 bytes per frame: u32 LE (an audiofp-haitsma-v1 block)
     triplets: Optional[bytes] = None    # 16 bytes per Panako triplet: u32 LE hash, t_a, t_b, t_c (DESIGN A14)
+    tlsh: Optional[bytes] = None        # the 35 bytes of a TLSH digest (DESIGN A15)
     terms: List[str] = field(default_factory=list)
     explain: bool = False
 
@@ -107,12 +111,16 @@ class QueryRequest:
             raise InvalidArgument(f"bad query body: {e}") from None
         k = int(body.get("k", DEFAULT_K))
         vector, h, lm = body.get("vector"), body.get("hash"), body.get("landmarks")
-        sub, tri = body.get("subfingerprints"), body.get("triplets")
+        sub, tri, tl = body.get("subfingerprints"), body.get("triplets"), body.get("tlsh")
         terms = body.get("terms") or []
         if not isinstance(terms, list) or not all(isinstance(t, str) for t in terms):
             raise InvalidArgument("`terms` must be a list of strings")
-        if vector is None and h is None and lm is None and sub is None and tri is None and not terms:
+        if vector is None and h is None and lm is None and sub is None and tri is None and tl is None and not terms:
             raise InvalidArgument("query needs `vector` (dto.rs:80-82), `terms`, `hash`, `landmarks` or `subfingerprints`")
+        if tl is not None:
+            tl = _tlsh_bytes(tl)
+            if body.get("algorithm") not in (None, "tlsh-128-1"):
+                raise InvalidArgument("`tlsh` goes with `algorithm` = \"tlsh-128-1\" or none")
         if tri is not None:
             tri = _triplet_bytes(tri)
         if sub is not None:
@@ -128,7 +136,7 @@ class QueryRequest:
         return cls(tenant_id=tenant_id, modality=modality, k=max(k, 1),       # handlers.rs:153: k.max(1)
                    vector=[float(x) for x in vector] if vector is not None else None,
                    hash=int(h) if h is not None else None, algorithm=body.get("algorithm"), landmarks=lm, subfingerprints=sub,
-                   triplets=tri,
+                   triplets=tri, tlsh=tl,
                    terms=list(terms), explain=_flag(body.get("explain", False)))
 
 
@@ -174,6 +182,33 @@ def _triplet_bytes(tri) -> bytes:
             raise InvalidArgument("every triplet must be [hash, t_a, t_b, t_c], integers below 2^32")
         out += b"".join(int(x).to_bytes(4, "little") for x in p)
     return bytes(out)
+
+
+def _tlsh_bytes(tl) -> bytes:
+    """`tlsh` of a query body -> the 35 digest bytes."""
+    from .errors import InvalidArgument
+    if isinstance(tl, list):
+        if len(tl) != 35 or not all(isinstance(x, int) and not isinstance(x, bool) and 0 <= x < 256 for x in tl):
+            raise InvalidArgument("`tlsh` as a list must be 35 integers below 256")
+        return bytes(tl)
+    if isinstance(tl, (bytes, bytearray)) and len(tl) == 35:
+        return bytes(tl)
+    if isinstance(tl, (bytes, bytearray)):
+        try:
+            tl = bytes(tl).decode("ascii")
+        except UnicodeDecodeError:
+            raise InvalidArgument("`tlsh` bytes must be the 35 digest bytes or the digest string") from None
+    if not isinstance(tl, str):
+        raise InvalidArgument("`tlsh` must be the digest string or the 35 digest bytes")
+    if len(tl) == 72 and tl[:2] in ("T1", "t1"):
+        tl = tl[2:]
+    try:
+        raw = bytes.fromhex(tl) if len(tl) == 70 else b""
+    except ValueError:
+        raw = b""
+    if len(raw) != 35:
+        raise InvalidArgument("`tlsh` must be 70 hex digits, with or without the T1 prefix")
+    return raw
 
 
 def _subfingerprint_bytes(sub) -> bytes:

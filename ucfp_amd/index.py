@@ -11,6 +11,7 @@ path, backed by the GPU-resident shard behind the C ABI (ucfp_index_*).
     GpuIndex.identify_stretched(tenant, records, k)  the same over whole Panako triplets, by a (scale, offset) vote that
                                       survives a change of tempo (DESIGN A14; PanakoIndex)
     GpuIndex.identify_frames(tenant, frames, k)  the same over Haitsma sub-fingerprints (DESIGN A12; HaitsmaIndex)
+    GpuIndex.nearest_tlsh(tenant, digest, k)  the `tlsh-128-1` records at the smallest TLSH distance (DESIGN A15; TlshIndex)
     GpuIndex.bm25(tenant, terms, k)   IndexBackend::bm25 / bm25_explain :37-50 over Record.text (DESIGN A11; Bm25Index)
     GpuIndex.flush()                  IndexBackend::flush    :63
 
@@ -28,6 +29,7 @@ from .audio import ALGORITHM_HAITSMA, ALGORITHM_PANAKO, ALGORITHM_WANG, panako_l
 from .core import Hit, HitSource, Record, TermHit
 from .errors import InvalidArgument, UnsupportedError
 from .terms import query_terms, tokenize
+from .text import ALGORITHM_TLSH
 
 HAMMING64, COSINE_F32 = 1, 2
 APPEND_ONLY = 1
@@ -471,6 +473,89 @@ class HaitsmaIndex:
                                                           stream or None))
 
 
+class TlshIndex:
+    """Thin RAII wrapper over one ucfp_tlsh_index (DESIGN A15): rows and queries are TLSH digests (35 bytes each, or
+    any form text.tlsh_digest_bytes takes); a query answers the k rows at the smallest TLSH distance, exactly."""
+
+    def __init__(self, flags: int = 0, ctx=None):
+        self._lib = _lib.load()
+        self.ctx = ctx or _lib.current_context()
+        h = C.c_void_p()
+        _lib.check(self._lib.ucfp_tlsh_index_create(self.ctx.handle, flags, C.byref(h)))
+        self.handle = h
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self._lib.ucfp_tlsh_index_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def upsert(self, tenant: int, ids, digests) -> None:
+        """ids [n]; digests: uint8 [n, 35], or n digests as bytes / strings."""
+        ids = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        rows = _pack_digests(digests)
+        if rows.shape[0] != ids.shape[0]:
+            raise InvalidArgument("ids and digests disagree on the number of rows")
+        _lib.check(self._lib.ucfp_tlsh_index_upsert(self.handle, tenant, ids.ctypes.data, rows.ctypes.data, ids.shape[0]))
+
+    def upsert_dev(self, tenant: int, ids_ptr: int, digests_ptr: int, n: int, stream: int = 0) -> None:
+        _lib.check(self._lib.ucfp_tlsh_index_upsert_dev(self.handle, tenant, ids_ptr, digests_ptr, n, stream or None))
+
+    def delete(self, tenant: int, ids) -> int:
+        ids = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        removed = C.c_size_t(0)
+        _lib.check(self._lib.ucfp_tlsh_index_delete(self.handle, tenant, ids.ctypes.data, ids.shape[0], C.byref(removed)))
+        return int(removed.value)
+
+    def size(self, tenant: int) -> int:
+        r = C.c_size_t(0)
+        _lib.check(self._lib.ucfp_tlsh_index_size(self.handle, tenant, C.byref(r)))
+        return int(r.value)
+
+    def flush(self) -> None:
+        _lib.check(self._lib.ucfp_tlsh_index_flush(self.handle))
+
+    def query(self, tenant: int, digests, k: int, max_distance: Optional[int] = None):
+        """-> (ids [nq,k] u64, dist [nq,k] u32, scores [nq,k] f32, counts [nq] u32); rows farther than `max_distance`
+        are left out (None: no cut)."""
+        q = _pack_digests(digests)
+        nq = q.shape[0]
+        kk = max(int(k), 1)
+        ids = np.full((nq, kk), INVALID_ID, np.uint64)
+        dist = np.full((nq, kk), 0xFFFFFFFF, np.uint32)
+        scores = np.full((nq, kk), -1.0, np.float32)
+        counts = np.zeros(nq, np.uint32)
+        md = 0xFFFFFFFF if max_distance is None else int(max_distance)
+        _lib.check(self._lib.ucfp_tlsh_index_query(self.handle, tenant, q.ctypes.data, nq, int(k), md, ids.ctypes.data,
+                                                   dist.ctypes.data, scores.ctypes.data, counts.ctypes.data))
+        return ids[:, :k], dist[:, :k], scores[:, :k], counts
+
+    def query_dev(self, tenant: int, digests_ptr: int, nq: int, k: int, max_distance: int, out_ids_ptr: int,
+                  out_dist_ptr: int, out_scores_ptr: int, out_n_ptr: int, stream: int = 0) -> None:
+        _lib.check(self._lib.ucfp_tlsh_index_query_dev(self.handle, tenant, digests_ptr, nq, k, max_distance,
+                                                       out_ids_ptr or None, out_dist_ptr or None, out_scores_ptr or None,
+                                                       out_n_ptr, stream or None))
+
+
+def _pack_digests(digests) -> np.ndarray:
+    """-> uint8 [n, 35] (one spare row behind it, so the pointer is never to an empty buffer)."""
+    from .text import TLSH_BYTES, tlsh_digest_bytes
+    if isinstance(digests, np.ndarray) and digests.dtype == np.uint8:
+        rows = digests.reshape(-1, TLSH_BYTES)
+    else:
+        if isinstance(digests, (bytes, bytearray, str)):
+            digests = [digests]
+        rows = np.frombuffer(b"".join(tlsh_digest_bytes(d) for d in digests), np.uint8).reshape(-1, TLSH_BYTES)
+    buf = np.zeros((rows.shape[0] + 1, TLSH_BYTES), np.uint8)
+    buf[:rows.shape[0]] = rows
+    return buf[:rows.shape[0]]
+
+
 class Bm25Index:
     """Thin RAII wrapper over one ucfp_bm25_index (DESIGN A11): BM25 over documents of (key, tf) pairs.  It keeps the
     term -> key dictionary of the index (keys number the terms in order of first sight); query terms it has never
@@ -625,6 +710,7 @@ class GpuIndex:
         self._ps = None       # PanakoIndex of the same records' triples: the (scale, offset) vote (DESIGN A14)
         self._hx = None       # HaitsmaIndex of the audiofp-haitsma-v1 records (DESIGN A12)
         self._bm = None       # Bm25Index of the records with text (DESIGN A11)
+        self._tl = None       # TlshIndex of the tlsh-128-1 records (DESIGN A15)
         self._sidecar = sidecar   # ucfp_amd.store.Sidecar: the stored-table mirror written at upsert
 
     def attach_sidecar(self, sidecar) -> None:
@@ -662,6 +748,11 @@ class GpuIndex:
             self._hx = HaitsmaIndex(0, 0, self.ctx)
         return self._hx
 
+    def _tlsh(self) -> TlshIndex:
+        if self._tl is None:
+            self._tl = TlshIndex(0, self.ctx)
+        return self._tl
+
     def _bm25(self) -> Bm25Index:
         if self._bm is None:
             self._bm = Bm25Index(0, self.ctx)
@@ -672,7 +763,8 @@ class GpuIndex:
                 + ([self._pk] if self._pk is not None else [])
                 + ([self._ps] if self._ps is not None else [])
                 + ([self._hx] if self._hx is not None else [])
-                + ([self._bm] if self._bm is not None else []))
+                + ([self._bm] if self._bm is not None else [])
+                + ([self._tl] if self._tl is not None else []))
 
     def upsert(self, records: Sequence[Record]) -> None:
         """Embeddings go to the cosine index of their dimension; image records also feed the
@@ -693,7 +785,7 @@ class GpuIndex:
         for r in records:
             last[(r.tenant_id, r.record_id)] = r
         by_cos, by_ham, stale_cos, stale_ham, by_lm, stale_lm, by_bm, stale_bm = {}, {}, {}, {}, {}, {}, {}, {}
-        by_hx, stale_hx, by_pk, stale_pk = {}, {}, {}, {}
+        by_hx, stale_hx, by_pk, stale_pk, by_tl, stale_tl = {}, {}, {}, {}, {}, {}
         for r in last.values():
             if r.text is not None:
                 by_bm.setdefault(r.tenant_id, []).append(r)
@@ -711,6 +803,10 @@ class GpuIndex:
                 by_hx.setdefault(r.tenant_id, []).append(r)
             elif self._hx is not None:
                 stale_hx.setdefault(r.tenant_id, []).append(r.record_id)
+            if r.algorithm == ALGORITHM_TLSH:
+                by_tl.setdefault(r.tenant_id, []).append(r)
+            elif self._tl is not None:
+                stale_tl.setdefault(r.tenant_id, []).append(r.record_id)
             dim = len(r.embedding) if r.embedding is not None else 0
             if dim > 0:
                 by_cos.setdefault((r.tenant_id, dim), []).append(r)
@@ -735,6 +831,8 @@ class GpuIndex:
             self._ps.delete(tenant, np.array(ids, np.uint64))
         for tenant, ids in stale_hx.items():
             self._hx.delete(tenant, np.array(ids, np.uint64))
+        for tenant, ids in stale_tl.items():
+            self._tl.delete(tenant, np.array(ids, np.uint64))
         for tenant, ids in stale_bm.items():
             self._bm.delete(tenant, np.array(ids, np.uint64))
         for tenant, recs in by_bm.items():
@@ -750,6 +848,9 @@ class GpuIndex:
         for tenant, recs in by_hx.items():
             self._haitsma().upsert(tenant, np.array([r.record_id for r in recs], np.uint64),
                                    [bytes(r.fingerprint) for r in recs])
+        for tenant, recs in by_tl.items():
+            self._tlsh().upsert(tenant, np.array([r.record_id for r in recs], np.uint64),
+                                [bytes(r.fingerprint) for r in recs])
         for (tenant, dim), recs in by_cos.items():
             ids = np.array([r.record_id for r in recs], np.uint64)
             rows = np.array([r.embedding for r in recs], np.float32)
@@ -825,6 +926,15 @@ class GpuIndex:
         return [Hit(tenant_id=tenant_id, record_id=int(ids[0, i]), score=float(scores[0, i]), source=HitSource.Haitsma,
                     distance=int(dist[0, i]), offset=int(offs[0, i])) for i in range(int(counts[0]))]
 
+    def nearest_tlsh(self, tenant_id: int, digest, k: int, max_distance: Optional[int] = None) -> List[Hit]:
+        """The `tlsh-128-1` records nearest to a digest (35 bytes, or the digest string a record stores): hits by TLSH
+        distance, nearest first (DESIGN A15); `distance` = the TLSH distance, score = (2473 - distance) / 2473."""
+        if k == 0 or self._tl is None:
+            return []
+        ids, dist, scores, counts = self._tl.query(tenant_id, [digest], min(k, MAX_K), max_distance)
+        return [Hit(tenant_id=tenant_id, record_id=int(ids[0, i]), score=float(scores[0, i]), source=HitSource.Tlsh,
+                    distance=int(dist[0, i])) for i in range(int(counts[0]))]
+
     def bm25(self, tenant_id: int, terms: Sequence[str], k: int, filter: Optional[bytes] = None,
              explain: bool = False) -> List[Hit]:
         """IndexBackend::bm25 / bm25_explain (src/index/embedded/mod.rs:127-150): "bm25" hits by BM25 score (DESIGN
@@ -839,17 +949,22 @@ class GpuIndex:
         """POST /v1/query (handlers.rs:143-187) with the additive `hash` field: a vector goes to the cosine kNN,
         a hash to the Hamming space `algorithm` (default: the only hash space present), `landmarks` to identify (the Panako
         index when `algorithm` is "audiofp-panako-v1", the Wang one otherwise), `triplets` to identify_stretched,
-        `subfingerprints` to identify_frames;
+        `subfingerprints` to identify_frames, `tlsh` to nearest_tlsh;
         `terms` go through the matcher (BM25, or vector + BM25 fused by RRF: src/matcher/mod.rs:140-207)."""
         if (getattr(req, "landmarks", None) is None and getattr(req, "subfingerprints", None) is None and req.hash is None
-                and getattr(req, "triplets", None) is None and getattr(req, "terms", None)):
+                and getattr(req, "triplets", None) is None and getattr(req, "tlsh", None) is None
+                and getattr(req, "terms", None)):
             from . import matcher
             hits = matcher.search(self, req)
             for rank, h in enumerate(hits):
                 if h.source == HitSource.Bm25:
                     h.bm25_score, h.bm25_rank = h.score, rank + 1
             return hits
-        if getattr(req, "triplets", None) is not None:
+        if getattr(req, "tlsh", None) is not None:
+            if getattr(req, "algorithm", None) not in (None, ALGORITHM_TLSH):
+                raise InvalidArgument(f"`tlsh` goes with `algorithm` = {ALGORITHM_TLSH!r} or none")
+            hits = self.nearest_tlsh(req.tenant_id, req.tlsh, req.k)
+        elif getattr(req, "triplets", None) is not None:
             if getattr(req, "algorithm", None) != ALGORITHM_PANAKO:
                 raise InvalidArgument(f"`triplets` need `algorithm` = {ALGORITHM_PANAKO!r}")
             hits = self.identify_stretched(req.tenant_id, req.triplets, req.k)

@@ -166,6 +166,7 @@ def rebuild(path: str, ctx=None, sidecar: bool = False):
     `sidecar=True` keeps the log attached, so later upserts / deletes are appended to it."""
     import torch
     from .audio import ALGORITHM_HAITSMA, ALGORITHM_PANAKO, ALGORITHM_WANG, panako_landmarks
+    from .text import ALGORITHM_TLSH
     from .index import GpuIndex
     ctx = ctx or _lib.current_context()
     lib = _lib.load()
@@ -194,7 +195,7 @@ def rebuild(path: str, ctx=None, sidecar: bool = False):
                 gi._hamming(algorithm).upsert(int(tenant), ids[sel], np.ascontiguousarray(blobs[sel]).view(np.uint64).reshape(-1))
         # Wang records are variable length: walk the rows (the landmark index keeps its record table on the host)
         # (so are Haitsma records: the sub-fingerprint index does the same)
-        wang, haitsma, panako = {}, {}, {}
+        wang, haitsma, panako, tlsh = {}, {}, {}, {}
         for r in snap:
             if r.algorithm == ALGORITHM_WANG:
                 wang.setdefault(r.tenant_id, []).append(r)
@@ -202,6 +203,8 @@ def rebuild(path: str, ctx=None, sidecar: bool = False):
                 haitsma.setdefault(r.tenant_id, []).append(r)
             elif r.algorithm == ALGORITHM_PANAKO:
                 panako.setdefault(r.tenant_id, []).append(r)
+            elif r.algorithm == ALGORITHM_TLSH:
+                tlsh.setdefault(r.tenant_id, []).append(r)
         for tenant, recs in wang.items():
             gi._landmarks().upsert(tenant, np.array([r.record_id for r in recs], np.uint64), [r.fingerprint for r in recs])
         for tenant, recs in panako.items():     # their (hash, t_anchor) pairs, in a landmark index of their own (A13)
@@ -211,6 +214,8 @@ def rebuild(path: str, ctx=None, sidecar: bool = False):
                                         [bytes(r.fingerprint) for r in recs])
         for tenant, recs in haitsma.items():
             gi._haitsma().upsert(tenant, np.array([r.record_id for r in recs], np.uint64), [r.fingerprint for r in recs])
+        for tenant, recs in tlsh.items():      # digest strings: the TLSH index keeps its row table on the host too (A15)
+            gi._tlsh().upsert(tenant, np.array([r.record_id for r in recs], np.uint64), [bytes(r.fingerprint) for r in recs])
         for dim in snap.dims():
             tenants, ids, rows = snap.gather_vectors(dim)
             for tenant in np.unique(tenants):

@@ -4,8 +4,9 @@
     fingerprint_minhash_with(text, opts, tenant_id, record_id)      text.rs:182-236  (H = 128)
     fingerprint_simhash_tf / fingerprint_simhash_idf                text.rs:328-362
     fingerprint_lsh                                                 text.rs:437-446
+    fingerprint_tlsh                                                text.rs:452-484  (TLSH 128/1, DESIGN A15)
 
-plus the batched form (`minhash_batch` / `simhash_batch`).  Hashing runs in the HIP library.
+plus the batched form (`minhash_batch` / `simhash_batch` / `tlsh_batch`).  Hashing runs in the HIP library.
 ASCII documents go to the GPU raw (it lower-cases and segments them); a document with non-ASCII
 characters is canonicalised (NFKC + case fold + Bidi/Cf stripping, text.rs:112-114) and segmented
 (UAX#29 via the `regex` module) here on the host, then submitted pre-tokenised -- Unicode tables are
@@ -29,6 +30,7 @@ ALGORITHM_MINHASH_128 = "minhash-h128"
 ALGORITHM_SIMHASH_TF = "simhash-b64-tf"
 ALGORITHM_SIMHASH_IDF = "simhash-b64-idf"
 ALGORITHM_LSH = "minhash-lsh-h128"
+ALGORITHM_TLSH = "tlsh-128-1"
 FORMAT_VERSION = 1   # txtfp::FORMAT_VERSION as stored by text.rs:227
 # MinHash / LSH records: the slot derivation (DESIGN T5) is KNOWN not to be txtfp 0.2.0's (the reference's
 # golden slot 0, src/server/tests.rs:1153-1157, is not reproduced), so these records carry their own
@@ -39,6 +41,9 @@ FORMAT_VERSION_MINHASH_HIP = 0x48500001
 RAW_ASCII, PRETOKENIZED = 0, 1
 NEEDS_HOST = 1
 MINHASH_BYTES, SIMHASH_BYTES = 1032, 8
+TLSH_BYTES = 35             # UCFP_TLSH_BYTES: swap(checksum), swap(L), Q1 << 4 | Q2, code[31] .. code[0]
+TLSH_MAX_DISTANCE = 2473    # UCFP_TLSH_MAX_DISTANCE
+TLSH_MIN_BYTES = 50         # shorter documents are refused (the reference's README.md:96)
 # UCFP_TEXT_MAX_WINDOW_BYTES (include/ucfp_hip.h, derived there): a document is always hashed when every window of k
 # consecutive tokens (the whole document below k tokens, the single token for SimHash) has at most this many
 # canonical bytes, separators included; longer windows may get status -2.
@@ -291,6 +296,82 @@ def fingerprint_lsh(text: str, opts: TextOpts, tenant_id: int, record_id: int,
     rec = fingerprint_minhash_with(text, opts, tenant_id, record_id, config_hash_value)
     rec.algorithm = ALGORITHM_LSH
     return rec
+
+
+def _tlsh_input(doc, opts: TextOpts) -> bytes:
+    """What TLSH hashes: bytes as they are; a string's UTF-8 after canonicalisation (the reference's tokenizer tag
+    "tlsh-bytes": no tokens, so non-ASCII text needs no host segmentation)."""
+    if isinstance(doc, (bytes, bytearray, memoryview)):
+        return bytes(doc)
+    if opts.preprocess is not None:
+        raise UnsupportedError(f"preprocess `{opts.preprocess}` is not built into the HIP path")
+    return opts.canonicalizer.apply(doc).encode("utf-8")
+
+
+def tlsh_batch(texts_or_bytes: Sequence, opts: Optional[TextOpts] = None, ctx=None):
+    """TLSH 128/1 of every document, one wave each (ucfp_text_tlsh_batch).
+    -> (digests uint8 [n, 35], status int32 [n]): status -1 and a zero digest for a document TLSH refuses (shorter than
+    50 bytes, or at most 64 of its 128 buckets non-zero)."""
+    opts = opts or TextOpts()
+    docs = [_tlsh_input(d, opts) for d in texts_or_bytes]
+    n = len(docs)
+    out = np.zeros((n, TLSH_BYTES), np.uint8)
+    status = np.zeros(n, np.int32)
+    if n == 0:
+        return out, status
+    ctx = ctx or _lib.current_context()
+    blob, offs = _pack(docs)
+    _lib.check(_lib.load().ucfp_text_tlsh_batch(ctx.handle, blob.ctypes.data, offs.ctypes.data, n, out.ctypes.data,
+                                                status.ctypes.data))
+    return out, status
+
+
+def tlsh_hex(digest) -> bytes:
+    """35 digest bytes -> the 72 bytes a record stores: "T1" + 70 upper-case hex digits (text.rs:478, `sig.hex`)."""
+    return b"T1" + bytes(digest).hex().upper().encode("ascii")
+
+
+def tlsh_digest_bytes(d) -> bytes:
+    """A digest in any of its forms -> the 35 raw bytes: raw bytes, or the 72 / 70-character hex digest (str or bytes)."""
+    if isinstance(d, np.ndarray):
+        d = d.astype(np.uint8).tobytes()
+    if isinstance(d, (bytes, bytearray, memoryview)):
+        d = bytes(d)
+        if len(d) == TLSH_BYTES:
+            return d
+        try:
+            d = d.decode("ascii")
+        except UnicodeDecodeError:
+            raise InvalidArgument("a TLSH digest is 35 raw bytes or 70 hex digits, with or without the T1 prefix") from None
+    if not isinstance(d, str):
+        raise InvalidArgument("a TLSH digest is bytes or a string")
+    if len(d) == 2 * TLSH_BYTES + 2 and d[:2] in ("T1", "t1"):
+        d = d[2:]
+    if len(d) != 2 * TLSH_BYTES:
+        raise InvalidArgument("a TLSH digest is 35 raw bytes or 70 hex digits, with or without the T1 prefix")
+    try:
+        return bytes.fromhex(d)
+    except ValueError:
+        raise InvalidArgument("a TLSH digest string must be hexadecimal") from None
+
+
+def tlsh_distance(a, b) -> int:
+    """The TLSH distance of two digests, 0 .. 2473 (host code: ucfp_tlsh_distance needs no device)."""
+    a, b = tlsh_digest_bytes(a), tlsh_digest_bytes(b)
+    return int(_lib.load().ucfp_tlsh_distance(a, b))
+
+
+def fingerprint_tlsh(text: str, opts: TextOpts, tenant_id: int, record_id: int,
+                     config_hash_value: Optional[int] = None) -> Record:
+    """text.rs:452-484: `fingerprint` = the digest string, `text` = the prepared text."""
+    digs, status = tlsh_batch([text], opts)
+    if int(status[0]) != 0:
+        raise ModalityError(f"TLSH refuses the document: fewer than {TLSH_MIN_BYTES} bytes after canonicalisation, or too "
+                            "little variety (at most 64 of the 128 buckets used)")
+    return Record(tenant_id=tenant_id, record_id=record_id, modality=Modality.Text, format_version=FORMAT_VERSION,
+                  algorithm=ALGORITHM_TLSH,
+                  config_hash=_record_config_hash(opts, "tlsh-bytes", ALGORITHM_TLSH, config_hash_value),
+                  fingerprint=tlsh_hex(digs[0]), embedding=None, model_id=None, metadata=b"", text=text)
 
 
 def _dev(a: np.ndarray):

@@ -456,11 +456,24 @@ int ucfp_audio_resample_linear_dev(ucfp_ctx* ctx, const float* d_in, size_t n, u
  *                           (Unicode tables live there) and resubmits it as
  *   UCFP_TEXT_PRETOKENIZED  tokens already canonical, separated by single spaces.  Every byte other
  *                           than ' ' is a token byte, 0x00 included.
+ *   UCFP_TEXT_RAW_UTF8      the GPU canonicalises (NFKC + case fold + Cf stripping, text.rs:112-114, as a table of
+ *                           per-code-point mappings) and segments (UAX#29 words as the host path finds them) any
+ *                           UTF-8 document over the COVERED set of code points (ASCII, Latin, Greek,
+ *                           Cyrillic, Hebrew, Arabic, punctuation, kana, Han, Hangul syllables, compatibility forms;
+ *                           include/ucfp_text_utab.h), then hashes the result as PRETOKENIZED.  The record is the one
+ *                           the host path (canonicalise + tokenise on the host, PRETOKENIZED) gives.  A document with
+ *                           malformed UTF-8 or an uncovered code point (combining marks, Hangul jamo, regional
+ *                           indicators, unassigned ...) gets UCFP_TEXT_NEEDS_HOST and a zero record; that status wins
+ *                           over the hash pass's.  Unlike RAW_ASCII this mode follows UAX#29 for '_' and has the
+ *                           `regex` module's apostrophe tailoring, so an ASCII document gives the same record in both
+ *                           modes iff it holds neither '_' nor '\''.  The _dev calls read d_offsets[0] and
+ *                           d_offsets[n] back (they wait for `stream` once) to size the context's scratch.
  * status[i]: 0, UCFP_TEXT_NEEDS_HOST, UCFP_E_MODALITY (no tokens), UCFP_E_UNSUPPORTED (k - 1 tokens
  * plus the token being read do not fit the LDS batch, see UCFP_TEXT_MAX_WINDOW_BYTES).
  */
 #define UCFP_TEXT_RAW_ASCII 0
 #define UCFP_TEXT_PRETOKENIZED 1
+#define UCFP_TEXT_RAW_UTF8 2
 #define UCFP_TEXT_NEEDS_HOST 1
 /* A document is ALWAYS hashed (never UCFP_E_UNSUPPORTED) when every window of k consecutive tokens -- the whole
  * document when it has fewer than k tokens, the single token for SimHash -- has a canonical length (token bytes plus
@@ -495,6 +508,29 @@ int ucfp_text_simhash_batch_dev(ucfp_ctx* ctx, const uint8_t* d_utf8, const uint
                                 int mode, uint8_t* d_out, int32_t* d_status, void* stream);
 int ucfp_text_simhash_batch(ucfp_ctx* ctx, const uint8_t* utf8, const uint64_t* offsets, size_t n, int mode,
                             uint8_t* out, int32_t* status);
+
+/* ---- the first half of UCFP_TEXT_RAW_UTF8 on its own: documents -> canonical token strings ----
+ * What the Rust host otherwise does with txtfp's canonicaliser and tokeniser before text::fingerprint_minhash_with
+ * (src/modality/text.rs:112-114,182-236).  tok_offsets has n + 1 entries (tok_offsets[0] = 0); document i's tokens, joined
+ * by single spaces, are tokens[tok_offsets[i] .. tok_offsets[i + 1]); status[i] is 0 or UCFP_TEXT_NEEDS_HOST (then the
+ * document has no token bytes).  The blob never exceeds ucfp_text_canon_bound(bytes of the batch) = 4 x the input. */
+/* src/modality/text.rs:112-114,182-236; host code, no device */
+size_t ucfp_text_canon_bound(size_t n_bytes);
+/* src/modality/text.rs:112-114,182-236; d_tokens holds ucfp_text_canon_bound(d_offsets[n] - d_offsets[0]) bytes; no
+ * workspace, no synchronisation: three launches on `stream` */
+int ucfp_text_canon_batch_dev(ucfp_ctx* ctx, const uint8_t* d_utf8, const uint64_t* d_offsets, size_t n, uint8_t* d_tokens,
+                              uint64_t* d_tok_offsets, int32_t* d_status, void* stream);
+/* src/modality/text.rs:112-114,182-236; host pointers; UCFP_E_INVALID when the blob is larger than tokens_cap */
+int ucfp_text_canon_batch(ucfp_ctx* ctx, const uint8_t* utf8, const uint64_t* offsets, size_t n, uint8_t* tokens,
+                          size_t tokens_cap, uint64_t* tok_offsets, int32_t* status);
+/* Host code, no device: the compiled code-point table (include/ucfp_text_utab.h).  Returns 1 when cp is covered (U1), else
+ * 0.  Covered: out_cps[0 .. *n) = M(cp), 0 .. 6 code points; when *n == 1, *cls_flags describes that one canonical code
+ * point -- bits 0-3 Word_Break class (0 Other, 1 ALetter, 2 Hebrew_Letter, 3 Numeric, 4 Katakana, 5 ExtendNumLet,
+ * 6 MidLetter, 7 MidNum, 8 MidNumLet, 9 Single_Quote, 10 Double_Quote), bit 4 str.isalnum, bit 5 vowel of the apostrophe
+ * tailoring -- otherwise 0: every code point of M(cp) is covered and maps to itself, look it up in turn.
+ * ucfp_text_utab_versions: "unicodedata <version> regex <version>" the table was generated with. */
+int ucfp_text_utab_lookup(uint32_t cp, uint32_t out_cps[8], uint32_t* n, uint32_t* cls_flags);
+const char* ucfp_text_utab_versions(void);
 
 /* ---- TLSH 128/1 (the `tlsh` arm of the text route, src/modality/text.rs:452-484, tag "tlsh-128-1") ----
  * The digest of a BYTE STRING: for a text record the UTF-8 of the canonicalised, preprocessed text (the reference's

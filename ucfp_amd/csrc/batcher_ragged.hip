@@ -198,7 +198,8 @@ int ucfp_text_batcher_create(ucfp_ctx* ctx, uint32_t algo, int mode, uint32_t sh
     *out = nullptr;
     if (algo != UCFP_TEXT_ALGO_MINHASH && algo != UCFP_TEXT_ALGO_SIMHASH)
         return capi_fail(UCFP_E_UNSUPPORTED, "text batcher algo %u (one of UCFP_TEXT_ALGO_*)", algo);
-    if (mode != UCFP_TEXT_RAW_ASCII && mode != UCFP_TEXT_PRETOKENIZED) return capi_fail(UCFP_E_INVALID, "unknown text mode %d", mode);
+    if (mode != UCFP_TEXT_RAW_ASCII && mode != UCFP_TEXT_PRETOKENIZED && mode != UCFP_TEXT_RAW_UTF8)
+        return capi_fail(UCFP_E_INVALID, "unknown text mode %d", mode);
     if (algo == UCFP_TEXT_ALGO_MINHASH && (shingle_k == 0 || shingle_k > 64))
         return capi_fail(UCFP_E_MODALITY, "shingle k must be in [1, 64] (got %u)", shingle_k);
     if (max_batch == 0 || max_batch > (1u << 20) || max_bytes == 0 || max_bytes >= ((size_t)1 << 32))

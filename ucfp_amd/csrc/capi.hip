@@ -126,6 +126,7 @@ int ucfp_ctx_create(int device_id, ucfp_ctx** out) {
     if (e2 == hipSuccess) e2 = hipEventCreateWithFlags(&c->audio_done, hipEventDisableTiming);
     if (e2 == hipSuccess) e2 = hipEventCreateWithFlags(&c->png_done, hipEventDisableTiming);
     if (e2 == hipSuccess) e2 = hipEventCreateWithFlags(&c->norm_done, hipEventDisableTiming);
+    if (e2 == hipSuccess) e2 = hipEventCreateWithFlags(&c->canon_done, hipEventDisableTiming);
     if (e2 == hipSuccess) e2 = hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking);
     if (e2 == hipSuccess) e2 = hipEventCreateWithFlags(&c->side_fork, hipEventDisableTiming);
     if (e2 == hipSuccess) e2 = hipEventCreateWithFlags(&c->side_join, hipEventDisableTiming);
@@ -156,6 +157,8 @@ void ucfp_ctx_destroy(ucfp_ctx* c) {
     if (c->b3_ws) (void)hipFree(c->b3_ws);
     if (c->norm_done) (void)hipEventDestroy(c->norm_done);
     if (c->geo) (void)hipFree(c->geo);
+    if (c->canon_ws) (void)hipFree(c->canon_ws);
+    if (c->canon_done) (void)hipEventDestroy(c->canon_done);
     for (int i = 0; i < 2; i++) {
         if (c->item_h[i]) (void)hipHostFree(c->item_h[i]);
         if (c->item_d[i]) (void)hipFree(c->item_d[i]);
@@ -831,7 +834,7 @@ int ucfp_audio_haitsma(ucfp_ctx* ctx, const float* pcm, size_t n, uint32_t sampl
 
 static int text_check(ucfp_ctx* ctx, const void* utf8, const void* offsets, size_t n, int mode, const void* out) {
     if (!ctx) return fail(UCFP_E_INVALID, "ctx is NULL");
-    if (mode != UCFP_TEXT_RAW_ASCII && mode != UCFP_TEXT_PRETOKENIZED)
+    if (mode != UCFP_TEXT_RAW_ASCII && mode != UCFP_TEXT_PRETOKENIZED && mode != UCFP_TEXT_RAW_UTF8)
         return fail(UCFP_E_INVALID, "unknown text mode %d", mode);
     if (n && (!offsets || !out)) return fail(UCFP_E_INVALID, "offsets/out is NULL");
     if (n > 0x7fffffffu) return fail(UCFP_E_INVALID, "batch of %zu documents exceeds one launch", n);
@@ -839,11 +842,25 @@ static int text_check(ucfp_ctx* ctx, const void* utf8, const void* offsets, size
     return UCFP_OK;
 }
 
+// Mode UCFP_TEXT_RAW_UTF8 of the _dev calls: the scratch is sized by the batch's bytes, which only the device knows --
+// d_offsets[0] and d_offsets[n] are read back behind the work already on `stream` (the one place these calls wait).
+static int text_utf8_dev(ucfp_ctx* ctx, bool sim, const uint8_t* d_utf8, const uint64_t* d_offsets, size_t n, uint32_t k,
+                         uint8_t* d_out, int32_t* d_status, hipStream_t stream) {
+    if (n == 0) return UCFP_OK;
+    uint64_t ends[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(&ends[0], d_offsets, 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(&ends[1], d_offsets + n, 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (ends[1] < ends[0]) return fail(UCFP_E_INVALID, "offsets must be non-decreasing");
+    return ucfp::text_utf8_hash(ctx, sim, d_utf8, d_offsets, n, (size_t)(ends[1] - ends[0]), k, d_out, d_status, stream);
+}
+
 int ucfp_text_minhash_batch_dev(ucfp_ctx* ctx, const uint8_t* d_utf8, const uint64_t* d_offsets, size_t n,
                                 int mode, uint32_t shingle_k, uint8_t* d_out, int32_t* d_status, void* stream) {
     int rc = text_check(ctx, d_utf8, d_offsets, n, mode, d_out);
     if (rc) return rc;
     if (shingle_k == 0 || shingle_k > 64) return fail(UCFP_E_MODALITY, "shingle k must be in [1, 64] (got %u)", shingle_k);
+    if (mode == UCFP_TEXT_RAW_UTF8) return text_utf8_dev(ctx, false, d_utf8, d_offsets, n, shingle_k, d_out, d_status, (hipStream_t)stream);
     ucfp::launch_text_minhash(d_utf8, d_offsets, n, mode, shingle_k, d_out, d_status, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return UCFP_OK;
@@ -853,6 +870,7 @@ int ucfp_text_simhash_batch_dev(ucfp_ctx* ctx, const uint8_t* d_utf8, const uint
                                 int mode, uint8_t* d_out, int32_t* d_status, void* stream) {
     int rc = text_check(ctx, d_utf8, d_offsets, n, mode, d_out);
     if (rc) return rc;
+    if (mode == UCFP_TEXT_RAW_UTF8) return text_utf8_dev(ctx, true, d_utf8, d_offsets, n, 1, d_out, d_status, (hipStream_t)stream);
     ucfp::launch_text_simhash(d_utf8, d_offsets, n, mode, d_out, d_status, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return UCFP_OK;
@@ -885,7 +903,10 @@ static int text_host(ucfp_ctx* ctx, bool sim, const uint8_t* utf8, const uint64_
     HIP_TRY(hipMemcpyAsync(ctx->stage_in + o_off, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
     const uint64_t* d_off = reinterpret_cast<const uint64_t*>(ctx->stage_in + o_off);
     int32_t* d_st = reinterpret_cast<int32_t*>(ctx->stage_out + o_st);
-    if (sim) ucfp::launch_text_simhash(ctx->stage_in, d_off, n, mode, ctx->stage_out, d_st, st);
+    if (mode == UCFP_TEXT_RAW_UTF8) {
+        rc = ucfp::text_utf8_hash(ctx, sim, ctx->stage_in, d_off, n, total, k, ctx->stage_out, d_st, st);
+        if (rc) return rc;
+    } else if (sim) ucfp::launch_text_simhash(ctx->stage_in, d_off, n, mode, ctx->stage_out, d_st, st);
     else ucfp::launch_text_minhash(ctx->stage_in, d_off, n, mode, k, ctx->stage_out, d_st, st);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out, ctx->stage_out, n * rec, hipMemcpyDeviceToHost, st));

@@ -310,6 +310,13 @@ int launch_text_minhash(const uint8_t* utf8, const uint64_t* offsets, size_t n, 
 int launch_text_simhash(const uint8_t* utf8, const uint64_t* offsets, size_t n, int mode, uint8_t* out,
                         int32_t* status, hipStream_t stream);
 
+// text_canon.hip: mode UCFP_TEXT_RAW_UTF8.  launch_text_canon: tok_off has n + 1 words, tokens ucfp_text_canon_bound(bytes
+// of the batch) bytes, status n words (0 / UCFP_TEXT_NEEDS_HOST); count, scan and emit are enqueued on `stream`.
+int launch_text_canon(const uint8_t* utf8, const uint64_t* offsets, size_t n, uint8_t* tokens, uint64_t* tok_off,
+                      int32_t* status, hipStream_t stream);
+int text_utf8_hash(ucfp_ctx* ctx, bool sim, const uint8_t* d_utf8, const uint64_t* d_offsets, size_t n, size_t total_bytes,
+                   uint32_t k, uint8_t* d_out, int32_t* d_status, hipStream_t stream);
+
 // audio.hip
 struct WangWs {
     size_t frames = 0;          // upper bounds (the per-clip lengths of a batch live on the device)

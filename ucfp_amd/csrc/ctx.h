@@ -34,6 +34,12 @@ struct ucfp_ctx {
     // BLAKE3 chaining values of the last batch (+ the digests when the PNG call computes `exact` itself); ordered by png_done
     uint8_t* b3_ws = nullptr;
     size_t b3_ws_cap = 0;
+    // text mode RAW_UTF8: token offsets, canon statuses and the token blob of the last batch (text_canon.hip); its users are
+    // ordered across streams by canon_done, enqueued under canon_mu
+    std::mutex canon_mu;
+    uint8_t* canon_ws = nullptr;
+    size_t canon_ws_cap = 0;
+    hipEvent_t canon_done = nullptr;
     // per-frame tables of ragged image batches (ImgItem rows, rejected slots): two pinned + device buffer pairs used in
     // turn; `used[i]` is recorded behind the kernels that read pair i and waited for before the host rewrites it
     std::mutex item_mu;

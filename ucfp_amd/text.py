@@ -7,13 +7,16 @@
     fingerprint_tlsh                                                text.rs:452-484  (TLSH 128/1, DESIGN A15)
 
 plus the batched form (`minhash_batch` / `simhash_batch` / `tlsh_batch`).  Hashing runs in the HIP library.
-ASCII documents go to the GPU raw (it lower-cases and segments them); a document with non-ASCII
-characters is canonicalised (NFKC + case fold + Bidi/Cf stripping, text.rs:112-114) and segmented
-(UAX#29 via the `regex` module) here on the host, then submitted pre-tokenised -- Unicode tables are
-host business (SURVEY "hard parts").
+ASCII documents go to the GPU raw (it lower-cases and segments them).  A document with non-ASCII characters goes
+to the GPU as UTF-8 (mode RAW_UTF8: the default canonicaliser -- NFKC + case fold + Bidi/Cf stripping,
+text.rs:112-114 -- and the UAX#29 word tokeniser as tables).  Only what the device hands back
+(combining marks, Hangul jamo, regional indicators, malformed text) or what it does not build (another
+canonicaliser) is canonicalised and segmented here on the host (`_prepare`, via the `regex` module) and submitted
+pre-tokenised; both routes give the same record.
 """
 import ctypes as C
 import math
+import threading
 import unicodedata
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence, Tuple
@@ -38,7 +41,7 @@ FORMAT_VERSION = 1   # txtfp::FORMAT_VERSION as stored by text.rs:227
 # incompatible instead of yielding meaningless Jaccard estimates.  Layout, schema word and tag are upstream's.
 FORMAT_VERSION_MINHASH_HIP = 0x48500001
 
-RAW_ASCII, PRETOKENIZED = 0, 1
+RAW_ASCII, PRETOKENIZED, RAW_UTF8 = 0, 1, 2
 NEEDS_HOST = 1
 MINHASH_BYTES, SIMHASH_BYTES = 1032, 8
 TLSH_BYTES = 35             # UCFP_TLSH_BYTES: swap(checksum), swap(L), Q1 << 4 | Q2, code[31] .. code[0]
@@ -146,14 +149,46 @@ def _run(kind: str, docs: Sequence[bytes], mode: int, k: int, ctx=None):
     return out, status
 
 
+def _device_utf8(text: str, opts: TextOpts) -> bool:
+    """The document goes to the GPU as UTF-8 (mode RAW_UTF8): not ASCII (mode RAW_ASCII is cheaper and keeps its own
+    documented `_` rule, DESIGN U6), default canonicaliser, `word` tokeniser."""
+    return opts.tokenizer == "word" and opts.canonicalizer.is_default() and not text.isascii()
+
+
+def canon_batch(docs: Sequence[bytes], ctx=None) -> Tuple[List[bytes], np.ndarray]:
+    """UTF-8 documents -> (their canonical tokens joined by single spaces, status int32 [n]) on the GPU
+    (ucfp_text_canon_batch).  Status NEEDS_HOST and an empty string for a document the device does not cover: for
+    every other document the bytes are the ones `_prepare` makes on the host."""
+    n = len(docs)
+    status = np.zeros(n, np.int32)
+    if n == 0:
+        return [], status
+    ctx = ctx or _lib.current_context()
+    lib = _lib.load()
+    blob, offs = _pack(docs)
+    cap = int(lib.ucfp_text_canon_bound(int(offs[n])))
+    toks = np.zeros(max(cap, 1), np.uint8)
+    toff = np.zeros(n + 1, np.uint64)
+    _lib.check(lib.ucfp_text_canon_batch(ctx.handle, blob.ctypes.data, offs.ctypes.data, n, toks.ctypes.data, cap,
+                                         toff.ctypes.data, status.ctypes.data))
+    return [toks[int(toff[i]):int(toff[i + 1])].tobytes() for i in range(n)], status
+
+
 def _batch(kind: str, texts: Sequence[str], opts: TextOpts, ctx=None):
-    """Split into the raw-ASCII and the host-pretokenised group, one launch each."""
-    prepared = [_prepare(t, opts) for t in texts]
+    """Split into the raw-ASCII, the raw-UTF-8 and the host-pretokenised group, one launch each; the documents the
+    UTF-8 launch hands back join the host group."""
     rec = SIMHASH_BYTES if kind == "simhash" else MINHASH_BYTES
     out = np.zeros((len(texts), rec), np.uint8)
     status = np.zeros(len(texts), np.int32)
+    dev = [i for i, t in enumerate(texts) if _device_utf8(t, opts)]
+    if dev:
+        o, s = _run(kind, [texts[i].encode("utf-8", "surrogatepass") for i in dev], RAW_UTF8, opts.k, ctx)
+        out[dev] = o
+        status[dev] = s
+    done = {i for i, st in zip(dev, status[dev]) if st != NEEDS_HOST}
+    prepared = [None if i in done else _prepare(t, opts) for i, t in enumerate(texts)]
     for mode in (RAW_ASCII, PRETOKENIZED):
-        idx = [i for i, (_, m) in enumerate(prepared) if m == mode]
+        idx = [i for i, p in enumerate(prepared) if p is not None and p[1] == mode]
         if not idx:
             continue
         o, s = _run(kind, [prepared[i][0] for i in idx], mode, opts.k, ctx)
@@ -176,8 +211,9 @@ ALGO_MINHASH, ALGO_SIMHASH = 1, 2
 
 class TextBatcher:
     """Host micro-batcher (handlers.rs:304-460 fingerprints one document per request): many request
-    threads call `submit` concurrently, the library packs them into one GPU launch.  Two C batchers sit behind this
-    object -- one for raw ASCII documents, one for the documents the host had to canonicalise and tokenise."""
+    threads call `submit` concurrently, the library packs them into one GPU launch.  Three C batchers sit behind this
+    object -- one for raw ASCII documents, one for raw UTF-8 documents, one for the documents the host had to
+    canonicalise and tokenise (the ones the UTF-8 batcher handed back among them)."""
 
     def __init__(self, kind: str = "minhash", opts: Optional[TextOpts] = None, *, max_batch: int = 4096,
                  max_bytes: int = 8 << 20, max_delay_us: int = 200, ctx=None):
@@ -190,7 +226,9 @@ class TextBatcher:
         self.rec = MINHASH_BYTES if kind == "minhash" else SIMHASH_BYTES
         algo = ALGO_MINHASH if kind == "minhash" else ALGO_SIMHASH
         self._handles = {}
-        for mode in (RAW_ASCII, PRETOKENIZED):
+        self._handed_back = 0
+        self._mu = threading.Lock()
+        for mode in (RAW_ASCII, PRETOKENIZED, RAW_UTF8):
             h = C.c_void_p()
             _lib.check(self._lib.ucfp_text_batcher_create(self.ctx.handle, algo, mode, self.opts.k, max_batch, max_bytes,
                                                           max_delay_us, C.byref(h)))
@@ -198,20 +236,27 @@ class TextBatcher:
 
     def submit(self, text: str):
         """-> (record bytes, status).  Blocks until this document's record is ready."""
-        doc, mode = _prepare(text, self.opts)
         out = (C.c_uint8 * self.rec)()
         st = C.c_int32(0)
+        if _device_utf8(text, self.opts):
+            doc = text.encode("utf-8", "surrogatepass")
+            _lib.check(self._lib.ucfp_text_batcher_submit(self._handles[RAW_UTF8], doc, len(doc), out, C.byref(st)))
+            if int(st.value) != NEEDS_HOST:
+                return bytes(out), int(st.value)
+            with self._mu:
+                self._handed_back += 1
+        doc, mode = _prepare(text, self.opts)
         _lib.check(self._lib.ucfp_text_batcher_submit(self._handles[mode], doc, len(doc), out, C.byref(st)))
         return bytes(out), int(st.value)
 
     def stats(self):
-        """-> (launches, documents) summed over both modes."""
+        """-> (launches, documents) summed over the modes; a document handed back by the device counts once."""
         tb = ti = 0
         for h in self._handles.values():
             b, i = C.c_uint64(0), C.c_uint64(0)
             _lib.check(self._lib.ucfp_text_batcher_stats(h, C.byref(b), C.byref(i)))
             tb, ti = tb + int(b.value), ti + int(i.value)
-        return tb, ti
+        return tb, ti - self._handed_back
 
     def close(self):
         for h in getattr(self, "_handles", {}).values():

@@ -582,6 +582,64 @@ int ucfp_tlsh_index_query_dev(ucfp_tlsh_index* ix, uint32_t tenant, const uint8_
                               uint32_t max_distance, uint64_t* d_out_ids, uint32_t* d_out_dist, float* d_out_scores,
                               uint32_t* d_out_n, void* stream);
 
+/* ---- image search over whole records: global and block hashes scored together ----
+ * The reference threads a compare-time MultiHashConfig through its adapter and its DTO (src/modality/image.rs:90-104,
+ * src/server/dto.rs:462-480: phash_weight, dhash_weight, ahash_weight, global_weight, block_weight,
+ * block_distance_threshold) and has no matcher that reads it; this is that matcher.  Rows and queries are the records
+ * ucfp_image_hash_batch* writes: 168 bytes (17 u64 LE codes: the global hash at byte 32, the 16 block hashes behind it)
+ * or the 536-byte bundle (3 x 17 codes, records at bytes 32, 200, 368 in the order ahash, phash, dhash); `exact` takes no
+ * part.  Per algorithm, with g and d_b the Hamming distances of the global and of block b and T the threshold:
+ *   S = sum over b of (d_b <= T ? 64 - d_b : 0);  sg = (float)(64 - g) * 2^-6;  sb = (float)S * 2^-10
+ *   s = (global_weight * sg) + (block_weight * sb)
+ * score = s for a 168-byte index (the three algorithm weights are then ignored), and for a bundle index
+ *   ((ahash_weight * s_ahash) + (phash_weight * s_phash)) + (dhash_weight * s_dhash)
+ * every product and sum rounded to f32 on its own; no normalisation, no clamp.  The defaults (ours; the reference
+ * states none) are 0.1 / 0.6 / 0.3, 0.4 / 0.6, T = 32, min_score = 0: a record against itself then scores 1.0f.
+ * UCFP_E_INVALID: a weight that is not finite or outside [0, 1] (-0 counts as 0), all three algorithm weights zero on a
+ * bundle, global_weight and block_weight both zero, block_distance_threshold > 64, min_score not finite or negative.
+ * PARITY: unpinned -- imgfprint's own compare is not in the tree; bit-exact against the restatement in
+ * tests/image_match_ref.py only. */
+typedef struct ucfp_image_match_config {
+    float ahash_weight;
+    float phash_weight;
+    float dhash_weight;
+    float global_weight;
+    float block_weight;
+    uint32_t block_distance_threshold;
+    float min_score; /* hits need score >= min_score */
+} ucfp_image_match_config;
+/* Host-only (no device needed): the defaults; the score of one pair of records of `algo` (one of UCFP_IMG_*; cfg NULL =
+ * defaults, validated as above). */
+void ucfp_image_match_config_default(ucfp_image_match_config* cfg);
+int ucfp_image_match_score(const uint8_t* a, const uint8_t* b, uint32_t algo, const ucfp_image_match_config* cfg, float* out);
+
+/* The index: the k <= UCFP_INDEX_MAX_K rows of a tenant that score highest against each query record, EXACT, ties included.
+ *   create           algo: one of UCFP_IMG_{AHASH,PHASH,DHASH,MULTI}, which fixes the record size (168 or 536 bytes);
+ *                    flags must be 0
+ *   upsert           a known id replaces its row; tenants are isolated; delete reports how many ids it removed;
+ *                    upsert_dev takes the records ucfp_image_hash_batch_dev wrote
+ *   query            cfg is a per-query setting (NULL = defaults), not index state.  Rows with score < min_score are left
+ *                    out; order (score descending, id ascending).  out_ids / out_scores: nq x k, unused slots
+ *                    UCFP_INVALID_ID / -1; out_n: nq.  An unknown tenant, k = 0 or nq = 0 gives 0 hits.
+ * Mutations are host bookkeeping; the device rows of a tenant are rebuilt at its next query (or by flush).  The
+ * *_dev calls take device pointers and a stream and are stream-ordered.  A tenant holds fewer than 2^31 rows; the row
+ * table lives on the host; one GPU.  Not built: sharding over GPUs, a search micro-batcher, save / load. */
+typedef struct ucfp_image_match_index ucfp_image_match_index;
+int ucfp_image_match_index_create(ucfp_ctx* ctx, uint32_t algo, uint32_t flags, ucfp_image_match_index** out);
+void ucfp_image_match_index_destroy(ucfp_image_match_index* ix);
+int ucfp_image_match_index_upsert(ucfp_image_match_index* ix, uint32_t tenant, const uint64_t* ids, const uint8_t* records,
+                                  size_t n);
+int ucfp_image_match_index_upsert_dev(ucfp_image_match_index* ix, uint32_t tenant, const uint64_t* d_ids,
+                                      const uint8_t* d_records, size_t n, void* stream);
+int ucfp_image_match_index_delete(ucfp_image_match_index* ix, uint32_t tenant, const uint64_t* ids, size_t n, size_t* n_removed);
+int ucfp_image_match_index_size(ucfp_image_match_index* ix, uint32_t tenant, size_t* rows);
+int ucfp_image_match_index_flush(ucfp_image_match_index* ix);
+int ucfp_image_match_index_query(ucfp_image_match_index* ix, uint32_t tenant, const uint8_t* records, size_t nq, uint32_t k,
+                                 const ucfp_image_match_config* cfg, uint64_t* out_ids, float* out_scores, uint32_t* out_n);
+int ucfp_image_match_index_query_dev(ucfp_image_match_index* ix, uint32_t tenant, const uint8_t* d_records, size_t nq, uint32_t k,
+                                     const ucfp_image_match_config* cfg, uint64_t* d_out_ids, float* d_out_scores,
+                                     uint32_t* d_out_n, void* stream);
+
 /* Host micro-batcher for documents: the caller side of handlers::ingest_text
  * (src/server/handlers.rs:304-460) fingerprints one document per request thread, up to 512 in flight
  * (src/bin/ucfp.rs:267).  submit() is BLOCKING and thread-safe: concurrent calls are packed back to back into one

@@ -51,6 +51,13 @@ class UploadInfo(C.Structure):
                 ("pixfmt", C.c_int32), ("reserved", C.c_uint32)]
 
 
+class ImageMatchConfig(C.Structure):
+    """ucfp_image_match_config: the compare-time weighting of the image match index (DESIGN A16, M4)."""
+    _fields_ = [("ahash_weight", C.c_float), ("phash_weight", C.c_float), ("dhash_weight", C.c_float),
+                ("global_weight", C.c_float), ("block_weight", C.c_float), ("block_distance_threshold", C.c_uint32),
+                ("min_score", C.c_float)]
+
+
 class ImagePreprocess(C.Structure):
     """ucfp_image_preprocess (imgfprint::PreprocessConfig guards)."""
     _fields_ = [("max_dimension", C.c_uint32), ("min_dimension", C.c_uint32)]
@@ -138,6 +145,20 @@ SIGNATURES = {
                                         C.c_void_p, C.c_void_p, C.c_void_p]),
     "ucfp_tlsh_index_query_dev": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ucfp_image_match_config_default": (None, [C.POINTER(ImageMatchConfig)]),
+    "ucfp_image_match_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ImageMatchConfig), C.POINTER(C.c_float)]),
+    "ucfp_image_match_index_create": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "ucfp_image_match_index_destroy": (None, [C.c_void_p]),
+    "ucfp_image_match_index_upsert": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "ucfp_image_match_index_upsert_dev": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ucfp_image_match_index_delete": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ucfp_image_match_index_size": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_size_t)]),
+    "ucfp_image_match_index_flush": (C.c_int, [C.c_void_p]),
+    "ucfp_image_match_index_query": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32,
+                                               C.POINTER(ImageMatchConfig), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ucfp_image_match_index_query_dev": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32,
+                                                   C.POINTER(ImageMatchConfig), C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p]),
     "ucfp_text_lsh_band_keys_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p,
                                               C.c_void_p]),
     "ucfp_lsh_create": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),

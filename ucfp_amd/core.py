@@ -21,6 +21,7 @@ class HitSource:
     Landmark = "landmark"  # audio identification over Wang landmarks (DESIGN A10); not in the reference
     Haitsma = "haitsma"    # audio identification over Haitsma sub-fingerprints (DESIGN A12); not in the reference
     Tlsh = "tlsh"          # nearest `tlsh-128-1` records by TLSH distance (DESIGN A15); not in the reference
+    ImageMatch = "image-match"   # image records by global and block hashes together (DESIGN A16); not in the reference
 
 
 @dataclass
@@ -81,6 +82,10 @@ FORMAT_VERSION = 1  # src/lib.rs:62
 # list of integers.
 # TLSH-distance search adds `tlsh` (DESIGN A15): the digest string a `tlsh-128-1` record stores ("T1" + 70 hex digits; the
 # prefix may be left out) or the 35 digest bytes (bytes, or a list of 35 integers); valid with `algorithm` = "tlsh-128-1" or none.
+# Image search over whole records adds `image_record` (DESIGN A16): the 168 bytes of a single-algorithm record or the 536 of
+# the bundle, as a list of integers, a hex string or bytes; `algorithm`, when given, must name the tag that goes with the
+# length.  `multi_hash` is the reference's MultiHashConfigDto object (kebab-case keys, dto.rs:462-480) and `min_score` a
+# number; both are optional and are checked when the query runs.
 # A body the reference accepts parses to the same query here.
 
 DEFAULT_K = 10   # dto.rs:85-87
@@ -98,6 +103,9 @@ class QueryRequest:
     subfingerprints: Optional[bytes] = None   # 4 bytes per frame: u32 LE (an audiofp-haitsma-v1 block)
     triplets: Optional[bytes] = None    # 16 bytes per Panako triplet: u32 LE hash, t_a, t_b, t_c (DESIGN A14)
     tlsh: Optional[bytes] = None        # the 35 bytes of a TLSH digest (DESIGN A15)
+    image_record: Optional[bytes] = None   # a whole image record, 168 or 536 bytes (DESIGN A16)
+    multi_hash: Optional[dict] = None   # MultiHashConfigDto of an `image_record` query (dto.rs:462-480)
+    min_score: Optional[float] = None   # hits of an `image_record` query need at least this score
     terms: List[str] = field(default_factory=list)
     explain: bool = False
 
@@ -112,11 +120,21 @@ class QueryRequest:
         k = int(body.get("k", DEFAULT_K))
         vector, h, lm = body.get("vector"), body.get("hash"), body.get("landmarks")
         sub, tri, tl = body.get("subfingerprints"), body.get("triplets"), body.get("tlsh")
+        img, mh, ms = body.get("image_record"), body.get("multi_hash"), body.get("min_score")
         terms = body.get("terms") or []
         if not isinstance(terms, list) or not all(isinstance(t, str) for t in terms):
             raise InvalidArgument("`terms` must be a list of strings")
-        if vector is None and h is None and lm is None and sub is None and tri is None and tl is None and not terms:
+        if (vector is None and h is None and lm is None and sub is None and tri is None and tl is None and img is None
+                and not terms):
             raise InvalidArgument("query needs `vector` (dto.rs:80-82), `terms`, `hash`, `landmarks` or `subfingerprints`")
+        if img is not None:
+            img = _image_record_bytes(img, body.get("algorithm"))
+            if mh is not None and not isinstance(mh, dict):
+                raise InvalidArgument("`multi_hash` must be an object")
+            if ms is not None and (isinstance(ms, bool) or not isinstance(ms, (int, float))):
+                raise InvalidArgument("`min_score` must be a number")
+        else:
+            mh = ms = None      # they belong to an `image_record` query
         if tl is not None:
             tl = _tlsh_bytes(tl)
             if body.get("algorithm") not in (None, "tlsh-128-1"):
@@ -136,7 +154,8 @@ class QueryRequest:
         return cls(tenant_id=tenant_id, modality=modality, k=max(k, 1),       # handlers.rs:153: k.max(1)
                    vector=[float(x) for x in vector] if vector is not None else None,
                    hash=int(h) if h is not None else None, algorithm=body.get("algorithm"), landmarks=lm, subfingerprints=sub,
-                   triplets=tri, tlsh=tl,
+                   triplets=tri, tlsh=tl, image_record=img, multi_hash=dict(mh) if mh is not None else None,
+                   min_score=float(ms) if ms is not None else None,
                    terms=list(terms), explain=_flag(body.get("explain", False)))
 
 
@@ -208,6 +227,34 @@ def _tlsh_bytes(tl) -> bytes:
         raw = b""
     if len(raw) != 35:
         raise InvalidArgument("`tlsh` must be 70 hex digits, with or without the T1 prefix")
+    return raw
+
+
+_IMAGE_RECORD_TAGS = {168: ("imgfprint-ahash-v1", "imgfprint-phash-v1", "imgfprint-dhash-v1"),
+                      536: ("imgfprint-multihash-v1",)}
+
+
+def _image_record_bytes(rec, algorithm) -> bytes:
+    """`image_record` of a query body -> the 168 or 536 record bytes; `algorithm`, when given, must go with the length."""
+    from .errors import InvalidArgument
+    if isinstance(rec, list):
+        if not all(isinstance(x, int) and not isinstance(x, bool) and 0 <= x < 256 for x in rec):
+            raise InvalidArgument("`image_record` as a list must be integers below 256")
+        raw = bytes(rec)
+    elif isinstance(rec, (bytes, bytearray)):
+        raw = bytes(rec)
+    elif isinstance(rec, str):
+        try:
+            raw = bytes.fromhex(rec)
+        except ValueError:
+            raise InvalidArgument("`image_record` as a string must be hexadecimal") from None
+    else:
+        raise InvalidArgument("`image_record` must be a list of integers, a hex string or bytes")
+    if len(raw) not in _IMAGE_RECORD_TAGS:
+        raise InvalidArgument(f"`image_record` must be 168 or 536 bytes, not {len(raw)}")
+    if algorithm is not None and algorithm not in _IMAGE_RECORD_TAGS[len(raw)]:
+        raise InvalidArgument(f"an `image_record` of {len(raw)} bytes goes with `algorithm` in "
+                              f"{list(_IMAGE_RECORD_TAGS[len(raw)])} or none, not {algorithm!r}")
     return raw
 
 

@@ -20,7 +20,7 @@ import numpy as np
 
 from . import _lib
 from .core import Modality, Record
-from .errors import ModalityError
+from .errors import InvalidArgument, ModalityError
 
 # algorithm tags: src/modality/image.rs:38-48
 ALGORITHM = "imgfprint-multihash-v1"
@@ -48,6 +48,83 @@ class PreprocessConfig:
 
     def _c(self) -> _lib.ImagePreprocess:
         return _lib.ImagePreprocess(self.max_dimension, self.min_dimension)
+
+
+@dataclass
+class MultiHashConfig:
+    """imgfprint::MultiHashConfig as the reference carries it (image.rs:90-104, dto.rs:462-480): the compare-time
+    weighting of the image match search (DESIGN A16, M4), plus the `min_score` cut.  The reference states no values; the
+    defaults are ours, chosen so that a record against itself scores exactly 1.0."""
+    ahash_weight: float = 0.1
+    phash_weight: float = 0.6
+    dhash_weight: float = 0.3
+    global_weight: float = 0.4
+    block_weight: float = 0.6
+    block_distance_threshold: int = 32
+    min_score: float = 0.0
+
+    _DTO = {"ahash-weight": "ahash_weight", "phash-weight": "phash_weight", "dhash-weight": "dhash_weight",
+            "global-weight": "global_weight", "block-weight": "block_weight",
+            "block-distance-threshold": "block_distance_threshold"}
+
+    @classmethod
+    def from_dto(cls, dto: Optional[dict]) -> "MultiHashConfig":
+        """MultiHashConfigDto (dto.rs:462-480): kebab-case keys, every one optional (absent or null = the default);
+        keys the DTO does not have are ignored, as serde ignores them."""
+        cfg = cls()
+        if dto is None:
+            return cfg
+        if not isinstance(dto, dict):
+            raise InvalidArgument("`multi_hash` must be an object")
+        for key, name in cls._DTO.items():
+            v = dto.get(key)
+            if v is None:
+                continue
+            if isinstance(v, bool) or not isinstance(v, (int, float)):
+                raise InvalidArgument(f"`{key}` must be a number")
+            if name == "block_distance_threshold":
+                if v != int(v) or not 0 <= v < 1 << 32:
+                    raise InvalidArgument("`block-distance-threshold` must be a u32")
+                v = int(v)
+            setattr(cfg, name, v)
+        return cfg
+
+    def _c(self) -> _lib.ImageMatchConfig:
+        t = int(self.block_distance_threshold)
+        if not 0 <= t < 1 << 32:
+            raise InvalidArgument("block_distance_threshold must be a u32")
+        return _lib.ImageMatchConfig(float(self.ahash_weight), float(self.phash_weight), float(self.dhash_weight),
+                                     float(self.global_weight), float(self.block_weight), t, float(self.min_score))
+
+
+_ALGO_OF_TAG = {ALGORITHM_AHASH: AHASH, ALGORITHM_PHASH: PHASH, ALGORITHM_DHASH: DHASH, ALGORITHM_MULTIHASH: MULTI}
+
+
+def match_algo(record_len: int, algorithm: Optional[str] = None) -> int:
+    """The UCFP_IMG_* value of an image record of `record_len` bytes: a 536-byte bundle is MULTI; a 168-byte record is
+    of the algorithm named (any of the three scores alike: PHASH when none is named).  A tag that does not match the
+    length is refused."""
+    if algorithm is not None and algorithm not in _ALGO_OF_TAG:
+        raise InvalidArgument(f"{algorithm!r} is no image algorithm")
+    if record_len == 536 and algorithm in (None, ALGORITHM_MULTIHASH):
+        return MULTI
+    if record_len == 168 and algorithm != ALGORITHM_MULTIHASH:
+        return PHASH if algorithm is None else _ALGO_OF_TAG[algorithm]
+    raise InvalidArgument(f"an image record is 168 bytes (one algorithm) or 536 (the bundle): {record_len} bytes"
+                          + (f" do not go with {algorithm!r}" if algorithm else ""))
+
+
+def match_score(a, b, config: Optional[MultiHashConfig] = None) -> float:
+    """The score of two image records of the same size, global and block hashes together (DESIGN A16, M2-M3); host code:
+    ucfp_image_match_score needs no device."""
+    a, b = bytes(a), bytes(b)
+    if len(a) != len(b):
+        raise InvalidArgument("the two records differ in size")
+    algo = match_algo(len(a))
+    out = C.c_float(0.0)
+    cfg = (config or MultiHashConfig())._c()
+    _lib.check(_lib.load().ucfp_image_match_score(a, b, algo, C.byref(cfg), C.byref(out)))
+    return float(out.value)
 
 
 def record_bytes(algo: int) -> int:
@@ -539,7 +616,8 @@ def fingerprint_with(data: bytes, tenant_id: int, record_id: int,
 
 def fingerprint_multi_with(data: bytes, preprocess: PreprocessConfig, _multi_cfg, tenant_id: int,
                            record_id: int) -> Record:
-    """image.rs:96-104: the MultiHashConfig is a compare-time setting and does not change the bytes."""
+    """image.rs:96-104: the MultiHashConfig is a compare-time setting and does not change the bytes; it is what
+    GpuIndex.similar_images and match_score take."""
     return fingerprint_with(data, tenant_id, record_id, preprocess)
 
 

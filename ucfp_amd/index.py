@@ -12,6 +12,8 @@ path, backed by the GPU-resident shard behind the C ABI (ucfp_index_*).
                                       survives a change of tempo (DESIGN A14; PanakoIndex)
     GpuIndex.identify_frames(tenant, frames, k)  the same over Haitsma sub-fingerprints (DESIGN A12; HaitsmaIndex)
     GpuIndex.nearest_tlsh(tenant, digest, k)  the `tlsh-128-1` records at the smallest TLSH distance (DESIGN A15; TlshIndex)
+    GpuIndex.similar_images(tenant, record, k)  the image records that score highest with global and block hashes
+                                      together (DESIGN A16; ImageMatchIndex)
     GpuIndex.bm25(tenant, terms, k)   IndexBackend::bm25 / bm25_explain :37-50 over Record.text (DESIGN A11; Bm25Index)
     GpuIndex.flush()                  IndexBackend::flush    :63
 
@@ -28,6 +30,8 @@ from . import _lib
 from .audio import ALGORITHM_HAITSMA, ALGORITHM_PANAKO, ALGORITHM_WANG, panako_landmarks
 from .core import Hit, HitSource, Record, TermHit
 from .errors import InvalidArgument, UnsupportedError
+from .image import MultiHashConfig, match_algo
+from .image import _TAG as _IMAGE_TAG
 from .terms import query_terms, tokenize
 from .text import ALGORITHM_TLSH
 
@@ -556,6 +560,95 @@ def _pack_digests(digests) -> np.ndarray:
     return buf[:rows.shape[0]]
 
 
+class ImageMatchIndex:
+    """Thin RAII wrapper over one ucfp_image_match_index (DESIGN A16): rows and queries are whole image records of one
+    size -- 168 bytes (`algo` AHASH, PHASH or DHASH) or the 536-byte bundle (MULTI); a query answers the k rows that score
+    highest with global and block hashes together, exactly.  The MultiHashConfig is passed per query."""
+
+    def __init__(self, algo: int, flags: int = 0, ctx=None):
+        self._lib = _lib.load()
+        self.ctx = ctx or _lib.current_context()
+        self.algo = int(algo)
+        self.record_bytes = int(self._lib.ucfp_image_record_bytes(self.algo))
+        h = C.c_void_p()
+        _lib.check(self._lib.ucfp_image_match_index_create(self.ctx.handle, self.algo, flags, C.byref(h)))
+        self.handle = h
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self._lib.ucfp_image_match_index_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _pack(self, records) -> np.ndarray:
+        """-> uint8 [n, record_bytes] (one spare row behind it, so the pointer is never to an empty buffer)."""
+        rb = self.record_bytes
+        if isinstance(records, np.ndarray) and records.dtype == np.uint8:
+            if records.size % rb:
+                raise InvalidArgument(f"records must be {rb} bytes each")
+            rows = records.reshape(-1, rb)
+        else:
+            if isinstance(records, (bytes, bytearray)):
+                records = [records]
+            records = [bytes(r) for r in records]
+            if any(len(r) != rb for r in records):
+                raise InvalidArgument(f"records must be {rb} bytes each")
+            rows = np.frombuffer(b"".join(records), np.uint8).reshape(-1, rb)
+        buf = np.zeros((rows.shape[0] + 1, rb), np.uint8)
+        buf[:rows.shape[0]] = rows
+        return buf[:rows.shape[0]]
+
+    def upsert(self, tenant: int, ids, records) -> None:
+        """ids [n]; records: uint8 [n, record_bytes], or n records as bytes."""
+        ids = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        rows = self._pack(records)
+        if rows.shape[0] != ids.shape[0]:
+            raise InvalidArgument("ids and records disagree on the number of rows")
+        _lib.check(self._lib.ucfp_image_match_index_upsert(self.handle, tenant, ids.ctypes.data, rows.ctypes.data, ids.shape[0]))
+
+    def upsert_dev(self, tenant: int, ids_ptr: int, records_ptr: int, n: int, stream: int = 0) -> None:
+        _lib.check(self._lib.ucfp_image_match_index_upsert_dev(self.handle, tenant, ids_ptr, records_ptr, n, stream or None))
+
+    def delete(self, tenant: int, ids) -> int:
+        ids = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        removed = C.c_size_t(0)
+        _lib.check(self._lib.ucfp_image_match_index_delete(self.handle, tenant, ids.ctypes.data, ids.shape[0], C.byref(removed)))
+        return int(removed.value)
+
+    def size(self, tenant: int) -> int:
+        r = C.c_size_t(0)
+        _lib.check(self._lib.ucfp_image_match_index_size(self.handle, tenant, C.byref(r)))
+        return int(r.value)
+
+    def flush(self) -> None:
+        _lib.check(self._lib.ucfp_image_match_index_flush(self.handle))
+
+    def query(self, tenant: int, records, k: int, config: Optional[MultiHashConfig] = None):
+        """-> (ids [nq,k] u64, scores [nq,k] f32, counts [nq] u32); rows scoring below config.min_score are left out."""
+        q = self._pack(records)
+        nq = q.shape[0]
+        kk = max(int(k), 1)
+        ids = np.full((nq, kk), INVALID_ID, np.uint64)
+        scores = np.full((nq, kk), -1.0, np.float32)
+        counts = np.zeros(nq, np.uint32)
+        cfg = (config or MultiHashConfig())._c()
+        _lib.check(self._lib.ucfp_image_match_index_query(self.handle, tenant, q.ctypes.data, nq, int(k), C.byref(cfg),
+                                                          ids.ctypes.data, scores.ctypes.data, counts.ctypes.data))
+        return ids[:, :k], scores[:, :k], counts
+
+    def query_dev(self, tenant: int, records_ptr: int, nq: int, k: int, config: Optional[MultiHashConfig], out_ids_ptr: int,
+                  out_scores_ptr: int, out_n_ptr: int, stream: int = 0) -> None:
+        cfg = (config or MultiHashConfig())._c()
+        _lib.check(self._lib.ucfp_image_match_index_query_dev(self.handle, tenant, records_ptr, nq, k, C.byref(cfg),
+                                                              out_ids_ptr or None, out_scores_ptr or None, out_n_ptr,
+                                                              stream or None))
+
+
 class Bm25Index:
     """Thin RAII wrapper over one ucfp_bm25_index (DESIGN A11): BM25 over documents of (key, tf) pairs.  It keeps the
     term -> key dictionary of the index (keys number the terms in order of first sight); query terms it has never
@@ -711,6 +804,7 @@ class GpuIndex:
         self._hx = None       # HaitsmaIndex of the audiofp-haitsma-v1 records (DESIGN A12)
         self._bm = None       # Bm25Index of the records with text (DESIGN A11)
         self._tl = None       # TlshIndex of the tlsh-128-1 records (DESIGN A15)
+        self._im = {}         # image algorithm tag -> ImageMatchIndex of its whole records (DESIGN A16)
         self._sidecar = sidecar   # ucfp_amd.store.Sidecar: the stored-table mirror written at upsert
 
     def attach_sidecar(self, sidecar) -> None:
@@ -753,6 +847,12 @@ class GpuIndex:
             self._tl = TlshIndex(0, self.ctx)
         return self._tl
 
+    def _image_match(self, tag: str) -> ImageMatchIndex:
+        ix = self._im.get(tag)
+        if ix is None:
+            ix = self._im[tag] = ImageMatchIndex(_IMAGE_ALGO[tag], 0, self.ctx)
+        return ix
+
     def _bm25(self) -> Bm25Index:
         if self._bm is None:
             self._bm = Bm25Index(0, self.ctx)
@@ -764,11 +864,12 @@ class GpuIndex:
                 + ([self._ps] if self._ps is not None else [])
                 + ([self._hx] if self._hx is not None else [])
                 + ([self._bm] if self._bm is not None else [])
-                + ([self._tl] if self._tl is not None else []))
+                + ([self._tl] if self._tl is not None else []) + list(self._im.values()))
 
     def upsert(self, records: Sequence[Record]) -> None:
         """Embeddings go to the cosine index of their dimension; image records also feed the
-        Hamming spaces `<algorithm>` with their 64-bit global hashes (SURVEY 8f N2 offsets);
+        Hamming spaces `<algorithm>` with their 64-bit global hashes (SURVEY 8f N2 offsets) and, whole, the image match
+        index of their algorithm tag (DESIGN A16);
         `audiofp-wang-v1` records feed the landmark index with their landmarks, `audiofp-panako-v1` records a second
         landmark index with their (hash, t_anchor) pairs (the two never share postings) and `audiofp-haitsma-v1` records
         the sub-fingerprint index with their frames; every record with `text`, whatever its
@@ -777,8 +878,8 @@ class GpuIndex:
         Overwrite semantics are the reference's: everything is keyed by (tenant_id, record_id), a re-ingested record
         REPLACES the old one -- "Drop any stale vector for this key" when the new record has no embedding
         (src/index/embedded/mod.rs:184-191), a new dimension or algorithm replaces the old row.  So before inserting,
-        the key is removed from every cosine index of another dimension, every hash space, both landmark indexes and the sub-fingerprint index when
-        the new record does not feed them.  Within one batch the last record of a key wins, as successive `insert`s in one redb transaction do."""
+        the key is removed from every cosine index of another dimension, every hash space, both landmark indexes, the sub-fingerprint index
+        and the image match indexes when the new record does not feed them.  Within one batch the last record of a key wins, as successive `insert`s in one redb transaction do."""
         if self._sidecar is not None:     # the log first (the host does this right after its redb commit), then the mirror
             self._sidecar.append(records)
         last = {}
@@ -786,6 +887,7 @@ class GpuIndex:
             last[(r.tenant_id, r.record_id)] = r
         by_cos, by_ham, stale_cos, stale_ham, by_lm, stale_lm, by_bm, stale_bm = {}, {}, {}, {}, {}, {}, {}, {}
         by_hx, stale_hx, by_pk, stale_pk, by_tl, stale_tl = {}, {}, {}, {}, {}, {}
+        by_im, stale_im = {}, {}
         for r in last.values():
             if r.text is not None:
                 by_bm.setdefault(r.tenant_id, []).append(r)
@@ -807,6 +909,12 @@ class GpuIndex:
                 by_tl.setdefault(r.tenant_id, []).append(r)
             elif self._tl is not None:
                 stale_tl.setdefault(r.tenant_id, []).append(r.record_id)
+            im_tag = r.algorithm if _feeds_image_match(r) else None
+            if im_tag is not None:
+                by_im.setdefault((r.tenant_id, im_tag), []).append(r)
+            for tag in self._im:
+                if tag != im_tag:
+                    stale_im.setdefault((r.tenant_id, tag), []).append(r.record_id)
             dim = len(r.embedding) if r.embedding is not None else 0
             if dim > 0:
                 by_cos.setdefault((r.tenant_id, dim), []).append(r)
@@ -833,6 +941,8 @@ class GpuIndex:
             self._hx.delete(tenant, np.array(ids, np.uint64))
         for tenant, ids in stale_tl.items():
             self._tl.delete(tenant, np.array(ids, np.uint64))
+        for (tenant, tag), ids in stale_im.items():
+            self._im[tag].delete(tenant, np.array(ids, np.uint64))
         for tenant, ids in stale_bm.items():
             self._bm.delete(tenant, np.array(ids, np.uint64))
         for tenant, recs in by_bm.items():
@@ -851,6 +961,9 @@ class GpuIndex:
         for tenant, recs in by_tl.items():
             self._tlsh().upsert(tenant, np.array([r.record_id for r in recs], np.uint64),
                                 [bytes(r.fingerprint) for r in recs])
+        for (tenant, tag), recs in by_im.items():
+            self._image_match(tag).upsert(tenant, np.array([r.record_id for r in recs], np.uint64),
+                                          [bytes(r.fingerprint) for r in recs])
         for (tenant, dim), recs in by_cos.items():
             ids = np.array([r.record_id for r in recs], np.uint64)
             rows = np.array([r.embedding for r in recs], np.float32)
@@ -935,6 +1048,34 @@ class GpuIndex:
         return [Hit(tenant_id=tenant_id, record_id=int(ids[0, i]), score=float(scores[0, i]), source=HitSource.Tlsh,
                     distance=int(dist[0, i])) for i in range(int(counts[0]))]
 
+    def similar_images(self, tenant_id: int, record_bytes, k: int, algorithm: Optional[str] = None,
+                       config: Optional[MultiHashConfig] = None) -> List[Hit]:
+        """The image records most similar to a whole record (168 bytes, or the 536-byte bundle), global and block hashes
+        scored together under `config` (DESIGN A16): a copy with a local edit -- a caption, a logo, an occluded corner --
+        keeps most of its block hashes and is still found.  `algorithm` names the tag of the records searched: it must
+        match the length; with none, a bundle searches the bundles and a 168-byte record the only single-algorithm
+        index present."""
+        rec = bytes(record_bytes)
+        algo = match_algo(len(rec), algorithm)
+        tag = algorithm
+        if tag is None:
+            if len(rec) == 536:
+                tag = _IMAGE_TAG[algo]
+            else:
+                present = [t for t in self._im if t != _IMAGE_TAG[7]]
+                if len(present) > 1:
+                    raise InvalidArgument("`algorithm` is required when 168-byte records of several algorithms are indexed")
+                tag = present[0] if present else None
+        cfg = config or MultiHashConfig()
+        ix = self._im.get(tag)
+        if ix is None or k == 0:
+            cfg_c = cfg._c()      # an invalid config is refused whether or not anything is indexed
+            _lib.check(_lib.load().ucfp_image_match_score(rec, rec, algo, C.byref(cfg_c), C.byref(C.c_float(0.0))))
+            return []
+        ids, scores, counts = ix.query(tenant_id, [rec], min(k, MAX_K), cfg)
+        return [Hit(tenant_id=tenant_id, record_id=int(ids[0, i]), score=float(scores[0, i]), source=HitSource.ImageMatch)
+                for i in range(int(counts[0]))]
+
     def bm25(self, tenant_id: int, terms: Sequence[str], k: int, filter: Optional[bytes] = None,
              explain: bool = False) -> List[Hit]:
         """IndexBackend::bm25 / bm25_explain (src/index/embedded/mod.rs:127-150): "bm25" hits by BM25 score (DESIGN
@@ -949,10 +1090,11 @@ class GpuIndex:
         """POST /v1/query (handlers.rs:143-187) with the additive `hash` field: a vector goes to the cosine kNN,
         a hash to the Hamming space `algorithm` (default: the only hash space present), `landmarks` to identify (the Panako
         index when `algorithm` is "audiofp-panako-v1", the Wang one otherwise), `triplets` to identify_stretched,
-        `subfingerprints` to identify_frames, `tlsh` to nearest_tlsh;
+        `subfingerprints` to identify_frames, `tlsh` to nearest_tlsh, `image_record` to similar_images;
         `terms` go through the matcher (BM25, or vector + BM25 fused by RRF: src/matcher/mod.rs:140-207)."""
         if (getattr(req, "landmarks", None) is None and getattr(req, "subfingerprints", None) is None and req.hash is None
                 and getattr(req, "triplets", None) is None and getattr(req, "tlsh", None) is None
+                and getattr(req, "image_record", None) is None
                 and getattr(req, "terms", None)):
             from . import matcher
             hits = matcher.search(self, req)
@@ -960,7 +1102,12 @@ class GpuIndex:
                 if h.source == HitSource.Bm25:
                     h.bm25_score, h.bm25_rank = h.score, rank + 1
             return hits
-        if getattr(req, "tlsh", None) is not None:
+        if getattr(req, "image_record", None) is not None:
+            cfg = MultiHashConfig.from_dto(getattr(req, "multi_hash", None))
+            if getattr(req, "min_score", None) is not None:
+                cfg.min_score = float(req.min_score)
+            hits = self.similar_images(req.tenant_id, req.image_record, req.k, getattr(req, "algorithm", None), cfg)
+        elif getattr(req, "tlsh", None) is not None:
             if getattr(req, "algorithm", None) not in (None, ALGORITHM_TLSH):
                 raise InvalidArgument(f"`tlsh` goes with `algorithm` = {ALGORITHM_TLSH!r} or none")
             hits = self.nearest_tlsh(req.tenant_id, req.tlsh, req.k)
@@ -993,6 +1140,16 @@ class GpuIndex:
             self._sidecar.sync()
         for ix in self._all():
             ix.flush()
+
+
+_IMAGE_ALGO = {tag: algo for algo, tag in _IMAGE_TAG.items()}   # image algorithm tag -> UCFP_IMG_*
+
+
+def _feeds_image_match(r: Record) -> bool:
+    """An `imgfprint-*-v1` record of the right length: 536 bytes for the bundle, 168 for one algorithm."""
+    if r.algorithm not in _IMAGE_ALGO:
+        return False
+    return len(r.fingerprint) == (536 if r.algorithm == _IMAGE_TAG[7] else 168)
 
 
 def _hash_spaces(r: Record):

@@ -188,6 +188,8 @@ def rebuild(path: str, ctx=None, sidecar: bool = False):
                     # the shard of a mutable index keeps an id map on the host: ids + 8-byte codes go back (the 168 / 536-byte
                     # records do not)
                     gi._hamming(space).upsert(int(tenant), ids[sel], d_codes.cpu().numpy().view(np.uint64))
+                # the whole records refill the image match index of their tag, whose row table lives on the host (A16)
+                gi._image_match(algorithm).upsert(int(tenant), ids[sel], np.ascontiguousarray(blobs[sel]))
         for algorithm in _SIMHASH:
             tenants, ids, blobs = snap.gather_fingerprints(algorithm, 8)
             for tenant in np.unique(tenants):

@@ -509,6 +509,55 @@ int ucfp_text_simhash_batch_dev(ucfp_ctx* ctx, const uint8_t* d_utf8, const uint
 int ucfp_text_simhash_batch(ucfp_ctx* ctx, const uint8_t* utf8, const uint64_t* offsets, size_t n, int mode,
                             uint8_t* out, int32_t* status);
 
+/* STREAMING MinHash: text::StreamingMinHashSession::new / push / finalize (src/modality/text.rs:645-730)
+ * behind POST /v1/ingest/text/{tid}/{rid}/stream (src/server/handlers.rs:590-626), with the state on the device and many
+ * streams advanced by one push.  The reference buffers the document and hashes it at the end; here a stream keeps the 128
+ * running minima, the last k - 1 complete tokens, the unfinished token and one held-back byte on the device
+ * (ucfp_text_streams_state_bytes, about 3 KiB), whatever its length.  A set holds max_streams slots.
+ * CONTRACT.  Let B be the concatenation of a stream's chunks, however they are cut.  The final record and status equal
+ * those of ucfp_text_minhash_batch(mode, shingle_k) on the one document B, byte for byte, whenever every k-token window
+ * of B has at most UCFP_TEXT_MAX_WINDOW_BYTES canonical bytes.  The derivation is the offline one: the state carried
+ * from push to push is what the offline kernel keeps over a flush, a prefix of one window, so the room check cannot
+ * fail twice in a row.  Above that limit a stream promises what the offline path promises: either status 0 with the
+ * exact record, or a zero record with a nonzero status -- always the latter above 1536 bytes.
+ *   - The last byte of a non-final push is held back and processed by the next one: whether a byte is inside a word
+ *     depends on the byte after it (offline, the byte past the end reads as 0; a stream does not guess it).
+ *   - d_status[i] is the stream's status after the push: 0; UCFP_TEXT_NEEDS_HOST (a byte >= 0x80 was seen in a
+ *     RAW_ASCII stream, the held-back byte included); UCFP_E_UNSUPPORTED (the window limit was hit); UCFP_E_MODALITY
+ *     (no tokens: only on a final entry).  NEEDS_HOST and UCFP_E_UNSUPPORTED are sticky: later pushes are accepted and
+ *     change nothing, the final record is all zero with that status.
+ *   - The set serialises its own calls: it is safe to call from several threads.  Consecutive pushes are ordered by
+ *     the set itself (an event), whatever `stream` the caller passes.  ucfp_text_streams_push_dev allocates nothing.
+ *   - One wave works on one chunk, so a long chunk is serial on that wave: cut long documents into several pushes
+ *     only if latency matters, the record does not depend on it.
+ *   - A failed call changes no state. */
+typedef struct ucfp_text_streams ucfp_text_streams;
+/* text.rs:645-730, handlers.rs:590-626.  shingle_k outside [1, 64] -> UCFP_E_MODALITY (as ucfp_text_minhash_batch), checked
+ * before anything else; max_streams in [1, 2^20].  Fails with UCFP_E_INDEX without a gfx950 device (no CPU fallback). */
+int ucfp_text_streams_create(ucfp_ctx* ctx, uint32_t shingle_k, uint32_t max_streams, ucfp_text_streams** out);
+/* text.rs:645-730, handlers.rs:590-626 */
+void ucfp_text_streams_destroy(ucfp_text_streams* s);
+/* text.rs:645-730, handlers.rs:590-626.  A fresh stream in the first free slot.  mode: UCFP_TEXT_RAW_ASCII or
+ * UCFP_TEXT_PRETOKENIZED; UCFP_TEXT_RAW_UTF8 -> UCFP_E_UNSUPPORTED (no streaming canonicaliser); any other value, or a
+ * full set -> UCFP_E_INVALID. */
+int ucfp_text_streams_open(ucfp_text_streams* s, int mode, uint32_t* slot);
+/* text.rs:645-730, handlers.rs:590-626.  Discard the stream, emit nothing. */
+int ucfp_text_streams_close(ucfp_text_streams* s, uint32_t slot);
+/* text.rs:645-730, handlers.rs:590-626.  Host-only: device bytes a set holds per stream. */
+size_t ucfp_text_streams_state_bytes(void);
+/* text.rs:645-730, handlers.rs:590-626.  slots / n_bytes / final: host arrays of n entries (distinct open slots; final may
+ * be NULL = none; a chunk of 0 bytes is legal, final or not); d_bytes: the n chunks concatenated in that order on the
+ * device (any alignment).  d_out: n x 1032 bytes, entry i is written only when final[i] is set (NULL allowed when no
+ * entry is final); a final entry frees its slot.  d_status: n x int32, see above.  UCFP_E_INVALID before ANY state
+ * changes: a slot out of range, not open or listed twice, a stream that would pass 2^63 bytes.  One launch whatever n
+ * is; no host synchronisation (the host waits only for the table copy of the push two back). */
+int ucfp_text_streams_push_dev(ucfp_text_streams* s, const uint32_t* slots, const uint64_t* n_bytes, const uint8_t* final,
+                               size_t n, const uint8_t* d_bytes, uint8_t* d_out, int32_t* d_status, void* stream);
+/* text.rs:645-730, handlers.rs:590-626.  Host-pointer convenience for one slot (the per-request shape of the reference
+ * route); synchronous.  out (1032 bytes) may be NULL unless final is set; status may be NULL. */
+int ucfp_text_streams_push(ucfp_text_streams* s, uint32_t slot, const uint8_t* bytes, size_t n, int final, uint8_t* out,
+                           int32_t* status);
+
 /* ---- the first half of UCFP_TEXT_RAW_UTF8 on its own: documents -> canonical token strings ----
  * What the Rust host otherwise does with txtfp's canonicaliser and tokeniser before text::fingerprint_minhash_with
  * (src/modality/text.rs:112-114,182-236).  tok_offsets has n + 1 entries (tok_offsets[0] = 0); document i's tokens, joined

@@ -123,6 +123,15 @@ SIGNATURES = {
                                               C.c_void_p, C.c_void_p, C.c_void_p]),
     "ucfp_text_simhash_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int,
                                           C.c_void_p, C.c_void_p]),
+    "ucfp_text_streams_create": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "ucfp_text_streams_destroy": (None, [C.c_void_p]),
+    "ucfp_text_streams_open": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint32)]),
+    "ucfp_text_streams_close": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "ucfp_text_streams_state_bytes": (C.c_size_t, []),
+    "ucfp_text_streams_push_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ucfp_text_streams_push": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p,
+                                         C.c_void_p]),
     "ucfp_text_canon_bound": (C.c_size_t, [C.c_size_t]),
     "ucfp_text_canon_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p]),

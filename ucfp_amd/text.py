@@ -6,7 +6,10 @@
     fingerprint_lsh                                                 text.rs:437-446
     fingerprint_tlsh                                                text.rs:452-484  (TLSH 128/1, DESIGN A15)
 
-plus the batched form (`minhash_batch` / `simhash_batch` / `tlsh_batch`).  Hashing runs in the HIP library.
+    StreamingMinHashSession(opts, tenant_id, record_id)             text.rs:645-730  (DESIGN T7)
+    ingest_stream_ndjson(body, opts, tenant_id, record_id)          handlers.rs:590-626
+
+plus the batched form (`minhash_batch` / `simhash_batch` / `tlsh_batch`) and the stream set (`MinHashStreams`).  Hashing runs in the HIP library.
 ASCII documents go to the GPU raw (it lower-cases and segments them).  A document with non-ASCII characters goes
 to the GPU as UTF-8 (mode RAW_UTF8: the default canonicaliser -- NFKC + case fold + Bidi/Cf stripping,
 text.rs:112-114 -- and the UAX#29 word tokeniser as tables).  Only what the device hands back
@@ -204,6 +207,220 @@ def minhash_batch(texts: Sequence[str], opts: Optional[TextOpts] = None, ctx=Non
 
 def simhash_batch(texts: Sequence[str], opts: Optional[TextOpts] = None, ctx=None):
     return _batch("simhash", texts, opts or TextOpts(), ctx)
+
+
+class MinHashStreams:
+    """A set of live MinHash streams on the device (ucfp_text_streams_*): `push` advances any subset of
+    them by one chunk each with one launch.  A stream's final record and status are those of `ucfp_text_minhash_batch`
+    on the concatenation of its chunks, however they were cut.  Modes: RAW_ASCII and PRETOKENIZED."""
+
+    def __init__(self, max_streams: int, k: int = DEFAULT_K, ctx=None):
+        self._lib = _lib.load()
+        self.ctx = ctx or _lib.current_context()
+        h = C.c_void_p()
+        _lib.check(self._lib.ucfp_text_streams_create(self.ctx.handle, k, max_streams, C.byref(h)))
+        self.handle = h
+        self.max_streams, self.k = max_streams, k
+
+    def open(self, mode: int = RAW_ASCII) -> int:
+        slot = C.c_uint32(0)
+        _lib.check(self._lib.ucfp_text_streams_open(self.handle, mode, C.byref(slot)))
+        return int(slot.value)
+
+    def close(self, slot: int) -> None:
+        """Discards the stream; emits nothing."""
+        _lib.check(self._lib.ucfp_text_streams_close(self.handle, slot))
+
+    def push_dev(self, slots, counts, d_bytes, d_out, d_status, final=(), stream: int = 0) -> None:
+        """Device variant (no sync): `d_bytes` the chunks of `slots` concatenated (uint8 tensor, any alignment), `d_out` a
+        uint8 [len(slots), 1032] tensor (row i is written only when slots[i] is in `final`; None when nothing is final),
+        `d_status` an int32 [len(slots)] tensor."""
+        final = set(final)
+        sl = np.ascontiguousarray(slots, dtype=np.uint32)
+        ns = np.ascontiguousarray(counts, dtype=np.uint64)
+        fi = np.array([1 if s in final else 0 for s in sl.tolist()], np.uint8)
+        _lib.check(self._lib.ucfp_text_streams_push_dev(
+            self.handle, sl.ctypes.data, ns.ctypes.data, fi.ctypes.data, sl.size,
+            d_bytes.data_ptr() if d_bytes is not None and d_bytes.numel() else None,
+            d_out.data_ptr() if d_out is not None else None, d_status.data_ptr() if d_status is not None else None,
+            stream or None))
+
+    def push(self, chunks: dict, final=()) -> dict:
+        """{slot: bytes} -> {slot: (record bytes or None, status)}; slots in `final` end (and free their slot) and
+        return their 1032-byte record."""
+        import torch
+        final = set(final)
+        slots = list(chunks)
+        if not slots:
+            return {}
+        blobs = [bytes(chunks[s]) for s in slots]
+        dev = f"cuda:{self.ctx.device}"
+        blob = b"".join(blobs)
+        d_bytes = torch.from_numpy(np.frombuffer(blob, np.uint8).copy()).to(dev) if blob else None
+        d_out = torch.zeros((len(slots), MINHASH_BYTES), dtype=torch.uint8, device=dev) if final else None
+        d_st = torch.zeros(len(slots), dtype=torch.int32, device=dev)
+        self.push_dev(slots, [len(b) for b in blobs], d_bytes, d_out, d_st, final,
+                      torch.cuda.current_stream().cuda_stream)
+        st = d_st.cpu().numpy()
+        out = d_out.cpu().numpy() if final else None
+        return {s: (out[i].tobytes() if s in final else None, int(st[i])) for i, s in enumerate(slots)}
+
+    def destroy(self):
+        if getattr(self, "handle", None):
+            self._lib.ucfp_text_streams_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+_CUT_AT = " \n\t\r"
+
+
+def _stream_cut(s: str) -> Tuple[str, str]:
+    """-> (head, tail): `s` cut just before its last ASCII whitespace character (head is empty when there is none).
+    A streaming session canonicalises and tokenises `head` now and keeps `tail`.  The cut is safe because an ASCII
+    whitespace character is a starter that never composes with what precedes it (normalisation of A + B is
+    normalisation of A + normalisation of B when B begins with one), case folding and Cf stripping work per character,
+    and UAX#29 always breaks before it after a non-space: tokens(A + B) = tokens(A) ++ tokens(B)."""
+    at = max(s.rfind(ch) for ch in _CUT_AT)
+    return (s[:at], s[at:]) if at > 0 else ("", s)
+
+
+class StreamingMinHashSession:
+    """Push/finalize wrapper (text.rs:655-730) on a one-slot MinHashStreams.  The reference's session buffers the whole
+    document; here every chunk advances the stream on the device.  `push` returns no records (as the reference's);
+    `finalize` returns the one record, equal to `minhash_batch([whole text], opts)` however the text was cut into
+    chunks, cuts inside a UTF-8 sequence included.  Routing follows `_prepare`:
+      - while every byte so far is ASCII and the canonicaliser folds case, chunks go raw to a RAW_ASCII stream; the
+        session keeps these ASCII bytes on the host (no more than the reference buffers), because
+      - at the first byte >= 0x80 (or from the start without case folding) the document is one the host canonicalises:
+        the session drops that stream, opens a PRETOKENIZED one, replays the kept bytes through the host route and
+        frees the buffer;
+      - host route: UTF-8 is decoded incrementally, the text seen so far is cut just before its last ASCII whitespace
+        character (`_stream_cut`), the head is canonicalised and tokenised and pushed, the tail stays on the host.
+        Text without ASCII whitespace is therefore held whole until `finalize`."""
+
+    def __init__(self, opts: Optional[TextOpts], tenant_id: int, record_id: int, config_hash_value: Optional[int] = None):
+        import codecs
+        self.opts = opts or TextOpts()
+        if self.opts.tokenizer != "word":
+            raise UnsupportedError(f"tokenizer `{self.opts.tokenizer}` is not built into the HIP path")
+        if self.opts.h != DEFAULT_H:
+            raise UnsupportedError("only H = 128 is built (the reference's public entry point, text.rs:172-174)")
+        self.tenant_id, self.record_id = tenant_id, record_id
+        self._config_hash_value = config_hash_value
+        self._set = MinHashStreams(1, self.opts.k)
+        self._dec = codecs.getincrementaldecoder("utf-8")("strict")
+        self._tail = ""
+        self._bad = None                  # the first UTF-8 error: reported by finalize
+        self._done = False
+        self._ascii = bool(self.opts.canonicalizer.case_fold)
+        self._kept = bytearray()          # ASCII route: the bytes so far, for the replay
+        self._slot = self._set.open(RAW_ASCII if self._ascii else PRETOKENIZED)
+
+    def _dev_push(self, data: bytes, final: bool):
+        out = (C.c_uint8 * MINHASH_BYTES)()
+        st = C.c_int32(0)
+        _lib.check(self._set._lib.ucfp_text_streams_push(self._set.handle, self._slot, data if data else None, len(data),
+                                                         1 if final else 0, out if final else None, C.byref(st)))
+        return bytes(out), int(st.value)
+
+    def _host_push(self, data: bytes, final: bool):
+        if self._bad is None:
+            try:
+                self._tail += self._dec.decode(data, final)
+            except UnicodeDecodeError as e:
+                self._bad = e
+        if self._bad is not None:
+            if final:
+                self._set.close(self._slot)
+                raise ModalityError(f"streamed text is not valid UTF-8: {self._bad}")
+            return None
+        head, tail = (self._tail, "") if final else _stream_cut(self._tail)
+        self._tail = tail
+        toks = _host_tokens(self.opts.canonicalizer.apply(head)) if head else []
+        if final:
+            return self._dev_push(" ".join(toks).encode("utf-8"), True)
+        if toks:
+            self._dev_push((" ".join(toks) + " ").encode("utf-8"), False)
+        return None
+
+    def _feed(self, chunk: bytes, final: bool):
+        if self._done:
+            raise ModalityError("streaming session already finalized")
+        chunk = bytes(chunk)
+        if self._ascii:
+            if chunk.isascii():
+                self._kept += chunk
+                return self._dev_push(chunk, final)
+            self._ascii = False
+            self._set.close(self._slot)
+            self._slot = self._set.open(PRETOKENIZED)
+            chunk = bytes(self._kept) + chunk
+            self._kept = bytearray()
+        return self._host_push(chunk, final)
+
+    def push(self, chunk: bytes) -> List[Record]:
+        self._feed(chunk, False)
+        return []
+
+    def finalize(self) -> List[Record]:
+        try:
+            rec, status = self._feed(b"", True)
+        finally:
+            if not self._done:
+                self._done = True
+                self._kept = bytearray()
+                self._set.destroy()
+        _raise_for(status)
+        o = self.opts
+        return [Record(tenant_id=self.tenant_id, record_id=self.record_id, modality=Modality.Text,
+                       format_version=FORMAT_VERSION_MINHASH_HIP, algorithm=ALGORITHM_MINHASH_128,
+                       config_hash=_record_config_hash(o, o.tokenizer_tag(), ALGORITHM_MINHASH_128, self._config_hash_value),
+                       fingerprint=rec, embedding=None, model_id=None, metadata=b"", text=None)]
+
+
+def _ndjson_chunks(body: bytes) -> List[bytes]:
+    """The lines of an NDJSON stream body (handlers.rs:603-612): split on LF, one trailing CR stripped, empty lines
+    skipped, every other line a JSON string."""
+    import json
+    chunks = []
+    for line in bytes(body).split(b"\n"):
+        if line.endswith(b"\r"):
+            line = line[:-1]
+        if not line:
+            continue
+        try:
+            v = json.loads(line)
+        except (ValueError, UnicodeDecodeError) as e:
+            raise ModalityError(f"NDJSON line: {e}") from None
+        if not isinstance(v, str):
+            raise ModalityError(f"NDJSON line: invalid type: {type(v).__name__}, expected a string")
+        chunks.append(v.encode("utf-8", "surrogatepass"))
+    return chunks
+
+
+def ingest_stream_ndjson(body: bytes, opts: Optional[TextOpts], tenant_id: int, record_id: int) -> Record:
+    """The body loop of POST /v1/ingest/text/{tid}/{rid}/stream (handlers.rs:603-617): every line is a JSON string
+    carrying a chunk; push each, finalise, return the record.  The body is parsed before any device work."""
+    chunks = _ndjson_chunks(body)
+    if not chunks:
+        raise ModalityError("streaming session produced no record")
+    session = StreamingMinHashSession(opts, tenant_id, record_id)
+    try:
+        for c in chunks:
+            session.push(c)
+    except Exception:
+        session._set.destroy()
+        raise
+    records = session.finalize()
+    if not records:
+        raise ModalityError("streaming session produced no record")
+    return records[-1]
 
 
 ALGO_MINHASH, ALGO_SIMHASH = 1, 2

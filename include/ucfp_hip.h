@@ -530,27 +530,61 @@ int ucfp_text_simhash_batch(ucfp_ctx* ctx, const uint8_t* utf8, const uint64_t* 
  *     the set itself (an event), whatever `stream` the caller passes.  ucfp_text_streams_push_dev allocates nothing.
  *   - One wave works on one chunk, so a long chunk is serial on that wave: cut long documents into several pushes
  *     only if latency matters, the record does not depend on it.
- *   - A failed call changes no state. */
+ *   - A failed call changes no state.
+ * UTF-8 STREAMS (a set created by ucfp_text_streams_create_ex with UCFP_TEXT_STREAMS_UTF8 also opens streams in mode
+ * UCFP_TEXT_RAW_UTF8).  The contract above holds for them, with the window limit counted in CANONICAL bytes and one
+ * more condition, on open segments, below.  A push stays ONE launch: the wave of an entry canonicalises its chunk into
+ * scratch the set owns (sized at creation from max_push_bytes) and hashes the canonical bytes as the next piece of a
+ * PRETOKENIZED stream.  Chunks may be cut anywhere: inside a UTF-8 sequence, between a letter and the MidLetter after
+ * it, inside a run of Cf characters.
+ *   - The trailing bytes of a UTF-8 sequence a non-final chunk does not finish (at most 3) are held, raw, for the next
+ *     chunk: no error.  A sequence still unfinished at the FINAL push is malformed.
+ *   - The last canonical code point made so far stays undecided until its right neighbour arrives (the boundary before
+ *     x[i] needs x[i + 1]); Cf code points make nothing, so a trailing run of them is consumed, not held.
+ *     A final push decides everything and closes the open segment.
+ *   - OPEN SEGMENT.  A segment is a token iff it holds an alphanumeric (U5).  The segment still open at the end of a
+ *     non-final push is emitted so far if it already holds one; otherwise its canonical bytes (its separator included)
+ *     wait in the slot's state, which has room for UCFP_TEXT_STREAM_OPEN_SEGMENT_BYTES.  THIS IS THE ONE PLACE WHERE A
+ *     STREAM MAY REFUSE WHAT THE OFFLINE CALL HASHES: if more are pending at a push boundary -- 256 or more bytes of
+ *     `_`, say, with no letter or digit yet -- the stream gets UCFP_TEXT_NEEDS_HOST.  Within one push any length is
+ *     handled as offline.
+ *   - UCFP_TEXT_NEEDS_HOST: an uncovered code point, malformed UTF-8 (U2's strict rules), or the open-segment
+ *     condition.  Sticky, zero final record, never reported before the offending byte was pushed, and it wins over the
+ *     hash stage's status, as offline.  UCFP_E_UNSUPPORTED and UCFP_E_MODALITY as above.
+ *   - The RAW_UTF8 chunks of one push may have max_push_bytes bytes in all; a push above that fails with UCFP_E_INVALID
+ *     and changes no state.  Per stream the set holds ucfp_text_streams_state_bytes_ex(UCFP_TEXT_STREAMS_UTF8) bytes. */
+#define UCFP_TEXT_STREAMS_UTF8 1u
+#define UCFP_TEXT_STREAM_OPEN_SEGMENT_BYTES 256u
 typedef struct ucfp_text_streams ucfp_text_streams;
 /* text.rs:645-730, handlers.rs:590-626.  shingle_k outside [1, 64] -> UCFP_E_MODALITY (as ucfp_text_minhash_batch), checked
  * before anything else; max_streams in [1, 2^20].  Fails with UCFP_E_INDEX without a gfx950 device (no CPU fallback). */
 int ucfp_text_streams_create(ucfp_ctx* ctx, uint32_t shingle_k, uint32_t max_streams, ucfp_text_streams** out);
+/* text.rs:645-730, handlers.rs:590-626, with txtfp's canonicaliser and tokeniser (text.rs:112-114,182-236) on the device for
+ * the streams opened RAW_UTF8.  flags: 0 (= ucfp_text_streams_create; max_push_bytes is ignored) or
+ * UCFP_TEXT_STREAMS_UTF8, then max_push_bytes in [1, 2^28]: the RAW_UTF8 chunk bytes one push may carry; the set
+ * allocates 4 x that plus about 400 bytes per slot of scratch once, here.  Unknown flags -> UCFP_E_INVALID. */
+int ucfp_text_streams_create_ex(ucfp_ctx* ctx, uint32_t shingle_k, uint32_t max_streams, uint32_t flags, uint64_t max_push_bytes,
+                                ucfp_text_streams** out);
 /* text.rs:645-730, handlers.rs:590-626 */
 void ucfp_text_streams_destroy(ucfp_text_streams* s);
 /* text.rs:645-730, handlers.rs:590-626.  A fresh stream in the first free slot.  mode: UCFP_TEXT_RAW_ASCII or
- * UCFP_TEXT_PRETOKENIZED; UCFP_TEXT_RAW_UTF8 -> UCFP_E_UNSUPPORTED (no streaming canonicaliser); any other value, or a
- * full set -> UCFP_E_INVALID. */
+ * UCFP_TEXT_PRETOKENIZED; UCFP_TEXT_RAW_UTF8 on a set created with UCFP_TEXT_STREAMS_UTF8, on any other set
+ * -> UCFP_E_UNSUPPORTED (the set has no streaming canonicaliser); any other value, or a full set -> UCFP_E_INVALID. */
 int ucfp_text_streams_open(ucfp_text_streams* s, int mode, uint32_t* slot);
 /* text.rs:645-730, handlers.rs:590-626.  Discard the stream, emit nothing. */
 int ucfp_text_streams_close(ucfp_text_streams* s, uint32_t slot);
 /* text.rs:645-730, handlers.rs:590-626.  Host-only: device bytes a set holds per stream. */
 size_t ucfp_text_streams_state_bytes(void);
+/* text.rs:645-730, handlers.rs:590-626.  Host-only: the same for a set created with `flags` (the canon stage's state on
+ * top for UCFP_TEXT_STREAMS_UTF8: context, held bytes, the pending open segment). */
+size_t ucfp_text_streams_state_bytes_ex(uint32_t flags);
 /* text.rs:645-730, handlers.rs:590-626.  slots / n_bytes / final: host arrays of n entries (distinct open slots; final may
  * be NULL = none; a chunk of 0 bytes is legal, final or not); d_bytes: the n chunks concatenated in that order on the
  * device (any alignment).  d_out: n x 1032 bytes, entry i is written only when final[i] is set (NULL allowed when no
  * entry is final); a final entry frees its slot.  d_status: n x int32, see above.  UCFP_E_INVALID before ANY state
- * changes: a slot out of range, not open or listed twice, a stream that would pass 2^63 bytes.  One launch whatever n
- * is; no host synchronisation (the host waits only for the table copy of the push two back). */
+ * changes: a slot out of range, not open or listed twice, a stream that would pass 2^63 bytes, RAW_UTF8 chunks of more
+ * than the set's max_push_bytes in all.  One launch whatever n is; no host synchronisation (the host waits only for the
+ * table copy of the push two back). */
 int ucfp_text_streams_push_dev(ucfp_text_streams* s, const uint32_t* slots, const uint64_t* n_bytes, const uint8_t* final,
                                size_t n, const uint8_t* d_bytes, uint8_t* d_out, int32_t* d_status, void* stream);
 /* text.rs:645-730, handlers.rs:590-626.  Host-pointer convenience for one slot (the per-request shape of the reference

@@ -124,6 +124,9 @@ SIGNATURES = {
     "ucfp_text_simhash_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int,
                                           C.c_void_p, C.c_void_p]),
     "ucfp_text_streams_create": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "ucfp_text_streams_create_ex": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
+                                              C.POINTER(C.c_void_p)]),
+    "ucfp_text_streams_state_bytes_ex": (C.c_size_t, [C.c_uint32]),
     "ucfp_text_streams_destroy": (None, [C.c_void_p]),
     "ucfp_text_streams_open": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint32)]),
     "ucfp_text_streams_close": (C.c_int, [C.c_void_p, C.c_uint32]),

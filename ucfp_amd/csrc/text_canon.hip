@@ -315,6 +315,40 @@ int launch_text_canon(const uint8_t* utf8, const uint64_t* offsets, size_t n, ui
     return 0;
 }
 
+// The device addresses of the code-point table, for the streaming canonicaliser (text_streams.hip): one copy of the
+// table serves both, so what the offline path keeps L2-resident is what a stream push reads.  The tables have internal
+// linkage (the runtime cannot look them up by name), so a one-thread kernel reports where they are.
+__global__ void text_canon_tables_kernel(const void** out) {
+    out[0] = d_stage1;
+    out[1] = d_stage2;
+    out[2] = d_pool;
+}
+
+int text_canon_tables(int device, const uint16_t** stage1, const uint32_t** stage2, const uint32_t** pool) {
+    static std::mutex mu;
+    static std::vector<const void*> known;   // three addresses per device, asked for once
+    std::lock_guard<std::mutex> lk(mu);
+    if (device < 0) return capi_fail(UCFP_E_INVALID, "device %d", device);
+    if (known.size() < 3 * ((size_t)device + 1)) known.resize(3 * ((size_t)device + 1), nullptr);
+    const void** h = &known[3 * (size_t)device];
+    if (!h[0]) {
+        const void** d = nullptr;
+        const void* got[3] = {nullptr, nullptr, nullptr};
+        HIP_TRY(hipSetDevice(device));
+        HIP_TRY(hipMalloc((void**)&d, sizeof(got)));
+        hipLaunchKernelGGL(text_canon_tables_kernel, dim3(1), dim3(1), 0, nullptr, d);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpy(got, d, sizeof(got), hipMemcpyDeviceToHost);   // waits for the kernel
+        (void)hipFree(d);
+        HIP_TRY(e);
+        h[0] = got[0], h[1] = got[1], h[2] = got[2];
+    }
+    *stage1 = static_cast<const uint16_t*>(h[0]);
+    *stage2 = static_cast<const uint32_t*>(h[1]);
+    *pool = static_cast<const uint32_t*>(h[2]);
+    return UCFP_OK;
+}
+
 // Mode UCFP_TEXT_RAW_UTF8 of the MinHash / SimHash calls: canon pass into the context's scratch, the hash pass over it
 // PRETOKENIZED, statuses merged.  total_bytes = d_offsets[n] - d_offsets[0].  Everything is enqueued on `stream`; users
 // of the scratch on other streams are ordered by canon_done, as the users of norm_ws are.

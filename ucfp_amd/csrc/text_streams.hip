@@ -17,6 +17,20 @@
 //   steps  tokenise / write canonical / room check / flush: the offline kernel's, unchanged (own copy of its two
 //          lambdas, so that text_hash_kernel's text and registers stay as they are)
 //   end    non-final: flush(false), then the state goes back; final: close an open token, flush(true), emit the record
+//
+// UTF-8 STREAMS (sets made with UCFP_TEXT_STREAMS_UTF8; DESIGN.md T7 "UTF-8 streams", restated in plain Python in
+// tests/text_canon_stream_ref.py).  ONE FUSED LAUNCH: text_stream_kernel<true> is the kernel above with a streaming form
+// of text_canon_kernel (text_canon.hip) in front for the entries whose slot is RAW_UTF8.  The wave canonicalises
+// held || chunk into its slice of the set's scratch as (' ' token)*, then hashes that slice as the next piece of a
+// PRETOKENIZED stream: a leading or a doubled space means nothing there, and a piece that ends inside a token continues
+// it.  The canon stage's wave state (CanonStreamState) is loaded and stored the same way:
+//   held   the bytes of a UTF-8 sequence a non-final chunk ends in (at most 3) wait, raw, for the next chunk
+//   pend   the last canonical code point stays undecided, as between two 64-byte steps offline; a final push decides it
+//   prov   an open segment that has an alphanumeric is a token and its bytes go out; one that has none is written, then
+//          taken back into the state (at most UCFP_TEXT_STREAM_OPEN_SEGMENT_BYTES, more is NEEDS_HOST) and restored to
+//          the front of the next push's slice
+// The step body is an OWN COPY of text_canon_kernel's (as the hash lambdas are of text_hash_kernel's): the offline
+// kernels' text and registers stay as they are.  text_stream_kernel<false> is what sets without the flag launch.
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
@@ -25,6 +39,7 @@
 #include <new>
 #include <vector>
 
+#include "../../include/ucfp_text_utab.h"
 #include "ctx.h"
 #include "text_core.h"
 
@@ -63,11 +78,311 @@ struct TextStreamEntry {
 
 __device__ __forceinline__ uint32_t uni(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
 
+// ---------------------------------------- the streaming canonicaliser ----------------------------------------
+
+constexpr uint32_t kProvCap = UCFP_TEXT_STREAM_OPEN_SEGMENT_BYTES;
+// a slice holds the restored provisional bytes, 4 x (held + chunk) (ucfp_text_canon_bound) and the code point the last
+// push left undecided with its separator; slices begin on 128-byte lines so that no two waves share one
+constexpr uint64_t kSliceSlack = kProvCap + 4 * 3 + 8;
+constexpr uint64_t kSliceAlign = 128;
+
+// one slot's canon stage between two pushes (wave-uniform in text_canon_kernel)
+struct CanonStreamState {
+    uint32_t x[3];              // two context code points and the undecided one (valid when pend)
+    uint32_t pend, seg_alnum;   // seg_alnum: the open segment has an alphanumeric, its bytes went out
+    uint32_t bad;               // sticky NEEDS_HOST
+    uint32_t nheld, held;       // raw bytes of an incomplete UTF-8 sequence, byte i in bits [8i, 8i + 8)
+    uint32_t nprov, pad_;
+    uint8_t prov[kProvCap];     // the open segment's canonical bytes, separator included, while it has no alphanumeric
+};
+static_assert(sizeof(CanonStreamState) == 40 + kProvCap && sizeof(CanonStreamState) % 8 == 0, "about 300 bytes per stream");
+
+struct CanonSlice {
+    uint64_t off;   // into the set's scratch
+    uint32_t cap, pad_;
+};
+
+struct CanonArgs {
+    CanonStreamState* cstates;
+    const CanonSlice* slices;   // per entry of the push
+    uint8_t* scratch;
+    const uint16_t* stage1;     // the code-point table of text_canon.hip
+    const uint32_t* stage2;
+    const uint32_t* pool;
+};
+
+constexpr uint32_t kCpMask = 0x1FFFFu, kAlnum = 1u << 28, kVowel = 1u << 27, kFlagMask = 0xFu << 23 | kAlnum | kVowel;
+constexpr uint32_t kNone = kCpMask | 15u << 23;   // "no code point": class 15 is in no class set, the value no apostrophe
+constexpr int kStepCps = 3 * 67;                  // canonical code points a 64-byte step can add (text_canon.hip)
+constexpr int kXCap = 2 + 1 + kStepCps + 4;
+
+struct CanonLds {
+    uint8_t bytes[3 + 64 + 3 + 2];   // [0, 3): the previous step's last bytes; [3, 67): this step; [67, 70): the next step's first
+    uint32_t x[kXCap];               // [0, 2): context; then the undecided code point of the last step, then this step's
+};
+static_assert(sizeof(CanonLds) <= sizeof(WaveLds::h1) && offsetof(WaveLds, h1) % 8 == 0, "the canon stage borrows h1");
+
+__device__ __forceinline__ uint32_t in_set(uint32_t w, uint32_t set) { return (set >> ((w >> 23) & 15u)) & 1u; }
+
+// U4: no boundary before b, given the canonical code points around it (kNone where there is none)
+__device__ __forceinline__ bool no_boundary(uint32_t aa, uint32_t a, uint32_t b, uint32_t bb) {
+    constexpr uint32_t HEB = 1u << 2, AHL = 1u << 1 | HEB, NUM = 1u << 3, KAT = 1u << 4, ENL = 1u << 5;
+    constexpr uint32_t SQ = 1u << 9, DQ = 1u << 10, MIDL = 1u << 6 | 1u << 8 | SQ, MIDN = 1u << 7 | 1u << 8 | SQ;
+    uint32_t j = in_set(a, AHL) & in_set(b, AHL);
+    j |= in_set(a, AHL) & in_set(b, MIDL) & in_set(bb, AHL);
+    j |= in_set(aa, AHL) & in_set(a, MIDL) & in_set(b, AHL);
+    j |= in_set(a, HEB) & in_set(b, SQ);
+    j |= in_set(a, HEB) & in_set(b, DQ) & in_set(bb, HEB);
+    j |= in_set(aa, HEB) & in_set(a, DQ) & in_set(b, HEB);
+    j |= in_set(a, NUM) & in_set(b, NUM | AHL);
+    j |= in_set(a, AHL) & in_set(b, NUM);
+    j |= in_set(aa, NUM) & in_set(a, MIDN) & in_set(b, NUM);
+    j |= in_set(a, NUM) & in_set(b, MIDN) & in_set(bb, NUM);
+    j |= in_set(a, KAT) & in_set(b, KAT);
+    j |= in_set(a, AHL | NUM | KAT | ENL) & in_set(b, ENL);
+    j |= in_set(a, ENL) & in_set(b, AHL | NUM | KAT);
+    const uint32_t ca = a & kCpMask;
+    j |= (uint32_t)((ca == 0x27u || ca == 0x2019u) && (b & kVowel));   // the `regex` module's apostrophe tailoring
+    return j != 0;
+}
+
+__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, int lane) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t t = __shfl_up(v, d, 64);
+        if (lane >= d) v += t;
+    }
+    return v;
+}
+
+// One push of one RAW_UTF8 stream through the canon stage: V = held || chunk, of which a non-final push processes all
+// but an incomplete sequence at the end.  Writes the piece -- the part of the stream (' ' token)* this push settles --
+// to out[0, cap) and returns its length; *bad_out: the stream is handed back (now or by an earlier push).  Steps A..D
+// are text_canon_kernel<true>'s; positions are relative to the slice, which begins with the restored provisional bytes.
+__device__ __forceinline__ uint32_t canon_stream_push(CanonLds& L, const CanonArgs& ca, CanonStreamState& C,
+                                                      const uint8_t* __restrict__ chunk, size_t clen, bool fin, bool fresh,
+                                                      uint8_t* out, uint32_t cap, int lane, bool* bad_out) {
+    uint32_t pend = 0, nheld = 0, held = 0, nprov = 0;
+    bool seg_alnum = false, bad = false;
+    uint32_t xin = kNone;
+    if (!fresh) {
+        pend = uni(C.pend) & 1u;
+        seg_alnum = uni(C.seg_alnum) != 0;
+        bad = uni(C.bad) != 0;
+        nheld = uni(C.nheld);
+        held = uni(C.held);
+        nprov = uni(C.nprov);
+        if (nheld > 3u) nheld = 0;                 // a stored state never has more: keeps every index in range
+        if (nprov > kProvCap) nprov = 0;
+        if (lane < 3) xin = C.x[lane];
+    }
+    if (bad) {
+        *bad_out = true;
+        return 0;
+    }
+    if (nprov > cap) nprov = 0;                    // (the host sizes every slice above kProvCap)
+    for (uint32_t i = lane; i < nprov; i += 64) out[i] = C.prov[i];
+    wave_lds_sync();                               // the LDS behind L was the hash stage's of the block's last entry
+    if (lane < 3) {
+        L.x[lane] = xin;
+        L.bytes[lane] = 0;   // V begins where a sequence begins: a continuation byte there is claimed by nobody
+    }
+
+    const size_t vlen = (size_t)nheld + clen;
+    auto V = [&](size_t i) -> uint32_t { return i < nheld ? (held >> (8u * (uint32_t)i)) & 0xffu : (uint32_t)chunk[i - nheld]; };
+    // the incomplete sequence a non-final push ends in: the last lead byte among the last three, reaching past the end
+    uint32_t nh = 0;
+    if (!fin) {
+        for (uint32_t back = 1; back <= 3u && back <= vlen; back++) {
+            const uint32_t b = V(vlen - back);
+            if (b < 0x80u) break;
+            if (b >= 0xC0u) {
+                const uint32_t seq = b >= 0xF0u ? 4u : b >= 0xE0u ? 3u : 2u;
+                nh = back < seq ? back : 0u;
+                break;
+            }
+        }
+    }
+    const size_t len = vlen - nh;
+    uint32_t new_held = 0;
+    for (uint32_t t = 0; t < nh; t++) new_held |= V(len + t) << (8u * t);
+
+    uint32_t out_pos = nprov;     // slice bytes so far, the open segment included
+    uint32_t seg_start = 0;       // where the open segment began (a provisional one: at the slice's front)
+
+    for (size_t base = 0; base < len || (fin && base == 0); base += 64) {   // a final push decides `pend` even without bytes
+        const size_t pos = base + lane;
+        const uint32_t c = pos < len ? V(pos) : 0u;
+        wave_lds_sync();
+        L.bytes[3 + lane] = (uint8_t)c;
+        if (lane < 3) L.bytes[67 + lane] = base + 64 + lane < len ? (uint8_t)V(base + 64 + lane) : (uint8_t)0;
+        wave_lds_sync();
+
+        // ---- A: decode (U2) ----
+        bool lead = false, err = false;
+        uint32_t cp = c;
+        if (pos < len) {
+            if (c < 0x80u) {
+                lead = true;
+            } else if (c < 0xC0u) {   // continuation: the nearest byte before it that is none must be a lead that reaches it
+                const uint32_t b1 = L.bytes[2 + lane], b2 = L.bytes[1 + lane], b3 = L.bytes[lane];
+                const uint32_t j = (b1 & 0xC0u) != 0x80u ? 1u : (b2 & 0xC0u) != 0x80u ? 2u : (b3 & 0xC0u) != 0x80u ? 3u : 0u;
+                const uint32_t lb = j == 1 ? b1 : j == 2 ? b2 : b3;
+                const uint32_t reach = lb >= 0xF0u ? 3u : lb >= 0xE0u ? 2u : lb >= 0xC0u ? 1u : 0u;
+                err = j == 0 || reach < j;
+            } else {
+                lead = true;
+                const uint32_t need = c >= 0xF0u ? 3u : c >= 0xE0u ? 2u : 1u;
+                const uint32_t c1 = L.bytes[4 + lane], c2 = L.bytes[5 + lane], c3 = L.bytes[6 + lane];
+                err = c < 0xC2u || c > 0xF4u || pos + need >= len || (c1 & 0xC0u) != 0x80u;   // cut by the end: a final push only
+                if (need == 1) {
+                    cp = (c & 0x1Fu) << 6 | (c1 & 0x3Fu);
+                } else if (need == 2) {
+                    cp = (c & 0x0Fu) << 12 | (c1 & 0x3Fu) << 6 | (c2 & 0x3Fu);
+                    err |= (c2 & 0xC0u) != 0x80u || cp < 0x800u || cp - 0xD800u < 0x800u;
+                } else {
+                    cp = (c & 0x07u) << 18 | (c1 & 0x3Fu) << 12 | (c2 & 0x3Fu) << 6 | (c3 & 0x3Fu);
+                    err |= (c2 & 0xC0u) != 0x80u || (c3 & 0xC0u) != 0x80u || cp < 0x10000u || cp > 0x10FFFFu;
+                }
+            }
+        }
+        // ---- B: M(c) through the table (U1, U3) ----
+        uint32_t e = 0, nout = 0;
+        if (lead && !err) {
+            if (cp >= UCFP_TEXT_UTAB_LIMIT) {
+                err = true;
+            } else {
+                e = ca.stage2[((uint32_t)ca.stage1[cp >> UCFP_TEXT_UTAB_SHIFT] << UCFP_TEXT_UTAB_SHIFT) |
+                              (cp & ((1u << UCFP_TEXT_UTAB_SHIFT) - 1u))];
+                if (!(e >> 31)) err = true;
+                else nout = ((e >> 29) & 3u) == 2u ? (e >> 17) & 7u : 1u;
+            }
+        }
+        if (__ballot(err)) {
+            bad = true;
+            break;
+        }
+        const uint32_t incl = wave_incl_scan(nout, lane);
+        const uint32_t added = __shfl(incl, 63, 64);
+        if (nout) {
+            const uint32_t at = 2u + pend + incl - nout;   // < 2 + 1 + kStepCps
+            const uint32_t kind = (e >> 29) & 3u;
+            if (kind == 0) L.x[at] = cp | (e & kFlagMask);
+            else if (kind == 1) L.x[at] = (e & kCpMask) | (e & kFlagMask);
+            else
+                for (uint32_t t = 0; t < nout; t++) L.x[at + t] = ca.pool[(e & kCpMask) + t];
+        }
+        wave_lds_sync();
+
+        // ---- C, D: boundaries, segments, tokens ----
+        const bool final = fin && base + 64 >= len;
+        const uint32_t m = pend + added;
+        const uint32_t ndec = final ? m : (m ? m - 1u : 0u);
+        for (uint32_t j0 = 0; j0 < ndec; j0 += 64) {
+            const uint32_t j = j0 + lane;
+            const bool has = j < ndec;
+            const uint32_t i = 2u + j;
+            uint32_t w = kNone;
+            bool bnd = false;
+            if (has) {
+                w = L.x[i];
+                bnd = !no_boundary(L.x[i - 2], L.x[i - 1], w, j + 1 < m ? L.x[i + 1] : kNone);
+            }
+            const uint64_t bmask = __ballot(bnd), amask = __ballot(has && (w & kAlnum));
+            // the carried segment runs up to the first boundary of the chunk; closed there without an alphanumeric, it goes
+            const int fb = bmask ? __builtin_ctzll(bmask) : 64;
+            const bool carried_has = seg_alnum || (amask & (fb == 64 ? ~0ull : (1ull << fb) - 1ull)) != 0;
+            const bool drop0 = bmask != 0 && !carried_has;
+            // this lane's segment: [its last boundary at or before the lane, the next boundary)
+            const uint64_t le = bmask & (~0ull >> (63 - lane));
+            const int sb = le ? 63 - __builtin_clzll(le) : -1;
+            const uint64_t gt = lane == 63 ? 0ull : bmask & (~0ull << (lane + 1));
+            const int eb = gt ? __builtin_ctzll(gt) : 64;
+            const uint64_t range = (eb == 64 ? ~0ull : (1ull << eb) - 1ull) & (sb <= 0 ? ~0ull : ~((1ull << sb) - 1ull));
+            const bool seg_has = (amask & range) != 0 || (sb < 0 && seg_alnum);
+            const bool keep = has && (eb == 64 || seg_has);   // the open segment is kept provisionally
+            const uint32_t cpw = w & kCpMask;
+            const uint32_t nb = cpw < 0x80u ? 1u : cpw < 0x800u ? 2u : cpw < 0x10000u ? 3u : 4u;
+            const uint32_t contrib = keep ? nb + (bnd ? 1u : 0u) : 0u;
+            const uint32_t cincl = wave_incl_scan(contrib, lane);
+            const uint32_t excl = cincl - contrib;
+            const uint32_t base_pos = drop0 ? seg_start : out_pos;
+            // a rewind: other lanes are about to store where the provisional bytes went (text_canon_kernel's fence)
+            if (drop0) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            if (keep) {
+                uint32_t p = base_pos + excl;
+                uint32_t bytes;
+                if (nb == 1) bytes = cpw;
+                else if (nb == 2) bytes = (0xC0u | cpw >> 6) | (0x80u | (cpw & 0x3Fu)) << 8;
+                else if (nb == 3) bytes = (0xE0u | cpw >> 12) | (0x80u | (cpw >> 6 & 0x3Fu)) << 8 | (0x80u | (cpw & 0x3Fu)) << 16;
+                else
+                    bytes = (0xF0u | cpw >> 18) | (0x80u | (cpw >> 12 & 0x3Fu)) << 8 | (0x80u | (cpw >> 6 & 0x3Fu)) << 16 |
+                            (0x80u | (cpw & 0x3Fu)) << 24;
+                if (bnd) {
+                    if (p < cap) out[p] = ' ';
+                    p++;
+                }
+                for (uint32_t t = 0; t < nb; t++, p++)
+                    if (p < cap) out[p] = (uint8_t)(bytes >> (8 * t));
+            }
+            if (bmask) {
+                const int hb = 63 - __builtin_clzll(bmask);
+                seg_start = base_pos + __shfl(excl, hb, 64);
+                seg_alnum = (amask >> hb) != 0;
+            } else {
+                seg_alnum = seg_alnum || amask != 0;
+            }
+            out_pos = base_pos + __shfl(cincl, 63, 64);
+        }
+        // context for the next step: the last two decided code points and the undecided one
+        wave_lds_sync();
+        const uint32_t keep3 = lane < 3 ? L.x[ndec + lane] : 0u;
+        wave_lds_sync();
+        if (lane < 3) L.x[lane] = keep3;
+        if (lane >= 61) L.bytes[lane - 61] = (uint8_t)c;
+        pend = m - ndec;
+    }
+    if (out_pos > cap) bad = true;   // cannot happen (the slice holds 4 x the bytes): refuse rather than hash a cut piece
+
+    // ---- what this push settles, and what goes back into the state ----
+    uint32_t plen = 0, np = 0;
+    if (!bad) {
+        if (fin) {
+            plen = seg_alnum ? out_pos : seg_start;   // the last segment closes at the stream's end
+        } else if (seg_alnum) {
+            plen = out_pos;                           // an open token: its bytes so far go out, the next piece continues it
+        } else {
+            plen = seg_start;
+            np = out_pos - seg_start;
+            if (np > kProvCap) bad = true, plen = 0, np = 0;   // the documented open-segment condition
+        }
+    }
+    if (!fin) {
+        if (np) {
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // the bytes were stored by other lanes of this wave
+            for (uint32_t i = lane; i < np; i += 64) C.prov[i] = out[seg_start + i];
+        }
+        wave_lds_sync();
+        if (lane < 3) C.x[lane] = L.x[lane];
+        if (lane == 0) {
+            C.pend = pend;
+            C.seg_alnum = seg_alnum ? 1u : 0u;
+            C.bad = bad ? 1u : 0u;
+            C.nheld = bad ? 0u : nh;
+            C.held = new_held;
+            C.nprov = np;
+        }
+    }
+    *bad_out = bad;
+    return plen;
+}
+
 }  // namespace
 
+template <bool UTF8>
 __global__ __launch_bounds__(64 * kWavesPerBlock) void text_stream_kernel(
     TextStreamState* __restrict__ states, const TextStreamEntry* __restrict__ ents, size_t n,
-    const uint8_t* __restrict__ bytes, uint32_t k, uint8_t* __restrict__ out, int32_t* __restrict__ status) {
+    const uint8_t* __restrict__ bytes, uint32_t k, uint8_t* __restrict__ out, int32_t* __restrict__ status, CanonArgs ca) {
     __shared__ WaveLds lds[kWavesPerBlock];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const size_t ei = (size_t)blockIdx.x * kWavesPerBlock + wave;
@@ -117,7 +432,24 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void text_stream_kernel(
             L.cend[lane] = S.cend[lane];
         }
     }
-    const bool pretok = mode == UCFP_TEXT_PRETOKENIZED;
+    const bool pretok = UTF8 ? mode != UCFP_TEXT_RAW_ASCII : mode == UCFP_TEXT_PRETOKENIZED;   // a canon piece is pre-tokenised
+
+    // ---- RAW_UTF8: canonicalise held || chunk into the entry's scratch slice; the hash stage below reads the piece ----
+    const uint8_t* src_bytes = bytes + ent.off;
+    size_t src_len = (size_t)ent.len;
+    bool canon_bad = false;
+    if (UTF8 && (eflags >> kEntModeShift) == (uint32_t)UCFP_TEXT_RAW_UTF8) {
+        const CanonSlice sl = ca.slices[ei];
+        uint8_t* piece = ca.scratch + sl.off;
+        // the hash stage's h1 is idle until the first flush: the canon stage's LDS lives there
+        CanonLds& CL = *reinterpret_cast<CanonLds*>(L.h1);
+        src_len = canon_stream_push(CL, ca, ca.cstates[uni(ent.slot)], src_bytes, src_len, fin, fresh, piece, uni(sl.cap), lane,
+                                    &canon_bad);
+        src_bytes = piece;
+        // the piece was stored by this wave's lanes and is loaded by others of them: the stores complete before the loads issue
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+        wave_sync();
+    }
 
     // consume the batch: hash complete shingles, fold them in, carry the tail to the front (text_hash_kernel's flush)
     auto flush = [&](bool final) {
@@ -188,8 +520,8 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void text_stream_kernel(
     // ---- the bytes of this push: V = pending || chunk; V[0, proc) is processed, V[proc] is the byte after it ----
     const uint32_t npend = dead ? 0u : (pend >> 8) & 1u;
     const uint32_t pbyte = pend & 0xffu;
-    const size_t clen = (size_t)ent.len;
-    const uint8_t* __restrict__ chunk = bytes + ent.off;      // V[i] = chunk[i - npend] for i >= npend
+    const size_t clen = src_len;
+    const uint8_t* __restrict__ chunk = src_bytes;            // V[i] = chunk[i - npend] for i >= npend
     const size_t vlen = dead ? 0 : npend + clen;
     const size_t proc = fin ? vlen : (vlen ? vlen - 1 : 0);
     const bool aligned4 = ((reinterpret_cast<uintptr_t>(chunk) - npend) & 3u) == 0;
@@ -266,6 +598,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void text_stream_kernel(
         pend = kPendValid | b;
         if (!pretok && b >= 0x80u) nonascii = true;
     }
+    if (UTF8 && canon_bad) nonascii = true;   // the canon stage's NEEDS_HOST: sticky, and it wins over the hash stage's status
     const bool na = __ballot(nonascii) != 0;
     total_bytes += clen;
 
@@ -343,11 +676,21 @@ struct ucfp_text_streams {
     hipEvent_t tab_copied[2] = {nullptr, nullptr};
     int tab_next = 0;
     hipEvent_t done = nullptr;            // behind the last push: the next one waits for it
+    // UTF-8 sets (UCFP_TEXT_STREAMS_UTF8); the push tables then carry a CanonSlice per entry behind the entries
+    bool utf8 = false;
+    uint64_t max_push_bytes = 0;          // RAW_UTF8 chunk bytes one push may carry: the scratch is sized for them
+    ucfp::CanonArgs ca = {};              // canon states, scratch, the code-point table
 };
 
 namespace {
 
 constexpr uint64_t kMaxStreamBytes = (uint64_t)1 << 63;
+constexpr uint64_t kMaxPushBytes = (uint64_t)1 << 28;   // 4 x this, and a slice's cap, stay below 2^32
+
+// the scratch slice of a RAW_UTF8 entry with a chunk of `len` bytes
+uint64_t slice_bytes(uint64_t len) {
+    return (ucfp_text_canon_bound((size_t)len) + ucfp::kSliceSlack + ucfp::kSliceAlign - 1) & ~(ucfp::kSliceAlign - 1);
+}
 
 // validates the push; nothing changes
 int check_push(ucfp_text_streams* s, const uint32_t* slots, const uint64_t* n_bytes, size_t n) {
@@ -366,6 +709,14 @@ int check_push(ucfp_text_streams* s, const uint32_t* slots, const uint64_t* n_by
         marked = i + 1;
     }
     for (size_t i = 0; i < marked; i++) s->seen[slots[i]] = 0;
+    if (rc == UCFP_OK && s->utf8) {
+        uint64_t total = 0;
+        for (size_t i = 0; i < n; i++)
+            if (s->mode[slots[i]] == UCFP_TEXT_RAW_UTF8) total += n_bytes[i] < kMaxPushBytes ? n_bytes[i] : kMaxPushBytes + 1;
+        if (total > s->max_push_bytes)
+            rc = fail(UCFP_E_INVALID, "the RAW_UTF8 chunks of this push have %llu bytes, the set was created for %llu (max_push_bytes)",
+                      (unsigned long long)total, (unsigned long long)s->max_push_bytes);
+    }
     return rc;
 }
 
@@ -379,7 +730,8 @@ int push_impl(ucfp_text_streams* s, const uint32_t* slots, const uint64_t* n_byt
     s->tab_next ^= 1;
     HIP_TRY(hipEventSynchronize(s->tab_copied[t]));
     ucfp::TextStreamEntry* tab = s->tab_h[t];
-    uint64_t off = 0;
+    ucfp::CanonSlice* slices = reinterpret_cast<ucfp::CanonSlice*>(tab + n);   // UTF-8 sets: behind the n entries
+    uint64_t off = 0, soff = 0;
     for (size_t i = 0; i < n; i++) {
         const uint32_t slot = slots[i];
         tab[i].off = off;
@@ -388,13 +740,28 @@ int push_impl(ucfp_text_streams* s, const uint32_t* slots, const uint64_t* n_byt
         tab[i].flags = ((fin && fin[i]) ? ucfp::kEntFinal : 0u) | (s->fresh[slot] ? ucfp::kEntFresh : 0u) |
                        ((uint32_t)s->mode[slot] << ucfp::kEntModeShift);
         off += n_bytes[i];
+        if (s->utf8) {
+            const uint64_t sb = s->mode[slot] == UCFP_TEXT_RAW_UTF8 ? slice_bytes(n_bytes[i]) : 0;   // check_push bounds the sum
+            slices[i].off = soff;
+            slices[i].cap = (uint32_t)sb;
+            slices[i].pad_ = 0;
+            soff += sb;
+        }
     }
+    const size_t tab_bytes = n * (sizeof(ucfp::TextStreamEntry) + (s->utf8 ? sizeof(ucfp::CanonSlice) : 0));
     HIP_TRY(hipStreamWaitEvent(st, s->done, 0));
-    HIP_TRY(hipMemcpyAsync(s->tab_d, tab, n * sizeof(ucfp::TextStreamEntry), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s->tab_d, tab, tab_bytes, hipMemcpyHostToDevice, st));
     HIP_TRY(hipEventRecord(s->tab_copied[t], st));
     const unsigned grid = (unsigned)((n + ucfp::kWavesPerBlock - 1) / ucfp::kWavesPerBlock);
-    hipLaunchKernelGGL(ucfp::text_stream_kernel, dim3(grid), dim3(64 * ucfp::kWavesPerBlock), 0, st, s->states, s->tab_d, n,
-                       d_bytes, s->k, d_out, d_status);
+    if (s->utf8) {
+        ucfp::CanonArgs ca = s->ca;
+        ca.slices = reinterpret_cast<const ucfp::CanonSlice*>(s->tab_d + n);
+        hipLaunchKernelGGL(ucfp::text_stream_kernel<true>, dim3(grid), dim3(64 * ucfp::kWavesPerBlock), 0, st, s->states, s->tab_d,
+                           n, d_bytes, s->k, d_out, d_status, ca);
+    } else {
+        hipLaunchKernelGGL(ucfp::text_stream_kernel<false>, dim3(grid), dim3(64 * ucfp::kWavesPerBlock), 0, st, s->states, s->tab_d,
+                           n, d_bytes, s->k, d_out, d_status, ucfp::CanonArgs{});
+    }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(s->done, st));
     for (size_t i = 0; i < n; i++) {
@@ -423,10 +790,23 @@ extern "C" {
 
 size_t ucfp_text_streams_state_bytes(void) { return sizeof(ucfp::TextStreamState); }
 
+size_t ucfp_text_streams_state_bytes_ex(uint32_t flags) {
+    return sizeof(ucfp::TextStreamState) + ((flags & UCFP_TEXT_STREAMS_UTF8) ? sizeof(ucfp::CanonStreamState) : 0);
+}
+
 int ucfp_text_streams_create(ucfp_ctx* ctx, uint32_t shingle_k, uint32_t max_streams, ucfp_text_streams** out) {
+    return ucfp_text_streams_create_ex(ctx, shingle_k, max_streams, 0, 0, out);
+}
+
+int ucfp_text_streams_create_ex(ucfp_ctx* ctx, uint32_t shingle_k, uint32_t max_streams, uint32_t flags, uint64_t max_push_bytes,
+                                ucfp_text_streams** out) {
     if (shingle_k == 0 || shingle_k > 64) return fail(UCFP_E_MODALITY, "shingle k must be in [1, 64] (got %u)", shingle_k);
     if (!out) return fail(UCFP_E_INVALID, "out is NULL");
     *out = nullptr;
+    if (flags & ~(uint32_t)UCFP_TEXT_STREAMS_UTF8) return fail(UCFP_E_INVALID, "unknown flags 0x%x", flags);
+    const bool utf8 = (flags & UCFP_TEXT_STREAMS_UTF8) != 0;
+    if (utf8 && (max_push_bytes == 0 || max_push_bytes > kMaxPushBytes))
+        return fail(UCFP_E_INVALID, "max_push_bytes %llu outside [1, 2^28]", (unsigned long long)max_push_bytes);
     if (!ctx) {
         if (!have_gfx950()) return fail(UCFP_E_INDEX, "no gfx950 device available; this library has no CPU path");
         return fail(UCFP_E_INVALID, "ctx is NULL");
@@ -443,8 +823,18 @@ int ucfp_text_streams_create(ucfp_ctx* ctx, uint32_t shingle_k, uint32_t max_str
     s->fresh.assign(max_streams, 0);
     s->mode.assign(max_streams, 0);
     s->seen.assign(max_streams, 0);
-    const size_t tab_bytes = (size_t)max_streams * sizeof(ucfp::TextStreamEntry);
+    s->utf8 = utf8;
+    s->max_push_bytes = utf8 ? max_push_bytes : 0;
+    const size_t tab_bytes = (size_t)max_streams * (sizeof(ucfp::TextStreamEntry) + (utf8 ? sizeof(ucfp::CanonSlice) : 0));
     hipError_t e = hipMalloc((void**)&s->states, (size_t)max_streams * sizeof(ucfp::TextStreamState));
+    if (utf8) {
+        // every slice of a push at once: 4 x the chunk bytes, and per entry the slack and the rounding to a line
+        const size_t scratch = (size_t)ucfp_text_canon_bound((size_t)max_push_bytes) +
+                               (size_t)max_streams * (size_t)(ucfp::kSliceSlack + ucfp::kSliceAlign) + 64;   // the hash stage reads whole dwords
+        if (e == hipSuccess) e = hipMalloc((void**)&s->ca.cstates, (size_t)max_streams * sizeof(ucfp::CanonStreamState));
+        if (e == hipSuccess) e = hipMalloc((void**)&s->ca.scratch, scratch);
+        if (e == hipSuccess && ucfp::text_canon_tables(ctx->device, &s->ca.stage1, &s->ca.stage2, &s->ca.pool) != UCFP_OK) e = hipErrorNotFound;
+    }
     if (e == hipSuccess) e = hipMalloc((void**)&s->tab_d, tab_bytes);
     for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipHostMalloc((void**)&s->tab_h[i], tab_bytes, 0);
     for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipEventCreateWithFlags(&s->tab_copied[i], hipEventDisableTiming);
@@ -461,6 +851,8 @@ void ucfp_text_streams_destroy(ucfp_text_streams* s) {
     if (!s) return;
     if (s->done) (void)hipEventSynchronize(s->done);
     if (s->states) (void)hipFree(s->states);
+    if (s->ca.cstates) (void)hipFree(s->ca.cstates);
+    if (s->ca.scratch) (void)hipFree(s->ca.scratch);
     if (s->tab_d) (void)hipFree(s->tab_d);
     for (int i = 0; i < 2; i++) {
         if (s->tab_h[i]) (void)hipHostFree(s->tab_h[i]);
@@ -472,9 +864,9 @@ void ucfp_text_streams_destroy(ucfp_text_streams* s) {
 
 int ucfp_text_streams_open(ucfp_text_streams* s, int mode, uint32_t* slot) {
     if (!s || !slot) return fail(UCFP_E_INVALID, "set / slot is NULL");
-    if (mode == UCFP_TEXT_RAW_UTF8)
+    if (mode == UCFP_TEXT_RAW_UTF8 && !s->utf8)
         return fail(UCFP_E_UNSUPPORTED, "RAW_UTF8 streams are not built: canonicalise on the host and open a PRETOKENIZED stream");
-    if (mode != UCFP_TEXT_RAW_ASCII && mode != UCFP_TEXT_PRETOKENIZED) return fail(UCFP_E_INVALID, "unknown text mode %d", mode);
+    if (mode != UCFP_TEXT_RAW_ASCII && mode != UCFP_TEXT_PRETOKENIZED && mode != UCFP_TEXT_RAW_UTF8) return fail(UCFP_E_INVALID, "unknown text mode %d", mode);
     std::lock_guard<std::mutex> lk(s->mu);
     for (uint32_t i = 0; i < s->max_streams; i++) {
         if (!s->open[i]) {

@@ -15,7 +15,8 @@ to the GPU as UTF-8 (mode RAW_UTF8: the default canonicaliser -- NFKC + case fol
 text.rs:112-114 -- and the UAX#29 word tokeniser as tables).  Only what the device hands back
 (combining marks, Hangul jamo, regional indicators, malformed text) or what it does not build (another
 canonicaliser) is canonicalised and segmented here on the host (`_prepare`, via the `regex` module) and submitted
-pre-tokenised; both routes give the same record.
+pre-tokenised; both routes give the same record.  Streams follow the same routing chunk by chunk: a
+`MinHashStreams(utf8=True)` set canonicalises and tokenises RAW_UTF8 chunks on the device, cut anywhere.
 """
 import ctypes as C
 import math
@@ -54,6 +55,10 @@ TLSH_MIN_BYTES = 50         # shorter documents are refused (the reference's REA
 # consecutive tokens (the whole document below k tokens, the single token for SimHash) has at most this many
 # canonical bytes, separators included; longer windows may get status -2.
 MAX_WINDOW_BYTES = 1405
+STREAMS_UTF8 = 1                     # UCFP_TEXT_STREAMS_UTF8: the set also opens RAW_UTF8 streams
+# UCFP_TEXT_STREAM_OPEN_SEGMENT_BYTES: canonical bytes of a segment without an alphanumeric a RAW_UTF8 stream can carry
+# from one push to the next; more at a push boundary and the stream is handed back (NEEDS_HOST).
+STREAM_OPEN_SEGMENT_BYTES = 256
 
 # txtfp::config_hash is not available offline and could not be reconstructed (DESIGN section 2 lists what was
 # tried).  The ONE value the reference's tests show (src/server/tests.rs:1158-1161: default canonicalizer,
@@ -212,15 +217,19 @@ def simhash_batch(texts: Sequence[str], opts: Optional[TextOpts] = None, ctx=Non
 class MinHashStreams:
     """A set of live MinHash streams on the device (ucfp_text_streams_*): `push` advances any subset of
     them by one chunk each with one launch.  A stream's final record and status are those of `ucfp_text_minhash_batch`
-    on the concatenation of its chunks, however they were cut.  Modes: RAW_ASCII and PRETOKENIZED."""
+    on the concatenation of its chunks, however they were cut.  Modes: RAW_ASCII and PRETOKENIZED; with `utf8=True`
+    also RAW_UTF8 (the device canonicalises and tokenises, cuts inside a UTF-8 sequence included), and the RAW_UTF8
+    chunks of one push may then have `max_push_bytes` bytes in all (the set's scratch is sized for them once)."""
 
-    def __init__(self, max_streams: int, k: int = DEFAULT_K, ctx=None):
+    def __init__(self, max_streams: int, k: int = DEFAULT_K, ctx=None, utf8: bool = False, max_push_bytes: int = 1 << 20):
         self._lib = _lib.load()
         self.ctx = ctx or _lib.current_context()
         h = C.c_void_p()
-        _lib.check(self._lib.ucfp_text_streams_create(self.ctx.handle, k, max_streams, C.byref(h)))
+        _lib.check(self._lib.ucfp_text_streams_create_ex(self.ctx.handle, k, max_streams, STREAMS_UTF8 if utf8 else 0,
+                                                         max_push_bytes if utf8 else 0, C.byref(h)))
         self.handle = h
         self.max_streams, self.k = max_streams, k
+        self.utf8, self.max_push_bytes = bool(utf8), int(max_push_bytes) if utf8 else 0
 
     def open(self, mode: int = RAW_ASCII) -> int:
         slot = C.c_uint32(0)
@@ -278,6 +287,7 @@ class MinHashStreams:
 
 
 _CUT_AT = " \n\t\r"
+_SESSION_PUSH_BYTES = 256 << 10      # RAW_UTF8 bytes a session gives the device at once (its set holds 4 x this of scratch)
 
 
 def _stream_cut(s: str) -> Tuple[str, str]:
@@ -297,12 +307,16 @@ class StreamingMinHashSession:
     chunks, cuts inside a UTF-8 sequence included.  Routing follows `_prepare`:
       - while every byte so far is ASCII and the canonicaliser folds case, chunks go raw to a RAW_ASCII stream; the
         session keeps these ASCII bytes on the host (no more than the reference buffers), because
-      - at the first byte >= 0x80 (or from the start without case folding) the document is one the host canonicalises:
-        the session drops that stream, opens a PRETOKENIZED one, replays the kept bytes through the host route and
-        frees the buffer;
-      - host route: UTF-8 is decoded incrementally, the text seen so far is cut just before its last ASCII whitespace
+      - at the first byte >= 0x80 the document is one the DEVICE canonicalises when the canonicaliser is the default
+        one (the condition of `_device_utf8`): the session drops that stream, opens a RAW_UTF8 one, replays the kept
+        bytes into it and goes on pushing raw chunks, cut wherever they are cut -- text without ASCII whitespace
+        advances like any other.  It keeps the bytes, as the ASCII route does, because
+      - if a push reports NEEDS_HOST (a combining mark, malformed UTF-8 ...) the session falls back,
+        once, to the host route and replays them there; with another canonicaliser (or without case folding, from the
+        start) the host route is taken directly.  `route` names the one in use: "ascii", "utf8" or "host";
+      - host route: a PRETOKENIZED stream; UTF-8 is decoded incrementally, the text seen so far is cut just before its last ASCII whitespace
         character (`_stream_cut`), the head is canonicalised and tokenised and pushed, the tail stays on the host.
-        Text without ASCII whitespace is therefore held whole until `finalize`."""
+        Text without ASCII whitespace is therefore held whole until `finalize` -- on this route only."""
 
     def __init__(self, opts: Optional[TextOpts], tenant_id: int, record_id: int, config_hash_value: Optional[int] = None):
         import codecs
@@ -313,14 +327,15 @@ class StreamingMinHashSession:
             raise UnsupportedError("only H = 128 is built (the reference's public entry point, text.rs:172-174)")
         self.tenant_id, self.record_id = tenant_id, record_id
         self._config_hash_value = config_hash_value
-        self._set = MinHashStreams(1, self.opts.k)
+        self._utf8_ok = self.opts.canonicalizer.is_default()
+        self._set = MinHashStreams(1, self.opts.k, utf8=self._utf8_ok, max_push_bytes=_SESSION_PUSH_BYTES)
         self._dec = codecs.getincrementaldecoder("utf-8")("strict")
         self._tail = ""
         self._bad = None                  # the first UTF-8 error: reported by finalize
         self._done = False
-        self._ascii = bool(self.opts.canonicalizer.case_fold)
-        self._kept = bytearray()          # ASCII route: the bytes so far, for the replay
-        self._slot = self._set.open(RAW_ASCII if self._ascii else PRETOKENIZED)
+        self.route = "ascii" if self.opts.canonicalizer.case_fold else "host"
+        self._kept = bytearray()          # ASCII and UTF-8 routes: the bytes so far, for the replay
+        self._slot = self._set.open(RAW_ASCII if self.route == "ascii" else PRETOKENIZED)
 
     def _dev_push(self, data: bytes, final: bool):
         out = (C.c_uint8 * MINHASH_BYTES)()
@@ -328,6 +343,17 @@ class StreamingMinHashSession:
         _lib.check(self._set._lib.ucfp_text_streams_push(self._set.handle, self._slot, data if data else None, len(data),
                                                          1 if final else 0, out if final else None, C.byref(st)))
         return bytes(out), int(st.value)
+
+    def _utf8_push(self, data: bytes, final: bool):
+        """A RAW_UTF8 push in pieces the set's scratch was sized for; stops at the first piece the device hands back."""
+        at = 0
+        while True:
+            piece = data[at:at + _SESSION_PUSH_BYTES]
+            at += len(piece)
+            last = at >= len(data)
+            rec, status = self._dev_push(piece, final and last)
+            if last or status == NEEDS_HOST:
+                return rec, status, final and last
 
     def _host_push(self, data: bytes, final: bool):
         if self._bad is None:
@@ -353,14 +379,25 @@ class StreamingMinHashSession:
         if self._done:
             raise ModalityError("streaming session already finalized")
         chunk = bytes(chunk)
-        if self._ascii:
+        if self.route == "ascii":
             if chunk.isascii():
                 self._kept += chunk
                 return self._dev_push(chunk, final)
-            self._ascii = False
+            self.route = "utf8" if self._utf8_ok else "host"
             self._set.close(self._slot)
-            self._slot = self._set.open(PRETOKENIZED)
+            self._slot = self._set.open(RAW_UTF8 if self._utf8_ok else PRETOKENIZED)
             chunk = bytes(self._kept) + chunk
+            self._kept = bytearray()
+        if self.route == "utf8":
+            self._kept += chunk
+            rec, status, ended = self._utf8_push(chunk, final)
+            if status != NEEDS_HOST:
+                return rec, status
+            self.route = "host"               # what the device does not cover: once, with everything seen so far
+            if not ended:
+                self._set.close(self._slot)
+            self._slot = self._set.open(PRETOKENIZED)
+            chunk = bytes(self._kept)
             self._kept = bytearray()
         return self._host_push(chunk, final)
 

@@ -115,15 +115,6 @@ __device__ uint32_t slow_code(uint64_t buf, const uint16_t* count, const uint16_
     return kInvalid;
 }
 
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(v, d, 64);
-        if (lane >= d) v += o;
-    }
-    return v;
-}
-
 // Builds one code from lens[0 .. n): first-level table, canonical arrays for the slow path.  Lane j owns symbols
 // [5 j, 5 j + 5).  Returns 0 complete, 1 incomplete, -1 over-subscribed; *used = symbols with a code.
 template <bool DIST>

@@ -6,7 +6,9 @@
 // submits PRETOKENIZED -- canonical tokens joined by single spaces -- so text_hash_kernel (text.hip) runs unchanged
 // over it.  Spec: DESIGN.md U1..U6; plain-Python restatement: tests/text_canon_ref.py; table: include/ucfp_text_utab.h.
 //
-// ONE WAVE PER DOCUMENT, 64 source bytes per step, no workgroup barrier:
+// ONE WAVE PER DOCUMENT, 64 source bytes per step, no workgroup barrier.  The step body -- A + B canon_place, C + D
+// canon_decide -- lives in text_canon_core.h, which the canon stage of text_stream_kernel (text_streams.hip) runs as well;
+// the kernel below is the document's byte reader, the two passes' store (DocStore) and the state around them:
 //   A  lane = byte.  A lead lane assembles its code point from the LDS byte stage (3 bytes of the previous step before,
 //      3 of the next behind) and validates it strictly (U2); a continuation lane checks that a lead claims it.
 //   B  the lead lane looks its code point up in the two-stage table (global memory, ~100 KiB, L2-resident) and a wave
@@ -35,21 +37,12 @@
 #include <mutex>
 #include <vector>
 
-#include "../../include/ucfp_text_utab.h"
-#include "common.h"
 #include "ctx.h"
+#include "text_canon_core.h"
 
 namespace ucfp {
 
 namespace {
-
-constexpr int kWavesPerBlock = 4;
-constexpr uint32_t kCpMask = 0x1FFFFu, kAlnum = 1u << 28, kVowel = 1u << 27, kFlagMask = 0xFu << 23 | kAlnum | kVowel;
-constexpr uint32_t kNone = kCpMask | 15u << 23;   // "no code point": class 15 is in no class set, the value no apostrophe
-// Canonical code points a step can add: a code point whose lead byte lies in the step has at most 3x its own bytes of
-// canonical UTF-8 (U1), and those code points span at most 64 + 3 bytes.
-constexpr int kStepCps = 3 * 67;
-constexpr int kXCap = 2 + 1 + kStepCps + 4;
 
 __device__ const uint16_t d_stage1[UCFP_TEXT_UTAB_STAGE1_N] = UCFP_TEXT_UTAB_STAGE1_INIT;
 __device__ const uint32_t d_stage2[UCFP_TEXT_UTAB_STAGE2_N] = UCFP_TEXT_UTAB_STAGE2_INIT;
@@ -58,43 +51,17 @@ const uint16_t h_stage1[UCFP_TEXT_UTAB_STAGE1_N] = UCFP_TEXT_UTAB_STAGE1_INIT;
 const uint32_t h_stage2[UCFP_TEXT_UTAB_STAGE2_N] = UCFP_TEXT_UTAB_STAGE2_INIT;
 const uint32_t h_pool[UCFP_TEXT_UTAB_POOL_N] = UCFP_TEXT_UTAB_POOL_INIT;
 
-struct CanonLds {
-    uint8_t bytes[3 + 64 + 3 + 2];   // [0, 3): the previous step's last bytes; [3, 67): this step; [67, 70): the next step's first
-    uint32_t x[kXCap];               // [0, 2): context; then the undecided code point of the last step, then this step's
-};
-
-__device__ __forceinline__ uint32_t in_set(uint32_t w, uint32_t set) { return (set >> ((w >> 23) & 15u)) & 1u; }
-
-// U4: no boundary before b, given the canonical code points around it (kNone where there is none)
-__device__ __forceinline__ bool no_boundary(uint32_t aa, uint32_t a, uint32_t b, uint32_t bb) {
-    constexpr uint32_t HEB = 1u << 2, AHL = 1u << 1 | HEB, NUM = 1u << 3, KAT = 1u << 4, ENL = 1u << 5;
-    constexpr uint32_t SQ = 1u << 9, DQ = 1u << 10, MIDL = 1u << 6 | 1u << 8 | SQ, MIDN = 1u << 7 | 1u << 8 | SQ;
-    uint32_t j = in_set(a, AHL) & in_set(b, AHL);
-    j |= in_set(a, AHL) & in_set(b, MIDL) & in_set(bb, AHL);
-    j |= in_set(aa, AHL) & in_set(a, MIDL) & in_set(b, AHL);
-    j |= in_set(a, HEB) & in_set(b, SQ);
-    j |= in_set(a, HEB) & in_set(b, DQ) & in_set(bb, HEB);
-    j |= in_set(aa, HEB) & in_set(a, DQ) & in_set(b, HEB);
-    j |= in_set(a, NUM) & in_set(b, NUM | AHL);
-    j |= in_set(a, AHL) & in_set(b, NUM);
-    j |= in_set(aa, NUM) & in_set(a, MIDN) & in_set(b, NUM);
-    j |= in_set(a, NUM) & in_set(b, MIDN) & in_set(bb, NUM);
-    j |= in_set(a, KAT) & in_set(b, KAT);
-    j |= in_set(a, AHL | NUM | KAT | ENL) & in_set(b, ENL);
-    j |= in_set(a, ENL) & in_set(b, AHL | NUM | KAT);
-    const uint32_t ca = a & kCpMask;
-    j |= (uint32_t)((ca == 0x27u || ca == 0x2019u) && (b & kVowel));   // the `regex` module's apostrophe tailoring
-    return j != 0;
-}
-
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t t = __shfl_up(v, d, 64);
-        if (lane >= d) v += t;
+// where a byte of the stream (' ' token)* goes: the output is that stream without its first byte, and the emit pass never
+// writes past the length the count pass found.  EMIT = false: the count pass stores nothing.
+template <bool EMIT>
+struct DocStore {
+    static constexpr bool kEmit = EMIT;
+    uint8_t* out;
+    uint64_t final_len;
+    __device__ __forceinline__ void operator()(uint64_t p, uint8_t v) const {
+        if (p >= 1 && p - 1 < final_len) out[p - 1] = v;
     }
-    return v;
-}
+};
 
 }  // namespace
 
@@ -120,11 +87,8 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void text_canon_kernel(
         if (final_len == 0) return;
     }
 
-    // wave-uniform state.  Positions count the stream (' ' token)*: the output is that stream without its first byte.
-    uint32_t pend = 0;            // 1: x[2] holds a code point whose boundary waits for its right neighbour
-    uint64_t out_pos = 0;         // stream bytes so far, the open segment included
-    uint64_t seg_start = 0;       // where the open segment began
-    bool seg_alnum = false;       // the open segment has an alphanumeric: it is a token
+    CanonSeg<uint64_t> S;
+    const DocStore<EMIT> store{out, final_len};
     bool bad = false;
     if (lane < 3) {
         L.x[lane] = kNone;
@@ -138,136 +102,15 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void text_canon_kernel(
         L.bytes[3 + lane] = (uint8_t)c;
         if (lane < 3) L.bytes[67 + lane] = base + 64 + lane < len ? text[base + 64 + lane] : (uint8_t)0;
         wave_lds_sync();
-
-        // ---- A: decode (U2) ----
-        bool lead = false, err = false;
-        uint32_t cp = c;
-        if (pos < len) {
-            if (c < 0x80u) {
-                lead = true;
-            } else if (c < 0xC0u) {   // continuation: the nearest byte before it that is none must be a lead that reaches it
-                const uint32_t b1 = L.bytes[2 + lane], b2 = L.bytes[1 + lane], b3 = L.bytes[lane];
-                const uint32_t j = (b1 & 0xC0u) != 0x80u ? 1u : (b2 & 0xC0u) != 0x80u ? 2u : (b3 & 0xC0u) != 0x80u ? 3u : 0u;
-                const uint32_t lb = j == 1 ? b1 : j == 2 ? b2 : b3;
-                const uint32_t reach = lb >= 0xF0u ? 3u : lb >= 0xE0u ? 2u : lb >= 0xC0u ? 1u : 0u;
-                err = j == 0 || reach < j;
-            } else {
-                lead = true;
-                const uint32_t need = c >= 0xF0u ? 3u : c >= 0xE0u ? 2u : 1u;
-                const uint32_t c1 = L.bytes[4 + lane], c2 = L.bytes[5 + lane], c3 = L.bytes[6 + lane];
-                err = c < 0xC2u || c > 0xF4u || pos + need >= len || (c1 & 0xC0u) != 0x80u;
-                if (need == 1) {
-                    cp = (c & 0x1Fu) << 6 | (c1 & 0x3Fu);
-                } else if (need == 2) {
-                    cp = (c & 0x0Fu) << 12 | (c1 & 0x3Fu) << 6 | (c2 & 0x3Fu);
-                    err |= (c2 & 0xC0u) != 0x80u || cp < 0x800u || cp - 0xD800u < 0x800u;
-                } else {
-                    cp = (c & 0x07u) << 18 | (c1 & 0x3Fu) << 12 | (c2 & 0x3Fu) << 6 | (c3 & 0x3Fu);
-                    err |= (c2 & 0xC0u) != 0x80u || (c3 & 0xC0u) != 0x80u || cp < 0x10000u || cp > 0x10FFFFu;
-                }
-            }
-        }
-        // ---- B: M(c) through the table (U1, U3) ----
-        uint32_t e = 0, nout = 0;
-        if (lead && !err) {
-            if (cp >= UCFP_TEXT_UTAB_LIMIT) {
-                err = true;
-            } else {
-                e = d_stage2[((uint32_t)d_stage1[cp >> UCFP_TEXT_UTAB_SHIFT] << UCFP_TEXT_UTAB_SHIFT) |
-                             (cp & ((1u << UCFP_TEXT_UTAB_SHIFT) - 1u))];
-                if (!(e >> 31)) err = true;
-                else nout = ((e >> 29) & 3u) == 2u ? (e >> 17) & 7u : 1u;
-            }
-        }
-        if (__ballot(err)) {
+        const CanonPlaced pl = canon_place(L, c, pos, len, lane, S.pend, d_stage1, d_stage2, d_pool);   // A, B
+        if (pl.err) {
             bad = true;
             break;
         }
-        const uint32_t incl = wave_incl_scan(nout, lane);
-        const uint32_t added = __shfl(incl, 63, 64);
-        if (nout) {
-            const uint32_t at = 2u + pend + incl - nout;   // < 2 + 1 + kStepCps
-            const uint32_t kind = (e >> 29) & 3u;
-            if (kind == 0) L.x[at] = cp | (e & kFlagMask);
-            else if (kind == 1) L.x[at] = (e & kCpMask) | (e & kFlagMask);
-            else
-                for (uint32_t t = 0; t < nout; t++) L.x[at + t] = d_pool[(e & kCpMask) + t];
-        }
-        wave_lds_sync();
-
-        // ---- C, D: boundaries, segments, tokens ----
-        const bool final = base + 64 >= len;
-        const uint32_t m = pend + added;
-        const uint32_t ndec = final ? m : (m ? m - 1u : 0u);
-        for (uint32_t j0 = 0; j0 < ndec; j0 += 64) {
-            const uint32_t j = j0 + lane;
-            const bool has = j < ndec;
-            const uint32_t i = 2u + j;
-            uint32_t w = kNone;
-            bool bnd = false;
-            if (has) {
-                w = L.x[i];
-                bnd = !no_boundary(L.x[i - 2], L.x[i - 1], w, j + 1 < m ? L.x[i + 1] : kNone);
-            }
-            const uint64_t bmask = __ballot(bnd), amask = __ballot(has && (w & kAlnum));
-            // the carried segment runs up to the first boundary of the chunk; closed there without an alphanumeric, it goes
-            const int fb = bmask ? __builtin_ctzll(bmask) : 64;
-            const bool carried_has = seg_alnum || (amask & (fb == 64 ? ~0ull : (1ull << fb) - 1ull)) != 0;
-            const bool drop0 = bmask != 0 && !carried_has;
-            // this lane's segment: [its last boundary at or before the lane, the next boundary)
-            const uint64_t le = bmask & (~0ull >> (63 - lane));
-            const int sb = le ? 63 - __builtin_clzll(le) : -1;
-            const uint64_t gt = lane == 63 ? 0ull : bmask & (~0ull << (lane + 1));
-            const int eb = gt ? __builtin_ctzll(gt) : 64;
-            const uint64_t range = (eb == 64 ? ~0ull : (1ull << eb) - 1ull) & (sb <= 0 ? ~0ull : ~((1ull << sb) - 1ull));
-            const bool seg_has = (amask & range) != 0 || (sb < 0 && seg_alnum);
-            const bool keep = has && (eb == 64 || seg_has);   // the open segment is kept provisionally
-            const uint32_t cpw = w & kCpMask;
-            const uint32_t nb = cpw < 0x80u ? 1u : cpw < 0x800u ? 2u : cpw < 0x10000u ? 3u : 4u;
-            const uint32_t contrib = keep ? nb + (bnd ? 1u : 0u) : 0u;
-            const uint32_t cincl = wave_incl_scan(contrib, lane);
-            const uint32_t excl = cincl - contrib;
-            const uint64_t base_pos = drop0 ? seg_start : out_pos;
-            if (EMIT) {
-                // A rewind: other lanes are about to store where the provisional bytes went.  One wave's stores are issued in
-                // program order, so a fence at WAVEFRONT scope is all the ordering the two generations of stores need.
-                if (drop0) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                if (keep) {
-                    uint64_t p = base_pos + excl;   // stream position; the output byte is p - 1
-                    uint32_t bytes, cnt = nb;
-                    if (nb == 1) bytes = cpw;
-                    else if (nb == 2) bytes = (0xC0u | cpw >> 6) | (0x80u | (cpw & 0x3Fu)) << 8;
-                    else if (nb == 3) bytes = (0xE0u | cpw >> 12) | (0x80u | (cpw >> 6 & 0x3Fu)) << 8 | (0x80u | (cpw & 0x3Fu)) << 16;
-                    else
-                        bytes = (0xF0u | cpw >> 18) | (0x80u | (cpw >> 12 & 0x3Fu)) << 8 | (0x80u | (cpw >> 6 & 0x3Fu)) << 16 |
-                                (0x80u | (cpw & 0x3Fu)) << 24;
-                    if (bnd) {
-                        if (p >= 1 && p - 1 < final_len) out[p - 1] = ' ';
-                        p++;
-                    }
-                    for (uint32_t t = 0; t < cnt; t++, p++)
-                        if (p >= 1 && p - 1 < final_len) out[p - 1] = (uint8_t)(bytes >> (8 * t));
-                }
-            }
-            if (bmask) {
-                const int hb = 63 - __builtin_clzll(bmask);
-                seg_start = base_pos + __shfl(excl, hb, 64);
-                seg_alnum = (amask >> hb) != 0;
-            } else {
-                seg_alnum = seg_alnum || amask != 0;
-            }
-            out_pos = base_pos + __shfl(cincl, 63, 64);
-        }
-        // context for the next step: the last two decided code points and the undecided one
-        wave_lds_sync();
-        const uint32_t keep3 = lane < 3 ? L.x[ndec + lane] : 0u;
-        wave_lds_sync();
-        if (lane < 3) L.x[lane] = keep3;
-        if (lane >= 61) L.bytes[lane - 61] = (uint8_t)c;
-        pend = m - ndec;
+        canon_decide(L, S, c, pl.added, base + 64 >= len, lane, store);                                 // C, D
     }
     if (EMIT) return;
-    if (!seg_alnum) out_pos = seg_start;   // the last segment closes at the document's end
+    const uint64_t out_pos = S.seg_alnum ? S.out_pos : S.seg_start;   // the last segment closes at the document's end
     if (lane == 0) {
         tok_off[doc + 1] = bad || out_pos == 0 ? 0ull : out_pos - 1;
         status[doc] = bad ? UCFP_TEXT_NEEDS_HOST : 0;

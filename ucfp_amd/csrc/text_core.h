@@ -1,5 +1,8 @@
-// text_core.h -- what the text hashing kernels share (text.hip: whole documents; text_streams.hip: streams): the LDS
-// batch of one wave and its limits, the ASCII word rule, XXH3 read from LDS, the MinHash second hash.
+// text_core.h -- the hash stage of the text kernels, once: text_hash_kernel (text.hip, whole documents) and
+// text_stream_kernel (text_streams.hip, streams) are this file's bodies around their own byte readers.  Here: the launch
+// shape, the LDS batch of one wave and its limits, the ASCII word rule, XXH3 read from LDS, the MinHash second hash, the
+// wave state (TextWave), the 64-byte tokeniser step (text_step), the flush of a batch (text_flush) and the record and
+// status of a finished document (text_emit).  The canon stage in front of it is text_canon_core.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -12,7 +15,7 @@ namespace ucfp {
 
 namespace {
 
-constexpr int kWavesPerBlock = 4;
+constexpr int kWavesPerBlock = 4;    // one wave per document / stream entry, in every text kernel
 constexpr int kTokCap = 256;        // tokens per LDS batch
 constexpr int kCanonCap = 1536;     // canonical bytes per LDS batch
 constexpr int kStepTok = 33;        // a 64-byte step can open at most 32 (+1 carried) tokens
@@ -83,6 +86,169 @@ __device__ __forceinline__ uint32_t popc_below(uint64_t m, int lane) {  // bits 
 }
 
 __device__ __forceinline__ void wave_sync() { wave_lds_sync(); }
+
+// what one wave carries through a document: between two steps offline, from one push to the next in a stream
+struct TextWave {
+    uint64_t m0 = ~0ull, m1 = ~0ull;  // MinHash running minima: slots lane, lane + 64
+    uint32_t ones = 0;                // SimHash: count of bit `lane`
+    uint32_t total_tok = 0;           // complete tokens consumed by flushes (net of carried ones)
+    bool any_shingle = false;
+    // wave-uniform tokenizer state of the current LDS batch
+    uint32_t ntok = 0;        // tokens opened in this batch (the last one may be unfinished)
+    uint32_t cbase = 0;       // word bytes written in this batch
+    bool carry = false;       // the byte just before the current step was a word byte
+    uint32_t prev_last = 0;   // that byte
+};
+
+// no room for another step: it opens at most 32 tokens and writes at most 64 + 32 bytes
+__device__ __forceinline__ bool text_batch_full(const TextWave& W) {
+    return W.ntok + kStepTok > (uint32_t)kTokCap || W.cbase + W.ntok + kStepRoom > (uint32_t)kCanonCap;
+}
+
+// consume the batch: hash complete items, fold them in, carry the tail to the front
+template <bool MODE_SIM>
+__device__ __forceinline__ void text_flush(WaveLds& L, TextWave& W, uint32_t k, int lane, bool final) {
+    wave_sync();
+    const uint32_t ncomplete = W.ntok - (W.carry && !final ? 1u : 0u);
+    uint32_t nitems, keep_from;
+    if (MODE_SIM) {
+        nitems = ncomplete;
+        keep_from = ncomplete;
+    } else if (ncomplete >= k) {
+        nitems = ncomplete - k + 1;
+        keep_from = ncomplete - (k - 1);
+    } else if (final && !W.any_shingle && ncomplete > 0) {
+        nitems = 1;  // fewer than k tokens in the whole document: one shingle of all of them
+        keep_from = ncomplete;
+    } else {
+        nitems = 0;
+        keep_from = 0;
+    }
+    for (uint32_t s0 = 0; s0 < nitems; s0 += 64) {
+        const uint32_t s = s0 + lane;
+        if (s < nitems) {
+            uint32_t e;
+            if (MODE_SIM) e = s;
+            else e = ncomplete >= k ? s + k - 1 : ncomplete - 1;
+            const uint32_t a = L.cstart[s], b = L.cend[e];
+            const uint64_t h = xxh3_lds(L.canon + a, (size_t)(b - a));
+            L.h1[s] = h;
+            if (!MODE_SIM) L.h2[s] = mix_h2(h);
+        }
+    }
+    wave_sync();
+    if (MODE_SIM) {
+        for (uint32_t s = 0; s < nitems; s++) W.ones += (uint32_t)((L.h1[s] >> lane) & 1ull);
+    } else {
+#pragma unroll 4
+        for (uint32_t s = 0; s < nitems; s++) {
+            const uint64_t h = L.h1[s], g = L.h2[s];
+            const uint64_t v0 = h + (uint64_t)lane * g;
+            const uint64_t v1 = v0 + (g << 6);
+            W.m0 = v0 < W.m0 ? v0 : W.m0;
+            W.m1 = v1 < W.m1 ? v1 : W.m1;
+        }
+    }
+    if (nitems) W.any_shingle = true;
+    W.total_tok += keep_from;
+    if (final) return;
+    // carry tokens [keep_from, ntok) to the front
+    if (keep_from == 0) return;  // nothing consumed (fewer than k complete tokens): the caller re-checks room
+    const uint32_t src0 = keep_from < W.ntok ? L.cstart[keep_from] : W.cbase + W.ntok - 1 + (W.carry ? 1u : 0u);
+    const uint32_t used = W.cbase + (W.ntok ? W.ntok - 1 : 0);   // bytes of canon in use
+    const uint32_t nkeep = W.ntok - keep_from;
+    wave_sync();
+    uint16_t ks = 0, ke = 0;
+    if ((uint32_t)lane < nkeep) {   // nkeep <= k <= 64
+        ks = (uint16_t)(L.cstart[keep_from + lane] - src0);
+        ke = (uint16_t)(L.cend[keep_from + lane] - src0);
+    }
+    for (uint32_t o = 0; src0 + o < used; o += 64) {
+        const uint32_t i = src0 + o + lane;
+        const uint8_t v = i < used ? L.canon[i] : 0;
+        wave_sync();
+        if (i < used) L.canon[o + lane] = v;
+        wave_sync();
+    }
+    if ((uint32_t)lane < nkeep) {
+        L.cstart[lane] = ks;
+        L.cend[lane] = ke;
+    }
+    // word bytes kept = total kept bytes minus the separators between kept tokens
+    const uint32_t kept_bytes = used > src0 ? used - src0 : 0;
+    W.ntok = nkeep;
+    W.cbase = kept_bytes - (nkeep ? nkeep - 1 : 0);
+    wave_sync();
+}
+
+// One 64-byte step over L.stage[64 sub ..]: lane = byte at `pos`, bytes at or past `end` are not processed.  Writes the
+// word bytes and token bounds into the batch (the caller made room) and returns the step's word mask.  carry and
+// prev_last come out as after a FULL step: a caller whose range can end inside a step (a stream's push) corrects them.
+__device__ __forceinline__ uint64_t text_step(WaveLds& L, TextWave& W, int sub, size_t pos, size_t end, bool pretok, int lane) {
+    const uint32_t c = L.stage[64 * sub + lane];
+    const uint32_t q = L.stage[64 * sub + lane + 1];
+    uint32_t p = __shfl_up(c, 1, 64);
+    if (lane == 0) p = W.prev_last;
+    const bool w = pos < end && inword(p, c, q, pretok);
+    const uint64_t inw = __ballot(w);
+    const uint64_t prev = (inw << 1) | (W.carry ? 1ull : 0ull);
+    const uint64_t starts = inw & ~prev;
+    const uint64_t endmark = ~inw & prev;   // first non-word byte after a token
+    const uint32_t nin_before = popc_below(inw, lane);
+    const uint32_t nst_before = popc_below(starts, lane);
+    const bool is_start = (starts >> lane) & 1ull;
+    if (w) {
+        const uint32_t tok = W.ntok + nst_before + (is_start ? 1u : 0u) - 1u;
+        const uint32_t cpos = W.cbase + nin_before + tok;
+        uint32_t ch = c;
+        if (!pretok && ch - 'A' <= 25u) ch += 32;
+        L.canon[cpos] = (uint8_t)ch;
+        if (is_start) {
+            L.cstart[tok] = (uint16_t)cpos;
+            if (cpos > 0) L.canon[cpos - 1] = ' ';
+        }
+    }
+    if ((endmark >> lane) & 1ull) {
+        const uint32_t tok = W.ntok + nst_before - 1u;   // starts strictly before this byte
+        L.cend[tok] = (uint16_t)(W.cbase + nin_before + tok);
+    }
+    W.ntok += (uint32_t)__popcll(starts);
+    W.cbase += (uint32_t)__popcll(inw);
+    W.carry = (inw >> 63) & 1ull;
+    W.prev_last = __shfl(c, 63, 64);
+    return inw;
+}
+
+// The end of a document: its status, and its record at `rec` (MinHash: 1032 bytes; SimHash: 8), zero unless the status is 0.
+template <bool MODE_SIM>
+__device__ __forceinline__ int32_t text_emit(uint8_t* rec, const TextWave& W, bool nonascii, bool too_long, int lane) {
+    int32_t stv = 0;
+    if (nonascii) stv = 1;                    // non-ASCII in raw mode: host must pre-tokenise
+    else if (too_long) stv = -2;              // UCFP_E_UNSUPPORTED: a token / k-token run exceeds the LDS batch
+    else if (W.total_tok == 0 || (!MODE_SIM && !W.any_shingle)) stv = -1;   // UCFP_E_MODALITY: no tokens
+    if (MODE_SIM) {
+        const uint64_t bits = __ballot(2u * W.ones > W.total_tok);
+        if (lane == 0) {
+            const uint64_t v = stv == 0 ? bits : 0ull;
+            for (int b = 0; b < 8; b++) rec[b] = (uint8_t)(v >> (8 * b));
+        }
+    } else {
+        const uint64_t a = stv == 0 ? W.m0 : 0ull, b = stv == 0 ? W.m1 : 0ull;
+        // 1032-byte records are only 8-byte aligned when the base is: write dwords
+        uint32_t* o0 = reinterpret_cast<uint32_t*>(rec + 8 + 8 * lane);
+        uint32_t* o1 = reinterpret_cast<uint32_t*>(rec + 8 + 8 * (lane + 64));
+        o0[0] = (uint32_t)a;
+        o0[1] = (uint32_t)(a >> 32);
+        o1[0] = (uint32_t)b;
+        o1[1] = (uint32_t)(b >> 32);
+        if (lane == 0) {
+            uint32_t* o32 = reinterpret_cast<uint32_t*>(rec);
+            o32[0] = stv == 0 ? 1u : 0u;  // schema: u16 = 1, pad
+            o32[1] = 0;
+        }
+    }
+    return stv;
+}
 }  // namespace
 
 }  // namespace ucfp

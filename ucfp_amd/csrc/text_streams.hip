@@ -14,8 +14,8 @@
 //          byte is inside a word depends on the byte after it, and a stream must not guess that byte.  A non-final push
 //          processes all but the last byte, which becomes the new `pending`; a final push processes every byte and the
 //          byte past the end reads as 0, as offline
-//   steps  tokenise / write canonical / room check / flush: the offline kernel's, unchanged (own copy of its two
-//          lambdas, so that text_hash_kernel's text and registers stay as they are)
+//   steps  tokenise / write canonical / room check / flush: the offline kernel's, the same code (text_step and text_flush
+//          of text_core.h); only a push's last step, which may be partial, corrects `carry` and `prev_last` afterwards
 //   end    non-final: flush(false), then the state goes back; final: close an open token, flush(true), emit the record
 //
 // UTF-8 STREAMS (sets made with UCFP_TEXT_STREAMS_UTF8; DESIGN.md T7 "UTF-8 streams", restated in plain Python in
@@ -29,8 +29,8 @@
 //   prov   an open segment that has an alphanumeric is a token and its bytes go out; one that has none is written, then
 //          taken back into the state (at most UCFP_TEXT_STREAM_OPEN_SEGMENT_BYTES, more is NEEDS_HOST) and restored to
 //          the front of the next push's slice
-// The step body is an OWN COPY of text_canon_kernel's (as the hash lambdas are of text_hash_kernel's): the offline
-// kernels' text and registers stay as they are.  text_stream_kernel<false> is what sets without the flag launch.
+// The step body is text_canon_kernel's, the same code (canon_place and canon_decide of text_canon_core.h), as the hash
+// stage's is text_hash_kernel's.  text_stream_kernel<false> is what sets without the flag launch.
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
@@ -39,8 +39,8 @@
 #include <new>
 #include <vector>
 
-#include "../../include/ucfp_text_utab.h"
 #include "ctx.h"
+#include "text_canon_core.h"
 #include "text_core.h"
 
 #define fail ucfp::capi_fail
@@ -111,63 +111,33 @@ struct CanonArgs {
     const uint32_t* pool;
 };
 
-constexpr uint32_t kCpMask = 0x1FFFFu, kAlnum = 1u << 28, kVowel = 1u << 27, kFlagMask = 0xFu << 23 | kAlnum | kVowel;
-constexpr uint32_t kNone = kCpMask | 15u << 23;   // "no code point": class 15 is in no class set, the value no apostrophe
-constexpr int kStepCps = 3 * 67;                  // canonical code points a 64-byte step can add (text_canon.hip)
-constexpr int kXCap = 2 + 1 + kStepCps + 4;
-
-struct CanonLds {
-    uint8_t bytes[3 + 64 + 3 + 2];   // [0, 3): the previous step's last bytes; [3, 67): this step; [67, 70): the next step's first
-    uint32_t x[kXCap];               // [0, 2): context; then the undecided code point of the last step, then this step's
-};
 static_assert(sizeof(CanonLds) <= sizeof(WaveLds::h1) && offsetof(WaveLds, h1) % 8 == 0, "the canon stage borrows h1");
 
-__device__ __forceinline__ uint32_t in_set(uint32_t w, uint32_t set) { return (set >> ((w >> 23) & 15u)) & 1u; }
-
-// U4: no boundary before b, given the canonical code points around it (kNone where there is none)
-__device__ __forceinline__ bool no_boundary(uint32_t aa, uint32_t a, uint32_t b, uint32_t bb) {
-    constexpr uint32_t HEB = 1u << 2, AHL = 1u << 1 | HEB, NUM = 1u << 3, KAT = 1u << 4, ENL = 1u << 5;
-    constexpr uint32_t SQ = 1u << 9, DQ = 1u << 10, MIDL = 1u << 6 | 1u << 8 | SQ, MIDN = 1u << 7 | 1u << 8 | SQ;
-    uint32_t j = in_set(a, AHL) & in_set(b, AHL);
-    j |= in_set(a, AHL) & in_set(b, MIDL) & in_set(bb, AHL);
-    j |= in_set(aa, AHL) & in_set(a, MIDL) & in_set(b, AHL);
-    j |= in_set(a, HEB) & in_set(b, SQ);
-    j |= in_set(a, HEB) & in_set(b, DQ) & in_set(bb, HEB);
-    j |= in_set(aa, HEB) & in_set(a, DQ) & in_set(b, HEB);
-    j |= in_set(a, NUM) & in_set(b, NUM | AHL);
-    j |= in_set(a, AHL) & in_set(b, NUM);
-    j |= in_set(aa, NUM) & in_set(a, MIDN) & in_set(b, NUM);
-    j |= in_set(a, NUM) & in_set(b, MIDN) & in_set(bb, NUM);
-    j |= in_set(a, KAT) & in_set(b, KAT);
-    j |= in_set(a, AHL | NUM | KAT | ENL) & in_set(b, ENL);
-    j |= in_set(a, ENL) & in_set(b, AHL | NUM | KAT);
-    const uint32_t ca = a & kCpMask;
-    j |= (uint32_t)((ca == 0x27u || ca == 0x2019u) && (b & kVowel));   // the `regex` module's apostrophe tailoring
-    return j != 0;
-}
-
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t t = __shfl_up(v, d, 64);
-        if (lane >= d) v += t;
+// where a byte of the piece goes: position p of the slice
+struct SliceStore {
+    static constexpr bool kEmit = true;
+    uint8_t* out;
+    uint32_t cap;
+    __device__ __forceinline__ void operator()(uint32_t p, uint8_t v) const {
+        if (p < cap) out[p] = v;
     }
-    return v;
-}
+};
 
 // One push of one RAW_UTF8 stream through the canon stage: V = held || chunk, of which a non-final push processes all
 // but an incomplete sequence at the end.  Writes the piece -- the part of the stream (' ' token)* this push settles --
 // to out[0, cap) and returns its length; *bad_out: the stream is handed back (now or by an earlier push).  Steps A..D
-// are text_canon_kernel<true>'s; positions are relative to the slice, which begins with the restored provisional bytes.
+// are text_canon_kernel<true>'s (text_canon_core.h); positions are relative to the slice, which begins with the restored
+// provisional bytes.
 __device__ __forceinline__ uint32_t canon_stream_push(CanonLds& L, const CanonArgs& ca, CanonStreamState& C,
                                                       const uint8_t* __restrict__ chunk, size_t clen, bool fin, bool fresh,
                                                       uint8_t* out, uint32_t cap, int lane, bool* bad_out) {
-    uint32_t pend = 0, nheld = 0, held = 0, nprov = 0;
-    bool seg_alnum = false, bad = false;
+    CanonSeg<uint32_t> S;
+    uint32_t nheld = 0, held = 0, nprov = 0;
+    bool bad = false;
     uint32_t xin = kNone;
     if (!fresh) {
-        pend = uni(C.pend) & 1u;
-        seg_alnum = uni(C.seg_alnum) != 0;
+        S.pend = uni(C.pend) & 1u;
+        S.seg_alnum = uni(C.seg_alnum) != 0;
         bad = uni(C.bad) != 0;
         nheld = uni(C.nheld);
         held = uni(C.held);
@@ -207,8 +177,9 @@ __device__ __forceinline__ uint32_t canon_stream_push(CanonLds& L, const CanonAr
     uint32_t new_held = 0;
     for (uint32_t t = 0; t < nh; t++) new_held |= V(len + t) << (8u * t);
 
-    uint32_t out_pos = nprov;     // slice bytes so far, the open segment included
-    uint32_t seg_start = 0;       // where the open segment began (a provisional one: at the slice's front)
+    S.out_pos = nprov;            // slice bytes so far, the open segment included
+    S.seg_start = 0;              // where the open segment began (a provisional one: at the slice's front)
+    const SliceStore store{out, cap};
 
     for (size_t base = 0; base < len || (fin && base == 0); base += 64) {   // a final push decides `pend` even without bytes
         const size_t pos = base + lane;
@@ -217,156 +188,38 @@ __device__ __forceinline__ uint32_t canon_stream_push(CanonLds& L, const CanonAr
         L.bytes[3 + lane] = (uint8_t)c;
         if (lane < 3) L.bytes[67 + lane] = base + 64 + lane < len ? (uint8_t)V(base + 64 + lane) : (uint8_t)0;
         wave_lds_sync();
-
-        // ---- A: decode (U2) ----
-        bool lead = false, err = false;
-        uint32_t cp = c;
-        if (pos < len) {
-            if (c < 0x80u) {
-                lead = true;
-            } else if (c < 0xC0u) {   // continuation: the nearest byte before it that is none must be a lead that reaches it
-                const uint32_t b1 = L.bytes[2 + lane], b2 = L.bytes[1 + lane], b3 = L.bytes[lane];
-                const uint32_t j = (b1 & 0xC0u) != 0x80u ? 1u : (b2 & 0xC0u) != 0x80u ? 2u : (b3 & 0xC0u) != 0x80u ? 3u : 0u;
-                const uint32_t lb = j == 1 ? b1 : j == 2 ? b2 : b3;
-                const uint32_t reach = lb >= 0xF0u ? 3u : lb >= 0xE0u ? 2u : lb >= 0xC0u ? 1u : 0u;
-                err = j == 0 || reach < j;
-            } else {
-                lead = true;
-                const uint32_t need = c >= 0xF0u ? 3u : c >= 0xE0u ? 2u : 1u;
-                const uint32_t c1 = L.bytes[4 + lane], c2 = L.bytes[5 + lane], c3 = L.bytes[6 + lane];
-                err = c < 0xC2u || c > 0xF4u || pos + need >= len || (c1 & 0xC0u) != 0x80u;   // cut by the end: a final push only
-                if (need == 1) {
-                    cp = (c & 0x1Fu) << 6 | (c1 & 0x3Fu);
-                } else if (need == 2) {
-                    cp = (c & 0x0Fu) << 12 | (c1 & 0x3Fu) << 6 | (c2 & 0x3Fu);
-                    err |= (c2 & 0xC0u) != 0x80u || cp < 0x800u || cp - 0xD800u < 0x800u;
-                } else {
-                    cp = (c & 0x07u) << 18 | (c1 & 0x3Fu) << 12 | (c2 & 0x3Fu) << 6 | (c3 & 0x3Fu);
-                    err |= (c2 & 0xC0u) != 0x80u || (c3 & 0xC0u) != 0x80u || cp < 0x10000u || cp > 0x10FFFFu;
-                }
-            }
-        }
-        // ---- B: M(c) through the table (U1, U3) ----
-        uint32_t e = 0, nout = 0;
-        if (lead && !err) {
-            if (cp >= UCFP_TEXT_UTAB_LIMIT) {
-                err = true;
-            } else {
-                e = ca.stage2[((uint32_t)ca.stage1[cp >> UCFP_TEXT_UTAB_SHIFT] << UCFP_TEXT_UTAB_SHIFT) |
-                              (cp & ((1u << UCFP_TEXT_UTAB_SHIFT) - 1u))];
-                if (!(e >> 31)) err = true;
-                else nout = ((e >> 29) & 3u) == 2u ? (e >> 17) & 7u : 1u;
-            }
-        }
-        if (__ballot(err)) {
+        const CanonPlaced pl = canon_place(L, c, pos, len, lane, S.pend, ca.stage1, ca.stage2, ca.pool);   // A, B
+        if (pl.err) {
             bad = true;
             break;
         }
-        const uint32_t incl = wave_incl_scan(nout, lane);
-        const uint32_t added = __shfl(incl, 63, 64);
-        if (nout) {
-            const uint32_t at = 2u + pend + incl - nout;   // < 2 + 1 + kStepCps
-            const uint32_t kind = (e >> 29) & 3u;
-            if (kind == 0) L.x[at] = cp | (e & kFlagMask);
-            else if (kind == 1) L.x[at] = (e & kCpMask) | (e & kFlagMask);
-            else
-                for (uint32_t t = 0; t < nout; t++) L.x[at + t] = ca.pool[(e & kCpMask) + t];
-        }
-        wave_lds_sync();
-
-        // ---- C, D: boundaries, segments, tokens ----
-        const bool final = fin && base + 64 >= len;
-        const uint32_t m = pend + added;
-        const uint32_t ndec = final ? m : (m ? m - 1u : 0u);
-        for (uint32_t j0 = 0; j0 < ndec; j0 += 64) {
-            const uint32_t j = j0 + lane;
-            const bool has = j < ndec;
-            const uint32_t i = 2u + j;
-            uint32_t w = kNone;
-            bool bnd = false;
-            if (has) {
-                w = L.x[i];
-                bnd = !no_boundary(L.x[i - 2], L.x[i - 1], w, j + 1 < m ? L.x[i + 1] : kNone);
-            }
-            const uint64_t bmask = __ballot(bnd), amask = __ballot(has && (w & kAlnum));
-            // the carried segment runs up to the first boundary of the chunk; closed there without an alphanumeric, it goes
-            const int fb = bmask ? __builtin_ctzll(bmask) : 64;
-            const bool carried_has = seg_alnum || (amask & (fb == 64 ? ~0ull : (1ull << fb) - 1ull)) != 0;
-            const bool drop0 = bmask != 0 && !carried_has;
-            // this lane's segment: [its last boundary at or before the lane, the next boundary)
-            const uint64_t le = bmask & (~0ull >> (63 - lane));
-            const int sb = le ? 63 - __builtin_clzll(le) : -1;
-            const uint64_t gt = lane == 63 ? 0ull : bmask & (~0ull << (lane + 1));
-            const int eb = gt ? __builtin_ctzll(gt) : 64;
-            const uint64_t range = (eb == 64 ? ~0ull : (1ull << eb) - 1ull) & (sb <= 0 ? ~0ull : ~((1ull << sb) - 1ull));
-            const bool seg_has = (amask & range) != 0 || (sb < 0 && seg_alnum);
-            const bool keep = has && (eb == 64 || seg_has);   // the open segment is kept provisionally
-            const uint32_t cpw = w & kCpMask;
-            const uint32_t nb = cpw < 0x80u ? 1u : cpw < 0x800u ? 2u : cpw < 0x10000u ? 3u : 4u;
-            const uint32_t contrib = keep ? nb + (bnd ? 1u : 0u) : 0u;
-            const uint32_t cincl = wave_incl_scan(contrib, lane);
-            const uint32_t excl = cincl - contrib;
-            const uint32_t base_pos = drop0 ? seg_start : out_pos;
-            // a rewind: other lanes are about to store where the provisional bytes went (text_canon_kernel's fence)
-            if (drop0) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            if (keep) {
-                uint32_t p = base_pos + excl;
-                uint32_t bytes;
-                if (nb == 1) bytes = cpw;
-                else if (nb == 2) bytes = (0xC0u | cpw >> 6) | (0x80u | (cpw & 0x3Fu)) << 8;
-                else if (nb == 3) bytes = (0xE0u | cpw >> 12) | (0x80u | (cpw >> 6 & 0x3Fu)) << 8 | (0x80u | (cpw & 0x3Fu)) << 16;
-                else
-                    bytes = (0xF0u | cpw >> 18) | (0x80u | (cpw >> 12 & 0x3Fu)) << 8 | (0x80u | (cpw >> 6 & 0x3Fu)) << 16 |
-                            (0x80u | (cpw & 0x3Fu)) << 24;
-                if (bnd) {
-                    if (p < cap) out[p] = ' ';
-                    p++;
-                }
-                for (uint32_t t = 0; t < nb; t++, p++)
-                    if (p < cap) out[p] = (uint8_t)(bytes >> (8 * t));
-            }
-            if (bmask) {
-                const int hb = 63 - __builtin_clzll(bmask);
-                seg_start = base_pos + __shfl(excl, hb, 64);
-                seg_alnum = (amask >> hb) != 0;
-            } else {
-                seg_alnum = seg_alnum || amask != 0;
-            }
-            out_pos = base_pos + __shfl(cincl, 63, 64);
-        }
-        // context for the next step: the last two decided code points and the undecided one
-        wave_lds_sync();
-        const uint32_t keep3 = lane < 3 ? L.x[ndec + lane] : 0u;
-        wave_lds_sync();
-        if (lane < 3) L.x[lane] = keep3;
-        if (lane >= 61) L.bytes[lane - 61] = (uint8_t)c;
-        pend = m - ndec;
+        canon_decide(L, S, c, pl.added, fin && base + 64 >= len, lane, store);                             // C, D
     }
-    if (out_pos > cap) bad = true;   // cannot happen (the slice holds 4 x the bytes): refuse rather than hash a cut piece
+    if (S.out_pos > cap) bad = true;   // cannot happen (the slice holds 4 x the bytes): refuse rather than hash a cut piece
 
     // ---- what this push settles, and what goes back into the state ----
     uint32_t plen = 0, np = 0;
     if (!bad) {
         if (fin) {
-            plen = seg_alnum ? out_pos : seg_start;   // the last segment closes at the stream's end
-        } else if (seg_alnum) {
-            plen = out_pos;                           // an open token: its bytes so far go out, the next piece continues it
+            plen = S.seg_alnum ? S.out_pos : S.seg_start;   // the last segment closes at the stream's end
+        } else if (S.seg_alnum) {
+            plen = S.out_pos;                           // an open token: its bytes so far go out, the next piece continues it
         } else {
-            plen = seg_start;
-            np = out_pos - seg_start;
+            plen = S.seg_start;
+            np = S.out_pos - S.seg_start;
             if (np > kProvCap) bad = true, plen = 0, np = 0;   // the documented open-segment condition
         }
     }
     if (!fin) {
         if (np) {
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // the bytes were stored by other lanes of this wave
-            for (uint32_t i = lane; i < np; i += 64) C.prov[i] = out[seg_start + i];
+            for (uint32_t i = lane; i < np; i += 64) C.prov[i] = out[S.seg_start + i];
         }
         wave_lds_sync();
         if (lane < 3) C.x[lane] = L.x[lane];
         if (lane == 0) {
-            C.pend = pend;
-            C.seg_alnum = seg_alnum ? 1u : 0u;
+            C.pend = S.pend;
+            C.seg_alnum = S.seg_alnum ? 1u : 0u;
             C.bad = bad ? 1u : 0u;
             C.nheld = bad ? 0u : nh;
             C.held = new_held;
@@ -393,12 +246,8 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void text_stream_kernel(
     const bool fin = eflags & kEntFinal, fresh = eflags & kEntFresh;
     TextStreamState& S = states[uni(ent.slot)];
 
-    uint64_t m0 = ~0ull, m1 = ~0ull;
-    uint32_t total_tok = 0;
-    bool any_shingle = false, nonascii = false, too_long = false;
-    uint32_t ntok = 0, cbase = 0;
-    bool carry = false;
-    uint32_t prev_last = 0;
+    TextWave W;
+    bool nonascii = false, too_long = false;
     uint32_t pend = 0;
     uint32_t mode = eflags >> kEntModeShift;
     uint64_t total_bytes = 0;
@@ -406,28 +255,28 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void text_stream_kernel(
 
     // ---- load ----
     if (!fresh) {
-        m0 = S.m0[lane];
-        m1 = S.m1[lane];
+        W.m0 = S.m0[lane];
+        W.m1 = S.m1[lane];
         total_bytes = S.total_bytes;
-        ntok = uni(S.ntok);
-        cbase = uni(S.cbase);
-        carry = uni(S.carry) != 0;
-        prev_last = uni(S.prev_last);
-        total_tok = uni(S.total_tok);
+        W.ntok = uni(S.ntok);
+        W.cbase = uni(S.cbase);
+        W.carry = uni(S.carry) != 0;
+        W.prev_last = uni(S.prev_last);
+        W.total_tok = uni(S.total_tok);
         const uint32_t f = uni(S.flags);
-        any_shingle = f & kAnyShingle;
+        W.any_shingle = f & kAnyShingle;
         nonascii = f & kNonAscii;
         too_long = f & kTooLong;
         dead = nonascii || too_long;
         pend = uni(S.pending);
         mode = uni(S.mode);
-        if (ntok > 64u) ntok = 64u;                                   // a stored state never has more: keeps every index in range
-        if (cbase + ntok > (uint32_t)kCanonCap) cbase = 0, ntok = 0;
-        const uint32_t used = cbase + (ntok ? ntok - 1 : 0);
+        if (W.ntok > 64u) W.ntok = 64u;                               // a stored state never has more: keeps every index in range
+        if (W.cbase + W.ntok > (uint32_t)kCanonCap) W.cbase = 0, W.ntok = 0;
+        const uint32_t used = W.cbase + (W.ntok ? W.ntok - 1 : 0);
         const uint32_t* src = reinterpret_cast<const uint32_t*>(S.canon);
         uint32_t* dst = reinterpret_cast<uint32_t*>(L.canon);
         for (uint32_t i = lane; 4 * i < used; i += 64) dst[i] = src[i];
-        if ((uint32_t)lane < ntok) {
+        if ((uint32_t)lane < W.ntok) {
             L.cstart[lane] = S.cstart[lane];
             L.cend[lane] = S.cend[lane];
         }
@@ -450,72 +299,6 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void text_stream_kernel(
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
         wave_sync();
     }
-
-    // consume the batch: hash complete shingles, fold them in, carry the tail to the front (text_hash_kernel's flush)
-    auto flush = [&](bool final) {
-        wave_sync();
-        const uint32_t ncomplete = ntok - (carry && !final ? 1u : 0u);
-        uint32_t nitems, keep_from;
-        if (ncomplete >= k) {
-            nitems = ncomplete - k + 1;
-            keep_from = ncomplete - (k - 1);
-        } else if (final && !any_shingle && ncomplete > 0) {
-            nitems = 1;  // fewer than k tokens in the whole stream: one shingle of all of them
-            keep_from = ncomplete;
-        } else {
-            nitems = 0;
-            keep_from = 0;
-        }
-        for (uint32_t s0 = 0; s0 < nitems; s0 += 64) {
-            const uint32_t s = s0 + lane;
-            if (s < nitems) {
-                const uint32_t e = ncomplete >= k ? s + k - 1 : ncomplete - 1;
-                const uint32_t a = L.cstart[s], b = L.cend[e];
-                const uint64_t h = xxh3_lds(L.canon + a, (size_t)(b - a));
-                L.h1[s] = h;
-                L.h2[s] = mix_h2(h);
-            }
-        }
-        wave_sync();
-#pragma unroll 4
-        for (uint32_t s = 0; s < nitems; s++) {
-            const uint64_t h = L.h1[s], g = L.h2[s];
-            const uint64_t v0 = h + (uint64_t)lane * g;
-            const uint64_t v1 = v0 + (g << 6);
-            m0 = v0 < m0 ? v0 : m0;
-            m1 = v1 < m1 ? v1 : m1;
-        }
-        if (nitems) any_shingle = true;
-        total_tok += keep_from;
-        if (final) return;
-        // carry tokens [keep_from, ntok) to the front
-        if (keep_from == 0) return;  // nothing consumed (fewer than k complete tokens): the caller re-checks room
-        const uint32_t src0 = keep_from < ntok ? L.cstart[keep_from] : cbase + ntok - 1 + (carry ? 1u : 0u);
-        const uint32_t used = cbase + (ntok ? ntok - 1 : 0);   // bytes of canon in use
-        const uint32_t nkeep = ntok - keep_from;
-        wave_sync();
-        uint16_t ks = 0, ke = 0;
-        if ((uint32_t)lane < nkeep) {   // nkeep <= k <= 64
-            ks = (uint16_t)(L.cstart[keep_from + lane] - src0);
-            ke = (uint16_t)(L.cend[keep_from + lane] - src0);
-        }
-        for (uint32_t o = 0; src0 + o < used; o += 64) {
-            const uint32_t i = src0 + o + lane;
-            const uint8_t v = i < used ? L.canon[i] : 0;
-            wave_sync();
-            if (i < used) L.canon[o + lane] = v;
-            wave_sync();
-        }
-        if ((uint32_t)lane < nkeep) {
-            L.cstart[lane] = ks;
-            L.cend[lane] = ke;
-        }
-        // word bytes kept = total kept bytes minus the separators between kept tokens
-        const uint32_t kept_bytes = used > src0 ? used - src0 : 0;
-        ntok = nkeep;
-        cbase = kept_bytes - (nkeep ? nkeep - 1 : 0);
-        wave_sync();
-    };
 
     // ---- the bytes of this push: V = pending || chunk; V[0, proc) is processed, V[proc] is the byte after it ----
     const uint32_t npend = dead ? 0u : (pend >> 8) & 1u;
@@ -548,46 +331,16 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void text_stream_kernel(
         for (int sub = 0; sub < 4; sub++) {
             const size_t pos = base + 64 * sub + lane;
             if (base + 64 * sub >= proc) break;
-            // make room: a step opens at most 32 tokens and writes at most 64 + 32 bytes
-            if (ntok + kStepTok > (uint32_t)kTokCap || cbase + ntok + kStepRoom > (uint32_t)kCanonCap) {
-                flush(false);
-                if (ntok + kStepTok > (uint32_t)kTokCap || cbase + ntok + kStepRoom > (uint32_t)kCanonCap) too_long = true;
+            if (text_batch_full(W)) {   // make room
+                text_flush<false>(L, W, k, lane, false);
+                if (text_batch_full(W)) too_long = true;
                 if (too_long) break;
             }
-            const uint32_t c = L.stage[64 * sub + lane];
-            const uint32_t q = L.stage[64 * sub + lane + 1];
-            uint32_t p = __shfl_up(c, 1, 64);
-            if (lane == 0) p = prev_last;
-            const bool w = pos < proc && inword(p, c, q, pretok);
-            const uint64_t inw = __ballot(w);
-            const uint64_t prev = (inw << 1) | (carry ? 1ull : 0ull);
-            const uint64_t starts = inw & ~prev;
-            const uint64_t endmark = ~inw & prev;   // first non-word byte after a token
-            const uint32_t nin_before = popc_below(inw, lane);
-            const uint32_t nst_before = popc_below(starts, lane);
-            const bool is_start = (starts >> lane) & 1ull;
-            if (w) {
-                const uint32_t tok = ntok + nst_before + (is_start ? 1u : 0u) - 1u;
-                const uint32_t cpos = cbase + nin_before + tok;
-                uint32_t ch = c;
-                if (!pretok && ch - 'A' <= 25u) ch += 32;
-                L.canon[cpos] = (uint8_t)ch;
-                if (is_start) {
-                    L.cstart[tok] = (uint16_t)cpos;
-                    if (cpos > 0) L.canon[cpos - 1] = ' ';
-                }
-            }
-            if ((endmark >> lane) & 1ull) {
-                const uint32_t tok = ntok + nst_before - 1u;   // starts strictly before this byte
-                L.cend[tok] = (uint16_t)(cbase + nin_before + tok);
-            }
-            ntok += (uint32_t)__popcll(starts);
-            cbase += (uint32_t)__popcll(inw);
-            carry = (inw >> 63) & 1ull;
-            // the last PROCESSED byte: a step that ends the push may be partial
+            const uint64_t inw = text_step(L, W, sub, pos, proc, pretok, lane);
+            // the last PROCESSED byte: a step that ends the push may be partial, text_step's carry and prev_last are a full one's
             const size_t left = proc - (base + 64 * sub);
-            if (left < 64) carry = (inw >> (left - 1)) & 1ull;
-            prev_last = __shfl(c, left < 64 ? (int)left - 1 : 63, 64);
+            if (left < 64) W.carry = (inw >> (left - 1)) & 1ull;
+            W.prev_last = __shfl((uint32_t)L.stage[64 * sub + lane], left < 64 ? (int)left - 1 : 63, 64);
         }
         cur = nxt;
     }
@@ -604,27 +357,27 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void text_stream_kernel(
 
     if (!fin) {
         // ---- store: what survives flush(false) is a prefix of one k-token window ----
-        if (!too_long && !dead) flush(false);
-        if (too_long) ntok = 0, cbase = 0, carry = false;
+        if (!too_long && !dead) text_flush<false>(L, W, k, lane, false);
+        if (too_long) W.ntok = 0, W.cbase = 0, W.carry = false;
         wave_sync();
-        S.m0[lane] = m0;
-        S.m1[lane] = m1;
-        const uint32_t used = cbase + (ntok ? ntok - 1 : 0);
+        S.m0[lane] = W.m0;
+        S.m1[lane] = W.m1;
+        const uint32_t used = W.cbase + (W.ntok ? W.ntok - 1 : 0);
         const uint32_t* src = reinterpret_cast<const uint32_t*>(L.canon);
         uint32_t* dst = reinterpret_cast<uint32_t*>(S.canon);
         for (uint32_t i = lane; 4 * i < used; i += 64) dst[i] = src[i];
-        if ((uint32_t)lane < ntok) {   // ntok <= k <= 64 after the flush
+        if ((uint32_t)lane < W.ntok) {   // ntok <= k <= 64 after the flush
             S.cstart[lane] = L.cstart[lane];
             S.cend[lane] = L.cend[lane];
         }
         if (lane == 0) {
             S.total_bytes = total_bytes;
-            S.ntok = ntok;
-            S.cbase = cbase;
-            S.carry = carry ? 1u : 0u;
-            S.prev_last = prev_last;
-            S.total_tok = total_tok;
-            S.flags = (any_shingle ? kAnyShingle : 0u) | (na ? kNonAscii : 0u) | (too_long ? kTooLong : 0u);
+            S.ntok = W.ntok;
+            S.cbase = W.cbase;
+            S.carry = W.carry ? 1u : 0u;
+            S.prev_last = W.prev_last;
+            S.total_tok = W.total_tok;
+            S.flags = (W.any_shingle ? kAnyShingle : 0u) | (na ? kNonAscii : 0u) | (too_long ? kTooLong : 0u);
             S.pending = pend;
             S.mode = mode;
             status[ei] = na ? 1 : (too_long ? -2 : 0);
@@ -633,27 +386,10 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void text_stream_kernel(
     }
 
     // ---- final: close a token that runs to the end of the stream, the final flush, emit as text_hash_kernel does ----
-    if (carry && ntok > 0 && lane == 0) L.cend[ntok - 1] = (uint16_t)(cbase + ntok - 1);
-    if (!too_long && !dead) flush(true);
-    int32_t stv = 0;
-    if (na) stv = 1;                          // non-ASCII in raw mode: host must pre-tokenise
-    else if (too_long) stv = -2;              // UCFP_E_UNSUPPORTED: a token / k-token run exceeds the LDS batch
-    else if (total_tok == 0 || !any_shingle) stv = -1;   // UCFP_E_MODALITY: no tokens
-    uint8_t* rec = out + ei * 1032;
-    const uint64_t a = stv == 0 ? m0 : 0ull, b = stv == 0 ? m1 : 0ull;
-    // 1032-byte records are only 8-byte aligned when the base is: write dwords
-    uint32_t* o0 = reinterpret_cast<uint32_t*>(rec + 8 + 8 * lane);
-    uint32_t* o1 = reinterpret_cast<uint32_t*>(rec + 8 + 8 * (lane + 64));
-    o0[0] = (uint32_t)a;
-    o0[1] = (uint32_t)(a >> 32);
-    o1[0] = (uint32_t)b;
-    o1[1] = (uint32_t)(b >> 32);
-    if (lane == 0) {
-        uint32_t* o32 = reinterpret_cast<uint32_t*>(rec);
-        o32[0] = stv == 0 ? 1u : 0u;  // schema: u16 = 1, pad
-        o32[1] = 0;
-        status[ei] = stv;
-    }
+    if (W.carry && W.ntok > 0 && lane == 0) L.cend[W.ntok - 1] = (uint16_t)(W.cbase + W.ntok - 1);
+    if (!too_long && !dead) text_flush<false>(L, W, k, lane, true);
+    const int32_t stv = text_emit<false>(out + ei * 1032, W, na, too_long, lane);
+    if (lane == 0) status[ei] = stv;
 }
 
 }  // namespace ucfp

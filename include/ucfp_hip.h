@@ -665,6 +665,49 @@ int ucfp_tlsh_index_query_dev(ucfp_tlsh_index* ix, uint32_t tenant, const uint8_
                               uint32_t max_distance, uint64_t* d_out_ids, uint32_t* d_out_dist, float* d_out_scores,
                               uint32_t* d_out_n, void* stream);
 
+/* ---- MinHash search: the k <= UCFP_INDEX_MAX_K MinHash-128 records of a tenant that agree with each query
+ * record in the most slots, EXACT, ties included.  The reference produces these records (`minhash-h128`,
+ * src/modality/text.rs:172; re-tagged `minhash-lsh-h128`, :428-446) and has no search over them; ucfp_lsh_* above is the
+ * approximate, build-once counterpart.
+ *   rows / queries   UCFP_MINHASH_BYTES records; the 8 header bytes are neither compared nor validated
+ *   agree(q, r)      the number of i < 128 with slot_i(q) == slot_i(r): all 64 bits, the same index only (the score
+ *                    numerator of ucfp_lsh_query_dev, the `agree` of ucfp_lsh_dedup_dev)
+ *   upsert           a known id replaces its row; tenants are isolated; delete reports how many ids it removed
+ *   query            rows with agree < min_agree are left out (0: every row is a hit; above 128: UCFP_E_INVALID); order
+ *                    (agree descending, id ascending); score = (float)agree / 128.0f.  out_ids / out_agree / out_scores:
+ *                    nq x k, unused slots UCFP_INVALID_ID / UINT32_MAX / -1; out_n: nq.  An unknown tenant, an empty
+ *                    tenant, k = 0 or nq = 0 gives 0 hits.
+ * Mutations are host bookkeeping; the device rows of a tenant are rebuilt at its next query (or by flush).  The
+ * *_dev calls take device pointers and a stream and are stream-ordered (no synchronisation beyond workspace growth and
+ * the rebuild after a mutation).  The key matrix of one pass is capped at 1 GiB; UCFP_MINHASH_KEY_BYTES in the
+ * environment, read once at creation, overrides the cap (floor 4096).  Not built: a compact filter plane, device-resident
+ * appends, sharding over GPUs, a search micro-batcher, save / load. */
+typedef struct ucfp_minhash_index ucfp_minhash_index;
+/* DESIGN.md A17; flags must be 0 */
+int ucfp_minhash_index_create(ucfp_ctx* ctx, uint32_t flags, ucfp_minhash_index** out);
+/* DESIGN.md A17 */
+void ucfp_minhash_index_destroy(ucfp_minhash_index* ix);
+/* DESIGN.md A17 */
+int ucfp_minhash_index_upsert(ucfp_minhash_index* ix, uint32_t tenant, const uint64_t* ids, const uint8_t* records, size_t n);
+/* DESIGN.md A17 */
+int ucfp_minhash_index_upsert_dev(ucfp_minhash_index* ix, uint32_t tenant, const uint64_t* d_ids, const uint8_t* d_records,
+                                  size_t n, void* stream);
+/* DESIGN.md A17 */
+int ucfp_minhash_index_delete(ucfp_minhash_index* ix, uint32_t tenant, const uint64_t* ids, size_t n, size_t* n_removed);
+/* DESIGN.md A17 */
+int ucfp_minhash_index_size(ucfp_minhash_index* ix, uint32_t tenant, size_t* rows);
+/* DESIGN.md A17 */
+int ucfp_minhash_index_flush(ucfp_minhash_index* ix);
+/* DESIGN.md A17; host pointers */
+int ucfp_minhash_index_query(ucfp_minhash_index* ix, uint32_t tenant, const uint8_t* records, size_t nq, uint32_t k,
+                             uint32_t min_agree, uint64_t* out_ids, uint32_t* out_agree, float* out_scores, uint32_t* out_n);
+/* DESIGN.md A17; device pointers, stream-ordered */
+int ucfp_minhash_index_query_dev(ucfp_minhash_index* ix, uint32_t tenant, const uint8_t* d_records, size_t nq, uint32_t k,
+                                 uint32_t min_agree, uint64_t* d_out_ids, uint32_t* d_out_agree, float* d_out_scores,
+                                 uint32_t* d_out_n, void* stream);
+/* DESIGN.md A17; host-only (no device needed): agree of two records, 0 .. 128 (a NULL argument gives 0) */
+uint32_t ucfp_minhash_agree(const uint8_t* a, const uint8_t* b);
+
 /* ---- image search over whole records: global and block hashes scored together ----
  * The reference threads a compare-time MultiHashConfig through its adapter and its DTO (src/modality/image.rs:90-104,
  * src/server/dto.rs:462-480: phash_weight, dhash_weight, ahash_weight, global_weight, block_weight,

@@ -157,6 +157,18 @@ SIGNATURES = {
                                         C.c_void_p, C.c_void_p, C.c_void_p]),
     "ucfp_tlsh_index_query_dev": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ucfp_minhash_index_create": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "ucfp_minhash_index_destroy": (None, [C.c_void_p]),
+    "ucfp_minhash_index_upsert": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "ucfp_minhash_index_upsert_dev": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ucfp_minhash_index_delete": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ucfp_minhash_index_size": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_size_t)]),
+    "ucfp_minhash_index_flush": (C.c_int, [C.c_void_p]),
+    "ucfp_minhash_index_query": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ucfp_minhash_index_query_dev": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ucfp_minhash_agree": (C.c_uint32, [C.c_void_p, C.c_void_p]),
     "ucfp_image_match_config_default": (None, [C.POINTER(ImageMatchConfig)]),
     "ucfp_image_match_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ImageMatchConfig), C.POINTER(C.c_float)]),
     "ucfp_image_match_index_create": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),

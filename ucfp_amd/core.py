@@ -22,6 +22,7 @@ class HitSource:
     Haitsma = "haitsma"    # audio identification over Haitsma sub-fingerprints (DESIGN A12); not in the reference
     Tlsh = "tlsh"          # nearest `tlsh-128-1` records by TLSH distance (DESIGN A15); not in the reference
     ImageMatch = "image-match"   # image records by global and block hashes together (DESIGN A16); not in the reference
+    MinHash = "minhash"    # MinHash-128 records by the number of equal slots (DESIGN A17); not in the reference
 
 
 @dataclass
@@ -59,7 +60,7 @@ class Hit:
     vector_rank: Optional[int] = None
     bm25_rank: Optional[int] = None
     term_hits: list = field(default_factory=list)
-    distance: Optional[int] = None    # Hamming distance when source == "hamming"; bit errors of the block when "haitsma"; TLSH distance when "tlsh"
+    distance: Optional[int] = None    # Hamming distance when source == "hamming"; bit errors of the block when "haitsma"; TLSH distance when "tlsh"; 128 - agree when "minhash"
     votes: Optional[int] = None       # offset-consistent landmark matches when source == "landmark"
     offset: Optional[int] = None      # where the query's frame 0 lies in the record (frames) when source == "landmark" / "haitsma"
     scale: Optional[float] = None     # record frames per query frame, from the (scale, offset) vote over Panako triplets (DESIGN A14)
@@ -86,6 +87,9 @@ FORMAT_VERSION = 1  # src/lib.rs:62
 # the bundle, as a list of integers, a hex string or bytes; `algorithm`, when given, must name the tag that goes with the
 # length.  `multi_hash` is the reference's MultiHashConfigDto object (kebab-case keys, dto.rs:462-480) and `min_score` a
 # number; both are optional and are checked when the query runs.
+# MinHash search adds `minhash` (DESIGN A17): the 1032 bytes of a MinHash-128 record as a hex string of 2064 digits, a list
+# of 1032 integers or bytes; `algorithm`, when given, names the tag of the records searched ("minhash-h128" or
+# "minhash-lsh-h128").  `min_similarity` in (0, 1] is optional and valid only with `minhash`: hits need that Jaccard estimate.
 # A body the reference accepts parses to the same query here.
 
 DEFAULT_K = 10   # dto.rs:85-87
@@ -106,6 +110,8 @@ class QueryRequest:
     image_record: Optional[bytes] = None   # a whole image record, 168 or 536 bytes (DESIGN A16)
     multi_hash: Optional[dict] = None   # MultiHashConfigDto of an `image_record` query (dto.rs:462-480)
     min_score: Optional[float] = None   # hits of an `image_record` query need at least this score
+    minhash: Optional[bytes] = None     # the 1032 bytes of a MinHash-128 record (DESIGN A17)
+    min_similarity: Optional[float] = None   # hits of a `minhash` query need agree / 128 >= this, in (0, 1]
     terms: List[str] = field(default_factory=list)
     explain: bool = False
 
@@ -121,11 +127,12 @@ class QueryRequest:
         vector, h, lm = body.get("vector"), body.get("hash"), body.get("landmarks")
         sub, tri, tl = body.get("subfingerprints"), body.get("triplets"), body.get("tlsh")
         img, mh, ms = body.get("image_record"), body.get("multi_hash"), body.get("min_score")
+        mhr, sim = body.get("minhash"), body.get("min_similarity")
         terms = body.get("terms") or []
         if not isinstance(terms, list) or not all(isinstance(t, str) for t in terms):
             raise InvalidArgument("`terms` must be a list of strings")
         if (vector is None and h is None and lm is None and sub is None and tri is None and tl is None and img is None
-                and not terms):
+                and mhr is None and not terms):
             raise InvalidArgument("query needs `vector` (dto.rs:80-82), `terms`, `hash`, `landmarks` or `subfingerprints`")
         if img is not None:
             img = _image_record_bytes(img, body.get("algorithm"))
@@ -135,6 +142,15 @@ class QueryRequest:
                 raise InvalidArgument("`min_score` must be a number")
         else:
             mh = ms = None      # they belong to an `image_record` query
+        if sim is not None:
+            if mhr is None:
+                raise InvalidArgument("`min_similarity` goes with `minhash`")
+            if isinstance(sim, bool) or not isinstance(sim, (int, float)) or not 0.0 < float(sim) <= 1.0:
+                raise InvalidArgument("`min_similarity` must be a number in (0, 1]")
+        if mhr is not None:
+            mhr = _minhash_bytes(mhr)
+            if body.get("algorithm") not in (None,) + _MINHASH_TAGS:
+                raise InvalidArgument(f"`minhash` goes with `algorithm` in {list(_MINHASH_TAGS)} or none")
         if tl is not None:
             tl = _tlsh_bytes(tl)
             if body.get("algorithm") not in (None, "tlsh-128-1"):
@@ -156,6 +172,7 @@ class QueryRequest:
                    hash=int(h) if h is not None else None, algorithm=body.get("algorithm"), landmarks=lm, subfingerprints=sub,
                    triplets=tri, tlsh=tl, image_record=img, multi_hash=dict(mh) if mh is not None else None,
                    min_score=float(ms) if ms is not None else None,
+                   minhash=mhr, min_similarity=float(sim) if sim is not None else None,
                    terms=list(terms), explain=_flag(body.get("explain", False)))
 
 
@@ -227,6 +244,31 @@ def _tlsh_bytes(tl) -> bytes:
         raw = b""
     if len(raw) != 35:
         raise InvalidArgument("`tlsh` must be 70 hex digits, with or without the T1 prefix")
+    return raw
+
+
+_MINHASH_TAGS = ("minhash-h128", "minhash-lsh-h128")
+_MINHASH_BYTES = 1032
+
+
+def _minhash_bytes(rec) -> bytes:
+    """`minhash` of a query body -> the 1032 record bytes."""
+    from .errors import InvalidArgument
+    if isinstance(rec, list):
+        if len(rec) != _MINHASH_BYTES or not all(isinstance(x, int) and not isinstance(x, bool) and 0 <= x < 256 for x in rec):
+            raise InvalidArgument("`minhash` as a list must be 1032 integers below 256")
+        return bytes(rec)
+    if isinstance(rec, (bytes, bytearray)):
+        raw = bytes(rec)
+    elif isinstance(rec, str):
+        try:
+            raw = bytes.fromhex(rec)
+        except ValueError:
+            raise InvalidArgument("`minhash` as a string must be hexadecimal") from None
+    else:
+        raise InvalidArgument("`minhash` must be a hex string, a list of integers or bytes")
+    if len(raw) != _MINHASH_BYTES:
+        raise InvalidArgument(f"`minhash` must be 1032 bytes (2064 hex digits), not {len(raw)}")
     return raw
 
 

@@ -14,6 +14,8 @@ path, backed by the GPU-resident shard behind the C ABI (ucfp_index_*).
     GpuIndex.nearest_tlsh(tenant, digest, k)  the `tlsh-128-1` records at the smallest TLSH distance (DESIGN A15; TlshIndex)
     GpuIndex.similar_images(tenant, record, k)  the image records that score highest with global and block hashes
                                       together (DESIGN A16; ImageMatchIndex)
+    GpuIndex.similar_text(tenant, record_or_text, k)  the MinHash-128 records that agree with a record (or a text's
+                                      record) in the most slots (DESIGN A17; MinHashIndex)
     GpuIndex.bm25(tenant, terms, k)   IndexBackend::bm25 / bm25_explain :37-50 over Record.text (DESIGN A11; Bm25Index)
     GpuIndex.flush()                  IndexBackend::flush    :63
 
@@ -33,7 +35,7 @@ from .errors import InvalidArgument, UnsupportedError
 from .image import MultiHashConfig, match_algo
 from .image import _TAG as _IMAGE_TAG
 from .terms import query_terms, tokenize
-from .text import ALGORITHM_TLSH
+from .text import ALGORITHM_LSH, ALGORITHM_MINHASH_128, ALGORITHM_TLSH, MINHASH_BYTES
 
 HAMMING64, COSINE_F32 = 1, 2
 APPEND_ONLY = 1
@@ -560,6 +562,94 @@ def _pack_digests(digests) -> np.ndarray:
     return buf[:rows.shape[0]]
 
 
+class MinHashIndex:
+    """Thin RAII wrapper over one ucfp_minhash_index (DESIGN A17): rows and queries are MinHash-128 records (1032 bytes
+    each); a query answers the k rows that agree with it in the most slots, exactly."""
+
+    def __init__(self, flags: int = 0, ctx=None):
+        self._lib = _lib.load()
+        self.ctx = ctx or _lib.current_context()
+        h = C.c_void_p()
+        _lib.check(self._lib.ucfp_minhash_index_create(self.ctx.handle, flags, C.byref(h)))
+        self.handle = h
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self._lib.ucfp_minhash_index_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def upsert(self, tenant: int, ids, records) -> None:
+        """ids [n]; records: uint8 [n, 1032], or n records as bytes."""
+        ids = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        rows = _pack_minhash(records)
+        if rows.shape[0] != ids.shape[0]:
+            raise InvalidArgument("ids and records disagree on the number of rows")
+        _lib.check(self._lib.ucfp_minhash_index_upsert(self.handle, tenant, ids.ctypes.data, rows.ctypes.data, ids.shape[0]))
+
+    def upsert_dev(self, tenant: int, ids_ptr: int, records_ptr: int, n: int, stream: int = 0) -> None:
+        _lib.check(self._lib.ucfp_minhash_index_upsert_dev(self.handle, tenant, ids_ptr, records_ptr, n, stream or None))
+
+    def delete(self, tenant: int, ids) -> int:
+        ids = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        removed = C.c_size_t(0)
+        _lib.check(self._lib.ucfp_minhash_index_delete(self.handle, tenant, ids.ctypes.data, ids.shape[0], C.byref(removed)))
+        return int(removed.value)
+
+    def size(self, tenant: int) -> int:
+        r = C.c_size_t(0)
+        _lib.check(self._lib.ucfp_minhash_index_size(self.handle, tenant, C.byref(r)))
+        return int(r.value)
+
+    def flush(self) -> None:
+        _lib.check(self._lib.ucfp_minhash_index_flush(self.handle))
+
+    def query(self, tenant: int, records, k: int, min_agree: int = 1):
+        """-> (ids [nq,k] u64, agree [nq,k] u32, scores [nq,k] f32, counts [nq] u32); rows that agree in fewer than
+        `min_agree` slots are left out (0: every row is a hit)."""
+        q = _pack_minhash(records)
+        nq = q.shape[0]
+        kk = max(int(k), 1)
+        ids = np.full((nq, kk), INVALID_ID, np.uint64)
+        agree = np.full((nq, kk), 0xFFFFFFFF, np.uint32)
+        scores = np.full((nq, kk), -1.0, np.float32)
+        counts = np.zeros(nq, np.uint32)
+        _lib.check(self._lib.ucfp_minhash_index_query(self.handle, tenant, q.ctypes.data, nq, int(k), int(min_agree),
+                                                      ids.ctypes.data, agree.ctypes.data, scores.ctypes.data,
+                                                      counts.ctypes.data))
+        return ids[:, :k], agree[:, :k], scores[:, :k], counts
+
+    def query_dev(self, tenant: int, records_ptr: int, nq: int, k: int, min_agree: int, out_ids_ptr: int,
+                  out_agree_ptr: int, out_scores_ptr: int, out_n_ptr: int, stream: int = 0) -> None:
+        _lib.check(self._lib.ucfp_minhash_index_query_dev(self.handle, tenant, records_ptr, nq, k, min_agree,
+                                                          out_ids_ptr or None, out_agree_ptr or None, out_scores_ptr or None,
+                                                          out_n_ptr, stream or None))
+
+
+def _pack_minhash(records) -> np.ndarray:
+    """uint8 [n, 1032], bytes (one record or several back to back) or a list of bytes -> uint8 [n, 1032] (one spare row
+    behind it, so the pointer is never to an empty buffer)."""
+    if isinstance(records, (bytes, bytearray)):
+        records = np.frombuffer(bytes(records), np.uint8)
+    if isinstance(records, np.ndarray) and records.dtype == np.uint8:
+        if records.size % MINHASH_BYTES:
+            raise InvalidArgument(f"records must be {MINHASH_BYTES} bytes each")
+        rows = records.reshape(-1, MINHASH_BYTES)
+    else:
+        records = [bytes(r) for r in records]
+        if any(len(r) != MINHASH_BYTES for r in records):
+            raise InvalidArgument(f"records must be {MINHASH_BYTES} bytes each")
+        rows = np.frombuffer(b"".join(records), np.uint8).reshape(-1, MINHASH_BYTES)
+    buf = np.zeros((rows.shape[0] + 1, MINHASH_BYTES), np.uint8)
+    buf[:rows.shape[0]] = rows
+    return buf[:rows.shape[0]]
+
+
 class ImageMatchIndex:
     """Thin RAII wrapper over one ucfp_image_match_index (DESIGN A16): rows and queries are whole image records of one
     size -- 168 bytes (`algo` AHASH, PHASH or DHASH) or the 536-byte bundle (MULTI); a query answers the k rows that score
@@ -805,6 +895,7 @@ class GpuIndex:
         self._bm = None       # Bm25Index of the records with text (DESIGN A11)
         self._tl = None       # TlshIndex of the tlsh-128-1 records (DESIGN A15)
         self._im = {}         # image algorithm tag -> ImageMatchIndex of its whole records (DESIGN A16)
+        self._mh = {}         # MinHash algorithm tag -> MinHashIndex of its 1032-byte records (DESIGN A17)
         self._sidecar = sidecar   # ucfp_amd.store.Sidecar: the stored-table mirror written at upsert
 
     def attach_sidecar(self, sidecar) -> None:
@@ -853,6 +944,12 @@ class GpuIndex:
             ix = self._im[tag] = ImageMatchIndex(_IMAGE_ALGO[tag], 0, self.ctx)
         return ix
 
+    def _minhash(self, tag: str) -> MinHashIndex:
+        ix = self._mh.get(tag)
+        if ix is None:
+            ix = self._mh[tag] = MinHashIndex(0, self.ctx)
+        return ix
+
     def _bm25(self) -> Bm25Index:
         if self._bm is None:
             self._bm = Bm25Index(0, self.ctx)
@@ -864,12 +961,14 @@ class GpuIndex:
                 + ([self._ps] if self._ps is not None else [])
                 + ([self._hx] if self._hx is not None else [])
                 + ([self._bm] if self._bm is not None else [])
-                + ([self._tl] if self._tl is not None else []) + list(self._im.values()))
+                + ([self._tl] if self._tl is not None else []) + list(self._im.values()) + list(self._mh.values()))
 
     def upsert(self, records: Sequence[Record]) -> None:
         """Embeddings go to the cosine index of their dimension; image records also feed the
         Hamming spaces `<algorithm>` with their 64-bit global hashes (SURVEY 8f N2 offsets) and, whole, the image match
-        index of their algorithm tag (DESIGN A16);
+        index of their algorithm tag (DESIGN A16); `minhash-h128` and `minhash-lsh-h128` records of 1032 bytes feed the
+        MinHash index of their tag (DESIGN A17: the two tags carry the same bytes and mean different things to the index
+        layer, so they are never searched together);
         `audiofp-wang-v1` records feed the landmark index with their landmarks, `audiofp-panako-v1` records a second
         landmark index with their (hash, t_anchor) pairs (the two never share postings) and `audiofp-haitsma-v1` records
         the sub-fingerprint index with their frames; every record with `text`, whatever its
@@ -879,7 +978,7 @@ class GpuIndex:
         REPLACES the old one -- "Drop any stale vector for this key" when the new record has no embedding
         (src/index/embedded/mod.rs:184-191), a new dimension or algorithm replaces the old row.  So before inserting,
         the key is removed from every cosine index of another dimension, every hash space, both landmark indexes, the sub-fingerprint index
-        and the image match indexes when the new record does not feed them.  Within one batch the last record of a key wins, as successive `insert`s in one redb transaction do."""
+        and the image match and MinHash indexes when the new record does not feed them.  Within one batch the last record of a key wins, as successive `insert`s in one redb transaction do."""
         if self._sidecar is not None:     # the log first (the host does this right after its redb commit), then the mirror
             self._sidecar.append(records)
         last = {}
@@ -887,7 +986,7 @@ class GpuIndex:
             last[(r.tenant_id, r.record_id)] = r
         by_cos, by_ham, stale_cos, stale_ham, by_lm, stale_lm, by_bm, stale_bm = {}, {}, {}, {}, {}, {}, {}, {}
         by_hx, stale_hx, by_pk, stale_pk, by_tl, stale_tl = {}, {}, {}, {}, {}, {}
-        by_im, stale_im = {}, {}
+        by_im, stale_im, by_mh, stale_mh = {}, {}, {}, {}
         for r in last.values():
             if r.text is not None:
                 by_bm.setdefault(r.tenant_id, []).append(r)
@@ -915,6 +1014,12 @@ class GpuIndex:
             for tag in self._im:
                 if tag != im_tag:
                     stale_im.setdefault((r.tenant_id, tag), []).append(r.record_id)
+            mh_tag = r.algorithm if _feeds_minhash(r) else None
+            if mh_tag is not None:
+                by_mh.setdefault((r.tenant_id, mh_tag), []).append(r)
+            for tag in self._mh:
+                if tag != mh_tag:
+                    stale_mh.setdefault((r.tenant_id, tag), []).append(r.record_id)
             dim = len(r.embedding) if r.embedding is not None else 0
             if dim > 0:
                 by_cos.setdefault((r.tenant_id, dim), []).append(r)
@@ -943,6 +1048,8 @@ class GpuIndex:
             self._tl.delete(tenant, np.array(ids, np.uint64))
         for (tenant, tag), ids in stale_im.items():
             self._im[tag].delete(tenant, np.array(ids, np.uint64))
+        for (tenant, tag), ids in stale_mh.items():
+            self._mh[tag].delete(tenant, np.array(ids, np.uint64))
         for tenant, ids in stale_bm.items():
             self._bm.delete(tenant, np.array(ids, np.uint64))
         for tenant, recs in by_bm.items():
@@ -964,6 +1071,9 @@ class GpuIndex:
         for (tenant, tag), recs in by_im.items():
             self._image_match(tag).upsert(tenant, np.array([r.record_id for r in recs], np.uint64),
                                           [bytes(r.fingerprint) for r in recs])
+        for (tenant, tag), recs in by_mh.items():
+            self._minhash(tag).upsert(tenant, np.array([r.record_id for r in recs], np.uint64),
+                                      [bytes(r.fingerprint) for r in recs])
         for (tenant, dim), recs in by_cos.items():
             ids = np.array([r.record_id for r in recs], np.uint64)
             rows = np.array([r.embedding for r in recs], np.float32)
@@ -1076,6 +1186,45 @@ class GpuIndex:
         return [Hit(tenant_id=tenant_id, record_id=int(ids[0, i]), score=float(scores[0, i]), source=HitSource.ImageMatch)
                 for i in range(int(counts[0]))]
 
+    def similar_text(self, tenant_id: int, record_or_text, k: int, *, algorithm: Optional[str] = None,
+                     min_agree: Optional[int] = None, threshold: Optional[float] = None) -> List[Hit]:
+        """The MinHash-128 records that agree with a record in the most slots (DESIGN A17): `record_or_text` is the 1032
+        record bytes, or a `str` that is fingerprinted with the default TextOpts first.  Hits need `min_agree` equal slots
+        (default 1), or the Jaccard estimate `threshold` (text.min_agree_for); score = agree / 128, `distance` =
+        128 - agree.  `algorithm` names the tag of the records searched (`minhash-h128` or `minhash-lsh-h128`); with
+        none, the only MinHash index present."""
+        if min_agree is not None and threshold is not None:
+            raise InvalidArgument("give `min_agree` or `threshold`, not both")
+        if threshold is not None:
+            from .text import min_agree_for
+            min_agree = min_agree_for(threshold)
+        elif min_agree is None:
+            min_agree = 1
+        if not 0 <= int(min_agree) <= 128:
+            raise InvalidArgument(f"min_agree must be in [0, 128] (got {min_agree!r})")
+        if algorithm is not None and algorithm not in _MINHASH_TAGS:
+            raise InvalidArgument(f"no MinHash index for algorithm {algorithm!r}")
+        if isinstance(record_or_text, str):
+            from .text import TextOpts, minhash_batch, _raise_for
+            recs, status = minhash_batch([record_or_text], TextOpts())
+            _raise_for(int(status[0]))
+            rec = recs[0].tobytes()
+        else:
+            rec = bytes(record_or_text)
+            if len(rec) != MINHASH_BYTES:
+                raise InvalidArgument(f"a MinHash record is {MINHASH_BYTES} bytes, not {len(rec)}")
+        tag = algorithm
+        if tag is None:
+            if len(self._mh) > 1:
+                raise InvalidArgument("`algorithm` is required when MinHash records of several algorithms are indexed")
+            tag = next(iter(self._mh), None)
+        ix = self._mh.get(tag)
+        if ix is None or k == 0:
+            return []
+        ids, agree, scores, counts = ix.query(tenant_id, [rec], min(k, MAX_K), int(min_agree))
+        return [Hit(tenant_id=tenant_id, record_id=int(ids[0, i]), score=float(scores[0, i]), source=HitSource.MinHash,
+                    distance=128 - int(agree[0, i])) for i in range(int(counts[0]))]
+
     def bm25(self, tenant_id: int, terms: Sequence[str], k: int, filter: Optional[bytes] = None,
              explain: bool = False) -> List[Hit]:
         """IndexBackend::bm25 / bm25_explain (src/index/embedded/mod.rs:127-150): "bm25" hits by BM25 score (DESIGN
@@ -1090,11 +1239,12 @@ class GpuIndex:
         """POST /v1/query (handlers.rs:143-187) with the additive `hash` field: a vector goes to the cosine kNN,
         a hash to the Hamming space `algorithm` (default: the only hash space present), `landmarks` to identify (the Panako
         index when `algorithm` is "audiofp-panako-v1", the Wang one otherwise), `triplets` to identify_stretched,
-        `subfingerprints` to identify_frames, `tlsh` to nearest_tlsh, `image_record` to similar_images;
+        `subfingerprints` to identify_frames, `tlsh` to nearest_tlsh, `image_record` to similar_images,
+        `minhash` to similar_text;
         `terms` go through the matcher (BM25, or vector + BM25 fused by RRF: src/matcher/mod.rs:140-207)."""
         if (getattr(req, "landmarks", None) is None and getattr(req, "subfingerprints", None) is None and req.hash is None
                 and getattr(req, "triplets", None) is None and getattr(req, "tlsh", None) is None
-                and getattr(req, "image_record", None) is None
+                and getattr(req, "image_record", None) is None and getattr(req, "minhash", None) is None
                 and getattr(req, "terms", None)):
             from . import matcher
             hits = matcher.search(self, req)
@@ -1107,6 +1257,9 @@ class GpuIndex:
             if getattr(req, "min_score", None) is not None:
                 cfg.min_score = float(req.min_score)
             hits = self.similar_images(req.tenant_id, req.image_record, req.k, getattr(req, "algorithm", None), cfg)
+        elif getattr(req, "minhash", None) is not None:
+            hits = self.similar_text(req.tenant_id, req.minhash, req.k, algorithm=getattr(req, "algorithm", None),
+                                     threshold=getattr(req, "min_similarity", None))
         elif getattr(req, "tlsh", None) is not None:
             if getattr(req, "algorithm", None) not in (None, ALGORITHM_TLSH):
                 raise InvalidArgument(f"`tlsh` goes with `algorithm` = {ALGORITHM_TLSH!r} or none")
@@ -1150,6 +1303,14 @@ def _feeds_image_match(r: Record) -> bool:
     if r.algorithm not in _IMAGE_ALGO:
         return False
     return len(r.fingerprint) == (536 if r.algorithm == _IMAGE_TAG[7] else 168)
+
+
+_MINHASH_TAGS = (ALGORITHM_MINHASH_128, ALGORITHM_LSH)
+
+
+def _feeds_minhash(r: Record) -> bool:
+    """A `minhash-h128` or `minhash-lsh-h128` record that is one whole MinHash-128 signature."""
+    return r.algorithm in _MINHASH_TAGS and len(r.fingerprint) == MINHASH_BYTES
 
 
 def _hash_spaces(r: Record):

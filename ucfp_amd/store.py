@@ -159,6 +159,7 @@ _IMAGE_SPACES = {
     ("imgfprint-dhash-v1", 168): [("imgfprint-dhash-v1", 4, 4)],
 }
 _SIMHASH = ("simhash-b64-tf", "simhash-b64-idf")
+_MINHASH = ("minhash-h128", "minhash-lsh-h128")
 
 
 def rebuild(path: str, ctx=None, sidecar: bool = False):
@@ -190,6 +191,11 @@ def rebuild(path: str, ctx=None, sidecar: bool = False):
                     gi._hamming(space).upsert(int(tenant), ids[sel], d_codes.cpu().numpy().view(np.uint64))
                 # the whole records refill the image match index of their tag, whose row table lives on the host (A16)
                 gi._image_match(algorithm).upsert(int(tenant), ids[sel], np.ascontiguousarray(blobs[sel]))
+        for algorithm in _MINHASH:     # whole records: the MinHash index keeps its row table on the host (A17)
+            tenants, ids, blobs = snap.gather_fingerprints(algorithm, 1032)
+            for tenant in np.unique(tenants):
+                sel = tenants == tenant
+                gi._minhash(algorithm).upsert(int(tenant), ids[sel], np.ascontiguousarray(blobs[sel]))
         for algorithm in _SIMHASH:
             tenants, ids, blobs = snap.gather_fingerprints(algorithm, 8)
             for tenant in np.unique(tenants):

@@ -713,6 +713,15 @@ def min_agree_for(threshold: float) -> int:
     return max(1, math.ceil(t * 128.0))
 
 
+def minhash_agree(a, b) -> int:
+    """The number of equal slots of two MinHash-128 records, 0 .. 128 (host code: ucfp_minhash_agree needs no device;
+    the headers are not compared)."""
+    a, b = bytes(a), bytes(b)
+    if len(a) != MINHASH_BYTES or len(b) != MINHASH_BYTES:
+        raise InvalidArgument(f"a MinHash record is {MINHASH_BYTES} bytes")
+    return int(_lib.load().ucfp_minhash_agree(a, b))
+
+
 SPAN_ALL = 0xFFFFFFFF   # dedup: every pair of a run of equal band keys
 
 

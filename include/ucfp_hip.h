@@ -957,6 +957,60 @@ int ucfp_haitsma_index_query_dev(ucfp_haitsma_index* ix, uint32_t tenant, const 
                                  uint32_t* d_out_dist, int32_t* d_out_offsets, float* d_out_scores, uint32_t* d_out_n,
                                  void* stream);
 
+/* STREAMING Haitsma: the input side of continuous monitoring, with the state on the device and many
+ * streams advanced by one push.  A set holds max_streams slots; a slot is one stream at the set's sample rate (1 000 ..
+ * 384 000 Hz, resampled to 5 kHz like ucfp_audio_haitsma unless it is 5000).  The Haitsma spec is local in time: frame f
+ * depends on 2048 samples at 5 kHz and on the band energies of frame f - 1.  After a push that brings a stream to n
+ * samples it has emitted its first Fr(n) sub-fingerprints (ucfp_haitsma_stream_frames), a final push emits the rest, and
+ * the concatenation over all pushes equals ucfp_audio_haitsma of the whole stream byte for byte, however the stream is
+ * cut into chunks (empty chunks and a final push without samples included).  Frame 0 of a stream has a zero history;
+ * every later frame uses the energies of the frame before it, also across pushes.
+ *   - The set serialises its own calls: it is safe to call from several threads.  Consecutive calls are ordered by the
+ *     set itself (an event), whatever `stream` the caller passes.
+ *   - Device bytes per stream: ucfp_haitsma_streams_state_bytes(sample_rate, block_frames) =
+ *     4 * (2048 + ceil(sample_rate / 5000) + 1 + 33 + block_frames): the 5 kHz tail of the next frame, the input samples
+ *     the next output still needs, the last frame's band energies and the ring of the latest block_frames
+ *     sub-fingerprints; fixed at creation, whatever the stream's length.  The push path allocates nothing beyond growing
+ *     the context's workspace to the largest push seen.
+ *   - Errors are status codes: UCFP_E_INVALID for a slot out of range or not open, a slot twice in one call, a chunk
+ *     above 2^29 samples, a push whose carried plus new 5 kHz samples reach 2^31, a stream that would pass 2^32 frames,
+ *     block_frames above UCFP_HAITSMA_MAX_QUERY_FRAMES, cap_frames below the bound; UCFP_E_MODALITY for a rate outside
+ *     1 000 .. 384 000 or band edges outside 1 <= fmin < fmax <= 2500.  A failed call changes no state. */
+typedef struct ucfp_haitsma_streams ucfp_haitsma_streams;
+/* cfg as ucfp_audio_haitsma, NULL = defaults.  The rate and the band edges are checked before anything else.
+ * block_frames in [0, UCFP_HAITSMA_MAX_QUERY_FRAMES]: the length of the live block (0: no ring).  Fails with UCFP_E_INDEX
+ * without a gfx950 device (no CPU fallback). */
+int ucfp_haitsma_streams_create(ucfp_ctx* ctx, uint32_t sample_rate, const ucfp_haitsma_config* cfg, uint32_t max_streams,
+                                uint32_t block_frames, ucfp_haitsma_streams** out);
+void ucfp_haitsma_streams_destroy(ucfp_haitsma_streams* s);
+int ucfp_haitsma_streams_open(ucfp_haitsma_streams* s, uint32_t* slot);     /* fresh stream: no samples, zero history */
+int ucfp_haitsma_streams_close(ucfp_haitsma_streams* s, uint32_t slot);     /* discard, emit nothing */
+/* Host-only, no GPU: Fr of A18 -- S(n) = n at 5 kHz, else min(ceil((n - 1) 5000 / sr), floor(n 5000 / sr)) (S(0) = 0;
+ * final: floor(n 5000 / sr)); Fr = S < 2048 ? 0 : (S - 2048) / 64 + 1.  0 for a rate outside 1 000 .. 384 000. */
+uint64_t ucfp_haitsma_stream_frames(uint64_t n_samples, uint32_t sample_rate, int final);
+/* Host-only: device bytes a set holds per stream (0 for a rate or block_frames out of range). */
+size_t ucfp_haitsma_streams_state_bytes(uint32_t sample_rate, uint32_t block_frames);
+/* The frames a push emits, exactly; host-computable from the per-slot sample counts (0 for an invalid push). */
+size_t ucfp_haitsma_streams_max_frames(ucfp_haitsma_streams* s, const uint32_t* slots, const uint64_t* n_samples,
+                                       const uint8_t* final, size_t n);
+/* slots / n_samples / final: host arrays of n entries (distinct open slots; final may be NULL = none); d_pcm: the n
+ * chunks concatenated in that order on the device.  Sub-fingerprints of entry i -> d_out[d_out_offsets[i] ..
+ * d_out_offsets[i+1]) (u32 each; n + 1 device u64 offsets).  final[i] != 0 emits the rest and closes the slot.
+ * cap_frames below ucfp_haitsma_streams_max_frames -> UCFP_E_INVALID before ANY state changes.  One launch sequence
+ * whatever n is; no host synchronisation (the host waits only for the table copy of the call two back). */
+int ucfp_haitsma_streams_push_dev(ucfp_haitsma_streams* s, const uint32_t* slots, const uint64_t* n_samples,
+                                  const uint8_t* final, size_t n, const float* d_pcm, uint32_t* d_out, size_t cap_frames,
+                                  uint64_t* d_out_offsets, void* stream);
+/* Host-pointer convenience for one slot; synchronous.  *n_frames = frames of this push. */
+int ucfp_haitsma_streams_push(ucfp_haitsma_streams* s, uint32_t slot, const float* pcm, size_t n, int final, uint32_t* out,
+                              size_t cap_frames, size_t* n_frames);
+/* Live blocks: item i = the latest min(block_frames, frames emitted) sub-fingerprints of open slot slots[i] in time
+ * order -> d_frames[d_offsets[i] .. d_offsets[i+1]) (element offsets, n + 1 of them): the ragged shape
+ * ucfp_haitsma_index_query_dev takes.  A stream without frames gives an empty item.  cap_frames below the total ->
+ * UCFP_E_INVALID.  No host synchronisation. */
+int ucfp_haitsma_streams_blocks_dev(ucfp_haitsma_streams* s, const uint32_t* slots, size_t n, uint32_t* d_frames,
+                                    size_t cap_frames, uint64_t* d_offsets, void* stream);
+
 /* ---- BM25 keyword index (src/index/embedded/bm25.rs:79-628) ----
  * A document is a list of (key u64, tf u32) pairs: item i of a batch is keys/tfs[offsets[i] .. offsets[i+1]) with
  * ELEMENT offsets (offsets[0] = 0, non-decreasing, n + 1 entries); dl = sum tf < 2^32.  Keys are the caller's: equal

@@ -315,6 +315,20 @@ SIGNATURES = {
                                              C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "ucfp_wang_streams_push": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p,
                                          C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ucfp_haitsma_streams_create": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(HaitsmaConfig), C.c_uint32, C.c_uint32,
+                                              C.POINTER(C.c_void_p)]),
+    "ucfp_haitsma_streams_destroy": (None, [C.c_void_p]),
+    "ucfp_haitsma_streams_open": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "ucfp_haitsma_streams_close": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "ucfp_haitsma_stream_frames": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_int]),
+    "ucfp_haitsma_streams_state_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    "ucfp_haitsma_streams_max_frames": (C.c_size_t, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "ucfp_haitsma_streams_push_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "ucfp_haitsma_streams_push": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p,
+                                            C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ucfp_haitsma_streams_blocks_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                  C.c_void_p]),
     "ucfp_audio_batcher_create": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(WangConfig), C.c_size_t, C.c_size_t,
                                             C.c_uint32, C.POINTER(C.c_void_p)]),
     "ucfp_audio_batcher_destroy": (None, [C.c_void_p]),

@@ -5,6 +5,7 @@
     fingerprint_panako / fingerprint_panako_with                              audio.rs:106-156
     fingerprint_haitsma / fingerprint_haitsma_with                            audio.rs:164-224
     StreamingWangSession(sample_rate, tenant_id, record_id).push/.finalize    audio.rs:414-480
+    HaitsmaStreams / StreamingHaitsmaSession                                  DESIGN.md A18 (no reference counterpart)
 
 All DSP runs in the HIP library through the C ABI (ucfp_audio_*); this module validates arguments
 the way the reference does and wraps bytes into `Record`s.
@@ -430,3 +431,150 @@ class StreamingWangSession:
         if not h:
             return []
         return [_record(ALGORITHM_WANG, np.concatenate(h).tobytes(), self.tenant_id, self.record_id)]
+
+
+class HaitsmaStreams:
+    """A set of live Haitsma streams on the device (ucfp_haitsma_streams_*): `push` advances any subset of
+    them by one chunk each with one launch sequence and returns the sub-fingerprints each one emits now -- frames
+    [Fr(before), Fr(after)) of its offline record, the rest on the final push.  `blocks` hands out each stream's latest
+    `block_frames` sub-fingerprints in the ragged shape `HaitsmaIndex.identify_frames` / ucfp_haitsma_index_query_dev take."""
+
+    def __init__(self, max_streams: int, sample_rate: int, cfg: Optional[HaitsmaConfig] = None, block_frames: int = 256,
+                 ctx=None):
+        self._lib = _lib.load()
+        self._cfg = (cfg or HaitsmaConfig())._c()
+        h = C.c_void_p()
+        # as ucfp_haitsma_streams_create: the rate and the band edges are judged before a device is asked for
+        if not (1000 <= int(sample_rate) <= 384_000):
+            raise ModalityError(f"invalid sample rate {sample_rate} (1 000 .. 384 000 Hz)")
+        if not (1.0 <= self._cfg.fmin < self._cfg.fmax <= 2500.0):
+            raise ModalityError("Haitsma band edges must satisfy 1 <= fmin < fmax <= 2500 Hz")
+        self.ctx = ctx or _lib.current_context()
+        _lib.check(self._lib.ucfp_haitsma_streams_create(self.ctx.handle, sample_rate, C.byref(self._cfg), max_streams,
+                                                         block_frames, C.byref(h)))
+        self.handle = h
+        self.max_streams, self.sample_rate, self.block_frames = max_streams, sample_rate, block_frames
+
+    def open(self) -> int:
+        slot = C.c_uint32(0)
+        _lib.check(self._lib.ucfp_haitsma_streams_open(self.handle, C.byref(slot)))
+        return int(slot.value)
+
+    def close(self, slot: int) -> None:
+        """Discards the stream; emits nothing."""
+        _lib.check(self._lib.ucfp_haitsma_streams_close(self.handle, slot))
+
+    def emitted(self, n_samples: int, final: bool = False) -> int:
+        """Fr(n): the frames a stream has emitted once it has received n samples (all of them after a final push)."""
+        return int(self._lib.ucfp_haitsma_stream_frames(n_samples, self.sample_rate, 1 if final else 0))
+
+    def _arrays(self, slots, counts, final):
+        sl = np.ascontiguousarray(slots, dtype=np.uint32)
+        ns = np.ascontiguousarray(counts, dtype=np.uint64)
+        fi = np.array([1 if s in final else 0 for s in sl.tolist()], np.uint8)
+        return sl, ns, fi
+
+    def max_frames(self, slots, counts, final=()) -> int:
+        sl, ns, fi = self._arrays(slots, counts, set(final))
+        return int(self._lib.ucfp_haitsma_streams_max_frames(self.handle, sl.ctypes.data, ns.ctypes.data, fi.ctypes.data,
+                                                             sl.size))
+
+    def push_dev(self, slots, counts, pcm, out, out_offsets, final=(), cap_frames: Optional[int] = None,
+                 stream: int = 0) -> None:
+        """Device variant (no sync): `pcm` the chunks of `slots` concatenated (float32 tensor), `out` an int32 [cap]
+        tensor, `out_offsets` an int64 [len(slots) + 1] tensor; frames of slots[i] = out[out_offsets[i]:out_offsets[i+1]]."""
+        sl, ns, fi = self._arrays(slots, counts, set(final))
+        cap = out.shape[0] if cap_frames is None else cap_frames
+        _lib.check(self._lib.ucfp_haitsma_streams_push_dev(self.handle, sl.ctypes.data, ns.ctypes.data, fi.ctypes.data,
+                                                           sl.size, pcm.data_ptr() if pcm.numel() else None,
+                                                           out.data_ptr() if cap else None, cap, out_offsets.data_ptr(),
+                                                           stream or None))
+
+    def push(self, chunks: dict, final=()) -> dict:
+        """{slot: samples} -> {slot: uint32 [n]} of the sub-fingerprints emitted now; slots in `final` end (and close)."""
+        import torch
+        final = set(final)
+        slots = list(chunks)
+        arrs = [np.ascontiguousarray(chunks[s], dtype=np.float32).reshape(-1) for s in slots]
+        counts = [a.size for a in arrs]
+        dev = f"cuda:{self.ctx.device}"
+        blob = np.concatenate(arrs) if sum(counts) else np.zeros(0, np.float32)
+        d_pcm = torch.from_numpy(blob).to(dev)
+        cap = self.max_frames(slots, counts, final)
+        d_out = torch.zeros(max(cap, 1), dtype=torch.int32, device=dev)
+        d_oo = torch.zeros(len(slots) + 1, dtype=torch.int64, device=dev)
+        self.push_dev(slots, counts, d_pcm, d_out, d_oo, final, cap, torch.cuda.current_stream().cuda_stream)
+        oo = d_oo.cpu().numpy()
+        out = d_out.cpu().numpy().view(np.uint32)
+        return {s: out[oo[i]:oo[i + 1]].copy() for i, s in enumerate(slots)}
+
+    def blocks_dev(self, slots, out, out_offsets, cap_frames: Optional[int] = None, stream: int = 0) -> None:
+        """Device variant (no sync): the live block of slots[i] -> out[out_offsets[i]:out_offsets[i+1]] (`out` an int32
+        tensor of at least len(slots) * block_frames, `out_offsets` an int64 [len(slots) + 1] tensor)."""
+        sl = np.ascontiguousarray(slots, dtype=np.uint32)
+        cap = out.shape[0] if cap_frames is None else cap_frames
+        _lib.check(self._lib.ucfp_haitsma_streams_blocks_dev(self.handle, sl.ctypes.data, sl.size,
+                                                             out.data_ptr() if cap else None, cap, out_offsets.data_ptr(),
+                                                             stream or None))
+
+    def blocks(self, slots) -> dict:
+        """{slot: uint32 [m]}: each stream's latest m = min(block_frames, frames emitted) sub-fingerprints, oldest first."""
+        import torch
+        slots = list(slots)
+        dev = f"cuda:{self.ctx.device}"
+        cap = len(slots) * self.block_frames
+        d_out = torch.zeros(max(cap, 1), dtype=torch.int32, device=dev)
+        d_oo = torch.zeros(len(slots) + 1, dtype=torch.int64, device=dev)
+        self.blocks_dev(slots, d_out, d_oo, cap, torch.cuda.current_stream().cuda_stream)
+        oo = d_oo.cpu().numpy()
+        out = d_out.cpu().numpy().view(np.uint32)
+        return {s: out[oo[i]:oo[i + 1]].copy() for i, s in enumerate(slots)}
+
+    def destroy(self):
+        if getattr(self, "handle", None):
+            self._lib.ucfp_haitsma_streams_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+class StreamingHaitsmaSession:
+    """Push/finalize wrapper on a one-slot HaitsmaStreams, the shape of StreamingWangSession: each `push` moves its PCM to
+    the device and advances the stream there; only the sub-fingerprints emitted so far are held on the host.  `push`
+    returns no records; `finalize` returns one record equal to `fingerprint_haitsma_with` of the whole stream byte for
+    byte, or none when the stream is too short for a frame."""
+
+    def __init__(self, sample_rate: int, tenant_id: int, record_id: int, cfg: Optional[HaitsmaConfig] = None):
+        self.tenant_id, self.record_id = tenant_id, record_id
+        self._set = HaitsmaStreams(1, sample_rate, cfg, block_frames=0)
+        self._slot = self._set.open()
+        self._n = 0
+        self._frames: List[np.ndarray] = []
+
+    def _push(self, samples, final: bool):
+        x = np.ascontiguousarray(samples, dtype=np.float32).reshape(-1)
+        cap = self._set.emitted(self._n + x.size, final) - self._set.emitted(self._n)
+        out = np.zeros(max(cap, 1), np.uint32)
+        n = C.c_size_t(0)
+        _lib.check(self._set._lib.ucfp_haitsma_streams_push(self._set.handle, self._slot, x.ctypes.data if x.size else None,
+                                                            x.size, 1 if final else 0, out.ctypes.data, cap, C.byref(n)))
+        self._n += x.size
+        if n.value:
+            self._frames.append(out[: n.value].copy())
+
+    def push(self, samples) -> List[Record]:
+        self._push(samples, False)
+        return []
+
+    def finalize(self) -> List[Record]:
+        self._push(np.zeros(0, np.float32), True)
+        self._slot = self._set.open()           # the session may be reused
+        self._n = 0
+        f, self._frames = self._frames, []
+        if not f:
+            return []
+        return [_record(ALGORITHM_HAITSMA, np.concatenate(f).tobytes(), self.tenant_id, self.record_id)]

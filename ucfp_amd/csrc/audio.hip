@@ -26,6 +26,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cmath>
+
 #include "../../include/ucfp_fft_tw.h"
 #include "common.h"
 
@@ -40,18 +42,30 @@ constexpr int kHkN = 2048, kHkHop = 64, kHkBands = 33, kHkSr = 5000;
 constexpr int kCandCap = 320;   // > (63/8 + 1) * (512/16) possible peaks per second
 
 // ---- A1 ----------------------------------------------------------------------------------
+// Output sample i of a stream resampled sr_in -> sr_out sits at input position i sr_in / sr_out, exact in integers:
+// the whole part picks the two neighbours, the remainder their weights.  One statement of A1 for the stand-alone kernel,
+// the Haitsma batch and the Haitsma streams (A18: i is the ABSOLUTE index of the stream, rem depends on it).
+struct ResamplePos {
+    uint64_t idx;
+    float frac;
+};
+__device__ __forceinline__ ResamplePos resample_pos(uint64_t i, uint32_t sr_in, uint32_t sr_out) {
+    const uint64_t num = i * sr_in;  // < 2^64 for any buffer that fits in memory
+    const uint32_t rem = (uint32_t)(num % sr_out);
+    return ResamplePos{num / sr_out, (float)((double)rem / (double)sr_out)};
+}
+__device__ __forceinline__ float resample_mix(float x0, float x1, float frac) {
+    const float d = x1 - x0;
+    const float mm = d * frac;
+    return x0 + mm;
+}
+
 __global__ void resample_linear_kernel(const float* __restrict__ in, size_t n, uint32_t sr_in, uint32_t sr_out,
                                        float* __restrict__ out, size_t m) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= m) return;
-    const uint64_t num = (uint64_t)i * sr_in;  // < 2^64 for any buffer that fits in memory
-    const size_t idx = (size_t)(num / sr_out);
-    const uint32_t rem = (uint32_t)(num % sr_out);
-    const float frac = (float)((double)rem / (double)sr_out);
-    const float x0 = in[idx], x1 = in[idx + 1 < n ? idx + 1 : n - 1];
-    const float d = x1 - x0;
-    const float mm = d * frac;
-    out[i] = x0 + mm;
+    const ResamplePos p = resample_pos(i, sr_in, sr_out);
+    out[i] = resample_mix(in[p.idx], in[p.idx + 1 < n ? p.idx + 1 : n - 1], p.frac);
 }
 
 // ---- A2/A3: one wave per frame, real-input FFT register-tiled -------------------------------------
@@ -1210,6 +1224,19 @@ __global__ void wang_clip_offsets_kernel(const uint32_t* __restrict__ sec_base, 
 }
 
 // ---- A8 ------------------------------------------------------------------------------------
+// cur / prv: the 33 band energies of a frame and of the frame before it (prv = nullptr: zero history)
+__device__ __forceinline__ uint32_t haitsma_bits_of(const float* __restrict__ cur, const float* __restrict__ prv) {
+    uint32_t h = 0;
+#pragma unroll
+    for (int b = 0; b < 32; b++) {
+        const float c = cur[b] - cur[b + 1];
+        const float p = prv ? prv[b] - prv[b + 1] : 0.0f;
+        const float dd = c - p;
+        if (dd > 0.0f) h |= 1u << b;
+    }
+    return h;
+}
+
 __global__ void haitsma_bits_kernel(const float* __restrict__ E, size_t first, size_t n, uint32_t* __restrict__ out,
                                     const uint64_t* __restrict__ src_map = nullptr, size_t cap = ~(size_t)0) {
     // E holds frames [first - 1, first + n) when first > 0 (row 0 = previous frame), else [0, n)
@@ -1223,16 +1250,7 @@ __global__ void haitsma_bits_kernel(const float* __restrict__ E, size_t first, s
         if (m == kFrameNone) return;
         has_prev = !(m & kFrameFirst);        // a clip's first frame has a zero history (A8), whatever precedes it in the batch
     }
-    const float* prv = cur - kHkBands;
-    uint32_t h = 0;
-#pragma unroll
-    for (int b = 0; b < 32; b++) {
-        const float c = cur[b] - cur[b + 1];
-        const float p = has_prev ? prv[b] - prv[b + 1] : 0.0f;
-        const float dd = c - p;
-        if (dd > 0.0f) h |= 1u << b;
-    }
-    out[first + i] = h;
+    out[first + i] = haitsma_bits_of(cur, has_prev ? cur - kHkBands : nullptr);
 }
 
 // ---- Haitsma over a ragged batch of clips ------------------------------------------------------------------------
@@ -1300,14 +1318,8 @@ __global__ void haitsma_resample_batch_kernel(const float* __restrict__ in, cons
     const size_t c = upper_clip(s5_off, n_clips, g);
     const uint64_t i = g - s5_off[c], n = offsets[c + 1] - offsets[c];
     const float* src = in + offsets[c];
-    const uint64_t num = i * sr;
-    const size_t idx = (size_t)(num / kHkSr);
-    const uint32_t rem = (uint32_t)(num % kHkSr);
-    const float frac = (float)((double)rem / (double)kHkSr);
-    const float x0 = src[idx], x1 = src[idx + 1 < n ? idx + 1 : n - 1];
-    const float d = x1 - x0;
-    const float mm = d * frac;
-    out[g] = x0 + mm;
+    const ResamplePos p = resample_pos(i, sr, (uint32_t)kHkSr);
+    out[g] = resample_mix(src[p.idx], src[p.idx + 1 < n ? p.idx + 1 : n - 1], p.frac);
 }
 
 // Frame g of the batch -> where its 2048 samples start (in the 5 kHz stream, or in the caller's own when sr = 5000).
@@ -1495,6 +1507,104 @@ __global__ __launch_bounds__(256) void wang_streams_save_kernel(const WangStream
     if (tid == 0) {
         st.cand_n[e.slot] = c;
         st.ret_n[e.slot] = r;
+    }
+}
+
+// ---- streaming Haitsma (A18): the kernels around stft_power_kernel<2048, true> for one push of a stream set.
+// The host builds the push's table (HaitsmaPushWs); every kernel here runs over all the push's streams at once.
+
+// input sample a of the entry's stream, a in [c_in, n1): carried in the state or in the chunk
+__device__ __forceinline__ float haitsma_stream_input(const HaitsmaStreamEntry& e, const HaitsmaStreamsDev& st,
+                                                      const float* __restrict__ pcm, uint64_t a) {
+    return a < e.n0 ? st.carry[(size_t)e.slot * st.carry_cap + (a - e.c_in)] : pcm[e.chunk_off + (a - e.n0)];
+}
+
+// Assemble: run i = the carried tail of its stream, then the 5 kHz samples that became final (A1 at the absolute index)
+__global__ void haitsma_streams_assemble_kernel(const float* __restrict__ pcm, const HaitsmaStreamEntry* __restrict__ ents,
+                                                const uint32_t* __restrict__ run_base, uint32_t n, HaitsmaStreamsDev st,
+                                                uint32_t sr, float* __restrict__ run) {
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= run_base[n]) return;
+    const uint32_t i = clip_of(run_base, n, g);
+    const HaitsmaStreamEntry e = ents[i];
+    const uint32_t r = g - run_base[i];
+    if (r < e.tail_in) {
+        run[g] = st.tail[(size_t)e.slot * kHkTailCap + r];
+        return;
+    }
+    const uint64_t o = e.s0 + (r - e.tail_in);
+    if (sr == (uint32_t)kHkSr) {                 // the offline path does not resample then
+        run[g] = haitsma_stream_input(e, st, pcm, o);
+        return;
+    }
+    const ResamplePos p = resample_pos(o, sr, (uint32_t)kHkSr);
+    uint64_t a1 = p.idx + 1;                     // < n1 by the emission rule, except on the final push
+    if (e.fin && a1 >= e.n1) a1 = e.n1 - 1;
+    run[g] = resample_mix(haitsma_stream_input(e, st, pcm, p.idx), haitsma_stream_input(e, st, pcm, a1), p.frac);
+}
+
+// frame g of the push -> where its 2048 samples start in `run`; fr_base is also the caller's output offset table
+__global__ void haitsma_streams_map_kernel(const uint32_t* __restrict__ run_base, const uint32_t* __restrict__ fr_base,
+                                           uint32_t n, uint64_t* __restrict__ src_map, uint64_t* __restrict__ out_off) {
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g <= n) out_off[g] = fr_base[g];
+    if (g >= fr_base[n]) return;
+    const uint32_t i = clip_of(fr_base, n, g);
+    src_map[g] = (uint64_t)run_base[i] + (uint64_t)(g - fr_base[i]) * kHkHop;
+}
+
+// Bits (A8), one thread per frame.  E as in haitsma_bits_kernel; the row before an entry's first frame of the push is the
+// one its state carries (zeros for the stream's frame 0); an entry's last row goes to last_e for Save.
+__global__ void haitsma_streams_bits_kernel(const float* __restrict__ E, uint32_t first, uint32_t cnt,
+                                            const HaitsmaStreamEntry* __restrict__ ents,
+                                            const uint32_t* __restrict__ fr_base, uint32_t n, HaitsmaStreamsDev st,
+                                            float* __restrict__ last_e, uint32_t* __restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cnt) return;
+    const uint32_t g = first + i;
+    const float* cur = E + (size_t)(first > 0 ? i + 1 : i) * kHkBands;
+    const uint32_t c = clip_of(fr_base, n, g);
+    const float* prv = cur - kHkBands;
+    if (g == fr_base[c]) prv = ents[c].f0 == 0 ? nullptr : st.energy + (size_t)ents[c].slot * kHkEnergies;
+    out[g] = haitsma_bits_of(cur, prv);
+    if (g + 1 == fr_base[c + 1])
+        for (int b = 0; b < kHkBands; b++) last_e[(size_t)c * kHkEnergies + b] = cur[b];
+}
+
+// Save, one workgroup per entry: what the next push needs goes back into the stream's state.  Everything it reads was
+// written by the kernels before it, except the carried inputs, which may move inside the slot's own buffer: each is read
+// by the thread that writes it, with a barrier in between.
+constexpr int kHkSaveThreads = 256;
+__global__ __launch_bounds__(kHkSaveThreads) void haitsma_streams_save_kernel(
+    const float* __restrict__ pcm, const HaitsmaStreamEntry* __restrict__ ents, const uint32_t* __restrict__ run_base,
+    const uint32_t* __restrict__ fr_base, HaitsmaStreamsDev st, const float* __restrict__ run,
+    const float* __restrict__ last_e, const uint32_t* __restrict__ out) {
+    const HaitsmaStreamEntry e = ents[blockIdx.x];
+    if (e.fin) return;                            // the slot closes: `open` starts it from nothing
+    const uint32_t tid = threadIdx.x;
+    const uint32_t frames = fr_base[blockIdx.x + 1] - fr_base[blockIdx.x];
+    const uint32_t n_carry = (uint32_t)(e.n1 - e.c_out);          // <= carry_cap <= kHkSaveThreads
+    const float v = tid < n_carry ? haitsma_stream_input(e, st, pcm, e.c_out + tid) : 0.0f;
+    __syncthreads();
+    if (tid < n_carry) st.carry[(size_t)e.slot * st.carry_cap + tid] = v;
+    const float* keep = run + run_base[blockIdx.x] + (size_t)frames * kHkHop;
+    for (uint32_t i = tid; i < e.tail_out; i += kHkSaveThreads) st.tail[(size_t)e.slot * kHkTailCap + i] = keep[i];
+    if (frames == 0) return;                      // the last energies and the ring stay as they are
+    if (tid < (uint32_t)kHkBands) st.energy[(size_t)e.slot * kHkEnergies + tid] = last_e[(size_t)blockIdx.x * kHkEnergies + tid];
+    for (uint32_t j = (frames > st.block ? frames - st.block : 0) + tid; j < frames && st.block; j += kHkSaveThreads)
+        st.ring[(size_t)e.slot * st.block + (e.f0 + j) % st.block] = out[fr_base[blockIdx.x] + j];
+}
+
+// one workgroup per item: the slot's latest m frames leave its ring in time order
+__global__ __launch_bounds__(256) void haitsma_streams_blocks_kernel(const HaitsmaBlockEntry* __restrict__ tab, uint32_t n,
+                                                                     HaitsmaStreamsDev st, uint32_t* __restrict__ out,
+                                                                     uint64_t* __restrict__ off) {
+    const HaitsmaBlockEntry e = tab[blockIdx.x];
+    for (uint32_t j = threadIdx.x; j < e.m; j += 256)
+        out[e.out_off + j] = st.ring[(size_t)e.slot * st.block + (e.start + j) % st.block];
+    if (threadIdx.x == 0) {
+        off[blockIdx.x] = e.out_off;
+        if (blockIdx.x + 1 == n) off[n] = e.out_off + e.m;
     }
 }
 
@@ -1861,6 +1971,92 @@ int launch_wang_streams_push(const float* pcm, const WangStreamsDev& st, uint32_
                        (const uint32_t*)u32(w.np), st, (const float*)f32(w.vbuf), (const uint32_t*)u32(w.cand_cnt),
                        (const uint32_t*)u32(w.cand_t), (const uint32_t*)u32(w.cand_k), (const float*)f32(w.cand_p),
                        (const uint32_t*)u32(w.pt), (const float*)f32(w.pp));
+    return 0;
+}
+
+// ---- streaming Haitsma orchestration (A18) ----------------------------------------------------------
+void haitsma_band_edges(float fmin, float fmax, uint32_t edges[34]) {
+    for (int b = 0; b <= kHkBands; b++) {
+        const double f = (double)fmin * pow((double)fmax / (double)fmin, (double)b / kHkBands);
+        const double bin = f * kHkN / kHkSr;
+        uint32_t e = (uint32_t)ceil(bin);
+        if (e > (uint32_t)kHkN / 2) e = kHkN / 2;
+        edges[b] = e;
+    }
+}
+
+static_assert(kHkTailCap == (uint32_t)kHkN && kHkEnergies == (uint32_t)kHkBands, "");
+
+HaitsmaPushWs haitsma_push_layout(size_t n, size_t total_run, size_t total_frames) {
+    auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    HaitsmaPushWs w;
+    w.n = n;
+    w.total_run = total_run;
+    w.total_frames = total_frames;
+    const size_t chunk = total_frames < kChunkFrames * 4 ? total_frames : kChunkFrames * 4;
+    size_t off = 0;
+    w.ents = off;      off += n * sizeof(HaitsmaStreamEntry);
+    w.run_base = off;  off += (n + 1) * 4;
+    w.fr_base = off;   off += (n + 1) * 4;
+    w.tab_bytes = off; off = align(off);
+    w.run = off;       off = align(off + total_run * 4);
+    w.src_map = off;   off = align(off + total_frames * 8);
+    w.E = off;         off = align(off + (chunk + 1) * kHkBands * 4);
+    w.last_e = off;    off = align(off + n * kHkEnergies * 4);
+    w.total = off + 256;
+    return w;
+}
+
+// The table [ws + w.ents, ws + w.tab_bytes) is on the device already (the caller copies it in front of this).
+// Launches: assemble, map, (transform, bits) per chunk of frames, save -- whatever n is.
+int launch_haitsma_streams_push(const float* pcm, const HaitsmaStreamsDev& st, uint32_t sr, uint8_t* ws,
+                                const HaitsmaPushWs& w, uint32_t* out, uint64_t* d_out_off, hipStream_t stream) {
+    const uint32_t n = (uint32_t)w.n;
+    if (n == 0) {
+        (void)hipMemsetAsync(d_out_off, 0, 8, stream);
+        return 0;
+    }
+    const HaitsmaStreamEntry* ents = reinterpret_cast<const HaitsmaStreamEntry*>(ws + w.ents);
+    const uint32_t* run_base = reinterpret_cast<const uint32_t*>(ws + w.run_base);
+    const uint32_t* fr_base = reinterpret_cast<const uint32_t*>(ws + w.fr_base);
+    float* run = reinterpret_cast<float*>(ws + w.run);
+    uint64_t* src_map = reinterpret_cast<uint64_t*>(ws + w.src_map);
+    float* E = reinterpret_cast<float*>(ws + w.E);
+    float* last_e = reinterpret_cast<float*>(ws + w.last_e);
+    if (w.total_run)
+        hipLaunchKernelGGL(haitsma_streams_assemble_kernel, dim3(blocks_for(w.total_run, 256)), dim3(256), 0, stream, pcm,
+                           ents, run_base, n, st, sr, run);
+    const size_t frames = w.total_frames;
+    hipLaunchKernelGGL(haitsma_streams_map_kernel, dim3(blocks_for(frames > n + 1 ? frames : n + 1, 256)), dim3(256), 0,
+                       stream, run_base, fr_base, n, src_map, d_out_off);
+    const size_t lds = sizeof(FftLds<kHkN>);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(stft_power_kernel<kHkN, true>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const size_t chunk = kChunkFrames * 4;
+    for (size_t e0 = 0; e0 < frames; e0 += chunk) {
+        const size_t e1 = e0 + chunk < frames ? e0 + chunk : frames;
+        const size_t w0 = e0 > 0 ? e0 - 1 : 0;  // one frame of history for the time difference
+        const size_t wn = e1 - w0;
+        unsigned grid = blocks_for(wn, kFftWaves);
+        if (grid > 256) grid = 256;
+        hipLaunchKernelGGL((stft_power_kernel<kHkN, true>), dim3(grid), dim3(kFftWaves * 64), lds, stream, (const float*)run,
+                           w0, wn, kHkHop, E, (const uint32_t*)st.edges, (float*)nullptr, (const uint64_t*)src_map);
+        hipLaunchKernelGGL(haitsma_streams_bits_kernel, dim3(blocks_for(e1 - e0, 256)), dim3(256), 0, stream,
+                           (const float*)E, (uint32_t)e0, (uint32_t)(e1 - e0), ents, fr_base, n, st, last_e, out);
+    }
+    hipLaunchKernelGGL(haitsma_streams_save_kernel, dim3(n), dim3(kHkSaveThreads), 0, stream, pcm, ents, run_base, fr_base,
+                       st, (const float*)run, (const float*)last_e, (const uint32_t*)out);
+    return 0;
+}
+
+int launch_haitsma_streams_blocks(const HaitsmaBlockEntry* d_tab, size_t n, const HaitsmaStreamsDev& st, uint32_t* out,
+                                  uint64_t* d_off, hipStream_t stream) {
+    if (n == 0) {
+        (void)hipMemsetAsync(d_off, 0, 8, stream);
+        return 0;
+    }
+    hipLaunchKernelGGL(haitsma_streams_blocks_kernel, dim3((uint32_t)n), dim3(256), 0, stream, d_tab, (uint32_t)n, st, out,
+                       d_off);
     return 0;
 }
 

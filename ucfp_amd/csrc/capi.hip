@@ -45,6 +45,15 @@ constexpr size_t kNormWsFrames = 2048;  // generic-geometry normalised planes he
 
 namespace ucfp {
 int ctx_device(const ucfp_ctx* ctx) { return ctx->device; }
+bool have_gfx950() {
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return false;
+    for (int d = 0; d < count; d++) {
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, d) == hipSuccess && strncmp(prop.gcnArchName, "gfx950", 6) == 0) return true;
+    }
+    return false;
+}
 int image_any_geometry_ready(ucfp_ctx* ctx, uint32_t w) {
     if (w > 2048) return (int)hipErrorInvalidValue;
     std::lock_guard<std::mutex> lk(ctx->geo_mu);
@@ -713,16 +722,6 @@ int ucfp_audio_resample_linear_dev(ucfp_ctx* ctx, const float* d_in, size_t n, u
     return UCFP_OK;
 }
 
-static void haitsma_edges(float fmin, float fmax, uint32_t edges[34]) {
-    for (int b = 0; b <= 33; b++) {
-        const double f = (double)fmin * pow((double)fmax / (double)fmin, (double)b / 33);
-        const double bin = f * 2048 / 5000;
-        uint32_t e = (uint32_t)ceil(bin);
-        if (e > 1024) e = 1024;
-        edges[b] = e;
-    }
-}
-
 size_t ucfp_audio_haitsma_frames(size_t n_samples, uint32_t sample_rate) {
     if (!sample_rate) return 0;
     const size_t n5 = sample_rate == 5000 ? n_samples : ucfp::audio_resample_len(n_samples, sample_rate, 5000);
@@ -740,7 +739,7 @@ int ucfp_audio_haitsma_dev(ucfp_ctx* ctx, const float* d_pcm5k, size_t n, const 
     if (frames == 0) return UCFP_OK;
     if (!d_pcm5k || !d_out) return fail(UCFP_E_INVALID, "NULL buffer");
     uint32_t edges[34];
-    haitsma_edges(fmin, fmax, edges);
+    ucfp::haitsma_band_edges(fmin, fmax, edges);
     hipStream_t st = (hipStream_t)stream;
     std::lock_guard<std::mutex> lk(ctx->mu);
     HIP_TRY(hipSetDevice(ctx->device));
@@ -774,7 +773,7 @@ int ucfp_audio_haitsma_batch_dev(ucfp_ctx* ctx, const float* d_pcm, const uint64
     if (!(fmin >= 1.0f) || !(fmax > fmin) || !(fmax <= 2500.0f))
         return fail(UCFP_E_MODALITY, "Haitsma band edges must satisfy 1 <= fmin < fmax <= 2500 Hz");
     uint32_t edges[34];
-    haitsma_edges(fmin, fmax, edges);
+    ucfp::haitsma_band_edges(fmin, fmax, edges);
     const ucfp::HaitsmaBatchWs w = ucfp::haitsma_batch_ws(n_total, n_clips, sample_rate);
     hipStream_t st = (hipStream_t)stream;
     std::lock_guard<std::mutex> lk(ctx->mu);

@@ -11,6 +11,8 @@ namespace ucfp {
 // capi.hip: sets the thread's last error message and returns `code`
 int capi_fail(int code, const char* fmt, ...);
 int ctx_device(const ucfp_ctx* ctx);
+// a stream set needs a gfx950 device; a NULL context on a host without one is "no device", not a caller bug
+bool have_gfx950();
 
 }  // namespace ucfp
 
@@ -415,5 +417,49 @@ int launch_haitsma_batch(const float* pcm, const uint64_t* d_offsets, size_t n_t
 size_t haitsma_ws_bytes(size_t n5k);
 int launch_haitsma(const float* pcm5k, size_t n, const uint32_t* h_edges, uint8_t* ws, uint32_t* out,
                    hipStream_t stream);
+void haitsma_band_edges(float fmin, float fmax, uint32_t edges[34]);   // host: the 34 FFT-bin edges of the 33 bands (A7)
+
+// ---- streaming Haitsma (A18): one push of a stream set (haitsma_streams.hip plans it, audio.hip runs it) ----
+constexpr uint32_t kHkTailCap = 2048;     // carried 5 kHz samples per stream: those of the next frame, <= 2047
+constexpr uint32_t kHkEnergies = 33;      // band energies of the last emitted frame
+// One stream's share of a push: a run of 5 kHz samples = its carried tail followed by the samples that became final,
+// whose frame j (64 j into the run) is frame f0 + j of the stream.  Sample positions are absolute (since `open`).
+struct HaitsmaStreamEntry {
+    uint64_t s0;          // 5 kHz index of the first new sample of the run
+    uint64_t n0, n1;      // input samples before / after the push
+    uint64_t c_in;        // the state's carried inputs are samples [c_in, n0)
+    uint64_t c_out;       // ... and [c_out, n1) after the push
+    uint64_t f0;          // stream frame of the run's frame 0 (0: zero history)
+    uint64_t chunk_off;   // the entry's chunk in the caller's buffer
+    uint32_t slot;
+    uint32_t tail_in;     // carried 5 kHz samples at the head of the run
+    uint32_t tail_out;    // 5 kHz samples carried into the next push: the run from frame `frames` on
+    uint32_t fin;         // final push: idx + 1 clamps to n1 - 1 (A1), nothing is saved
+};
+// device state of a stream set, per slot (sized at creation)
+struct HaitsmaStreamsDev {
+    float* tail;          // [slots][kHkTailCap]
+    float* carry;         // [slots][carry_cap] input samples the next output still needs
+    float* energy;        // [slots][kHkEnergies]
+    uint32_t* ring;       // [slots][block] the latest sub-fingerprints, frame f at f % block
+    uint32_t* edges;      // [34]
+    uint32_t carry_cap, block;
+};
+// one push in the context's workspace; [ents, ents + tab_bytes) is the host-built table:
+// ents[n], run_base[n + 1] (runs in `run`), fr_base[n + 1] (frames of the push = the output offsets)
+struct HaitsmaPushWs {
+    size_t n = 0, total_run = 0, total_frames = 0;
+    size_t ents, run_base, fr_base, tab_bytes, run, src_map, E, last_e, total = 0;
+};
+HaitsmaPushWs haitsma_push_layout(size_t n, size_t total_run, size_t total_frames);
+int launch_haitsma_streams_push(const float* pcm, const HaitsmaStreamsDev& st, uint32_t sr, uint8_t* ws,
+                                const HaitsmaPushWs& w, uint32_t* out, uint64_t* d_out_off, hipStream_t stream);
+// the latest m frames of a slot, from its ring, in time order
+struct HaitsmaBlockEntry {
+    uint64_t out_off;     // first frame of the item in the output
+    uint32_t slot, start, m, pad;    // ring positions (start + j) % block, j < m
+};
+int launch_haitsma_streams_blocks(const HaitsmaBlockEntry* d_tab, size_t n, const HaitsmaStreamsDev& st, uint32_t* out,
+                                  uint64_t* d_off, hipStream_t stream);
 
 }  // namespace ucfp

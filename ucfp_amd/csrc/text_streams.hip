@@ -509,17 +509,6 @@ int push_impl(ucfp_text_streams* s, const uint32_t* slots, const uint64_t* n_byt
     return UCFP_OK;
 }
 
-// a set needs a gfx950 device; a NULL context on a host without one is "no device", not a caller bug
-bool have_gfx950() {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return false;
-    for (int d = 0; d < count; d++) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, d) == hipSuccess && strncmp(prop.gcnArchName, "gfx950", 6) == 0) return true;
-    }
-    return false;
-}
-
 }  // namespace
 
 extern "C" {
@@ -544,7 +533,7 @@ int ucfp_text_streams_create_ex(ucfp_ctx* ctx, uint32_t shingle_k, uint32_t max_
     if (utf8 && (max_push_bytes == 0 || max_push_bytes > kMaxPushBytes))
         return fail(UCFP_E_INVALID, "max_push_bytes %llu outside [1, 2^28]", (unsigned long long)max_push_bytes);
     if (!ctx) {
-        if (!have_gfx950()) return fail(UCFP_E_INDEX, "no gfx950 device available; this library has no CPU path");
+        if (!ucfp::have_gfx950()) return fail(UCFP_E_INDEX, "no gfx950 device available; this library has no CPU path");
         return fail(UCFP_E_INVALID, "ctx is NULL");
     }
     if (max_streams == 0 || max_streams > (1u << 20)) return fail(UCFP_E_INVALID, "max_streams %u outside [1, 2^20]", max_streams);

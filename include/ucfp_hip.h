@@ -420,6 +420,56 @@ int ucfp_wang_streams_push_dev(ucfp_wang_streams* s, const uint32_t* slots, cons
 int ucfp_wang_streams_push(ucfp_wang_streams* s, uint32_t slot, const float* pcm, size_t n, int final, uint8_t* out,
                            size_t cap_hashes, size_t* n_hashes);
 
+/* STREAMING Panako (the reference has no streaming Panako): the stream set above with triplets behind
+ * the same front end, plus a LIVE WINDOW per stream for ucfp_panako_index_query*.  A slot is one stream at 8 kHz.  After
+ * a push that brings a stream to n samples the records emitted so far are exactly the offline records
+ * (ucfp_audio_panako on the same samples) with t_a < F(n) (ucfp_panako_stream_frontier: A9's rule with the Panako
+ * target_zone_t), in offline order; a final push emits the rest.  The concatenation over all pushes equals
+ * ucfp_audio_panako of the whole stream byte for byte, however the stream is cut into chunks.  t_a, t_b, t_c count
+ * frames since the stream was opened (u32; the 2^23-frame limit of one offline clip does not apply).
+ *   - window_frames = W (0 .. UCFP_PANAKO_STREAM_MAX_WINDOW_FRAMES; 0 = no windows).  The window of an open stream at n
+ *     samples is its emitted records with t_a >= w0 = max(0, F(n) - W), in emission order, with w0 subtracted from
+ *     t_a, t_b and t_c (a query's t_a must stay below 2^28); at most ucfp_panako_streams_window_cap(cfg, W) =
+ *     (ceil(2 W / 125) + 1) * peaks_per_sec * fan_out records.  Nothing emitted yet, a final push or close: empty.
+ *     A hit's `offset` then says where stream frame w0 lies in the matched record.
+ *   - Device bytes per stream: ucfp_panako_streams_state_bytes(cfg, W) = the Wang state for this config, plus (W != 0)
+ *     8 bytes of ring header and 16 bytes per window record.
+ *   - Serialisation, errors and "a failed call changes no state" as the Wang set; W above the maximum, a misaligned
+ *     record buffer, a window call on a set without windows: UCFP_E_INVALID. */
+typedef struct ucfp_panako_streams ucfp_panako_streams;
+#define UCFP_PANAKO_STREAM_MAX_WINDOW_FRAMES 8192u /* 131 s */
+/* sample_rate must be 8000, cfg inside the ranges of ucfp_panako_config (NULL = defaults): UCFP_E_MODALITY otherwise,
+ * checked before anything else. */
+int ucfp_panako_streams_create(ucfp_ctx* ctx, uint32_t sample_rate, const ucfp_panako_config* cfg, uint32_t max_streams,
+                               uint32_t window_frames, ucfp_panako_streams** out);
+void ucfp_panako_streams_destroy(ucfp_panako_streams* s);
+int ucfp_panako_streams_open(ucfp_panako_streams* s, uint32_t* slot);     /* fresh stream, t = 0, empty window */
+int ucfp_panako_streams_close(ucfp_panako_streams* s, uint32_t slot);     /* discard, emit nothing */
+/* Host-only, no GPU: F(n) as ucfp_wang_stream_frontier, with the Panako target_zone_t. */
+uint64_t ucfp_panako_stream_frontier(uint64_t n_samples, const ucfp_panako_config* cfg);
+/* Host-only: device bytes a set holds per stream (0 for an out-of-range config or window). */
+size_t ucfp_panako_streams_state_bytes(const ucfp_panako_config* cfg, uint32_t window_frames);
+/* Host-only: records one stream's window can hold (0 for window_frames = 0 or out-of-range arguments). */
+size_t ucfp_panako_streams_window_cap(const ucfp_panako_config* cfg, uint32_t window_frames);
+/* Upper bound on the records a push can emit (0 for an invalid push). */
+size_t ucfp_panako_streams_max_hashes(ucfp_panako_streams* s, const uint32_t* slots, const uint64_t* n_samples,
+                                      const uint8_t* final, size_t n);
+/* As ucfp_wang_streams_push_dev; records of entry i -> d_out[d_out_offsets[i] .. d_out_offsets[i+1]) in RECORDS (16 B
+ * each; n + 1 device u64).  d_out must be 16-byte aligned.  cap_hashes below ucfp_panako_streams_max_hashes ->
+ * UCFP_E_INVALID before ANY state changes.  No host synchronisation. */
+int ucfp_panako_streams_push_dev(ucfp_panako_streams* s, const uint32_t* slots, const uint64_t* n_samples,
+                                 const uint8_t* final, size_t n, const float* d_pcm, uint8_t* d_out, size_t cap_hashes,
+                                 uint64_t* d_out_offsets, void* stream);
+/* Host-pointer convenience for one slot; synchronous.  *n_hashes = records of this push. */
+int ucfp_panako_streams_push(ucfp_panako_streams* s, uint32_t slot, const float* pcm, size_t n, int final, uint8_t* out,
+                             size_t cap_hashes, size_t* n_hashes);
+/* The live windows of n distinct open slots: item i = d_records[d_offsets[i] .. d_offsets[i+1]) with BYTE offsets
+ * (multiples of 16, n + 1 device u64) -- the query shape of ucfp_panako_index_query_dev -- and d_origins[i] = w0 (device
+ * u32, may be NULL).  cap_records (16-byte records d_records holds) below n * ucfp_panako_streams_window_cap ->
+ * UCFP_E_INVALID.  No host synchronisation. */
+int ucfp_panako_streams_windows_dev(ucfp_panako_streams* s, const uint32_t* slots, size_t n, uint8_t* d_records,
+                                    size_t cap_records, uint64_t* d_offsets, uint32_t* d_origins, void* stream);
+
 size_t ucfp_audio_haitsma_frames(size_t n_samples, uint32_t sample_rate);
 int ucfp_audio_haitsma(ucfp_ctx* ctx, const float* pcm, size_t n, uint32_t sample_rate,
                        const ucfp_haitsma_config* cfg, uint32_t* out, size_t cap_frames, size_t* n_frames);

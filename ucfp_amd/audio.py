@@ -6,6 +6,7 @@
     fingerprint_haitsma / fingerprint_haitsma_with                            audio.rs:164-224
     StreamingWangSession(sample_rate, tenant_id, record_id).push/.finalize    audio.rs:414-480
     HaitsmaStreams / StreamingHaitsmaSession                                  DESIGN.md A18 (no reference counterpart)
+    PanakoStreams / StreamingPanakoSession                                    DESIGN.md A19 (no reference counterpart)
 
 All DSP runs in the HIP library through the C ABI (ucfp_audio_*); this module validates arguments
 the way the reference does and wraps bytes into `Record`s.
@@ -578,3 +579,151 @@ class StreamingHaitsmaSession:
         if not f:
             return []
         return [_record(ALGORITHM_HAITSMA, np.concatenate(f).tobytes(), self.tenant_id, self.record_id)]
+
+
+class PanakoStreams:
+    """A set of live Panako streams on the device (ucfp_panako_streams_*): `push` advances any subset of
+    them by one chunk each with one launch sequence and returns the records each one emits now -- exactly the offline
+    records with t_a < frontier(n) so far, the rest on the final push (times = frames since `open`).  With
+    `window_frames` = W > 0, `windows` hands out each stream's latest W frames of records, rebased to the window's
+    origin, in the ragged shape `PanakoIndex.query_dev` / ucfp_panako_index_query_dev take."""
+
+    def __init__(self, max_streams: int, cfg: Optional[PanakoConfig] = None, window_frames: int = 0,
+                 sample_rate: int = WANG_SR, ctx=None):
+        self._lib = _lib.load()
+        self.ctx = ctx or _lib.current_context()
+        self._cfg = (cfg or PanakoConfig())._c()
+        h = C.c_void_p()
+        _lib.check(self._lib.ucfp_panako_streams_create(self.ctx.handle, sample_rate, C.byref(self._cfg), max_streams,
+                                                        window_frames, C.byref(h)))
+        self.handle = h
+        self.max_streams, self.window_frames = max_streams, window_frames
+        self.window_cap = int(self._lib.ucfp_panako_streams_window_cap(C.byref(self._cfg), window_frames))
+
+    def open(self) -> int:
+        slot = C.c_uint32(0)
+        _lib.check(self._lib.ucfp_panako_streams_open(self.handle, C.byref(slot)))
+        return int(slot.value)
+
+    def close(self, slot: int) -> None:
+        """Discards the stream and its window; emits nothing."""
+        _lib.check(self._lib.ucfp_panako_streams_close(self.handle, slot))
+
+    def frontier(self, n_samples: int) -> int:
+        """F(n): after a non-final push, every record with t_a < F(n) has been emitted, and no other."""
+        return int(self._lib.ucfp_panako_stream_frontier(n_samples, C.byref(self._cfg)))
+
+    def _arrays(self, slots, counts, final):
+        sl = np.ascontiguousarray(slots, dtype=np.uint32)
+        ns = np.ascontiguousarray(counts, dtype=np.uint64)
+        fi = np.array([1 if s in final else 0 for s in sl.tolist()], np.uint8)
+        return sl, ns, fi
+
+    def max_hashes(self, slots, counts, final=()) -> int:
+        sl, ns, fi = self._arrays(slots, counts, set(final))
+        return int(self._lib.ucfp_panako_streams_max_hashes(self.handle, sl.ctypes.data, ns.ctypes.data, fi.ctypes.data,
+                                                            sl.size))
+
+    def push_dev(self, slots, counts, pcm, out, out_offsets, final=(), cap_hashes: Optional[int] = None,
+                 stream: int = 0) -> None:
+        """Device variant (no sync): `pcm` the chunks of `slots` concatenated (float32 tensor), `out` an int32 [cap, 4]
+        tensor (16-byte aligned), `out_offsets` an int64 [len(slots) + 1] tensor; records of slots[i] =
+        out[out_offsets[i]:out_offsets[i+1]]."""
+        sl, ns, fi = self._arrays(slots, counts, set(final))
+        cap = out.shape[0] if cap_hashes is None else cap_hashes
+        _lib.check(self._lib.ucfp_panako_streams_push_dev(self.handle, sl.ctypes.data, ns.ctypes.data, fi.ctypes.data,
+                                                          sl.size, pcm.data_ptr() if pcm.numel() else None,
+                                                          out.data_ptr() if cap else None, cap, out_offsets.data_ptr(),
+                                                          stream or None))
+
+    def push(self, chunks: dict, final=()) -> dict:
+        """{slot: samples} -> {slot: uint32 [n, 4]} of the records emitted now; slots in `final` end (and close)."""
+        import torch
+        final = set(final)
+        slots = list(chunks)
+        arrs = [np.ascontiguousarray(chunks[s], dtype=np.float32).reshape(-1) for s in slots]
+        counts = [a.size for a in arrs]
+        cap = self.max_hashes(slots, counts, final)
+        dev = f"cuda:{self.ctx.device}"
+        blob = np.concatenate(arrs) if sum(counts) else np.zeros(0, np.float32)
+        d_pcm = torch.from_numpy(blob).to(dev)
+        d_out = torch.zeros((max(cap, 1), 4), dtype=torch.int32, device=dev)
+        d_oo = torch.zeros(len(slots) + 1, dtype=torch.int64, device=dev)
+        self.push_dev(slots, counts, d_pcm, d_out, d_oo, final, cap, torch.cuda.current_stream().cuda_stream)
+        oo = d_oo.cpu().numpy()
+        out = d_out.cpu().numpy().view(np.uint32)
+        return {s: out[oo[i]:oo[i + 1]].copy() for i, s in enumerate(slots)}
+
+    def windows_dev(self, slots, records, offsets, origins=None, cap_records: Optional[int] = None,
+                    stream: int = 0) -> None:
+        """Device variant (no sync): the live window of slots[i] -> the bytes records[offsets[i]:offsets[i+1]] (`records`
+        an int32 [cap, 4] tensor of at least len(slots) * window_cap records, `offsets` an int64 [len(slots) + 1] tensor
+        of BYTE offsets, `origins` an optional int32 [len(slots)] tensor of the windows' first frames)."""
+        sl = np.ascontiguousarray(slots, dtype=np.uint32)
+        cap = records.shape[0] if cap_records is None else cap_records
+        _lib.check(self._lib.ucfp_panako_streams_windows_dev(self.handle, sl.ctypes.data, sl.size,
+                                                             records.data_ptr() if cap else None, cap, offsets.data_ptr(),
+                                                             origins.data_ptr() if origins is not None else None,
+                                                             stream or None))
+
+    def windows(self, slots) -> dict:
+        """{slot: (uint32 [m, 4] records rebased to the window's origin, origin)}, oldest record first."""
+        import torch
+        slots = list(slots)
+        dev = f"cuda:{self.ctx.device}"
+        cap = len(slots) * self.window_cap
+        d_rec = torch.zeros((max(cap, 1), 4), dtype=torch.int32, device=dev)
+        d_off = torch.zeros(len(slots) + 1, dtype=torch.int64, device=dev)
+        d_org = torch.zeros(max(len(slots), 1), dtype=torch.int32, device=dev)
+        self.windows_dev(slots, d_rec, d_off, d_org, cap, torch.cuda.current_stream().cuda_stream)
+        off = d_off.cpu().numpy() // 16
+        org = d_org.cpu().numpy().view(np.uint32)
+        rec = d_rec.cpu().numpy().view(np.uint32)
+        return {s: (rec[off[i]:off[i + 1]].copy(), int(org[i])) for i, s in enumerate(slots)}
+
+    def destroy(self):
+        if getattr(self, "handle", None):
+            self._lib.ucfp_panako_streams_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+class StreamingPanakoSession:
+    """Push/finalize wrapper on a one-slot PanakoStreams, the shape of StreamingWangSession: each `push` moves its PCM
+    to the device and advances the stream there; only the records emitted so far are held on the host.  `push` returns
+    no records; `finalize` returns one record equal to `fingerprint_panako_with` of the whole stream byte for byte."""
+
+    def __init__(self, sample_rate: int, tenant_id: int, record_id: int, cfg: Optional[PanakoConfig] = None):
+        if sample_rate != WANG_SR:
+            raise ModalityError(f"Panako requires 8 kHz mono input (got {sample_rate} Hz); resample upstream")
+        self.tenant_id, self.record_id = tenant_id, record_id
+        self._set = PanakoStreams(1, cfg)
+        self._slot = self._set.open()
+        self._hashes: List[np.ndarray] = []
+
+    def _push(self, samples, final: bool):
+        x = np.ascontiguousarray(samples, dtype=np.float32).reshape(-1)
+        cap = self._set.max_hashes([self._slot], [x.size], [self._slot] if final else ())
+        out = _aligned_records(max(cap, 1))
+        n = C.c_size_t(0)
+        _lib.check(self._set._lib.ucfp_panako_streams_push(self._set.handle, self._slot, x.ctypes.data if x.size else None,
+                                                           x.size, 1 if final else 0, out.ctypes.data, cap, C.byref(n)))
+        if n.value:
+            self._hashes.append(out[: n.value].copy())
+
+    def push(self, samples) -> List[Record]:
+        self._push(samples, False)
+        return []
+
+    def finalize(self) -> List[Record]:
+        self._push(np.zeros(0, np.float32), True)
+        self._slot = self._set.open()           # the session may be reused
+        h, self._hashes = self._hashes, []
+        if not h:
+            return []
+        return [_record(ALGORITHM_PANAKO, np.concatenate(h).tobytes(), self.tenant_id, self.record_id)]

@@ -1111,12 +1111,13 @@ __global__ void wang_pair_kernel(const uint32_t* __restrict__ ptk, const float* 
 // Anchor i walks its target zone exactly as wang_pair_walk does (P3); when the m-th qualifying target c arrives it
 // closes a triplet with every earlier target b = q_0 .. q_{m-1} (P4), until fan_out triplets exist.  C(12, 2) = 66 >=
 // 64, so the 12th target always ends the anchor and only 11 earlier ones are ever kept: q[] is indexed by unrolled
-// constants only and stays in registers.  One 16-byte record per triplet (P5): hash, t_a, t_b, t_c.
+// constants only and stays in registers.  One 16-byte record per triplet (P5): hash, t_a, t_b, t_c, the three times
+// counted from t_org (0 offline; the origin of a push's peak list in a stream, A19).
 constexpr int kPanakoKeep = 11;
 template <bool EMIT>
 __device__ __forceinline__ uint32_t panako_triplet_walk(const uint32_t* __restrict__ ptk, uint32_t i, uint32_t end,
-                                                        uint32_t fan_out, uint32_t zone_t, uint32_t zone_f, size_t o,
-                                                        uint4* __restrict__ out, size_t cap) {
+                                                        uint32_t fan_out, uint32_t zone_t, uint32_t zone_f,
+                                                        uint32_t t_org, size_t o, uint4* __restrict__ out, size_t cap) {
     const uint32_t a = ptk[i];
     const int32_t ta = (int32_t)(a >> 9), ka = (int32_t)(a & 511u);
     uint32_t q[kPanakoKeep];
@@ -1151,7 +1152,7 @@ __device__ __forceinline__ uint32_t panako_triplet_walk(const uint32_t* __restri
                         uint32_t r = (32u * dtb) / (uint32_t)dtc;
                         r = r > 31u ? 31u : r;
                         out[o] = make_uint4(((uint32_t)ka << 23) | ((b & 511u) << 14) | ((uint32_t)kc << 5) | r,
-                                            (uint32_t)ta, b >> 9, c >> 9);
+                                            (uint32_t)ta + t_org, (b >> 9) + t_org, (c >> 9) + t_org);
                     }
                     o++;
                     taken++;
@@ -1181,7 +1182,7 @@ __global__ void panako_triplet_kernel(const uint32_t* __restrict__ ptk, const fl
     uint32_t taken = 0;
     if (pp[i] >= floor_p) {
         const uint32_t end = sel_off[sec_base[pc[i] + 1]];         // first peak of the next clip
-        taken = panako_triplet_walk<EMIT>(ptk, i, end, fan_out, zone_t, zone_f, EMIT ? offs[i] : 0, out, cap);
+        taken = panako_triplet_walk<EMIT>(ptk, i, end, fan_out, zone_t, zone_f, 0u, EMIT ? offs[i] : 0, out, cap);
     }
     if (!EMIT) counts[i] = taken;
 }
@@ -1507,6 +1508,112 @@ __global__ __launch_bounds__(256) void wang_streams_save_kernel(const WangStream
     if (tid == 0) {
         st.cand_n[e.slot] = c;
         st.ret_n[e.slot] = r;
+    }
+}
+
+// ---- streaming Panako (A19): the same push with triplets behind it, and a ring per stream that keeps the latest
+// window of emitted records in the shape the Panako index takes as a query.
+
+// one thread per peak position of the push, as wang_streams_pair_kernel: the anchors inside the entry's emission window
+// walk their target zone (A13 P3-P5, panako_triplet_walk); the records carry frames since the stream was opened
+template <bool EMIT>
+__global__ void panako_streams_triplet_kernel(const WangStreamEntry* __restrict__ ents, const uint32_t* __restrict__ pk_base,
+                                              uint32_t n, const uint32_t* __restrict__ np,
+                                              const uint32_t* __restrict__ ptk, const float* __restrict__ pp,
+                                              uint32_t fan_out, uint32_t zone_t, uint32_t zone_f, float floor_p,
+                                              uint32_t* __restrict__ counts, const uint32_t* __restrict__ offs,
+                                              uint4* __restrict__ out, size_t cap) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= pk_base[n]) return;
+    const uint32_t c = clip_of(pk_base, n, i);
+    const uint32_t end = pk_base[c] + np[c];
+    uint32_t taken = 0;
+    if (i < end && pp[i] >= floor_p) {
+        const WangStreamEntry e = ents[c];
+        const uint32_t t = e.o + (ptk[i] >> 9);
+        if (t >= e.f_lo && (e.fin || t < e.f_hi))
+            taken = panako_triplet_walk<EMIT>(ptk, i, end, fan_out, zone_t, zone_f, e.o, EMIT ? offs[i] : 0, out, cap);
+    }
+    if (!EMIT) counts[i] = taken;
+}
+
+// One workgroup per entry, behind the emit pass: the entry's new records out[a .. b) join the stream's ring and the
+// head moves past every record with t_a < w0 = max(0, F(n1) - W).  Records are emitted in anchor order, so those to
+// drop are a prefix of (ring, new).  What is kept fits the ring (A19's bound); if it ever did not, the oldest go.
+__global__ __launch_bounds__(256) void panako_streams_ring_kernel(const WangStreamEntry* __restrict__ ents,
+                                                                  const uint32_t* __restrict__ pk_base,
+                                                                  const uint32_t* __restrict__ rec_off,
+                                                                  const uint4* __restrict__ out, PanakoRingsDev rg) {
+    __shared__ uint32_t s_old, s_new;
+    const WangStreamEntry e = ents[blockIdx.x];
+    const uint32_t tid = threadIdx.x;
+    if (e.fin) {
+        if (tid == 0) rg.head[e.slot] = rg.count[e.slot] = 0;
+        return;
+    }
+    const uint32_t R = rg.cap;
+    const uint32_t a = rec_off[pk_base[blockIdx.x]], b = rec_off[pk_base[blockIdx.x + 1]];
+    const uint32_t h = e.fresh ? 0u : rg.head[e.slot], c = e.fresh ? 0u : rg.count[e.slot];
+    const uint32_t w0 = e.f_hi > rg.window ? e.f_hi - rg.window : 0u;
+    uint4* ring = rg.rec + (size_t)e.slot * R;
+    if (tid == 0) s_old = s_new = 0;
+    __syncthreads();
+    uint32_t d_old = 0, d_new = 0;
+    for (uint32_t i = tid; i < c; i += 256) d_old += ring[(h + i) % R].y < w0 ? 1u : 0u;
+    for (uint32_t i = tid; i < b - a; i += 256) d_new += out[(size_t)a + i].y < w0 ? 1u : 0u;
+    if (d_old) atomicAdd(&s_old, d_old);
+    if (d_new) atomicAdd(&s_new, d_new);
+    __syncthreads();
+    d_old = s_old;
+    d_new = s_new;
+    uint32_t kept = c - d_old, m = (b - a) - d_new;
+    if (kept + m > R) {
+        uint32_t ex = kept + m - R;
+        const uint32_t d = ex < kept ? ex : kept;
+        d_old += d;
+        kept -= d;
+        ex -= d;
+        d_new += ex;
+        m -= ex;
+    }
+    const uint32_t tail = (h + c) % R;          // kept + m <= R: the new records never reach the kept ones
+    for (uint32_t j = tid; j < m; j += 256) ring[(tail + j) % R] = out[(size_t)a + d_new + j];
+    if (tid == 0) {
+        rg.head[e.slot] = (h + d_old) % R;
+        rg.count[e.slot] = kept + m;
+    }
+}
+
+// the records in each item's ring (none for a stream that has not been pushed to since it was opened)
+__global__ void panako_streams_window_counts_kernel(const PanakoWindowItem* __restrict__ items, uint32_t n,
+                                                    PanakoRingsDev rg, uint32_t* __restrict__ cnt) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) cnt[i] = items[i].live ? rg.count[items[i].slot] : 0u;
+}
+
+// One workgroup per item: the ring from its head on, the three times rebased to the window's origin w0; byte offsets
+// (the query shape of the Panako index) and origins
+__global__ __launch_bounds__(256) void panako_streams_windows_kernel(const PanakoWindowItem* __restrict__ items, uint32_t n,
+                                                                     const uint32_t* __restrict__ off, PanakoRingsDev rg,
+                                                                     uint4* __restrict__ out, size_t cap,
+                                                                     uint64_t* __restrict__ d_offsets,
+                                                                     uint32_t* __restrict__ d_origins) {
+    const PanakoWindowItem it = items[blockIdx.x];
+    const uint32_t o0 = off[blockIdx.x], o1 = off[blockIdx.x + 1], tid = threadIdx.x;
+    if (tid == 0) {
+        d_offsets[blockIdx.x] = (uint64_t)o0 * 16;
+        if (blockIdx.x + 1 == n) d_offsets[n] = (uint64_t)o1 * 16;
+        if (d_origins) d_origins[blockIdx.x] = it.w0;
+    }
+    if (o1 == o0) return;
+    const uint32_t R = rg.cap, h = rg.head[it.slot];
+    const uint4* ring = rg.rec + (size_t)it.slot * R;
+    for (uint32_t j = tid; j < o1 - o0; j += 256) {
+        uint4 r = ring[(h + j) % R];
+        r.y -= it.w0;
+        r.z -= it.w0;
+        r.w -= it.w0;
+        if ((size_t)o0 + j < cap) out[(size_t)o0 + j] = r;
     }
 }
 
@@ -1919,15 +2026,10 @@ WangPushWs wang_push_layout(size_t n, size_t n_slots, size_t n_closed, size_t to
 }
 
 // The table [ws + w.clips, ws + w.tab_bytes) is on the device already (the caller copies it in front of this).
-// Launches: load, gather, stream, select, peaks, pair count, scan (1 or 3), pair emit, offsets, save -- whatever n is.
-int launch_wang_streams_push(const float* pcm, const WangStreamsDev& st, uint32_t fan_out, uint32_t zone_t,
-                             uint32_t zone_f, uint32_t pps, float floor_power, uint8_t* ws, const WangPushWs& w,
-                             uint32_t* out, size_t cap, uint64_t* d_out_off, hipStream_t stream) {
+// The front end of a push, shared by Wang (A9) and Panako (A19): load, gather, stream, select, peaks -- whatever n is.
+static void launch_wang_streams_front(const float* pcm, const WangStreamsDev& st, uint32_t pps, uint8_t* ws,
+                                      const WangPushWs& w, hipStream_t stream) {
     const uint32_t n = (uint32_t)w.n;
-    if (n == 0) {
-        (void)hipMemsetAsync(d_out_off, 0, 8, stream);
-        return 0;
-    }
     auto f32 = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
     auto u32 = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
     const WangStreamClip* clips = reinterpret_cast<const WangStreamClip*>(ws + w.clips);
@@ -1956,6 +2058,39 @@ int launch_wang_streams_push(const float* pcm, const WangStreamsDev& st, uint32_
     hipLaunchKernelGGL(wang_streams_peaks_kernel, dim3(n), dim3(64), 0, stream, clips, ents, pk_base, st,
                        (const uint32_t*)u32(w.sel_cnt), (const uint32_t*)u32(w.sel_t), (const uint32_t*)u32(w.sel_k),
                        (const float*)f32(w.sel_p), pps, u32(w.pt), f32(w.pp), u32(w.np));
+}
+
+// the end of a push, behind either back end: per-entry output offsets, then the streams' state for the next push
+static void launch_wang_streams_back(const WangStreamsDev& st, uint8_t* ws, const WangPushWs& w, uint64_t* d_out_off,
+                                     hipStream_t stream) {
+    const uint32_t n = (uint32_t)w.n;
+    auto f32 = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    auto u32 = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
+    const WangStreamClip* clips = reinterpret_cast<const WangStreamClip*>(ws + w.clips);
+    const WangStreamEntry* ents = reinterpret_cast<const WangStreamEntry*>(ws + w.ents);
+    const uint32_t* pk_base = u32(w.pk_base);
+    hipLaunchKernelGGL(wang_streams_offsets_kernel, dim3(blocks_for(n + 1, 256)), dim3(256), 0, stream, pk_base, n,
+                       (const uint32_t*)u32(w.pair_off), d_out_off);
+    hipLaunchKernelGGL(wang_streams_save_kernel, dim3(n), dim3(256), 0, stream, clips, ents, pk_base,
+                       (const uint32_t*)u32(w.np), st, (const float*)f32(w.vbuf), (const uint32_t*)u32(w.cand_cnt),
+                       (const uint32_t*)u32(w.cand_t), (const uint32_t*)u32(w.cand_k), (const float*)f32(w.cand_p),
+                       (const uint32_t*)u32(w.pt), (const float*)f32(w.pp));
+}
+
+// Launches: the front end, pair count, scan (1 or 3), pair emit, offsets, save.
+int launch_wang_streams_push(const float* pcm, const WangStreamsDev& st, uint32_t fan_out, uint32_t zone_t,
+                             uint32_t zone_f, uint32_t pps, float floor_power, uint8_t* ws, const WangPushWs& w,
+                             uint32_t* out, size_t cap, uint64_t* d_out_off, hipStream_t stream) {
+    const uint32_t n = (uint32_t)w.n;
+    if (n == 0) {
+        (void)hipMemsetAsync(d_out_off, 0, 8, stream);
+        return 0;
+    }
+    launch_wang_streams_front(pcm, st, pps, ws, w, stream);
+    auto f32 = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    auto u32 = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
+    const WangStreamEntry* ents = reinterpret_cast<const WangStreamEntry*>(ws + w.ents);
+    const uint32_t* pk_base = u32(w.pk_base);
     const size_t tc = w.total_cap;
     hipLaunchKernelGGL(wang_streams_pair_kernel<false>, dim3(blocks_for(tc, 256)), dim3(256), 0, stream, ents, pk_base,
                        n, (const uint32_t*)u32(w.np), (const uint32_t*)u32(w.pt), (const float*)f32(w.pp), fan_out,
@@ -1965,12 +2100,72 @@ int launch_wang_streams_push(const float* pcm, const WangStreamsDev& st, uint32_
                        n, (const uint32_t*)u32(w.np), (const uint32_t*)u32(w.pt), (const float*)f32(w.pp), fan_out,
                        zone_t, zone_f, floor_power, (uint32_t*)nullptr, (const uint32_t*)u32(w.pair_off),
                        reinterpret_cast<uint2*>(out), cap);
-    hipLaunchKernelGGL(wang_streams_offsets_kernel, dim3(blocks_for(n + 1, 256)), dim3(256), 0, stream, pk_base, n,
-                       (const uint32_t*)u32(w.pair_off), d_out_off);
-    hipLaunchKernelGGL(wang_streams_save_kernel, dim3(n), dim3(256), 0, stream, clips, ents, pk_base,
-                       (const uint32_t*)u32(w.np), st, (const float*)f32(w.vbuf), (const uint32_t*)u32(w.cand_cnt),
-                       (const uint32_t*)u32(w.cand_t), (const uint32_t*)u32(w.cand_k), (const float*)f32(w.cand_p),
-                       (const uint32_t*)u32(w.pt), (const float*)f32(w.pp));
+    launch_wang_streams_back(st, ws, w, d_out_off, stream);
+    return 0;
+}
+
+// ---- streaming Panako orchestration (A19) -----------------------------------------------------------
+// As launch_wang_streams_push with triplets in the middle (out: 16-byte records, 16-byte aligned); with a ring
+// (rg.cap != 0) every entry's new records then join its stream's window.
+int launch_panako_streams_push(const float* pcm, const WangStreamsDev& st, const PanakoRingsDev& rg, uint32_t fan_out,
+                               uint32_t zone_t, uint32_t zone_f, uint32_t pps, float floor_power, uint8_t* ws,
+                               const WangPushWs& w, uint32_t* out, size_t cap, uint64_t* d_out_off, hipStream_t stream) {
+    const uint32_t n = (uint32_t)w.n;
+    if (n == 0) {
+        (void)hipMemsetAsync(d_out_off, 0, 8, stream);
+        return 0;
+    }
+    launch_wang_streams_front(pcm, st, pps, ws, w, stream);
+    auto f32 = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    auto u32 = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
+    const WangStreamEntry* ents = reinterpret_cast<const WangStreamEntry*>(ws + w.ents);
+    const uint32_t* pk_base = u32(w.pk_base);
+    const size_t tc = w.total_cap;
+    hipLaunchKernelGGL(panako_streams_triplet_kernel<false>, dim3(blocks_for(tc, 256)), dim3(256), 0, stream, ents,
+                       pk_base, n, (const uint32_t*)u32(w.np), (const uint32_t*)u32(w.pt), (const float*)f32(w.pp),
+                       fan_out, zone_t, zone_f, floor_power, u32(w.pair_cnt), (const uint32_t*)nullptr, (uint4*)nullptr,
+                       (size_t)0);
+    launch_exclusive_scan(u32(w.pair_cnt), tc, u32(w.pair_off), u32(w.scan_tmp), stream);
+    hipLaunchKernelGGL(panako_streams_triplet_kernel<true>, dim3(blocks_for(tc, 256)), dim3(256), 0, stream, ents,
+                       pk_base, n, (const uint32_t*)u32(w.np), (const uint32_t*)u32(w.pt), (const float*)f32(w.pp),
+                       fan_out, zone_t, zone_f, floor_power, (uint32_t*)nullptr, (const uint32_t*)u32(w.pair_off),
+                       reinterpret_cast<uint4*>(out), cap);
+    if (rg.cap)
+        hipLaunchKernelGGL(panako_streams_ring_kernel, dim3(n), dim3(256), 0, stream, ents, pk_base,
+                           (const uint32_t*)u32(w.pair_off), reinterpret_cast<const uint4*>(out), rg);
+    launch_wang_streams_back(st, ws, w, d_out_off, stream);
+    return 0;
+}
+
+PanakoWindowsWs panako_windows_layout(size_t n) {
+    auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    PanakoWindowsWs w;
+    w.n = n;
+    size_t off = 0;
+    w.items = off;    off += n * sizeof(PanakoWindowItem);
+    w.tab_bytes = off; off = align(off);
+    w.cnt = off;      off = align(off + (n + 1) * 4);
+    w.off = off;      off = align(off + (n + 1) * 4);
+    w.scan_tmp = off; off = align(off + 2 * (n / 4096 + 4) * 4);
+    w.total = off + 256;
+    return w;
+}
+
+// the items [ws + w.items, ws + w.tab_bytes) are on the device already.  Launches: counts, scan (1 or 3), copy.
+int launch_panako_streams_windows(const PanakoRingsDev& rg, uint8_t* ws, const PanakoWindowsWs& w, uint8_t* out,
+                                  size_t cap, uint64_t* d_offsets, uint32_t* d_origins, hipStream_t stream) {
+    const uint32_t n = (uint32_t)w.n;
+    if (n == 0) {
+        (void)hipMemsetAsync(d_offsets, 0, 8, stream);
+        return 0;
+    }
+    auto u32 = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
+    const PanakoWindowItem* items = reinterpret_cast<const PanakoWindowItem*>(ws + w.items);
+    hipLaunchKernelGGL(panako_streams_window_counts_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, stream, items, n, rg,
+                       u32(w.cnt));
+    launch_exclusive_scan(u32(w.cnt), n, u32(w.off), u32(w.scan_tmp), stream);
+    hipLaunchKernelGGL(panako_streams_windows_kernel, dim3(n), dim3(256), 0, stream, items, n,
+                       (const uint32_t*)u32(w.off), rg, reinterpret_cast<uint4*>(out), cap, d_offsets, d_origins);
     return 0;
 }
 

@@ -406,6 +406,33 @@ int launch_wang_streams_push(const float* pcm, const WangStreamsDev& st, uint32_
                              uint32_t zone_f, uint32_t pps, float floor_power, uint8_t* ws, const WangPushWs& w,
                              uint32_t* out, size_t cap, uint64_t* d_out_off, hipStream_t stream);
 
+// ---- streaming Panako (A19): the Wang push with triplets behind it (panako_streams.hip plans it with the shared
+// wang_streams_core.h, audio.hip runs it), and a ring per stream that holds the latest window of emitted records ----
+struct PanakoRingsDev {
+    uint4* rec;           // [slots][cap] records with absolute times, in emission order from head on
+    uint32_t* head;       // [slots]
+    uint32_t* count;      // [slots]
+    uint32_t cap;         // records per ring (0: the set keeps no windows)
+    uint32_t window;      // W in frames
+};
+// one item of a windows call, host-built
+struct PanakoWindowItem {
+    uint32_t slot;
+    uint32_t w0;          // origin of the window: max(0, F(n) - W)
+    uint32_t live;        // 0: nothing pushed since the slot was opened, whatever the ring holds
+    uint32_t pad;
+};
+struct PanakoWindowsWs {
+    size_t n = 0;
+    size_t items, tab_bytes, cnt, off, scan_tmp, total = 0;
+};
+int launch_panako_streams_push(const float* pcm, const WangStreamsDev& st, const PanakoRingsDev& rg, uint32_t fan_out,
+                               uint32_t zone_t, uint32_t zone_f, uint32_t pps, float floor_power, uint8_t* ws,
+                               const WangPushWs& w, uint32_t* out, size_t cap, uint64_t* d_out_off, hipStream_t stream);
+PanakoWindowsWs panako_windows_layout(size_t n);
+int launch_panako_streams_windows(const PanakoRingsDev& rg, uint8_t* ws, const PanakoWindowsWs& w, uint8_t* out,
+                                  size_t cap, uint64_t* d_offsets, uint32_t* d_origins, hipStream_t stream);
+
 struct HaitsmaBatchWs {
     size_t n5_ub = 0, frames_ub = 0;      // upper bounds (the per-clip lengths of a batch live on the device)
     size_t edges, s5_off, fr_off, src_map, pcm5k, E, total = 0;

@@ -5,238 +5,29 @@
 // subset of them by one chunk each with one launch sequence (audio.hip, launch_wang_streams_push).  The host tracks
 // how many samples each stream has seen, which fixes every frame range of the push (A9): the host plans, the device
 // keeps the data (carried samples, the open second's candidates, the retained peaks).
-#include <hip/hip_runtime.h>
-
-#include <cmath>
-#include <cstring>
-#include <mutex>
-#include <new>
-#include <vector>
-
-#include "../../include/ucfp_hip.h"
-#include "common.h"
-#include "ctx.h"
+#include "wang_streams_core.h"
 
 #define fail ucfp::capi_fail
 
-namespace {
+using namespace ucfp::wstreams;   // the plan of a push, shared with panako_streams.hip
 
-constexpr uint64_t kMaxChunk = (uint64_t)1 << 29;     // samples of one stream in one push (18.6 h): t << 9 | k stays packable
-constexpr uint64_t kMaxPushSamples = (uint64_t)1 << 31;   // carried + new samples of one push (32-bit sample offsets)
-constexpr uint64_t kMaxFrames = ((uint64_t)1 << 32) - 1024;   // frames of a stream (u32 t_anchor, ~795 days)
-
-ucfp_wang_config defaults() { return ucfp_wang_config{10u, 63u, 64u, 30u, -50.0f}; }
-
-bool cfg_ok(const ucfp_wang_config& c) {
-    return c.fan_out >= 1 && c.fan_out <= 64 && c.target_zone_t >= 1 && c.target_zone_t <= 512 && c.target_zone_f >= 1 &&
-           c.target_zone_f <= 1024 && c.peaks_per_sec >= 1 && c.peaks_per_sec <= 256;
-}
-
-// A9, all in frames / samples since the stream was opened
-uint64_t frames_of(uint64_t n) { return n < 1024 ? 0 : (n - 1024) / 128 + 1; }
-uint64_t judged_of(uint64_t n) { const uint64_t f = frames_of(n); return f > 7 ? f - 7 : 0; }   // J(n)
-uint64_t sec_of(uint64_t t) { return (t * 128) / 8000; }
-uint64_t f0_of(uint64_t s) { return (125 * s + 1) / 2; }                                        // ceil(125 s / 2)
-uint64_t closed_of(uint64_t j) { return f0_of(sec_of(j)); }     // C = f0(S), S = the second holding frame J
-uint64_t frontier_of(uint64_t j, uint32_t zone_t) { const uint64_t c = closed_of(j); return c > zone_t ? c - zone_t : 0; }
-
-// retained peaks: the selected peaks of [F, C), zone_t frames wide
-uint32_t ret_cap_of(const ucfp_wang_config& c) { return c.peaks_per_sec * ((c.target_zone_t * 2 + 124) / 125 + 2); }
-
-// one entry of a push, planned on the host
-struct Plan {
-    uint32_t slot;
-    uint64_t m, n0, n1;
-    bool fin;
-    uint64_t vbase, o, j0, j1, s0, n_closed, f_lo, f_hi, cap, bound;
-};
-
-}  // namespace
-
-struct ucfp_wang_streams {
-    ucfp_ctx* ctx = nullptr;
-    ucfp_wang_config cfg{};
-    float floor_p = 0.0f;
-    uint32_t max_streams = 0;
-    std::mutex mu;                        // serialises the set's calls
-    std::vector<uint64_t> n;              // samples seen per slot
-    std::vector<uint8_t> open;
-    std::vector<uint8_t> seen;            // duplicate-slot check of one push
-    std::vector<Plan> plan;
-    ucfp::WangStreamsDev dev{};
-    uint8_t* dev_mem = nullptr;
-    uint8_t* tab_h[2] = {nullptr, nullptr};   // pinned push tables, used in turn
-    hipEvent_t tab_copied[2] = {nullptr, nullptr};
-    int tab_next = 0;
-    hipEvent_t done = nullptr;            // behind the last push: the next one waits for it
-};
+struct ucfp_wang_streams : Set {};
 
 namespace {
 
-size_t state_bytes_per_stream(uint32_t ret_cap) {
-    return (size_t)ucfp::kWangCarry * 4 + 4 + (size_t)ucfp::kWangCandCap * 12 + 4 + (size_t)ret_cap * 12;
-}
-
-size_t tab_bytes_max(uint32_t max_streams) {
-    return (size_t)max_streams * (sizeof(ucfp::WangStreamClip) + sizeof(ucfp::WangStreamEntry)) +
-           3 * ((size_t)max_streams + 1) * 4 + 4 + 256;
-}
-
-// validates the push and plans every entry; nothing changes.  *bound: hashes the push can emit
-int plan_push(ucfp_wang_streams* s, const uint32_t* slots, const uint64_t* n_samples, const uint8_t* fin, size_t n,
-              size_t* bound) {
-    if (n && (!slots || !n_samples)) return fail(UCFP_E_INVALID, "slots / n_samples is NULL");
-    if (n > s->max_streams) return fail(UCFP_E_INVALID, "%zu entries in one push, the set has %u slots", n, s->max_streams);
-    const ucfp_wang_config& c = s->cfg;
-    s->plan.resize(n);
-    size_t total = 0;
-    uint64_t total_v = 0;
-    int rc = UCFP_OK;
-    for (size_t i = 0; i < n && rc == UCFP_OK; i++) {
-        const uint32_t slot = slots[i];
-        if (slot >= s->max_streams) rc = fail(UCFP_E_INVALID, "slot %u out of range [0, %u)", slot, s->max_streams);
-        else if (!s->open[slot]) rc = fail(UCFP_E_INVALID, "slot %u is not open", slot);
-        else if (s->seen[slot]) rc = fail(UCFP_E_INVALID, "slot %u appears twice in one push", slot);
-        else if (n_samples[i] > kMaxChunk)
-            rc = fail(UCFP_E_INVALID, "a chunk of %llu samples exceeds 2^29: split it", (unsigned long long)n_samples[i]);
-        else if (frames_of(s->n[slot] + n_samples[i]) > kMaxFrames)
-            rc = fail(UCFP_E_INVALID, "slot %u would pass 2^32 frames", slot);
-        if (rc) break;
-        s->seen[slot] = 1;
-        Plan& p = s->plan[i];
-        p.slot = slot;
-        p.m = n_samples[i];
-        p.n0 = s->n[slot];
-        p.n1 = p.n0 + p.m;
-        p.fin = fin && fin[i];
-        p.j0 = judged_of(p.n0);
-        p.s0 = sec_of(p.j0);
-        p.f_lo = frontier_of(p.j0, c.target_zone_t);
-        p.vbase = p.j0 > 7 ? p.j0 - 7 : 0;
-        p.o = p.vbase < p.f_lo ? p.vbase : p.f_lo;
-        const uint64_t fr1 = frames_of(p.n1);
-        uint64_t emit_hi;                                  // anchors emitted: [f_lo, emit_hi)
-        if (p.fin) {
-            p.j1 = fr1;
-            const uint64_t last = fr1 ? sec_of(fr1 - 1) + 1 : 0;     // seconds below `last` hold frames
-            p.n_closed = last > p.s0 ? last - p.s0 : 0;
-            p.f_hi = fr1;
-            emit_hi = fr1;
-        } else {
-            p.j1 = judged_of(p.n1);
-            p.n_closed = sec_of(p.j1) - p.s0;
-            p.f_hi = frontier_of(p.j1, c.target_zone_t);
-            emit_hi = p.f_hi;
-        }
-        p.cap = ret_cap_of(c) + p.n_closed * c.peaks_per_sec;
-        p.bound = emit_hi > p.f_lo ? (sec_of(emit_hi - 1) - sec_of(p.f_lo) + 1) * c.peaks_per_sec * c.fan_out : 0;
-        total += p.bound;
-        total_v += p.n0 - 128 * p.vbase + p.m;
-    }
-    for (size_t i = 0; i < n; i++)
-        if (slots && slots[i] < s->max_streams) s->seen[slots[i]] = 0;
-    if (rc) return rc;
-    if (total_v >= kMaxPushSamples) return fail(UCFP_E_INVALID, "push of %llu samples exceeds 2^31: split it",
-                                                (unsigned long long)total_v);
-    *bound = total;
-    return UCFP_OK;
-}
+Cfg defaults() { return Cfg{10u, 63u, 64u, 30u, -50.0f}; }
 
 // the set's and the context's locks are held; the plan is current
 int push_impl(ucfp_wang_streams* s, size_t n, const float* d_pcm, uint8_t* d_out, size_t cap_hashes,
               uint64_t* d_out_offsets, hipStream_t st) {
-    ucfp_ctx* ctx = s->ctx;
-    const ucfp_wang_config& c = s->cfg;
-    size_t n_closed = 0, n_open = 0, total_v = 0, total_cap = 0, judged = 0;
-    for (size_t i = 0; i < n; i++) {
-        const Plan& p = s->plan[i];
-        n_closed += p.n_closed;
-        n_open += p.fin ? 0 : 1;
-        total_v += p.n0 - 128 * p.vbase + p.m;
-        total_cap += p.cap;
-        judged += p.j1 - p.j0;
-    }
-    ucfp::WangPushWs w = ucfp::wang_push_layout(n, n_closed + n_open, n_closed, total_v, total_cap, judged, c.peaks_per_sec);
-    if (total_cap >= 0x7fffffffu || (n_closed + n_open) * ucfp::kWangCandCap >= ((size_t)1 << 30))
-        return fail(UCFP_E_INVALID, "push too large for one call: split it");
-    HIP_TRY(hipSetDevice(ctx->device));
-    int rc = ucfp::grow(&ctx->audio_ws, &ctx->audio_ws_cap, w.total);
+    const Cfg& c = s->cfg;
+    ucfp::WangPushWs w;
+    int rc = push_begin(s, n, st, &w);
     if (rc) return rc;
-    // the pinned table this push fills was last copied two pushes ago
-    const int k = s->tab_next;
-    s->tab_next ^= 1;
-    HIP_TRY(hipEventSynchronize(s->tab_copied[k]));
-    uint8_t* tab = s->tab_h[k];
-    auto* clips = reinterpret_cast<ucfp::WangStreamClip*>(tab + w.clips);
-    auto* ents = reinterpret_cast<ucfp::WangStreamEntry*>(tab + w.ents);
-    auto* v_base = reinterpret_cast<uint32_t*>(tab + w.v_base);
-    auto* seg_base = reinterpret_cast<uint32_t*>(tab + w.seg_base);
-    auto* pk_base = reinterpret_cast<uint32_t*>(tab + w.pk_base);
-    uint32_t vb = 0, sb = 0, pb = 0, closed_base = 0, open_slot = (uint32_t)n_closed;
-    for (size_t i = 0; i < n; i++) {
-        const Plan& p = s->plan[i];
-        const uint64_t carry_in = p.n0 - 128 * p.vbase, vlen = carry_in + p.m;
-        ucfp::WangStreamClip& cl = clips[i];
-        cl.src_off = vb;
-        cl.src_n = cl.n8k = vlen;
-        cl.frames = (uint32_t)frames_of(vlen);
-        cl.j_lo = (uint32_t)(p.j0 - p.vbase);
-        cl.j_hi = (uint32_t)(p.j1 - p.vbase);
-        cl.t_shift = (uint32_t)(p.vbase - p.o);
-        cl.t_org = (uint32_t)p.o;
-        cl.sec_org = (uint32_t)p.s0;
-        cl.n_closed = (uint32_t)p.n_closed;
-        cl.closed_base = closed_base;
-        cl.open_slot = p.fin ? 0xffffffffu : open_slot;
-        cl.pad = 0;
-        ucfp::WangStreamEntry& e = ents[i];
-        e.slot = p.slot;
-        e.carry_in = (uint32_t)carry_in;
-        const uint64_t keep = p.j1 > 7 ? p.j1 - 7 : 0;           // the next push starts at frame J - 7
-        e.keep_rel = p.fin ? 0 : (uint32_t)(128 * (keep - p.vbase));
-        e.carry_out = p.fin ? 0 : (uint32_t)(p.n1 - 128 * keep);
-        e.chunk_off = 0;
-        e.o = (uint32_t)p.o;
-        e.f_lo = (uint32_t)p.f_lo;
-        e.f_hi = (uint32_t)p.f_hi;
-        e.fin = p.fin ? 1u : 0u;
-        e.ret_from = (uint32_t)p.f_hi;
-        e.fresh = p.n0 == 0 ? 1u : 0u;
-        v_base[i] = vb;
-        seg_base[i] = sb;
-        pk_base[i] = pb;
-        vb += (uint32_t)vlen;
-        sb += (uint32_t)((p.j1 - p.j0 + w.seg - 1) / w.seg);
-        pb += (uint32_t)p.cap;
-        closed_base += (uint32_t)p.n_closed;
-        if (!p.fin) open_slot++;
-    }
-    uint64_t chunk = 0;
-    for (size_t i = 0; i < n; i++) {
-        ents[i].chunk_off = chunk;
-        chunk += s->plan[i].m;
-    }
-    v_base[n] = vb;
-    seg_base[n] = sb;
-    pk_base[n] = pb;
-    *reinterpret_cast<uint32_t*>(tab + w.n_closed_w) = (uint32_t)n_closed;
-    w.n_seg = sb;
-    HIP_TRY(hipStreamWaitEvent(st, ctx->audio_done, 0));
-    HIP_TRY(hipStreamWaitEvent(st, s->done, 0));
-    HIP_TRY(hipMemcpyAsync(ctx->audio_ws + w.clips, tab, w.tab_bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipEventRecord(s->tab_copied[k], st));
     ucfp::launch_wang_streams_push(d_pcm, s->dev, c.fan_out, c.target_zone_t, c.target_zone_f, c.peaks_per_sec,
-                                   s->floor_p, ctx->audio_ws, w, reinterpret_cast<uint32_t*>(d_out), cap_hashes,
+                                   s->floor_p, s->ctx->audio_ws, w, reinterpret_cast<uint32_t*>(d_out), cap_hashes,
                                    d_out_offsets, st);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ctx->audio_done, st));
-    HIP_TRY(hipEventRecord(s->done, st));
-    for (size_t i = 0; i < n; i++) {
-        const Plan& p = s->plan[i];
-        s->n[p.slot] = p.fin ? 0 : p.n1;
-        if (p.fin) s->open[p.slot] = 0;
-    }
-    return UCFP_OK;
+    return push_end(s, n, st);
 }
 
 }  // namespace
@@ -244,12 +35,12 @@ int push_impl(ucfp_wang_streams* s, size_t n, const float* d_pcm, uint8_t* d_out
 extern "C" {
 
 uint64_t ucfp_wang_stream_frontier(uint64_t n_samples, const ucfp_wang_config* cfg) {
-    const ucfp_wang_config c = cfg ? *cfg : defaults();
+    const Cfg c = cfg ? cfg_of(*cfg) : defaults();
     return frontier_of(judged_of(n_samples), c.target_zone_t);
 }
 
 size_t ucfp_wang_streams_state_bytes(const ucfp_wang_config* cfg) {
-    const ucfp_wang_config c = cfg ? *cfg : defaults();
+    const Cfg c = cfg ? cfg_of(*cfg) : defaults();
     return cfg_ok(c) ? state_bytes_per_stream(ret_cap_of(c)) : 0;
 }
 
@@ -257,7 +48,7 @@ int ucfp_wang_streams_create(ucfp_ctx* ctx, uint32_t sample_rate, const ucfp_wan
                              ucfp_wang_streams** out) {
     if (sample_rate != 8000)
         return fail(UCFP_E_MODALITY, "Wang requires 8 kHz mono input (got %u Hz); resample upstream", sample_rate);
-    const ucfp_wang_config c = cfg ? *cfg : defaults();
+    const Cfg c = cfg ? cfg_of(*cfg) : defaults();
     if (!cfg_ok(c)) return fail(UCFP_E_MODALITY, "WangConfig outside the ranges of /v1/algorithms");
     if (!ctx || !out) return fail(UCFP_E_INVALID, "ctx / out is NULL");
     *out = nullptr;
@@ -265,34 +56,7 @@ int ucfp_wang_streams_create(ucfp_ctx* ctx, uint32_t sample_rate, const ucfp_wan
     HIP_TRY(hipSetDevice(ctx->device));
     ucfp_wang_streams* s = new (std::nothrow) ucfp_wang_streams();
     if (!s) return fail(UCFP_E_INDEX, "out of host memory");
-    s->ctx = ctx;
-    s->cfg = c;
-    s->floor_p = (float)(65536.0 * pow(10.0, (double)c.min_anchor_mag_db / 10.0));
-    s->max_streams = max_streams;
-    s->n.assign(max_streams, 0);
-    s->open.assign(max_streams, 0);
-    s->seen.assign(max_streams, 0);
-    const uint32_t rc = ret_cap_of(c);
-    const size_t ms = max_streams;
-    const size_t bytes = ms * state_bytes_per_stream(rc) + 16 * 256;
-    hipError_t e = hipMalloc((void**)&s->dev_mem, bytes);
-    if (e == hipSuccess) {
-        size_t off = 0;
-        auto take = [&](size_t b) { uint8_t* p = s->dev_mem + off; off = (off + b + 255) & ~(size_t)255; return p; };
-        s->dev.smp = reinterpret_cast<float*>(take(ms * ucfp::kWangCarry * 4));
-        s->dev.cand_n = reinterpret_cast<uint32_t*>(take(ms * 4));
-        s->dev.cand_t = reinterpret_cast<uint32_t*>(take(ms * ucfp::kWangCandCap * 4));
-        s->dev.cand_k = reinterpret_cast<uint32_t*>(take(ms * ucfp::kWangCandCap * 4));
-        s->dev.cand_p = reinterpret_cast<float*>(take(ms * ucfp::kWangCandCap * 4));
-        s->dev.ret_n = reinterpret_cast<uint32_t*>(take(ms * 4));
-        s->dev.ret_t = reinterpret_cast<uint32_t*>(take(ms * rc * 4));
-        s->dev.ret_k = reinterpret_cast<uint32_t*>(take(ms * rc * 4));
-        s->dev.ret_p = reinterpret_cast<float*>(take(ms * rc * 4));
-        s->dev.ret_cap = rc;
-    }
-    for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipHostMalloc((void**)&s->tab_h[i], tab_bytes_max(max_streams), 0);
-    for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipEventCreateWithFlags(&s->tab_copied[i], hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&s->done, hipEventDisableTiming);
+    const hipError_t e = set_init(s, ctx, c, max_streams);
     if (e != hipSuccess) {
         ucfp_wang_streams_destroy(s);
         return fail(UCFP_E_INDEX, "stream set allocation failed: %s", hipGetErrorString(e));
@@ -303,37 +67,18 @@ int ucfp_wang_streams_create(ucfp_ctx* ctx, uint32_t sample_rate, const ucfp_wan
 
 void ucfp_wang_streams_destroy(ucfp_wang_streams* s) {
     if (!s) return;
-    if (s->done) (void)hipEventSynchronize(s->done);
-    if (s->dev_mem) (void)hipFree(s->dev_mem);
-    for (int i = 0; i < 2; i++) {
-        if (s->tab_h[i]) (void)hipHostFree(s->tab_h[i]);
-        if (s->tab_copied[i]) (void)hipEventDestroy(s->tab_copied[i]);
-    }
-    if (s->done) (void)hipEventDestroy(s->done);
+    set_release(s);
     delete s;
 }
 
 int ucfp_wang_streams_open(ucfp_wang_streams* s, uint32_t* slot) {
     if (!s || !slot) return fail(UCFP_E_INVALID, "set / slot is NULL");
-    std::lock_guard<std::mutex> lk(s->mu);
-    for (uint32_t i = 0; i < s->max_streams; i++) {
-        if (!s->open[i]) {
-            s->open[i] = 1;
-            s->n[i] = 0;
-            *slot = i;
-            return UCFP_OK;
-        }
-    }
-    return fail(UCFP_E_INVALID, "all %u slots are open", s->max_streams);
+    return set_open(s, slot);
 }
 
 int ucfp_wang_streams_close(ucfp_wang_streams* s, uint32_t slot) {
     if (!s) return fail(UCFP_E_INVALID, "set is NULL");
-    std::lock_guard<std::mutex> lk(s->mu);
-    if (slot >= s->max_streams || !s->open[slot]) return fail(UCFP_E_INVALID, "slot %u is not open", slot);
-    s->open[slot] = 0;
-    s->n[slot] = 0;
-    return UCFP_OK;
+    return set_close(s, slot);
 }
 
 size_t ucfp_wang_streams_max_hashes(ucfp_wang_streams* s, const uint32_t* slots, const uint64_t* n_samples,

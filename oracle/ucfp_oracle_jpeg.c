@@ -18,8 +18,8 @@
  *
  * Decoded here (everything else that parses as a JPEG -> JPG_NEEDS_HOST: the host's decoder takes it):
  *   SOF0 / SOF1 (sequential Huffman), 8-bit samples, 1 component or 3 components coded as YCbCr, ONE interleaved scan,
- *   the luma component sampled at the MCU's full resolution (4:4:4, 4:2:2, 4:2:0, 4:4:0, 4:1:1 ...), 8-bit quantisation
- *   tables, optional restart intervals.  Any irregularity of the entropy-coded data (a code that is not in the table, a
+ *   the luma component sampled at the MCU's full resolution (4:4:4, 4:2:2, 4:2:0, 4:4:0, 4:1:1 ...), at most 10 blocks
+ *   per MCU (T.81 B.2.3: libjpeg refuses more), 8-bit quantisation tables, optional restart intervals.  Any irregularity of the entropy-coded data (a code that is not in the table, a
  *   run past coefficient 63, data that ends early, a stray marker) is NEEDS_HOST as well -- decoders differ in what they
  *   forgive, so the host's decides.  Not a JPEG at all (no SOI) -> JPG_CORRUPT.
  */
@@ -176,6 +176,8 @@ static int jpg_parse(const uint8_t* p, size_t n, jpg_t* J) {
         else if (J->cid[0] == 'R' && J->cid[1] == 'G' && J->cid[2] == 'B') ycc = 0;
         if (!ycc) return JPG_NEEDS_HOST;
         if (J->hs[0] != J->hmax || J->vs[0] != J->vmax) return JPG_NEEDS_HOST;   /* luma below the MCU's resolution */
+        /* an interleaved MCU holds at most 10 blocks (T.81 B.2.3); libjpeg refuses a frame that declares more */
+        if (J->hs[0] * J->vs[0] + J->hs[1] * J->vs[1] + J->hs[2] * J->vs[2] > 10) return JPG_NEEDS_HOST;
     } else {
         J->hmax = J->hs[0] = 1;      /* a single-component scan is not interleaved: one block per MCU (T.81 A.2.2) */
         J->vmax = J->vs[0] = 1;

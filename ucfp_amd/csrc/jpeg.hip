@@ -26,7 +26,7 @@
 //                      (IJG jidctint "islow": 13-bit fixed point, two 1-D passes of 8, all in registers), range limit,
 //                      eight 8-byte row stores.
 // Anything this file does not decode -- progressive / arithmetic / 12-bit / CMYK / RGB-coded files, several scans, luma
-// coded below the MCU's resolution, 16-bit quantisation tables -- and any irregularity of the entropy-coded data gets
+// coded below the MCU's resolution, more than 10 blocks per MCU (T.81 B.2.3), 16-bit quantisation tables -- and any irregularity of the entropy-coded data gets
 // UCFP_IMAGE_NEEDS_HOST: decoders differ in what they forgive, the host's decides.  No SOI at all: UCFP_E_MODALITY.
 
 #include <hip/hip_runtime.h>
@@ -163,6 +163,8 @@ __device__ int jpeg_parse(const uint8_t* p, size_t n, uint32_t width, uint32_t h
         else if (adobe >= 0) ycc = adobe == 1;
         else if (cid[0] == 'R' && cid[1] == 'G' && cid[2] == 'B') ycc = false;
         if (!ycc || J.hs[0] != J.hmax || J.vs[0] != J.vmax) return UCFP_IMAGE_NEEDS_HOST;
+        // an interleaved MCU holds at most 10 blocks (T.81 B.2.3); libjpeg refuses a frame that declares more
+        if (J.hs[0] * J.vs[0] + J.hs[1] * J.vs[1] + J.hs[2] * J.vs[2] > 10) return UCFP_IMAGE_NEEDS_HOST;
     } else {
         J.hmax = J.vmax = 1;          // a one-component scan is not interleaved: one block per MCU (T.81 A.2.2)
         J.hs[0] = J.vs[0] = 1;

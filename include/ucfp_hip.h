@@ -559,6 +559,72 @@ int ucfp_text_simhash_batch_dev(ucfp_ctx* ctx, const uint8_t* d_utf8, const uint
 int ucfp_text_simhash_batch(ucfp_ctx* ctx, const uint8_t* utf8, const uint64_t* offsets, size_t n, int mode,
                             uint8_t* out, int32_t* status);
 
+/* TOKENISERS.  Every text request of the reference names a tokeniser (src/server/dto.rs,
+ * handlers.rs:532-539; text.rs:66-83): MinHash wraps it in ShingleTokenizer { k, inner } (text.rs:194-219), SimHash is fed
+ * its raw tokens (text.rs:379-398).  The _ex entries take it as a parameter:
+ *   UCFP_TEXT_TOK_WORD      the entries above, unchanged (every mode).
+ *   UCFP_TEXT_TOK_GRAPHEME  the tokens are the UAX#29 extended grapheme clusters of the canonical text, as the host finds
+ *                           them with `regex.findall(r"\X", canon)`; EVERY cluster is a token, whitespace, punctuation
+ *                           and controls included.  Modes:
+ *     UCFP_TEXT_RAW_ASCII   canonical text = the bytes with A-Z lower-cased, every byte kept (0x00 too); a cluster is one
+ *                           byte, CR LF one cluster.  A byte >= 0x80 gives UCFP_TEXT_NEEDS_HOST.  One launch.
+ *     UCFP_TEXT_RAW_UTF8    canonical text = the concatenation of M(c) (U2, U3: strict decode, NFKC + case fold + Cf
+ *                           stripping as a table); a cluster is one canonical code point, CR LF one cluster.  That holds
+ *                           over the GRAPHEME SET (G3): the code points U1 covers, less those with a code point of M(c)
+ *                           whose Grapheme_Cluster_Break is Prepend, L, V or T (twelve Prepend letters, the Hangul jamo
+ *                           U1 keeps; include/ucfp_text_gtab.h; ucfp_text_grapheme_covered).  A document with another
+ *                           code point or malformed UTF-8 gets UCFP_TEXT_NEEDS_HOST and a zero record, and that status
+ *                           wins; the host cuts its clusters and submits them to the token entries below.  An ASCII
+ *                           document gives the same record in both modes.  The _dev calls read d_offsets[0] and
+ *                           d_offsets[n] back once, as the word route's do.
+ *     UCFP_TEXT_PRETOKENIZED  UCFP_E_INVALID: a cluster may be or hold a space; tokens go to the token entries.
+ *   Shingles, hashes, records, statuses, shingle_k's range and the alignment of the outputs are those of the entries above
+ *   (k consecutive tokens joined by one 0x20; fewer than k tokens in the document: one shingle of all of them; none:
+ *   UCFP_E_MODALITY).  An unknown tokeniser or mode gives UCFP_E_INVALID.
+ * CALLER-SEGMENTED TOKENS: the route for any tokeniser the host runs itself (grapheme hand-backs, Lindera's cjk-jp /
+ * cjk-ko tokens).  Token t is bytes[tok_offsets[t], tok_offsets[t + 1]), any byte string, 0x20 and 0x00 included, hashed
+ * as it is; an empty token is not a token.  Document i owns the tokens doc_tokens[i] .. doc_tokens[i + 1] - 1; tok_offsets
+ * has doc_tokens[n] + 1 entries.  For tokens that hold no 0x20 the record and status are those of the PRETOKENIZED entries
+ * over the tokens joined by single spaces, byte for byte.
+ *   - The host entries check both tables whole before anything runs (ucfp_text_tokens_validate: non-decreasing, which
+ *     keeps every token inside [tok_offsets[doc_tokens[0]], tok_offsets[doc_tokens[n]])); otherwise UCFP_E_INVALID.
+ *   - The _dev entries cannot: there the wave of a document checks its own slice before it reads a byte of the blob.  A
+ *     document with a decreasing pair of offsets, or with a range outside the announced one (tokens doc_tokens[0] ..
+ *     doc_tokens[n], bytes between those two tokens' offsets), gets status UCFP_E_INVALID and a zero record; the others
+ *     are hashed.  No byte outside the announced range is read.  Nothing is read back and no scratch is used.
+ * WINDOW LIMIT: UCFP_TEXT_MAX_WINDOW_BYTES holds for all of these entries as stated above.  A step of these kernels can open
+ * 64 tokens and add 64 separators where the word step opens 32; the room a step demands (130 bytes) covers 64 + 64, and
+ * the token cap is checked against 64 (ntok + 64 <= 256), which cannot fail after a flush either: at most k <= 64 tokens
+ * are kept (text_core.h pins both with static_asserts). */
+#define UCFP_TEXT_TOK_WORD 0
+#define UCFP_TEXT_TOK_GRAPHEME 1
+/* text.rs:194-219 with `inner` = the tokeniser named by `tokenizer` (text.rs:66-83); handlers.rs:532-539 */
+int ucfp_text_minhash_batch_ex_dev(ucfp_ctx* ctx, const uint8_t* d_utf8, const uint64_t* d_offsets, size_t n, int mode,
+                                   int tokenizer, uint32_t shingle_k, uint8_t* d_out, int32_t* d_status, void* stream);
+int ucfp_text_minhash_batch_ex(ucfp_ctx* ctx, const uint8_t* utf8, const uint64_t* offsets, size_t n, int mode, int tokenizer,
+                               uint32_t shingle_k, uint8_t* out, int32_t* status);
+/* text.rs:379-398 (raw tokens of the tokeniser named by `tokenizer`, no shingling); handlers.rs:532-539 */
+int ucfp_text_simhash_batch_ex_dev(ucfp_ctx* ctx, const uint8_t* d_utf8, const uint64_t* d_offsets, size_t n, int mode,
+                                   int tokenizer, uint8_t* d_out, int32_t* d_status, void* stream);
+int ucfp_text_simhash_batch_ex(ucfp_ctx* ctx, const uint8_t* utf8, const uint64_t* offsets, size_t n, int mode, int tokenizer,
+                               uint8_t* out, int32_t* status);
+/* text.rs:194-219 behind a tokeniser the host ran (text.rs:66-83: cjk-jp, cjk-ko; grapheme hand-backs) */
+int ucfp_text_minhash_tokens_batch_dev(ucfp_ctx* ctx, const uint8_t* d_bytes, const uint64_t* d_tok_offsets,
+                                       const uint64_t* d_doc_tokens, size_t n, uint32_t shingle_k, uint8_t* d_out,
+                                       int32_t* d_status, void* stream);
+int ucfp_text_minhash_tokens_batch(ucfp_ctx* ctx, const uint8_t* bytes, const uint64_t* tok_offsets, const uint64_t* doc_tokens,
+                                   size_t n, uint32_t shingle_k, uint8_t* out, int32_t* status);
+/* text.rs:379-398 behind a tokeniser the host ran */
+int ucfp_text_simhash_tokens_batch_dev(ucfp_ctx* ctx, const uint8_t* d_bytes, const uint64_t* d_tok_offsets,
+                                       const uint64_t* d_doc_tokens, size_t n, uint8_t* d_out, int32_t* d_status, void* stream);
+int ucfp_text_simhash_tokens_batch(ucfp_ctx* ctx, const uint8_t* bytes, const uint64_t* tok_offsets, const uint64_t* doc_tokens,
+                                   size_t n, uint8_t* out, int32_t* status);
+/* Host-only (no device, no context): 1 iff the grapheme set (G3) covers cp.  text.rs:66-83 (Grapheme). */
+int ucfp_text_grapheme_covered(uint32_t cp);
+/* Host-only: the check the host token entries make of their tables -- doc_tokens[0 .. n] and tok_offsets[doc_tokens[0] ..
+ * doc_tokens[n]] non-decreasing.  UCFP_OK or UCFP_E_INVALID.  text.rs:194-219 (the tokens of one document are a sequence). */
+int ucfp_text_tokens_validate(const uint64_t* tok_offsets, const uint64_t* doc_tokens, size_t n);
+
 /* STREAMING MinHash: text::StreamingMinHashSession::new / push / finalize (src/modality/text.rs:645-730)
  * behind POST /v1/ingest/text/{tid}/{rid}/stream (src/server/handlers.rs:590-626), with the state on the device and many
  * streams advanced by one push.  The reference buffers the document and hashes it at the end; here a stream keeps the 128

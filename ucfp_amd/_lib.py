@@ -123,6 +123,24 @@ SIGNATURES = {
                                               C.c_void_p, C.c_void_p, C.c_void_p]),
     "ucfp_text_simhash_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int,
                                           C.c_void_p, C.c_void_p]),
+    "ucfp_text_minhash_batch_ex_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_uint32,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ucfp_text_minhash_batch_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_uint32,
+                                             C.c_void_p, C.c_void_p]),
+    "ucfp_text_simhash_batch_ex_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ucfp_text_simhash_batch_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int,
+                                             C.c_void_p, C.c_void_p]),
+    "ucfp_text_minhash_tokens_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ucfp_text_minhash_tokens_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32,
+                                                 C.c_void_p, C.c_void_p]),
+    "ucfp_text_simhash_tokens_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ucfp_text_simhash_tokens_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                 C.c_void_p, C.c_void_p]),
+    "ucfp_text_grapheme_covered": (C.c_int, [C.c_uint32]),
+    "ucfp_text_tokens_validate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "ucfp_text_streams_create": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
     "ucfp_text_streams_create_ex": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
                                               C.POINTER(C.c_void_p)]),

@@ -326,6 +326,8 @@ int launch_text_simhash(const uint8_t* utf8, const uint64_t* offsets, size_t n, 
 // of the batch) bytes, status n words (0 / UCFP_TEXT_NEEDS_HOST); count, scan and emit are enqueued on `stream`.
 int launch_text_canon(const uint8_t* utf8, const uint64_t* offsets, size_t n, uint8_t* tokens, uint64_t* tok_off,
                       int32_t* status, hipStream_t stream);
+void launch_text_canon_scan(uint64_t* tok_off, size_t n, hipStream_t stream);   // tok_off[1 .. n] lengths -> offsets, tok_off[0] = 0
+void launch_text_canon_merge(const int32_t* cstatus, size_t n, int32_t* status, hipStream_t stream);   // a nonzero cstatus wins
 int text_canon_tables(int device, const uint16_t** stage1, const uint32_t** stage2, const uint32_t** pool);   // device addresses
 int text_utf8_hash(ucfp_ctx* ctx, bool sim, const uint8_t* d_utf8, const uint64_t* d_offsets, size_t n, size_t total_bytes,
                    uint32_t k, uint8_t* d_out, int32_t* d_status, hipStream_t stream);

@@ -158,6 +158,14 @@ int launch_text_canon(const uint8_t* utf8, const uint64_t* offsets, size_t n, ui
     return 0;
 }
 
+// the scan and the status merge on their own, for the grapheme tokeniser's canon pass (text_grapheme.hip)
+void launch_text_canon_scan(uint64_t* tok_off, size_t n, hipStream_t stream) {
+    hipLaunchKernelGGL(text_canon_scan_kernel, dim3(1), dim3(1024), 0, stream, tok_off, n);
+}
+void launch_text_canon_merge(const int32_t* cstatus, size_t n, int32_t* status, hipStream_t stream) {
+    if (n) hipLaunchKernelGGL(text_canon_merge_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, cstatus, n, status);
+}
+
 // The device addresses of the code-point table, for the streaming canonicaliser (text_streams.hip): one copy of the
 // table serves both, so what the offline path keeps L2-resident is what a stream push reads.  The tables have internal
 // linkage (the runtime cannot look them up by name), so a one-thread kernel reports where they are.

@@ -3,7 +3,8 @@
 // text_stream_kernel<true> (text_streams.hip, held || chunk of a push) run it.  Here: the flag words of a canonical code
 // point, the LDS stage of one wave, the UAX#29 boundary table, step parts A + B (canon_place: decode, validate, look up,
 // place) and C + D (canon_decide: boundaries, segments, the provisional keep and its rewind, the UTF-8 re-encode, the
-// context for the next step).  The kernels keep what differs between them: where a byte comes from, which step is the
+// context for the next step), and canon_whole, which the grapheme tokeniser (text_grapheme.hip) runs in place
+// of C + D: the whole canonical stream, no boundaries.  The kernels keep what differs between them: where a byte comes from, which step is the
 // last, where a byte goes (the store functor), and the load and store of their state.
 // A header of its own, not a part of text_core.h: the hash stage needs nothing of the code-point table and the canon
 // stage nothing of the LDS batch; what the two share is the launch shape, which this header takes from text_core.h.
@@ -11,6 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/ucfp_text_gtab.h"
 #include "../../include/ucfp_text_utab.h"
 #include "common.h"
 #include "text_core.h"
@@ -202,6 +204,49 @@ __device__ __forceinline__ void canon_decide(CanonLds& L, CanonSeg<P>& S, uint32
     if (lane < 3) L.x[lane] = keep3;
     if (lane >= 61) L.bytes[lane - 61] = (uint8_t)c;
     S.pend = m - ndec;
+}
+
+// a canonical code point whose Grapheme_Cluster_Break is Prepend, L, V or T (include/ucfp_text_gtab.h)
+__device__ __host__ __forceinline__ bool grapheme_excluded(uint32_t cp) {
+    constexpr uint32_t r[UCFP_TEXT_GTAB_N][2] = UCFP_TEXT_GTAB_RANGES;
+    if (cp < UCFP_TEXT_GTAB_MIN || cp > UCFP_TEXT_GTAB_MAX) return false;
+    bool in = false;
+#pragma unroll
+    for (int i = 0; i < UCFP_TEXT_GTAB_N; i++) in = in || (cp >= r[i][0] && cp <= r[i][1]);
+    return in;
+}
+
+// The store mode of the grapheme tokeniser in place of parts C + D: the whole U3 stream, every one of
+// the `added` code points canon_place put in L.x (there is no undecided one: pend = 0), re-encoded at stream position
+// out_pos on; no boundaries, no segments, nothing dropped.  Returns false (wave-uniform) when a code point is outside
+// the grapheme set.  Leaves the byte context for the next step, as canon_decide does.
+template <class P, class Store>
+__device__ __forceinline__ bool canon_whole(CanonLds& L, P& out_pos, uint32_t c, uint32_t added, int lane, const Store& store) {
+    bool excl_any = false;
+    for (uint32_t j0 = 0; j0 < added; j0 += 64) {
+        const uint32_t j = j0 + lane;
+        const bool has = j < added;
+        const uint32_t cpw = has ? L.x[2u + j] & kCpMask : 0u;
+        excl_any |= has && grapheme_excluded(cpw);
+        const uint32_t nb = cpw < 0x80u ? 1u : cpw < 0x800u ? 2u : cpw < 0x10000u ? 3u : 4u;
+        const uint32_t contrib = has ? nb : 0u;
+        const uint32_t cincl = wave_incl_scan(contrib, lane);
+        if (Store::kEmit && has) {
+            P p = out_pos + (cincl - contrib);
+            uint32_t bytes;
+            if (nb == 1) bytes = cpw;
+            else if (nb == 2) bytes = (0xC0u | cpw >> 6) | (0x80u | (cpw & 0x3Fu)) << 8;
+            else if (nb == 3) bytes = (0xE0u | cpw >> 12) | (0x80u | (cpw >> 6 & 0x3Fu)) << 8 | (0x80u | (cpw & 0x3Fu)) << 16;
+            else
+                bytes = (0xF0u | cpw >> 18) | (0x80u | (cpw >> 12 & 0x3Fu)) << 8 | (0x80u | (cpw >> 6 & 0x3Fu)) << 16 |
+                        (0x80u | (cpw & 0x3Fu)) << 24;
+            for (uint32_t t = 0; t < nb; t++, p++) store(p, (uint8_t)(bytes >> (8 * t)));
+        }
+        out_pos += __shfl(cincl, 63, 64);
+    }
+    wave_lds_sync();
+    if (lane >= 61) L.bytes[lane - 61] = (uint8_t)c;
+    return __ballot(excl_any) == 0;
 }
 
 }  // namespace

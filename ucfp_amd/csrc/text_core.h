@@ -2,7 +2,9 @@
 // text_stream_kernel (text_streams.hip, streams) are this file's bodies around their own byte readers.  Here: the launch
 // shape, the LDS batch of one wave and its limits, the ASCII word rule, XXH3 read from LDS, the MinHash second hash, the
 // wave state (TextWave), the 64-byte tokeniser step (text_step), the flush of a batch (text_flush) and the record and
-// status of a finished document (text_emit).  The canon stage in front of it is text_canon_core.h.
+// status of a finished document (text_emit).  The canon stage in front of it is text_canon_core.h.  text_marked_kernel
+// (text_grapheme.hip: graphemes, caller-segmented tokens) runs the same flush and record behind text_step_marked, the step
+// whose token starts are a mask.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -217,6 +219,49 @@ __device__ __forceinline__ uint64_t text_step(WaveLds& L, TextWave& W, int sub, 
     W.carry = (inw >> 63) & 1ull;
     W.prev_last = __shfl(c, 63, 64);
     return inw;
+}
+
+// ---- the marked step (text_grapheme.hip): token starts come from a mask, not from the word rule ----
+// Every byte of the document is a token byte and tokens abut, so a 64-byte step can open 64 tokens and add 64 bytes plus
+// 64 separators.  The byte room of the word step already covers that; the token cap is checked against 64.  After a
+// flush at most k <= 64 tokens remain (k - 1 complete ones and the unfinished one), so, as for the word step, the token
+// cap cannot fail right after a flush and UCFP_TEXT_MAX_WINDOW_BYTES holds unchanged: the kept bytes are a prefix of one
+// k-token window, refused exactly when prefix + 1 + kStepRoom > kCanonCap.
+constexpr int kMarkedStepTok = 64;
+static_assert(64 + kMarkedStepTok <= kStepRoom, "a marked step's bytes and separators fit the room every step demands");
+static_assert(64 + kMarkedStepTok <= kTokCap, "the k <= 64 tokens a flush keeps leave room for a marked step's tokens");
+
+__device__ __forceinline__ bool text_batch_full_marked(const TextWave& W) {
+    return W.ntok + kMarkedStepTok > (uint32_t)kTokCap || W.cbase + W.ntok + kStepRoom > (uint32_t)kCanonCap;
+}
+
+// One 64-byte step: lane = the byte `ch` (already canonical) at `pos`, bytes at or past `end` are not processed; bit i of
+// `starts` says that lane i's byte begins a token; the document's first byte always does.  The last token of a step
+// stays open (W.carry): the next start, or the caller at the document's end, closes it.
+__device__ __forceinline__ void text_step_marked(WaveLds& L, TextWave& W, uint32_t ch, uint64_t starts, size_t pos, size_t end,
+                                                 int lane) {
+    const bool w = pos < end;
+    const uint64_t inw = __ballot(w);
+    if (W.ntok == 0) starts |= 1ull;   // a document's first byte begins its first token, whatever the mask says
+    starts &= inw;
+    const uint32_t nin_before = popc_below(inw, lane);
+    const uint32_t nst_before = popc_below(starts, lane);
+    const bool is_start = (starts >> lane) & 1ull;
+    if (w) {
+        const uint32_t tok = W.ntok + nst_before + (is_start ? 1u : 0u) - 1u;
+        const uint32_t cpos = W.cbase + nin_before + tok;
+        L.canon[cpos] = (uint8_t)ch;
+        if (is_start) {
+            L.cstart[tok] = (uint16_t)cpos;
+            if (tok > 0) {   // the separator in front of it, and the end of the token before it
+                L.canon[cpos - 1] = ' ';
+                L.cend[tok - 1] = (uint16_t)(cpos - 1);
+            }
+        }
+    }
+    W.ntok += (uint32_t)__popcll(starts);
+    W.cbase += (uint32_t)__popcll(inw);
+    W.carry = W.carry || inw != 0;
 }
 
 // The end of a document: its status, and its record at `rec` (MinHash: 1032 bytes; SimHash: 8), zero unless the status is 0.

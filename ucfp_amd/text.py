@@ -17,6 +17,12 @@ text.rs:112-114 -- and the UAX#29 word tokeniser as tables).  O
 canonicaliser) is canonicalised and segmented here on the host (`_prepare`, via the `regex` module) and submitted
 pre-tokenised; both routes give the same record.  Streams follow the same routing chunk by chunk: a
 `MinHashStreams(utf8=True)` set canonicalises and tokenises RAW_UTF8 chunks on the device, cut anywhere.
+
+`TextOpts(tokenizer="grapheme")` routes the same way through the entries that take a tokeniser: every
+UAX#29 extended grapheme cluster of the canonical text is a token, found on the device for ASCII and for the grapheme
+set of UTF-8; what the device hands back and every other canonicaliser is cut into clusters here (`regex`, \\X) and
+hashed through the token entries, which `minhash_tokens` / `simhash_tokens` also open to any tokeniser the caller runs
+itself (the reference's cjk-jp / cjk-ko).  Streams and the micro-batcher are built for the `word` tokeniser only.
 """
 import ctypes as C
 import math
@@ -46,6 +52,7 @@ FORMAT_VERSION = 1   # txtfp::FORMAT_VERSION as stored by text.rs:227
 FORMAT_VERSION_MINHASH_HIP = 0x48500001
 
 RAW_ASCII, PRETOKENIZED, RAW_UTF8 = 0, 1, 2
+TOK_WORD, TOK_GRAPHEME = 0, 1        # UCFP_TEXT_TOK_*: the tokeniser of the ucfp_text_*_batch_ex entries
 NEEDS_HOST = 1
 MINHASH_BYTES, SIMHASH_BYTES = 1032, 8
 TLSH_BYTES = 35             # UCFP_TLSH_BYTES: swap(checksum), swap(L), Q1 << 4 | Q2, code[31] .. code[0]
@@ -122,10 +129,23 @@ def _host_tokens(s: str) -> List[str]:
     return [t for t in regex.split(r"(?w)\b", s, flags=regex.V1) if any(ch.isalnum() for ch in t)]
 
 
+def _host_graphemes(s: str) -> List[str]:
+    import regex  # UAX#29 extended grapheme clusters
+    return regex.findall(r"\X", s)
+
+
+def _unsupported_tokenizer(opts: "TextOpts") -> UnsupportedError:
+    if opts.tokenizer in ("cjk-jp", "cjk-ko"):
+        return UnsupportedError(f"tokenizer `{opts.tokenizer}` is not built into the HIP path: there is no segmenter here.  Run it "
+                                "on the host and pass its tokens to text.minhash_tokens / text.simhash_tokens "
+                                "(ucfp_text_minhash_tokens_batch / ucfp_text_simhash_tokens_batch)")
+    return UnsupportedError(f"tokenizer `{opts.tokenizer}` is not built into the HIP path")
+
+
 def _prepare(text: str, opts: TextOpts) -> Tuple[bytes, int]:
-    """-> (bytes for the GPU, mode)."""
+    """-> (bytes for the GPU, mode); the `word` tokeniser's host route."""
     if opts.tokenizer != "word":
-        raise UnsupportedError(f"tokenizer `{opts.tokenizer}` is not built into the HIP path")
+        raise _unsupported_tokenizer(opts)
     c = opts.canonicalizer
     if text.isascii() and c.case_fold:
         return text.encode("ascii"), RAW_ASCII
@@ -182,9 +202,101 @@ def canon_batch(docs: Sequence[bytes], ctx=None) -> Tuple[List[bytes], np.ndarra
     return [toks[int(toff[i]):int(toff[i + 1])].tobytes() for i in range(n)], status
 
 
+def _run_ex(kind: str, docs: Sequence[bytes], mode: int, tokenizer: int, k: int, ctx=None):
+    """`_run` through the entries that take a tokeniser (ucfp_text_*_batch_ex)."""
+    ctx = ctx or _lib.current_context()
+    lib = _lib.load()
+    blob, offs = _pack(docs)
+    n = len(docs)
+    out = np.zeros((n, SIMHASH_BYTES if kind == "simhash" else MINHASH_BYTES), np.uint8)
+    status = np.zeros(n, np.int32)
+    if kind == "simhash":
+        _lib.check(lib.ucfp_text_simhash_batch_ex(ctx.handle, blob.ctypes.data, offs.ctypes.data, n, mode, tokenizer,
+                                                  out.ctypes.data, status.ctypes.data))
+    else:
+        _lib.check(lib.ucfp_text_minhash_batch_ex(ctx.handle, blob.ctypes.data, offs.ctypes.data, n, mode, tokenizer, k,
+                                                  out.ctypes.data, status.ctypes.data))
+    return out, status
+
+
+def _pack_tokens(docs: Sequence[Sequence[bytes]]):
+    """-> (blob uint8, tok_offsets uint64 [T + 1], doc_tokens uint64 [n + 1]) of the caller-segmented form."""
+    toks = [bytes(t) for d in docs for t in d]
+    tok_offs = np.zeros(len(toks) + 1, np.uint64)
+    np.cumsum([len(t) for t in toks], out=tok_offs[1:])
+    doc_toks = np.zeros(len(docs) + 1, np.uint64)
+    np.cumsum([len(d) for d in docs], out=doc_toks[1:])
+    blob = np.frombuffer(b"".join(toks) + b"\0" * 16, np.uint8)
+    return blob, tok_offs, doc_toks
+
+
+def _run_tokens(kind: str, docs: Sequence[Sequence[bytes]], k: int, ctx=None):
+    ctx = ctx or _lib.current_context()
+    lib = _lib.load()
+    blob, tok_offs, doc_toks = _pack_tokens(docs)
+    n = len(docs)
+    out = np.zeros((n, SIMHASH_BYTES if kind == "simhash" else MINHASH_BYTES), np.uint8)
+    status = np.zeros(n, np.int32)
+    if kind == "simhash":
+        _lib.check(lib.ucfp_text_simhash_tokens_batch(ctx.handle, blob.ctypes.data, tok_offs.ctypes.data, doc_toks.ctypes.data, n,
+                                                      out.ctypes.data, status.ctypes.data))
+    else:
+        _lib.check(lib.ucfp_text_minhash_tokens_batch(ctx.handle, blob.ctypes.data, tok_offs.ctypes.data, doc_toks.ctypes.data, n,
+                                                      k, out.ctypes.data, status.ctypes.data))
+    return out, status
+
+
+def minhash_tokens(docs: Sequence[Sequence[bytes]], k: int = DEFAULT_K, ctx=None):
+    """MinHash-128 of documents the caller has tokenised: `docs` is a sequence of token sequences, a
+    token any `bytes`, spaces and NULs included, hashed as it is; an empty token is not a token.  The route for any
+    tokeniser the caller runs itself (the reference's cjk-jp / cjk-ko).  -> (records uint8 [n, 1032], status int32 [n])."""
+    return _run_tokens("minhash", docs, k, ctx)
+
+
+def simhash_tokens(docs: Sequence[Sequence[bytes]], ctx=None):
+    """SimHash-64 of caller-tokenised documents (see `minhash_tokens`).  -> (records uint8 [n, 8], status int32 [n])."""
+    return _run_tokens("simhash", docs, 1, ctx)
+
+
+def _batch_grapheme(kind: str, texts: Sequence[str], opts: TextOpts, ctx=None):
+    """The `grapheme` tokeniser: ASCII documents go raw (RAW_ASCII, when the canonicaliser folds case),
+    other documents as UTF-8 when the canonicaliser is the default one (RAW_UTF8); what the device hands back and every
+    other canonicaliser is canonicalised and cut into clusters here (`Canonicalizer.apply`, then \\X) and goes to the
+    token entries.  All three routes give the same record."""
+    rec = SIMHASH_BYTES if kind == "simhash" else MINHASH_BYTES
+    out = np.zeros((len(texts), rec), np.uint8)
+    status = np.zeros(len(texts), np.int32)
+    c = opts.canonicalizer
+    host = []
+    groups = {RAW_ASCII: [], RAW_UTF8: []}
+    for i, t in enumerate(texts):
+        if t.isascii() and c.case_fold:
+            groups[RAW_ASCII].append(i)
+        elif not t.isascii() and c.is_default():
+            groups[RAW_UTF8].append(i)
+        else:
+            host.append(i)
+    for mode, idx in groups.items():
+        if not idx:
+            continue
+        o, s = _run_ex(kind, [texts[i].encode("utf-8", "surrogatepass") for i in idx], mode, TOK_GRAPHEME, opts.k, ctx)
+        out[idx] = o
+        status[idx] = s
+        host += [i for i, st in zip(idx, s) if st == NEEDS_HOST]
+    if host:
+        host.sort()
+        docs = [[g.encode("utf-8", "surrogatepass") for g in _host_graphemes(c.apply(texts[i]))] for i in host]
+        o, s = _run_tokens(kind, docs, opts.k, ctx)
+        out[host] = o
+        status[host] = s
+    return out, status
+
+
 def _batch(kind: str, texts: Sequence[str], opts: TextOpts, ctx=None):
     """Split into the raw-ASCII, the raw-UTF-8 and the host-pretokenised group, one launch each; the documents the
     UTF-8 launch hands back join the host group."""
+    if opts.tokenizer == "grapheme":
+        return _batch_grapheme(kind, texts, opts, ctx)
     rec = SIMHASH_BYTES if kind == "simhash" else MINHASH_BYTES
     out = np.zeros((len(texts), rec), np.uint8)
     status = np.zeros(len(texts), np.int32)

@@ -1252,7 +1252,10 @@ int ucfp_index_search_batcher_stats(ucfp_search_batcher* b, uint64_t* batches, u
 /* Final step of a sharded search: merge `parts` per-shard top-k lists -- the
  * all-gathered [parts][nq][k] ids + keys -- into one. Keys: Hamming distance (kind
  * HAMMING64) or the order-preserving u32 image of -score (COSINE_F32) as produced by
- * ucfp_index_search_dev in d_out_dist. Device pointers. */
+ * ucfp_index_search_dev in d_out_dist. Device pointers.
+ * The answer is the best k by (key, id) ascending, both unsigned; an entry with key 2^32-1 is no entry wherever it
+ * stands in its list.  Equal (key, id) pairs from different parts (a stale row that lives in two shards) are emitted
+ * ONCE; the same id under two different keys is two entries.  Any number of parts. */
 int ucfp_topk_merge_dev(ucfp_ctx* ctx, int kind, const uint64_t* d_part_ids, const uint32_t* d_part_keys,
                         uint32_t parts, size_t nq, uint32_t k, uint64_t* d_out_ids, float* d_out_scores,
                         uint32_t* d_out_keys, uint32_t* d_out_counts, void* stream);
@@ -1262,12 +1265,15 @@ int ucfp_topk_merge_dev(ucfp_ctx* ctx, int kind, const uint64_t* d_part_ids, con
  * pack -> (their all-gather into [parts][nq][k] entries) -> merge_packed. */
 int ucfp_topk_pack_dev(ucfp_ctx* ctx, const uint64_t* d_ids, const uint32_t* d_keys, size_t nq, uint32_t k,
                        void* d_entries, void* stream);
+/* The same merge and the same rule as ucfp_topk_merge_dev (equal (key, id) pairs from different parts are emitted once).
+ * Limits: parts <= 64, or any number of parts while parts * k <= 2048; beyond that UCFP_E_UNSUPPORTED. */
 int ucfp_topk_merge_packed_dev(ucfp_ctx* ctx, int kind, const void* d_entries, uint32_t parts, size_t nq, uint32_t k,
                                uint64_t* d_out_ids, float* d_out_scores, uint32_t* d_out_keys, uint32_t* d_out_counts,
                                void* stream);
 /* The same with the missing-shard mask: a shard that could not scan sends nq x k entries of 0xff bytes (id 2^64-1, key
  * 2^32-1 like an empty list, and the pad word 0xffffffff where ucfp_topk_pack_dev writes 0); bit p of *d_missing (device
- * u64, may be NULL; parts <= 64) is set for every such part. */
+ * u64, may be NULL) is set for every such part.  With a mask parts <= 64 always (one bit per part), also where the
+ * merge alone would take more: UCFP_E_UNSUPPORTED otherwise. */
 int ucfp_topk_merge_packed_ex_dev(ucfp_ctx* ctx, int kind, const void* d_entries, uint32_t parts, size_t nq, uint32_t k,
                                   uint64_t* d_out_ids, float* d_out_scores, uint32_t* d_out_keys, uint32_t* d_out_counts,
                                   uint64_t* d_missing, void* stream);

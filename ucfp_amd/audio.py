@@ -18,6 +18,7 @@ from typing import List, Optional
 import numpy as np
 
 from . import _lib
+from ._streams import AudioStreamSet
 from .core import Modality, Record
 from .errors import ModalityError
 
@@ -316,110 +317,62 @@ def fingerprint_haitsma_with(samples, sample_rate: int, cfg: HaitsmaConfig, tena
     return _record(ALGORITHM_HAITSMA, haitsma_frames(samples, sample_rate, cfg).tobytes(), tenant_id, record_id)
 
 
-class WangStreams:
+class WangStreams(AudioStreamSet):
     """A set of live Wang streams on the device (ucfp_wang_streams_*): `push` advances any subset of them
     by one chunk each with one launch sequence and returns the hashes each one emits now -- exactly the offline hashes
     with t_anchor < frontier(n) so far, the rest on the final push (t_anchor = frames since `open`)."""
+    _abi, _cap_entry, _row = "ucfp_wang_streams", "max_hashes", (2,)
 
     def __init__(self, max_streams: int, cfg: Optional[WangConfig] = None, sample_rate: int = WANG_SR, ctx=None):
-        self._lib = _lib.load()
-        self.ctx = ctx or _lib.current_context()
         self._cfg = (cfg or WangConfig())._c()
-        h = C.c_void_p()
-        _lib.check(self._lib.ucfp_wang_streams_create(self.ctx.handle, sample_rate, C.byref(self._cfg), max_streams,
-                                                      C.byref(h)))
-        self.handle = h
+        self._create(ctx, "create", sample_rate, C.byref(self._cfg), max_streams)
         self.max_streams = max_streams
-
-    def open(self) -> int:
-        slot = C.c_uint32(0)
-        _lib.check(self._lib.ucfp_wang_streams_open(self.handle, C.byref(slot)))
-        return int(slot.value)
-
-    def close(self, slot: int) -> None:
-        """Discards the stream; emits nothing."""
-        _lib.check(self._lib.ucfp_wang_streams_close(self.handle, slot))
 
     def frontier(self, n_samples: int) -> int:
         """F(n): after a non-final push, every hash with t_anchor < F(n) has been emitted, and no other."""
         return int(self._lib.ucfp_wang_stream_frontier(n_samples, C.byref(self._cfg)))
 
-    def _arrays(self, slots, counts, final):
-        sl = np.ascontiguousarray(slots, dtype=np.uint32)
-        ns = np.ascontiguousarray(counts, dtype=np.uint64)
-        fi = np.array([1 if s in final else 0 for s in sl.tolist()], np.uint8)
-        return sl, ns, fi
-
-    def max_hashes(self, slots, counts, final=()) -> int:
-        sl, ns, fi = self._arrays(slots, counts, set(final))
-        return int(self._lib.ucfp_wang_streams_max_hashes(self.handle, sl.ctypes.data, ns.ctypes.data, fi.ctypes.data,
-                                                          sl.size))
+    max_hashes = AudioStreamSet._max_rows
 
     def push_dev(self, slots, counts, pcm, out, out_offsets, final=(), cap_hashes: Optional[int] = None,
                  stream: int = 0) -> None:
         """Device variant (no sync): `pcm` the chunks of `slots` concatenated (float32 tensor), `out` an int32 [cap, 2]
         tensor, `out_offsets` an int64 [len(slots) + 1] tensor; hashes of slots[i] = out[out_offsets[i]:out_offsets[i+1]]."""
-        sl, ns, fi = self._arrays(slots, counts, set(final))
-        cap = out.shape[0] if cap_hashes is None else cap_hashes
-        _lib.check(self._lib.ucfp_wang_streams_push_dev(self.handle, sl.ctypes.data, ns.ctypes.data, fi.ctypes.data,
-                                                        sl.size, pcm.data_ptr() if pcm.numel() else None,
-                                                        out.data_ptr() if cap else None, cap, out_offsets.data_ptr(),
-                                                        stream or None))
+        self._push_dev(slots, counts, pcm, out, out_offsets, final, cap_hashes, stream)
 
     def push(self, chunks: dict, final=()) -> dict:
         """{slot: samples} -> {slot: uint32 [n, 2]} of the hashes emitted now; slots in `final` end (and close)."""
-        import torch
-        final = set(final)
-        slots = list(chunks)
-        arrs = [np.ascontiguousarray(chunks[s], dtype=np.float32).reshape(-1) for s in slots]
-        counts = [a.size for a in arrs]
-        cap = self.max_hashes(slots, counts, final)
-        dev = f"cuda:{self.ctx.device}"
-        blob = np.concatenate(arrs) if sum(counts) else np.zeros(0, np.float32)
-        d_pcm = torch.from_numpy(blob).to(dev)
-        d_out = torch.zeros((max(cap, 1), 2), dtype=torch.int32, device=dev)
-        d_oo = torch.zeros(len(slots) + 1, dtype=torch.int64, device=dev)
-        self.push_dev(slots, counts, d_pcm, d_out, d_oo, final, cap, torch.cuda.current_stream().cuda_stream)
-        oo = d_oo.cpu().numpy()
-        out = d_out.cpu().numpy().view(np.uint32)
-        return {s: out[oo[i]:oo[i + 1]].copy() for i, s in enumerate(slots)}
-
-    def destroy(self):
-        if getattr(self, "handle", None):
-            self._lib.ucfp_wang_streams_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
+        return self._push(chunks, final)
 
 
-class StreamingWangSession:
-    """Push/finalize wrapper (audio.rs:414-480) on a one-slot WangStreams: each `push` moves its PCM to the device and
-    advances the stream there; only the hashes emitted so far are held on the host, so memory stays bounded however
-    long the stream runs.  `push` returns no records -- allowed by the reference contract ("typically zero or one");
-    `finalize` returns one record with every hash (the offline hashes of the whole stream, byte for byte)."""
+class _StreamingSession:
+    """push / finalize on a one-slot audio set through its staged single-stream entry: each `push` moves its PCM to the
+    device and advances the stream there; only the rows emitted so far are held on the host."""
+    _algorithm = ""
 
-    def __init__(self, sample_rate: int, tenant_id: int, record_id: int):
-        if sample_rate != WANG_SR:
-            raise ModalityError(f"Wang requires 8 kHz mono input (got {sample_rate} Hz); resample upstream")
+    def _start(self, stream_set, tenant_id: int, record_id: int) -> None:
         self.tenant_id, self.record_id = tenant_id, record_id
-        self._set = WangStreams(1)
+        self._set = stream_set
         self._slot = self._set.open()
-        self._hashes: List[np.ndarray] = []
+        self._n = 0                   # samples since the stream began
+        self._rows: List[np.ndarray] = []
+
+    def _cap(self, n_new: int, final: bool) -> int:
+        return self._set._max_rows([self._slot], [n_new], [self._slot] if final else ())
+
+    def _buffer(self, rows: int) -> np.ndarray:
+        return np.zeros((rows, *self._set._row), np.uint32)
 
     def _push(self, samples, final: bool):
         x = np.ascontiguousarray(samples, dtype=np.float32).reshape(-1)
-        lib = self._set._lib
-        cap = self._set.max_hashes([self._slot], [x.size], [self._slot] if final else ())
-        out = np.zeros((max(cap, 1), 2), np.uint32)
+        cap = self._cap(x.size, final)
+        out = self._buffer(max(cap, 1))
         n = C.c_size_t(0)
-        _lib.check(lib.ucfp_wang_streams_push(self._set.handle, self._slot, x.ctypes.data if x.size else None, x.size,
-                                              1 if final else 0, out.ctypes.data, cap, C.byref(n)))
+        _lib.check(self._set._fn("push")(self._set.handle, self._slot, x.ctypes.data if x.size else None, x.size,
+                                         1 if final else 0, out.ctypes.data, cap, C.byref(n)))
+        self._n += x.size
         if n.value:
-            self._hashes.append(out[: n.value].copy())
+            self._rows.append(out[: n.value].copy())
 
     def push(self, samples) -> List[Record]:
         self._push(samples, False)
@@ -427,87 +380,60 @@ class StreamingWangSession:
 
     def finalize(self) -> List[Record]:
         self._push(np.zeros(0, np.float32), True)
-        self._slot = self._set.open()           # the session may be reused, as before
-        h, self._hashes = self._hashes, []
-        if not h:
+        self._slot = self._set.open()           # the session may be reused
+        self._n = 0
+        rows, self._rows = self._rows, []
+        if not rows:
             return []
-        return [_record(ALGORITHM_WANG, np.concatenate(h).tobytes(), self.tenant_id, self.record_id)]
+        return [_record(self._algorithm, np.concatenate(rows).tobytes(), self.tenant_id, self.record_id)]
 
 
-class HaitsmaStreams:
+class StreamingWangSession(_StreamingSession):
+    """Push/finalize wrapper (audio.rs:414-480) on a one-slot WangStreams: each `push` moves its PCM to the device and
+    advances the stream there; only the hashes emitted so far are held on the host, so memory stays bounded however
+    long the stream runs.  `push` returns no records -- allowed by the reference contract ("typically zero or one");
+    `finalize` returns one record with every hash (the offline hashes of the whole stream, byte for byte)."""
+    _algorithm = ALGORITHM_WANG
+
+    def __init__(self, sample_rate: int, tenant_id: int, record_id: int):
+        if sample_rate != WANG_SR:
+            raise ModalityError(f"Wang requires 8 kHz mono input (got {sample_rate} Hz); resample upstream")
+        self._start(WangStreams(1), tenant_id, record_id)
+
+
+class HaitsmaStreams(AudioStreamSet):
     """A set of live Haitsma streams on the device (ucfp_haitsma_streams_*): `push` advances any subset of
     them by one chunk each with one launch sequence and returns the sub-fingerprints each one emits now -- frames
     [Fr(before), Fr(after)) of its offline record, the rest on the final push.  `blocks` hands out each stream's latest
     `block_frames` sub-fingerprints in the ragged shape `HaitsmaIndex.identify_frames` / ucfp_haitsma_index_query_dev take."""
+    _abi, _cap_entry, _row = "ucfp_haitsma_streams", "max_frames", ()
 
     def __init__(self, max_streams: int, sample_rate: int, cfg: Optional[HaitsmaConfig] = None, block_frames: int = 256,
                  ctx=None):
-        self._lib = _lib.load()
         self._cfg = (cfg or HaitsmaConfig())._c()
-        h = C.c_void_p()
         # as ucfp_haitsma_streams_create: the rate and the band edges are judged before a device is asked for
         if not (1000 <= int(sample_rate) <= 384_000):
             raise ModalityError(f"invalid sample rate {sample_rate} (1 000 .. 384 000 Hz)")
         if not (1.0 <= self._cfg.fmin < self._cfg.fmax <= 2500.0):
             raise ModalityError("Haitsma band edges must satisfy 1 <= fmin < fmax <= 2500 Hz")
-        self.ctx = ctx or _lib.current_context()
-        _lib.check(self._lib.ucfp_haitsma_streams_create(self.ctx.handle, sample_rate, C.byref(self._cfg), max_streams,
-                                                         block_frames, C.byref(h)))
-        self.handle = h
+        self._create(ctx, "create", sample_rate, C.byref(self._cfg), max_streams, block_frames)
         self.max_streams, self.sample_rate, self.block_frames = max_streams, sample_rate, block_frames
-
-    def open(self) -> int:
-        slot = C.c_uint32(0)
-        _lib.check(self._lib.ucfp_haitsma_streams_open(self.handle, C.byref(slot)))
-        return int(slot.value)
-
-    def close(self, slot: int) -> None:
-        """Discards the stream; emits nothing."""
-        _lib.check(self._lib.ucfp_haitsma_streams_close(self.handle, slot))
 
     def emitted(self, n_samples: int, final: bool = False) -> int:
         """Fr(n): the frames a stream has emitted once it has received n samples (all of them after a final push)."""
         return int(self._lib.ucfp_haitsma_stream_frames(n_samples, self.sample_rate, 1 if final else 0))
 
-    def _arrays(self, slots, counts, final):
-        sl = np.ascontiguousarray(slots, dtype=np.uint32)
-        ns = np.ascontiguousarray(counts, dtype=np.uint64)
-        fi = np.array([1 if s in final else 0 for s in sl.tolist()], np.uint8)
-        return sl, ns, fi
-
-    def max_frames(self, slots, counts, final=()) -> int:
-        sl, ns, fi = self._arrays(slots, counts, set(final))
-        return int(self._lib.ucfp_haitsma_streams_max_frames(self.handle, sl.ctypes.data, ns.ctypes.data, fi.ctypes.data,
-                                                             sl.size))
+    max_frames = AudioStreamSet._max_rows
 
     def push_dev(self, slots, counts, pcm, out, out_offsets, final=(), cap_frames: Optional[int] = None,
                  stream: int = 0) -> None:
         """Device variant (no sync): `pcm` the chunks of `slots` concatenated (float32 tensor), `out` an int32 [cap]
         tensor, `out_offsets` an int64 [len(slots) + 1] tensor; frames of slots[i] = out[out_offsets[i]:out_offsets[i+1]]."""
-        sl, ns, fi = self._arrays(slots, counts, set(final))
-        cap = out.shape[0] if cap_frames is None else cap_frames
-        _lib.check(self._lib.ucfp_haitsma_streams_push_dev(self.handle, sl.ctypes.data, ns.ctypes.data, fi.ctypes.data,
-                                                           sl.size, pcm.data_ptr() if pcm.numel() else None,
-                                                           out.data_ptr() if cap else None, cap, out_offsets.data_ptr(),
-                                                           stream or None))
+        self._push_dev(slots, counts, pcm, out, out_offsets, final, cap_frames, stream)
 
     def push(self, chunks: dict, final=()) -> dict:
         """{slot: samples} -> {slot: uint32 [n]} of the sub-fingerprints emitted now; slots in `final` end (and close)."""
-        import torch
-        final = set(final)
-        slots = list(chunks)
-        arrs = [np.ascontiguousarray(chunks[s], dtype=np.float32).reshape(-1) for s in slots]
-        counts = [a.size for a in arrs]
-        dev = f"cuda:{self.ctx.device}"
-        blob = np.concatenate(arrs) if sum(counts) else np.zeros(0, np.float32)
-        d_pcm = torch.from_numpy(blob).to(dev)
-        cap = self.max_frames(slots, counts, final)
-        d_out = torch.zeros(max(cap, 1), dtype=torch.int32, device=dev)
-        d_oo = torch.zeros(len(slots) + 1, dtype=torch.int64, device=dev)
-        self.push_dev(slots, counts, d_pcm, d_out, d_oo, final, cap, torch.cuda.current_stream().cuda_stream)
-        oo = d_oo.cpu().numpy()
-        out = d_out.cpu().numpy().view(np.uint32)
-        return {s: out[oo[i]:oo[i + 1]].copy() for i, s in enumerate(slots)}
+        return self._push(chunks, final)
 
     def blocks_dev(self, slots, out, out_offsets, cap_frames: Optional[int] = None, stream: int = 0) -> None:
         """Device variant (no sync): the live block of slots[i] -> out[out_offsets[i]:out_offsets[i+1]] (`out` an int32
@@ -520,139 +446,61 @@ class HaitsmaStreams:
 
     def blocks(self, slots) -> dict:
         """{slot: uint32 [m]}: each stream's latest m = min(block_frames, frames emitted) sub-fingerprints, oldest first."""
-        import torch
         slots = list(slots)
-        dev = f"cuda:{self.ctx.device}"
-        cap = len(slots) * self.block_frames
-        d_out = torch.zeros(max(cap, 1), dtype=torch.int32, device=dev)
-        d_oo = torch.zeros(len(slots) + 1, dtype=torch.int64, device=dev)
-        self.blocks_dev(slots, d_out, d_oo, cap, torch.cuda.current_stream().cuda_stream)
-        oo = d_oo.cpu().numpy()
-        out = d_out.cpu().numpy().view(np.uint32)
-        return {s: out[oo[i]:oo[i + 1]].copy() for i, s in enumerate(slots)}
-
-    def destroy(self):
-        if getattr(self, "handle", None):
-            self._lib.ucfp_haitsma_streams_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
+        rows = self._ragged(len(slots), len(slots) * self.block_frames, (),
+                            lambda out, oo, cap, st: self.blocks_dev(slots, out, oo, cap, st))
+        return dict(zip(slots, rows))
 
 
-class StreamingHaitsmaSession:
+class StreamingHaitsmaSession(_StreamingSession):
     """Push/finalize wrapper on a one-slot HaitsmaStreams, the shape of StreamingWangSession: each `push` moves its PCM to
     the device and advances the stream there; only the sub-fingerprints emitted so far are held on the host.  `push`
     returns no records; `finalize` returns one record equal to `fingerprint_haitsma_with` of the whole stream byte for
     byte, or none when the stream is too short for a frame."""
+    _algorithm = ALGORITHM_HAITSMA
 
     def __init__(self, sample_rate: int, tenant_id: int, record_id: int, cfg: Optional[HaitsmaConfig] = None):
-        self.tenant_id, self.record_id = tenant_id, record_id
-        self._set = HaitsmaStreams(1, sample_rate, cfg, block_frames=0)
-        self._slot = self._set.open()
-        self._n = 0
-        self._frames: List[np.ndarray] = []
+        self._start(HaitsmaStreams(1, sample_rate, cfg, block_frames=0), tenant_id, record_id)
 
-    def _push(self, samples, final: bool):
-        x = np.ascontiguousarray(samples, dtype=np.float32).reshape(-1)
-        cap = self._set.emitted(self._n + x.size, final) - self._set.emitted(self._n)
-        out = np.zeros(max(cap, 1), np.uint32)
-        n = C.c_size_t(0)
-        _lib.check(self._set._lib.ucfp_haitsma_streams_push(self._set.handle, self._slot, x.ctypes.data if x.size else None,
-                                                            x.size, 1 if final else 0, out.ctypes.data, cap, C.byref(n)))
-        self._n += x.size
-        if n.value:
-            self._frames.append(out[: n.value].copy())
-
-    def push(self, samples) -> List[Record]:
-        self._push(samples, False)
-        return []
-
-    def finalize(self) -> List[Record]:
-        self._push(np.zeros(0, np.float32), True)
-        self._slot = self._set.open()           # the session may be reused
-        self._n = 0
-        f, self._frames = self._frames, []
-        if not f:
-            return []
-        return [_record(ALGORITHM_HAITSMA, np.concatenate(f).tobytes(), self.tenant_id, self.record_id)]
+    def _cap(self, n_new: int, final: bool) -> int:      # from the closed form, without a call into the set
+        return self._set.emitted(self._n + n_new, final) - self._set.emitted(self._n)
 
 
-class PanakoStreams:
+class PanakoStreams(AudioStreamSet):
     """A set of live Panako streams on the device (ucfp_panako_streams_*): `push` advances any subset of
     them by one chunk each with one launch sequence and returns the records each one emits now -- exactly the offline
     records with t_a < frontier(n) so far, the rest on the final push (times = frames since `open`).  With
     `window_frames` = W > 0, `windows` hands out each stream's latest W frames of records, rebased to the window's
     origin, in the ragged shape `PanakoIndex.query_dev` / ucfp_panako_index_query_dev take."""
+    _abi, _cap_entry, _row = "ucfp_panako_streams", "max_hashes", (4,)
 
     def __init__(self, max_streams: int, cfg: Optional[PanakoConfig] = None, window_frames: int = 0,
                  sample_rate: int = WANG_SR, ctx=None):
-        self._lib = _lib.load()
-        self.ctx = ctx or _lib.current_context()
         self._cfg = (cfg or PanakoConfig())._c()
-        h = C.c_void_p()
-        _lib.check(self._lib.ucfp_panako_streams_create(self.ctx.handle, sample_rate, C.byref(self._cfg), max_streams,
-                                                        window_frames, C.byref(h)))
-        self.handle = h
+        self._create(ctx, "create", sample_rate, C.byref(self._cfg), max_streams, window_frames)
         self.max_streams, self.window_frames = max_streams, window_frames
         self.window_cap = int(self._lib.ucfp_panako_streams_window_cap(C.byref(self._cfg), window_frames))
 
-    def open(self) -> int:
-        slot = C.c_uint32(0)
-        _lib.check(self._lib.ucfp_panako_streams_open(self.handle, C.byref(slot)))
-        return int(slot.value)
-
     def close(self, slot: int) -> None:
         """Discards the stream and its window; emits nothing."""
-        _lib.check(self._lib.ucfp_panako_streams_close(self.handle, slot))
+        super().close(slot)
 
     def frontier(self, n_samples: int) -> int:
         """F(n): after a non-final push, every record with t_a < F(n) has been emitted, and no other."""
         return int(self._lib.ucfp_panako_stream_frontier(n_samples, C.byref(self._cfg)))
 
-    def _arrays(self, slots, counts, final):
-        sl = np.ascontiguousarray(slots, dtype=np.uint32)
-        ns = np.ascontiguousarray(counts, dtype=np.uint64)
-        fi = np.array([1 if s in final else 0 for s in sl.tolist()], np.uint8)
-        return sl, ns, fi
-
-    def max_hashes(self, slots, counts, final=()) -> int:
-        sl, ns, fi = self._arrays(slots, counts, set(final))
-        return int(self._lib.ucfp_panako_streams_max_hashes(self.handle, sl.ctypes.data, ns.ctypes.data, fi.ctypes.data,
-                                                            sl.size))
+    max_hashes = AudioStreamSet._max_rows
 
     def push_dev(self, slots, counts, pcm, out, out_offsets, final=(), cap_hashes: Optional[int] = None,
                  stream: int = 0) -> None:
         """Device variant (no sync): `pcm` the chunks of `slots` concatenated (float32 tensor), `out` an int32 [cap, 4]
         tensor (16-byte aligned), `out_offsets` an int64 [len(slots) + 1] tensor; records of slots[i] =
         out[out_offsets[i]:out_offsets[i+1]]."""
-        sl, ns, fi = self._arrays(slots, counts, set(final))
-        cap = out.shape[0] if cap_hashes is None else cap_hashes
-        _lib.check(self._lib.ucfp_panako_streams_push_dev(self.handle, sl.ctypes.data, ns.ctypes.data, fi.ctypes.data,
-                                                          sl.size, pcm.data_ptr() if pcm.numel() else None,
-                                                          out.data_ptr() if cap else None, cap, out_offsets.data_ptr(),
-                                                          stream or None))
+        self._push_dev(slots, counts, pcm, out, out_offsets, final, cap_hashes, stream)
 
     def push(self, chunks: dict, final=()) -> dict:
         """{slot: samples} -> {slot: uint32 [n, 4]} of the records emitted now; slots in `final` end (and close)."""
-        import torch
-        final = set(final)
-        slots = list(chunks)
-        arrs = [np.ascontiguousarray(chunks[s], dtype=np.float32).reshape(-1) for s in slots]
-        counts = [a.size for a in arrs]
-        cap = self.max_hashes(slots, counts, final)
-        dev = f"cuda:{self.ctx.device}"
-        blob = np.concatenate(arrs) if sum(counts) else np.zeros(0, np.float32)
-        d_pcm = torch.from_numpy(blob).to(dev)
-        d_out = torch.zeros((max(cap, 1), 4), dtype=torch.int32, device=dev)
-        d_oo = torch.zeros(len(slots) + 1, dtype=torch.int64, device=dev)
-        self.push_dev(slots, counts, d_pcm, d_out, d_oo, final, cap, torch.cuda.current_stream().cuda_stream)
-        oo = d_oo.cpu().numpy()
-        out = d_out.cpu().numpy().view(np.uint32)
-        return {s: out[oo[i]:oo[i + 1]].copy() for i, s in enumerate(slots)}
+        return self._push(chunks, final)
 
     def windows_dev(self, slots, records, offsets, origins=None, cap_records: Optional[int] = None,
                     stream: int = 0) -> None:
@@ -670,60 +518,23 @@ class PanakoStreams:
         """{slot: (uint32 [m, 4] records rebased to the window's origin, origin)}, oldest record first."""
         import torch
         slots = list(slots)
-        dev = f"cuda:{self.ctx.device}"
-        cap = len(slots) * self.window_cap
-        d_rec = torch.zeros((max(cap, 1), 4), dtype=torch.int32, device=dev)
-        d_off = torch.zeros(len(slots) + 1, dtype=torch.int64, device=dev)
-        d_org = torch.zeros(max(len(slots), 1), dtype=torch.int32, device=dev)
-        self.windows_dev(slots, d_rec, d_off, d_org, cap, torch.cuda.current_stream().cuda_stream)
-        off = d_off.cpu().numpy() // 16
+        d_org = torch.zeros(max(len(slots), 1), dtype=torch.int32, device=f"cuda:{self.ctx.device}")
+        recs = self._ragged(len(slots), len(slots) * self.window_cap, (4,),
+                            lambda out, off, cap, st: self.windows_dev(slots, out, off, d_org, cap, st), unit=16)
         org = d_org.cpu().numpy().view(np.uint32)
-        rec = d_rec.cpu().numpy().view(np.uint32)
-        return {s: (rec[off[i]:off[i + 1]].copy(), int(org[i])) for i, s in enumerate(slots)}
-
-    def destroy(self):
-        if getattr(self, "handle", None):
-            self._lib.ucfp_panako_streams_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
+        return {s: (recs[i], int(org[i])) for i, s in enumerate(slots)}
 
 
-class StreamingPanakoSession:
+class StreamingPanakoSession(_StreamingSession):
     """Push/finalize wrapper on a one-slot PanakoStreams, the shape of StreamingWangSession: each `push` moves its PCM
     to the device and advances the stream there; only the records emitted so far are held on the host.  `push` returns
     no records; `finalize` returns one record equal to `fingerprint_panako_with` of the whole stream byte for byte."""
+    _algorithm = ALGORITHM_PANAKO
 
     def __init__(self, sample_rate: int, tenant_id: int, record_id: int, cfg: Optional[PanakoConfig] = None):
         if sample_rate != WANG_SR:
             raise ModalityError(f"Panako requires 8 kHz mono input (got {sample_rate} Hz); resample upstream")
-        self.tenant_id, self.record_id = tenant_id, record_id
-        self._set = PanakoStreams(1, cfg)
-        self._slot = self._set.open()
-        self._hashes: List[np.ndarray] = []
+        self._start(PanakoStreams(1, cfg), tenant_id, record_id)
 
-    def _push(self, samples, final: bool):
-        x = np.ascontiguousarray(samples, dtype=np.float32).reshape(-1)
-        cap = self._set.max_hashes([self._slot], [x.size], [self._slot] if final else ())
-        out = _aligned_records(max(cap, 1))
-        n = C.c_size_t(0)
-        _lib.check(self._set._lib.ucfp_panako_streams_push(self._set.handle, self._slot, x.ctypes.data if x.size else None,
-                                                           x.size, 1 if final else 0, out.ctypes.data, cap, C.byref(n)))
-        if n.value:
-            self._hashes.append(out[: n.value].copy())
-
-    def push(self, samples) -> List[Record]:
-        self._push(samples, False)
-        return []
-
-    def finalize(self) -> List[Record]:
-        self._push(np.zeros(0, np.float32), True)
-        self._slot = self._set.open()           # the session may be reused
-        h, self._hashes = self._hashes, []
-        if not h:
-            return []
-        return [_record(ALGORITHM_PANAKO, np.concatenate(h).tobytes(), self.tenant_id, self.record_id)]
+    def _buffer(self, rows: int) -> np.ndarray:
+        return _aligned_records(rows)

@@ -15,6 +15,7 @@
 #include "../../include/ucfp_hip.h"
 #include "common.h"
 #include "ctx.h"
+#include "stream_set.h"
 
 #define fail ucfp::capi_fail
 
@@ -57,21 +58,14 @@ struct Plan {
 
 }  // namespace
 
-struct ucfp_haitsma_streams {
+// the slot table counts samples; the pinned tables hold a push or the entries of a blocks call
+struct ucfp_haitsma_streams : ucfp::streams::Slots, ucfp::streams::Tables {
     ucfp_ctx* ctx = nullptr;
-    uint32_t sr = 0, block = 0, max_streams = 0;
-    std::mutex mu;                        // serialises the set's calls
-    std::vector<uint64_t> n;              // samples seen per slot
-    std::vector<uint8_t> open;
-    std::vector<uint8_t> seen;            // duplicate-slot check of one call
+    uint32_t sr = 0, block = 0;
     std::vector<Plan> plan;
     ucfp::HaitsmaStreamsDev dev{};
     uint8_t* dev_mem = nullptr;
     ucfp::HaitsmaBlockEntry* blk_d = nullptr;   // the table of the last blocks call
-    uint8_t* tab_h[2] = {nullptr, nullptr};     // pinned tables (pushes and blocks calls), used in turn
-    hipEvent_t tab_copied[2] = {nullptr, nullptr};
-    int tab_next = 0;
-    hipEvent_t done = nullptr;            // behind the last push / blocks call: the next one waits for it
 };
 
 namespace {
@@ -80,28 +74,12 @@ size_t tab_bytes_max(uint32_t max_streams) {
     return (size_t)max_streams * sizeof(ucfp::HaitsmaStreamEntry) + 2 * ((size_t)max_streams + 1) * 4 + 256;
 }
 
-// slots of one call: in range, open, distinct (s->seen is all zero between calls)
-int check_slots(ucfp_haitsma_streams* s, const uint32_t* slots, size_t n) {
-    if (n && !slots) return fail(UCFP_E_INVALID, "slots is NULL");
-    if (n > s->max_streams) return fail(UCFP_E_INVALID, "%zu entries in one call, the set has %u slots", n, s->max_streams);
-    int rc = UCFP_OK;
-    for (size_t i = 0; i < n && rc == UCFP_OK; i++) {
-        const uint32_t slot = slots[i];
-        if (slot >= s->max_streams) rc = fail(UCFP_E_INVALID, "slot %u out of range [0, %u)", slot, s->max_streams);
-        else if (!s->open[slot]) rc = fail(UCFP_E_INVALID, "slot %u is not open", slot);
-        else if (s->seen[slot]) rc = fail(UCFP_E_INVALID, "slot %u appears twice in one call", slot);
-        else s->seen[slot] = 1;
-    }
-    for (size_t j = 0; j < n; j++)
-        if (slots[j] < s->max_streams) s->seen[slots[j]] = 0;
-    return rc;
-}
-
 // validates the push and plans every entry; nothing changes.  *frames: what the push emits, *run: its 5 kHz samples
 int plan_push(ucfp_haitsma_streams* s, const uint32_t* slots, const uint64_t* n_samples, const uint8_t* fin, size_t n,
               size_t* frames, uint64_t* run) {
     if (n && !n_samples) return fail(UCFP_E_INVALID, "n_samples is NULL");
-    int rc = check_slots(s, slots, n);
+    if (n && !slots) return fail(UCFP_E_INVALID, "slots is NULL");
+    int rc = s->check(slots, n, "entries", "call");   // every slot is judged before anything else
     if (rc) return rc;
     s->plan.resize(n);
     uint64_t total_f = 0, total_r = 0;
@@ -132,14 +110,6 @@ int plan_push(ucfp_haitsma_streams* s, const uint32_t* slots, const uint64_t* n_
     return UCFP_OK;
 }
 
-// the next pinned table; the one it replaces was copied two calls ago
-int next_table(ucfp_haitsma_streams* s, int* k) {
-    *k = s->tab_next;
-    s->tab_next ^= 1;
-    HIP_TRY(hipEventSynchronize(s->tab_copied[*k]));
-    return UCFP_OK;
-}
-
 // the set's and the context's locks are held; the plan is current
 int push_impl(ucfp_haitsma_streams* s, size_t n, size_t frames, uint64_t run, const float* d_pcm, uint32_t* d_out,
               uint64_t* d_out_offsets, hipStream_t st) {
@@ -149,7 +119,7 @@ int push_impl(ucfp_haitsma_streams* s, size_t n, size_t frames, uint64_t run, co
     int rc = ucfp::grow(&ctx->audio_ws, &ctx->audio_ws_cap, w.total);
     if (rc) return rc;
     int k = 0;
-    rc = next_table(s, &k);
+    rc = s->next(&k);
     if (rc) return rc;
     uint8_t* tab = s->tab_h[k];
     auto* ents = reinterpret_cast<ucfp::HaitsmaStreamEntry*>(tab + w.ents);
@@ -230,10 +200,7 @@ int ucfp_haitsma_streams_create(ucfp_ctx* ctx, uint32_t sample_rate, const ucfp_
     s->ctx = ctx;
     s->sr = sample_rate;
     s->block = block_frames;
-    s->max_streams = max_streams;
-    s->n.assign(max_streams, 0);
-    s->open.assign(max_streams, 0);
-    s->seen.assign(max_streams, 0);
+    s->init(max_streams);
     const uint32_t cc = carry_cap_of(sample_rate);
     const size_t ms = max_streams;
     const size_t bytes = ms * (state_bytes_per_stream(sample_rate, block_frames) + sizeof(ucfp::HaitsmaBlockEntry)) + 8 * 256;
@@ -253,9 +220,7 @@ int ucfp_haitsma_streams_create(ucfp_ctx* ctx, uint32_t sample_rate, const ucfp_
         s->dev.block = block_frames;
         e = hipMemcpy(s->dev.edges, edges, sizeof edges, hipMemcpyHostToDevice);
     }
-    for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipHostMalloc((void**)&s->tab_h[i], tab_bytes_max(max_streams), 0);
-    for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipEventCreateWithFlags(&s->tab_copied[i], hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&s->done, hipEventDisableTiming);
+    if (e == hipSuccess) e = s->setup(tab_bytes_max(max_streams));
     if (e != hipSuccess) {
         ucfp_haitsma_streams_destroy(s);
         return fail(UCFP_E_INDEX, "stream set allocation failed: %s", hipGetErrorString(e));
@@ -266,37 +231,21 @@ int ucfp_haitsma_streams_create(ucfp_ctx* ctx, uint32_t sample_rate, const ucfp_
 
 void ucfp_haitsma_streams_destroy(ucfp_haitsma_streams* s) {
     if (!s) return;
-    if (s->done) (void)hipEventSynchronize(s->done);
+    s->teardown();
     if (s->dev_mem) (void)hipFree(s->dev_mem);
-    for (int i = 0; i < 2; i++) {
-        if (s->tab_h[i]) (void)hipHostFree(s->tab_h[i]);
-        if (s->tab_copied[i]) (void)hipEventDestroy(s->tab_copied[i]);
-    }
-    if (s->done) (void)hipEventDestroy(s->done);
     delete s;
 }
 
 int ucfp_haitsma_streams_open(ucfp_haitsma_streams* s, uint32_t* slot) {
     if (!s || !slot) return fail(UCFP_E_INVALID, "set / slot is NULL");
     std::lock_guard<std::mutex> lk(s->mu);
-    for (uint32_t i = 0; i < s->max_streams; i++) {
-        if (!s->open[i]) {
-            s->open[i] = 1;
-            s->n[i] = 0;
-            *slot = i;
-            return UCFP_OK;
-        }
-    }
-    return fail(UCFP_E_INVALID, "all %u slots are open", s->max_streams);
+    return s->acquire(slot);
 }
 
 int ucfp_haitsma_streams_close(ucfp_haitsma_streams* s, uint32_t slot) {
     if (!s) return fail(UCFP_E_INVALID, "set is NULL");
     std::lock_guard<std::mutex> lk(s->mu);
-    if (slot >= s->max_streams || !s->open[slot]) return fail(UCFP_E_INVALID, "slot %u is not open", slot);
-    s->open[slot] = 0;
-    s->n[slot] = 0;
-    return UCFP_OK;
+    return s->release(slot);
 }
 
 size_t ucfp_haitsma_streams_max_frames(ucfp_haitsma_streams* s, const uint32_t* slots, const uint64_t* n_samples,
@@ -364,7 +313,8 @@ int ucfp_haitsma_streams_blocks_dev(ucfp_haitsma_streams* s, const uint32_t* slo
     if (!s) return fail(UCFP_E_INVALID, "set is NULL");
     if (!d_offsets || (cap_frames && !d_frames)) return fail(UCFP_E_INVALID, "NULL buffer");
     std::lock_guard<std::mutex> lk(s->mu);
-    int rc = check_slots(s, slots, n);
+    if (n && !slots) return fail(UCFP_E_INVALID, "slots is NULL");
+    int rc = s->check(slots, n, "entries", "call");   // every slot is judged before anything else
     if (rc) return rc;
     uint64_t total = 0;
     for (size_t i = 0; i < n; i++) {
@@ -376,7 +326,7 @@ int ucfp_haitsma_streams_blocks_dev(ucfp_haitsma_streams* s, const uint32_t* slo
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipSetDevice(s->ctx->device));
     int k = 0;
-    rc = next_table(s, &k);
+    rc = s->next(&k);
     if (rc) return rc;
     auto* tab = reinterpret_cast<ucfp::HaitsmaBlockEntry*>(s->tab_h[k]);
     uint64_t off = 0;

@@ -29,18 +29,22 @@ size_t window_cap_of(const Cfg& c, uint32_t w) {
     return w ? ((size_t)(2 * w + 124) / 125 + 1) * c.peaks_per_sec * c.fan_out : 0;
 }
 
-// the set's and the context's locks are held; the plan is current
-int push_impl(ucfp_panako_streams* s, size_t n, const float* d_pcm, uint8_t* d_out, size_t cap_hashes,
-              uint64_t* d_out_offsets, hipStream_t st) {
-    const Cfg& c = s->cfg;
-    ucfp::WangPushWs w;
-    int rc = push_begin(s, n, st, &w);
-    if (rc) return rc;
-    ucfp::launch_panako_streams_push(d_pcm, s->dev, s->rings, c.fan_out, c.target_zone_t, c.target_zone_f,
-                                     c.peaks_per_sec, s->floor_p, s->ctx->audio_ws, w,
-                                     reinterpret_cast<uint32_t*>(d_out), cap_hashes, d_out_offsets, st);
-    return push_end(s, n, st);
-}
+// what Panako's entries put into the shared ones (wang_streams_core.h): 16-byte aligned records, fewer than 2^32 - 1 of
+// them per push, its name, its launch
+struct Panako {
+    using set = ucfp_panako_streams;
+    static constexpr size_t rec_bytes = 16, align = 16;
+    static constexpr const char* align_msg = "the record buffer must be 16-byte aligned";
+    static constexpr const char* abi = "panako";
+    static constexpr bool bound32 = true;
+    static void launch(set* s, const float* d_pcm, const ucfp::WangPushWs& w, uint8_t* d_out, size_t cap_hashes,
+                       uint64_t* d_out_offsets, hipStream_t st) {
+        const Cfg& c = s->cfg;
+        ucfp::launch_panako_streams_push(d_pcm, s->dev, s->rings, c.fan_out, c.target_zone_t, c.target_zone_f,
+                                         c.peaks_per_sec, s->floor_p, s->ctx->audio_ws, w,
+                                         reinterpret_cast<uint32_t*>(d_out), cap_hashes, d_out_offsets, st);
+    }
+};
 
 }  // namespace
 
@@ -120,65 +124,18 @@ int ucfp_panako_streams_close(ucfp_panako_streams* s, uint32_t slot) {
 
 size_t ucfp_panako_streams_max_hashes(ucfp_panako_streams* s, const uint32_t* slots, const uint64_t* n_samples,
                                       const uint8_t* final, size_t n) {
-    if (!s) return 0;
-    std::lock_guard<std::mutex> lk(s->mu);
-    size_t bound = 0;
-    return plan_push(s, slots, n_samples, final, n, &bound) == UCFP_OK ? bound : 0;
+    return entry_max_hashes<Panako>(s, slots, n_samples, final, n);
 }
 
 int ucfp_panako_streams_push_dev(ucfp_panako_streams* s, const uint32_t* slots, const uint64_t* n_samples,
                                  const uint8_t* final, size_t n, const float* d_pcm, uint8_t* d_out, size_t cap_hashes,
                                  uint64_t* d_out_offsets, void* stream) {
-    if (!s) return fail(UCFP_E_INVALID, "set is NULL");
-    if (!d_out_offsets || (cap_hashes && !d_out)) return fail(UCFP_E_INVALID, "NULL buffer");
-    if (cap_hashes && ((uintptr_t)d_out & 15u)) return fail(UCFP_E_INVALID, "the record buffer must be 16-byte aligned");
-    std::lock_guard<std::mutex> lk(s->mu);
-    size_t bound = 0;
-    int rc = plan_push(s, slots, n_samples, final, n, &bound);
-    if (rc) return rc;
-    uint64_t total = 0;
-    for (size_t i = 0; i < n; i++) total += n_samples[i];
-    if (total && !d_pcm) return fail(UCFP_E_INVALID, "d_pcm is NULL");
-    if (cap_hashes < bound)
-        return fail(UCFP_E_INVALID, "cap_hashes %zu below ucfp_panako_streams_max_hashes = %zu", cap_hashes, bound);
-    if (bound >= 0xffffffffu) return fail(UCFP_E_INVALID, "push too large for one call: split it");
-    std::lock_guard<std::mutex> lk2(s->ctx->mu);
-    return push_impl(s, n, d_pcm, d_out, cap_hashes, d_out_offsets, (hipStream_t)stream);
+    return entry_push_dev<Panako>(s, slots, n_samples, final, n, d_pcm, d_out, cap_hashes, d_out_offsets, stream);
 }
 
 int ucfp_panako_streams_push(ucfp_panako_streams* s, uint32_t slot, const float* pcm, size_t n, int final, uint8_t* out,
                              size_t cap_hashes, size_t* n_hashes) {
-    if (!s || !n_hashes) return fail(UCFP_E_INVALID, "set / n_hashes is NULL");
-    *n_hashes = 0;
-    if ((n && !pcm) || (cap_hashes && !out)) return fail(UCFP_E_INVALID, "NULL buffer");
-    std::lock_guard<std::mutex> lk(s->mu);
-    const uint64_t m = n;
-    const uint8_t fin = final ? 1 : 0;
-    size_t bound = 0;
-    int rc = plan_push(s, &slot, &m, &fin, 1, &bound);
-    if (rc) return rc;
-    if (cap_hashes < bound)
-        return fail(UCFP_E_INVALID, "cap_hashes %zu below ucfp_panako_streams_max_hashes = %zu", cap_hashes, bound);
-    if (bound >= 0xffffffffu) return fail(UCFP_E_INVALID, "push too large for one call: split it");
-    ucfp_ctx* ctx = s->ctx;
-    std::lock_guard<std::mutex> lk2(ctx->mu);
-    HIP_TRY(hipSetDevice(ctx->device));
-    rc = ucfp::grow(&ctx->stage_in, &ctx->stage_in_cap, (n ? n : 1) * 4);
-    if (!rc) rc = ucfp::grow(&ctx->stage_out, &ctx->stage_out_cap, 256 + (bound ? bound : 1) * 16);
-    if (rc) return rc;
-    hipStream_t st = ctx->host_stream;
-    uint64_t* d_off = reinterpret_cast<uint64_t*>(ctx->stage_out);
-    uint8_t* d_out = ctx->stage_out + 256;          // hipMalloc'ed, so 256 on keeps the 16-byte alignment
-    if (n) HIP_TRY(hipMemcpyAsync(ctx->stage_in, pcm, n * 4, hipMemcpyHostToDevice, st));
-    rc = push_impl(s, 1, reinterpret_cast<const float*>(ctx->stage_in), d_out, bound, d_off, st);
-    if (rc) return rc;
-    uint64_t off[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(off, d_off, 16, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const size_t h = (size_t)(off[1] - off[0]);
-    if (h) HIP_TRY(hipMemcpy(out, d_out + off[0] * 16, h * 16, hipMemcpyDeviceToHost));
-    *n_hashes = h;
-    return UCFP_OK;
+    return entry_push<Panako>(s, slot, pcm, n, final, out, cap_hashes, n_hashes);
 }
 
 int ucfp_panako_streams_windows_dev(ucfp_panako_streams* s, const uint32_t* slots, size_t n, uint8_t* d_records,
@@ -188,17 +145,7 @@ int ucfp_panako_streams_windows_dev(ucfp_panako_streams* s, const uint32_t* slot
     if (cap_records && ((uintptr_t)d_records & 15u)) return fail(UCFP_E_INVALID, "the record buffer must be 16-byte aligned");
     std::lock_guard<std::mutex> lk(s->mu);
     if (!s->window) return fail(UCFP_E_INVALID, "the set was created with window_frames = 0: it keeps no windows");
-    if (n > s->max_streams) return fail(UCFP_E_INVALID, "%zu items in one call, the set has %u slots", n, s->max_streams);
-    int rc = UCFP_OK;
-    for (size_t i = 0; i < n && rc == UCFP_OK; i++) {
-        const uint32_t slot = slots[i];
-        if (slot >= s->max_streams) rc = fail(UCFP_E_INVALID, "slot %u out of range [0, %u)", slot, s->max_streams);
-        else if (!s->open[slot]) rc = fail(UCFP_E_INVALID, "slot %u is not open", slot);
-        else if (s->seen[slot]) rc = fail(UCFP_E_INVALID, "slot %u appears twice in one call", slot);
-        else s->seen[slot] = 1;
-    }
-    for (size_t i = 0; i < n; i++)
-        if (slots[i] < s->max_streams) s->seen[slots[i]] = 0;
+    int rc = s->check(slots, n, "items", "call");
     if (rc) return rc;
     const size_t need = n * (size_t)s->rings.cap;
     if (cap_records < need)
@@ -212,9 +159,9 @@ int ucfp_panako_streams_windows_dev(ucfp_panako_streams* s, const uint32_t* slot
     rc = ucfp::grow(&ctx->audio_ws, &ctx->audio_ws_cap, w.total);
     if (rc) return rc;
     // the items go through the set's pinned tables, in turn with the pushes'
-    const int k = s->tab_next;
-    s->tab_next ^= 1;
-    HIP_TRY(hipEventSynchronize(s->tab_copied[k]));
+    int k = 0;
+    rc = s->next(&k);
+    if (rc) return rc;
     auto* items = reinterpret_cast<ucfp::PanakoWindowItem*>(s->tab_h[k]);
     for (size_t i = 0; i < n; i++) {
         const uint64_t ns = s->n[slots[i]], f = frontier_of(judged_of(ns), s->cfg.target_zone_t);

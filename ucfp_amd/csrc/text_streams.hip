@@ -396,22 +396,16 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void text_stream_kernel(
 
 // ================================================ host ================================================
 
-struct ucfp_text_streams {
+#include "stream_set.h"
+
+// the slot table counts bytes; the pinned tables hold a push
+struct ucfp_text_streams : ucfp::streams::Slots, ucfp::streams::Tables {
     ucfp_ctx* ctx = nullptr;
     uint32_t k = 0;
-    uint32_t max_streams = 0;
-    std::mutex mu;                        // serialises the set's calls
-    std::vector<uint64_t> n;              // bytes seen per slot
-    std::vector<uint8_t> open;
     std::vector<uint8_t> fresh;           // opened, not pushed yet: the device state is not read
     std::vector<uint8_t> mode;
-    std::vector<uint8_t> seen;            // duplicate-slot check of one push
     ucfp::TextStreamState* states = nullptr;
     ucfp::TextStreamEntry* tab_d = nullptr;           // the push table on the device; the next push waits for `done`
-    ucfp::TextStreamEntry* tab_h[2] = {nullptr, nullptr};   // pinned push tables, used in turn
-    hipEvent_t tab_copied[2] = {nullptr, nullptr};
-    int tab_next = 0;
-    hipEvent_t done = nullptr;            // behind the last push: the next one waits for it
     // UTF-8 sets (UCFP_TEXT_STREAMS_UTF8); the push tables then carry a CanonSlice per entry behind the entries
     bool utf8 = false;
     uint64_t max_push_bytes = 0;          // RAW_UTF8 chunk bytes one push may carry: the scratch is sized for them
@@ -431,20 +425,14 @@ uint64_t slice_bytes(uint64_t len) {
 // validates the push; nothing changes
 int check_push(ucfp_text_streams* s, const uint32_t* slots, const uint64_t* n_bytes, size_t n) {
     if (n && (!slots || !n_bytes)) return fail(UCFP_E_INVALID, "slots / n_bytes is NULL");
-    if (n > s->max_streams) return fail(UCFP_E_INVALID, "%zu entries in one push, the set has %u slots", n, s->max_streams);
-    int rc = UCFP_OK;
-    size_t marked = 0;
+    int rc = s->fits(n, "entries", "push");
+    if (rc) return rc;
     for (size_t i = 0; i < n && rc == UCFP_OK; i++) {
         const uint32_t slot = slots[i];
-        if (slot >= s->max_streams) rc = fail(UCFP_E_INVALID, "slot %u out of range [0, %u)", slot, s->max_streams);
-        else if (!s->open[slot]) rc = fail(UCFP_E_INVALID, "slot %u is not open", slot);
-        else if (s->seen[slot]) rc = fail(UCFP_E_INVALID, "slot %u appears twice in one push", slot);
-        else if (n_bytes[i] > kMaxStreamBytes - s->n[slot]) rc = fail(UCFP_E_INVALID, "slot %u would pass 2^63 bytes", slot);
-        if (rc) break;
-        s->seen[slot] = 1;
-        marked = i + 1;
+        rc = s->mark(slot, "push");
+        if (!rc && n_bytes[i] > kMaxStreamBytes - s->n[slot]) rc = fail(UCFP_E_INVALID, "slot %u would pass 2^63 bytes", slot);
     }
-    for (size_t i = 0; i < marked; i++) s->seen[slots[i]] = 0;
+    s->unmark(slots, n);
     if (rc == UCFP_OK && s->utf8) {
         uint64_t total = 0;
         for (size_t i = 0; i < n; i++)
@@ -462,10 +450,10 @@ int push_impl(ucfp_text_streams* s, const uint32_t* slots, const uint64_t* n_byt
     if (n == 0) return UCFP_OK;
     HIP_TRY(hipSetDevice(s->ctx->device));
     // the pinned table this push fills was last copied two pushes ago
-    const int t = s->tab_next;
-    s->tab_next ^= 1;
-    HIP_TRY(hipEventSynchronize(s->tab_copied[t]));
-    ucfp::TextStreamEntry* tab = s->tab_h[t];
+    int t = 0;
+    int rc = s->next(&t);
+    if (rc) return rc;
+    ucfp::TextStreamEntry* tab = reinterpret_cast<ucfp::TextStreamEntry*>(s->tab_h[t]);
     ucfp::CanonSlice* slices = reinterpret_cast<ucfp::CanonSlice*>(tab + n);   // UTF-8 sets: behind the n entries
     uint64_t off = 0, soff = 0;
     for (size_t i = 0; i < n; i++) {
@@ -542,12 +530,9 @@ int ucfp_text_streams_create_ex(ucfp_ctx* ctx, uint32_t shingle_k, uint32_t max_
     if (!s) return fail(UCFP_E_INDEX, "out of host memory");
     s->ctx = ctx;
     s->k = shingle_k;
-    s->max_streams = max_streams;
-    s->n.assign(max_streams, 0);
-    s->open.assign(max_streams, 0);
+    s->init(max_streams);
     s->fresh.assign(max_streams, 0);
     s->mode.assign(max_streams, 0);
-    s->seen.assign(max_streams, 0);
     s->utf8 = utf8;
     s->max_push_bytes = utf8 ? max_push_bytes : 0;
     const size_t tab_bytes = (size_t)max_streams * (sizeof(ucfp::TextStreamEntry) + (utf8 ? sizeof(ucfp::CanonSlice) : 0));
@@ -561,9 +546,7 @@ int ucfp_text_streams_create_ex(ucfp_ctx* ctx, uint32_t shingle_k, uint32_t max_
         if (e == hipSuccess && ucfp::text_canon_tables(ctx->device, &s->ca.stage1, &s->ca.stage2, &s->ca.pool) != UCFP_OK) e = hipErrorNotFound;
     }
     if (e == hipSuccess) e = hipMalloc((void**)&s->tab_d, tab_bytes);
-    for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipHostMalloc((void**)&s->tab_h[i], tab_bytes, 0);
-    for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipEventCreateWithFlags(&s->tab_copied[i], hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&s->done, hipEventDisableTiming);
+    if (e == hipSuccess) e = s->setup(tab_bytes);
     if (e != hipSuccess) {
         ucfp_text_streams_destroy(s);
         return fail(UCFP_E_INDEX, "stream set allocation failed: %s", hipGetErrorString(e));
@@ -574,16 +557,11 @@ int ucfp_text_streams_create_ex(ucfp_ctx* ctx, uint32_t shingle_k, uint32_t max_
 
 void ucfp_text_streams_destroy(ucfp_text_streams* s) {
     if (!s) return;
-    if (s->done) (void)hipEventSynchronize(s->done);
+    s->teardown();
     if (s->states) (void)hipFree(s->states);
     if (s->ca.cstates) (void)hipFree(s->ca.cstates);
     if (s->ca.scratch) (void)hipFree(s->ca.scratch);
     if (s->tab_d) (void)hipFree(s->tab_d);
-    for (int i = 0; i < 2; i++) {
-        if (s->tab_h[i]) (void)hipHostFree(s->tab_h[i]);
-        if (s->tab_copied[i]) (void)hipEventDestroy(s->tab_copied[i]);
-    }
-    if (s->done) (void)hipEventDestroy(s->done);
     delete s;
 }
 
@@ -593,26 +571,17 @@ int ucfp_text_streams_open(ucfp_text_streams* s, int mode, uint32_t* slot) {
         return fail(UCFP_E_UNSUPPORTED, "RAW_UTF8 streams are not built: canonicalise on the host and open a PRETOKENIZED stream");
     if (mode != UCFP_TEXT_RAW_ASCII && mode != UCFP_TEXT_PRETOKENIZED && mode != UCFP_TEXT_RAW_UTF8) return fail(UCFP_E_INVALID, "unknown text mode %d", mode);
     std::lock_guard<std::mutex> lk(s->mu);
-    for (uint32_t i = 0; i < s->max_streams; i++) {
-        if (!s->open[i]) {
-            s->open[i] = 1;
-            s->fresh[i] = 1;
-            s->mode[i] = (uint8_t)mode;
-            s->n[i] = 0;
-            *slot = i;
-            return UCFP_OK;
-        }
-    }
-    return fail(UCFP_E_INVALID, "all %u slots are open", s->max_streams);
+    const int rc = s->acquire(slot);
+    if (rc) return rc;
+    s->fresh[*slot] = 1;
+    s->mode[*slot] = (uint8_t)mode;
+    return UCFP_OK;
 }
 
 int ucfp_text_streams_close(ucfp_text_streams* s, uint32_t slot) {
     if (!s) return fail(UCFP_E_INVALID, "set is NULL");
     std::lock_guard<std::mutex> lk(s->mu);
-    if (slot >= s->max_streams || !s->open[slot]) return fail(UCFP_E_INVALID, "slot %u is not open", slot);
-    s->open[slot] = 0;
-    s->n[slot] = 0;
-    return UCFP_OK;
+    return s->release(slot);   // `fresh` stays as it is: the next open sets it
 }
 
 int ucfp_text_streams_push_dev(ucfp_text_streams* s, const uint32_t* slots, const uint64_t* n_bytes, const uint8_t* final,

@@ -17,18 +17,21 @@ namespace {
 
 Cfg defaults() { return Cfg{10u, 63u, 64u, 30u, -50.0f}; }
 
-// the set's and the context's locks are held; the plan is current
-int push_impl(ucfp_wang_streams* s, size_t n, const float* d_pcm, uint8_t* d_out, size_t cap_hashes,
-              uint64_t* d_out_offsets, hipStream_t st) {
-    const Cfg& c = s->cfg;
-    ucfp::WangPushWs w;
-    int rc = push_begin(s, n, st, &w);
-    if (rc) return rc;
-    ucfp::launch_wang_streams_push(d_pcm, s->dev, c.fan_out, c.target_zone_t, c.target_zone_f, c.peaks_per_sec,
-                                   s->floor_p, s->ctx->audio_ws, w, reinterpret_cast<uint32_t*>(d_out), cap_hashes,
-                                   d_out_offsets, st);
-    return push_end(s, n, st);
-}
+// what Wang's entries put into the shared ones (wang_streams_core.h): 8-byte hashes, its name, its launch
+struct Wang {
+    using set = ucfp_wang_streams;
+    static constexpr size_t rec_bytes = 8, align = 8;
+    static constexpr const char* align_msg = "the hash buffer must be 8-byte aligned";
+    static constexpr const char* abi = "wang";
+    static constexpr bool bound32 = false;
+    static void launch(set* s, const float* d_pcm, const ucfp::WangPushWs& w, uint8_t* d_out, size_t cap_hashes,
+                       uint64_t* d_out_offsets, hipStream_t st) {
+        const Cfg& c = s->cfg;
+        ucfp::launch_wang_streams_push(d_pcm, s->dev, c.fan_out, c.target_zone_t, c.target_zone_f, c.peaks_per_sec,
+                                       s->floor_p, s->ctx->audio_ws, w, reinterpret_cast<uint32_t*>(d_out), cap_hashes,
+                                       d_out_offsets, st);
+    }
+};
 
 }  // namespace
 
@@ -83,63 +86,18 @@ int ucfp_wang_streams_close(ucfp_wang_streams* s, uint32_t slot) {
 
 size_t ucfp_wang_streams_max_hashes(ucfp_wang_streams* s, const uint32_t* slots, const uint64_t* n_samples,
                                     const uint8_t* final, size_t n) {
-    if (!s) return 0;
-    std::lock_guard<std::mutex> lk(s->mu);
-    size_t bound = 0;
-    return plan_push(s, slots, n_samples, final, n, &bound) == UCFP_OK ? bound : 0;
+    return entry_max_hashes<Wang>(s, slots, n_samples, final, n);
 }
 
 int ucfp_wang_streams_push_dev(ucfp_wang_streams* s, const uint32_t* slots, const uint64_t* n_samples,
                                const uint8_t* final, size_t n, const float* d_pcm, uint8_t* d_out, size_t cap_hashes,
                                uint64_t* d_out_offsets, void* stream) {
-    if (!s) return fail(UCFP_E_INVALID, "set is NULL");
-    if (!d_out_offsets || (cap_hashes && !d_out)) return fail(UCFP_E_INVALID, "NULL buffer");
-    if (cap_hashes && ((uintptr_t)d_out & 7u)) return fail(UCFP_E_INVALID, "the hash buffer must be 8-byte aligned");
-    std::lock_guard<std::mutex> lk(s->mu);
-    size_t bound = 0;
-    int rc = plan_push(s, slots, n_samples, final, n, &bound);
-    if (rc) return rc;
-    uint64_t total = 0;
-    for (size_t i = 0; i < n; i++) total += n_samples[i];
-    if (total && !d_pcm) return fail(UCFP_E_INVALID, "d_pcm is NULL");
-    if (cap_hashes < bound)
-        return fail(UCFP_E_INVALID, "cap_hashes %zu below ucfp_wang_streams_max_hashes = %zu", cap_hashes, bound);
-    std::lock_guard<std::mutex> lk2(s->ctx->mu);
-    return push_impl(s, n, d_pcm, d_out, cap_hashes, d_out_offsets, (hipStream_t)stream);
+    return entry_push_dev<Wang>(s, slots, n_samples, final, n, d_pcm, d_out, cap_hashes, d_out_offsets, stream);
 }
 
 int ucfp_wang_streams_push(ucfp_wang_streams* s, uint32_t slot, const float* pcm, size_t n, int final, uint8_t* out,
                            size_t cap_hashes, size_t* n_hashes) {
-    if (!s || !n_hashes) return fail(UCFP_E_INVALID, "set / n_hashes is NULL");
-    *n_hashes = 0;
-    if ((n && !pcm) || (cap_hashes && !out)) return fail(UCFP_E_INVALID, "NULL buffer");
-    std::lock_guard<std::mutex> lk(s->mu);
-    const uint64_t m = n;
-    const uint8_t fin = final ? 1 : 0;
-    size_t bound = 0;
-    int rc = plan_push(s, &slot, &m, &fin, 1, &bound);
-    if (rc) return rc;
-    if (cap_hashes < bound)
-        return fail(UCFP_E_INVALID, "cap_hashes %zu below ucfp_wang_streams_max_hashes = %zu", cap_hashes, bound);
-    ucfp_ctx* ctx = s->ctx;
-    std::lock_guard<std::mutex> lk2(ctx->mu);
-    HIP_TRY(hipSetDevice(ctx->device));
-    rc = ucfp::grow(&ctx->stage_in, &ctx->stage_in_cap, (n ? n : 1) * 4);
-    if (!rc) rc = ucfp::grow(&ctx->stage_out, &ctx->stage_out_cap, 256 + (bound ? bound : 1) * 8);
-    if (rc) return rc;
-    hipStream_t st = ctx->host_stream;
-    uint64_t* d_off = reinterpret_cast<uint64_t*>(ctx->stage_out);
-    uint8_t* d_out = ctx->stage_out + 256;
-    if (n) HIP_TRY(hipMemcpyAsync(ctx->stage_in, pcm, n * 4, hipMemcpyHostToDevice, st));
-    rc = push_impl(s, 1, reinterpret_cast<const float*>(ctx->stage_in), d_out, bound, d_off, st);
-    if (rc) return rc;
-    uint64_t off[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(off, d_off, 16, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const size_t h = (size_t)(off[1] - off[0]);
-    if (h) HIP_TRY(hipMemcpy(out, d_out + off[0] * 8, h * 8, hipMemcpyDeviceToHost));
-    *n_hashes = h;
-    return UCFP_OK;
+    return entry_push<Wang>(s, slot, pcm, n, final, out, cap_hashes, n_hashes);
 }
 
 }  // extern "C"

@@ -14,6 +14,7 @@
 #include "../../include/ucfp_hip.h"
 #include "common.h"
 #include "ctx.h"
+#include "stream_set.h"
 
 namespace ucfp {
 namespace wstreams {
@@ -56,22 +57,14 @@ struct Plan {
     uint64_t vbase, o, j0, j1, s0, n_closed, f_lo, f_hi, cap, bound;
 };
 
-struct Set {
+// the slot table counts samples; the pinned tables hold a push (or, for Panako, the items of a windows call)
+struct Set : streams::Slots, streams::Tables {
     ucfp_ctx* ctx = nullptr;
     Cfg cfg{};
     float floor_p = 0.0f;
-    uint32_t max_streams = 0;
-    std::mutex mu;                        // serialises the set's calls
-    std::vector<uint64_t> n;              // samples seen per slot
-    std::vector<uint8_t> open;
-    std::vector<uint8_t> seen;            // duplicate-slot check of one call
     std::vector<Plan> plan;
     WangStreamsDev dev{};
     uint8_t* dev_mem = nullptr;
-    uint8_t* tab_h[2] = {nullptr, nullptr};   // pinned tables, used in turn
-    hipEvent_t tab_copied[2] = {nullptr, nullptr};
-    int tab_next = 0;
-    hipEvent_t done = nullptr;            // behind the last push: the next one waits for it
 };
 
 inline size_t state_bytes_per_stream(uint32_t ret_cap) {
@@ -88,10 +81,7 @@ inline hipError_t set_init(Set* s, ucfp_ctx* ctx, const Cfg& c, uint32_t max_str
     s->ctx = ctx;
     s->cfg = c;
     s->floor_p = (float)(65536.0 * pow(10.0, (double)c.min_anchor_mag_db / 10.0));
-    s->max_streams = max_streams;
-    s->n.assign(max_streams, 0);
-    s->open.assign(max_streams, 0);
-    s->seen.assign(max_streams, 0);
+    s->init(max_streams);
     const uint32_t rc = ret_cap_of(c);
     const size_t ms = max_streams;
     const size_t bytes = ms * state_bytes_per_stream(rc) + 16 * 256;
@@ -110,65 +100,43 @@ inline hipError_t set_init(Set* s, ucfp_ctx* ctx, const Cfg& c, uint32_t max_str
         s->dev.ret_p = reinterpret_cast<float*>(take(ms * rc * 4));
         s->dev.ret_cap = rc;
     }
-    for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipHostMalloc((void**)&s->tab_h[i], tab_bytes_max(max_streams), 0);
-    for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipEventCreateWithFlags(&s->tab_copied[i], hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&s->done, hipEventDisableTiming);
-    return e;
+    return e == hipSuccess ? s->setup(tab_bytes_max(max_streams)) : e;
 }
 
 inline void set_release(Set* s) {
-    if (s->done) (void)hipEventSynchronize(s->done);
+    s->teardown();
     if (s->dev_mem) (void)hipFree(s->dev_mem);
-    for (int i = 0; i < 2; i++) {
-        if (s->tab_h[i]) (void)hipHostFree(s->tab_h[i]);
-        if (s->tab_copied[i]) (void)hipEventDestroy(s->tab_copied[i]);
-    }
-    if (s->done) (void)hipEventDestroy(s->done);
 }
 
 inline int set_open(Set* s, uint32_t* slot) {
     std::lock_guard<std::mutex> lk(s->mu);
-    for (uint32_t i = 0; i < s->max_streams; i++) {
-        if (!s->open[i]) {
-            s->open[i] = 1;
-            s->n[i] = 0;
-            *slot = i;
-            return UCFP_OK;
-        }
-    }
-    return capi_fail(UCFP_E_INVALID, "all %u slots are open", s->max_streams);
+    return s->acquire(slot);
 }
 
 inline int set_close(Set* s, uint32_t slot) {
     std::lock_guard<std::mutex> lk(s->mu);
-    if (slot >= s->max_streams || !s->open[slot]) return capi_fail(UCFP_E_INVALID, "slot %u is not open", slot);
-    s->open[slot] = 0;
-    s->n[slot] = 0;
-    return UCFP_OK;
+    return s->release(slot);
 }
 
 // validates the push and plans every entry; nothing changes.  *bound: hashes / records the push can emit (either back
 // end emits at most fan_out per anchor)
 inline int plan_push(Set* s, const uint32_t* slots, const uint64_t* n_samples, const uint8_t* fin, size_t n, size_t* bound) {
     if (n && (!slots || !n_samples)) return capi_fail(UCFP_E_INVALID, "slots / n_samples is NULL");
-    if (n > s->max_streams)
-        return capi_fail(UCFP_E_INVALID, "%zu entries in one push, the set has %u slots", n, s->max_streams);
+    int rc = s->fits(n, "entries", "push");
+    if (rc) return rc;
     const Cfg& c = s->cfg;
     s->plan.resize(n);
     size_t total = 0;
     uint64_t total_v = 0;
-    int rc = UCFP_OK;
-    for (size_t i = 0; i < n && rc == UCFP_OK; i++) {
+    for (size_t i = 0; i < n; i++) {
         const uint32_t slot = slots[i];
-        if (slot >= s->max_streams) rc = capi_fail(UCFP_E_INVALID, "slot %u out of range [0, %u)", slot, s->max_streams);
-        else if (!s->open[slot]) rc = capi_fail(UCFP_E_INVALID, "slot %u is not open", slot);
-        else if (s->seen[slot]) rc = capi_fail(UCFP_E_INVALID, "slot %u appears twice in one push", slot);
-        else if (n_samples[i] > kMaxChunk)
+        rc = s->mark(slot, "push");
+        if (rc) break;
+        if (n_samples[i] > kMaxChunk)
             rc = capi_fail(UCFP_E_INVALID, "a chunk of %llu samples exceeds 2^29: split it", (unsigned long long)n_samples[i]);
         else if (frames_of(s->n[slot] + n_samples[i]) > kMaxFrames)
             rc = capi_fail(UCFP_E_INVALID, "slot %u would pass 2^32 frames", slot);
         if (rc) break;
-        s->seen[slot] = 1;
         Plan& p = s->plan[i];
         p.slot = slot;
         p.m = n_samples[i];
@@ -199,8 +167,7 @@ inline int plan_push(Set* s, const uint32_t* slots, const uint64_t* n_samples, c
         total += p.bound;
         total_v += p.n0 - 128 * p.vbase + p.m;
     }
-    for (size_t i = 0; i < n; i++)
-        if (slots && slots[i] < s->max_streams) s->seen[slots[i]] = 0;
+    s->unmark(slots, n);
     if (rc) return rc;
     if (total_v >= kMaxPushSamples)
         return capi_fail(UCFP_E_INVALID, "push of %llu samples exceeds 2^31: split it", (unsigned long long)total_v);
@@ -230,9 +197,9 @@ inline int push_begin(Set* s, size_t n, hipStream_t st, WangPushWs* out_w) {
     int rc = grow(&ctx->audio_ws, &ctx->audio_ws_cap, w.total);
     if (rc) return rc;
     // the pinned table this push fills was last copied two pushes ago
-    const int k = s->tab_next;
-    s->tab_next ^= 1;
-    HIP_TRY(hipEventSynchronize(s->tab_copied[k]));
+    int k = 0;
+    rc = s->next(&k);
+    if (rc) return rc;
     uint8_t* tab = s->tab_h[k];
     auto* clips = reinterpret_cast<WangStreamClip*>(tab + w.clips);
     auto* ents = reinterpret_cast<WangStreamEntry*>(tab + w.ents);
@@ -307,6 +274,92 @@ inline int push_end(Set* s, size_t n, hipStream_t st) {
         s->n[p.slot] = p.fin ? 0 : p.n1;
         if (p.fin) s->open[p.slot] = 0;
     }
+    return UCFP_OK;
+}
+
+// ---- the entries both back ends export: max_hashes, push_dev and the staged single-stream push.  A back end K names
+// its set type `set`, the bytes of a record `rec_bytes`, the alignment asked of the caller's record buffer `align`
+// with the refusal `align_msg`, its name in the C ABI `abi`, whether a push must emit fewer than 2^32 - 1 records
+// `bound32`, and `launch`, its kernels behind push_begin. ----
+
+// the set's and the context's locks are held; the plan is current
+template <class K>
+int push_impl(typename K::set* s, size_t n, const float* d_pcm, uint8_t* d_out, size_t cap_hashes, uint64_t* d_out_offsets,
+              hipStream_t st) {
+    WangPushWs w;
+    int rc = push_begin(s, n, st, &w);
+    if (rc) return rc;
+    K::launch(s, d_pcm, w, d_out, cap_hashes, d_out_offsets, st);
+    return push_end(s, n, st);
+}
+
+// the set's lock is held; the plan is current and bounds the push by `bound` records
+template <class K>
+int check_cap(size_t cap_hashes, size_t bound) {
+    if (cap_hashes < bound)
+        return capi_fail(UCFP_E_INVALID, "cap_hashes %zu below ucfp_%s_streams_max_hashes = %zu", cap_hashes, K::abi, bound);
+    if (K::bound32 && bound >= 0xffffffffu) return capi_fail(UCFP_E_INVALID, "push too large for one call: split it");
+    return UCFP_OK;
+}
+
+template <class K>
+size_t entry_max_hashes(typename K::set* s, const uint32_t* slots, const uint64_t* n_samples, const uint8_t* fin, size_t n) {
+    if (!s) return 0;
+    std::lock_guard<std::mutex> lk(s->mu);
+    size_t bound = 0;
+    return plan_push(s, slots, n_samples, fin, n, &bound) == UCFP_OK ? bound : 0;
+}
+
+template <class K>
+int entry_push_dev(typename K::set* s, const uint32_t* slots, const uint64_t* n_samples, const uint8_t* fin, size_t n,
+                   const float* d_pcm, uint8_t* d_out, size_t cap_hashes, uint64_t* d_out_offsets, void* stream) {
+    if (!s) return capi_fail(UCFP_E_INVALID, "set is NULL");
+    if (!d_out_offsets || (cap_hashes && !d_out)) return capi_fail(UCFP_E_INVALID, "NULL buffer");
+    if (cap_hashes && ((uintptr_t)d_out & (K::align - 1))) return capi_fail(UCFP_E_INVALID, "%s", K::align_msg);
+    std::lock_guard<std::mutex> lk(s->mu);
+    size_t bound = 0;
+    int rc = plan_push(s, slots, n_samples, fin, n, &bound);
+    if (rc) return rc;
+    uint64_t total = 0;
+    for (size_t i = 0; i < n; i++) total += n_samples[i];
+    if (total && !d_pcm) return capi_fail(UCFP_E_INVALID, "d_pcm is NULL");
+    rc = check_cap<K>(cap_hashes, bound);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk2(s->ctx->mu);
+    return push_impl<K>(s, n, d_pcm, d_out, cap_hashes, d_out_offsets, (hipStream_t)stream);
+}
+
+template <class K>
+int entry_push(typename K::set* s, uint32_t slot, const float* pcm, size_t n, int fin_flag, uint8_t* out, size_t cap_hashes,
+               size_t* n_hashes) {
+    if (!s || !n_hashes) return capi_fail(UCFP_E_INVALID, "set / n_hashes is NULL");
+    *n_hashes = 0;
+    if ((n && !pcm) || (cap_hashes && !out)) return capi_fail(UCFP_E_INVALID, "NULL buffer");
+    std::lock_guard<std::mutex> lk(s->mu);
+    const uint64_t m = n;
+    const uint8_t fin = fin_flag ? 1 : 0;
+    size_t bound = 0;
+    int rc = plan_push(s, &slot, &m, &fin, 1, &bound);
+    if (!rc) rc = check_cap<K>(cap_hashes, bound);
+    if (rc) return rc;
+    ucfp_ctx* ctx = s->ctx;
+    std::lock_guard<std::mutex> lk2(ctx->mu);
+    HIP_TRY(hipSetDevice(ctx->device));
+    rc = grow(&ctx->stage_in, &ctx->stage_in_cap, (n ? n : 1) * 4);
+    if (!rc) rc = grow(&ctx->stage_out, &ctx->stage_out_cap, 256 + (bound ? bound : 1) * K::rec_bytes);
+    if (rc) return rc;
+    hipStream_t st = ctx->host_stream;
+    uint64_t* d_off = reinterpret_cast<uint64_t*>(ctx->stage_out);
+    uint8_t* d_out = ctx->stage_out + 256;          // hipMalloc'ed, so 256 on keeps a record's alignment
+    if (n) HIP_TRY(hipMemcpyAsync(ctx->stage_in, pcm, n * 4, hipMemcpyHostToDevice, st));
+    rc = push_impl<K>(s, 1, reinterpret_cast<const float*>(ctx->stage_in), d_out, bound, d_off, st);
+    if (rc) return rc;
+    uint64_t off[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(off, d_off, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const size_t h = (size_t)(off[1] - off[0]);
+    if (h) HIP_TRY(hipMemcpy(out, d_out + off[0] * K::rec_bytes, h * K::rec_bytes, hipMemcpyDeviceToHost));
+    *n_hashes = h;
     return UCFP_OK;
 }
 

@@ -34,6 +34,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
+from ._streams import StreamSet, slot_arrays
 from .core import Modality, Record
 from .errors import InvalidArgument, ModalityError, UnsupportedError
 
@@ -326,40 +327,27 @@ def simhash_batch(texts: Sequence[str], opts: Optional[TextOpts] = None, ctx=Non
     return _batch("simhash", texts, opts or TextOpts(), ctx)
 
 
-class MinHashStreams:
+class MinHashStreams(StreamSet):
     """A set of live MinHash streams on the device (ucfp_text_streams_*): `push` advances any subset of
     them by one chunk each with one launch.  A stream's final record and status are those of `ucfp_text_minhash_batch`
     on the concatenation of its chunks, however they were cut.  Modes: RAW_ASCII and PRETOKENIZED; with `utf8=True`
     also RAW_UTF8 (the device canonicalises and tokenises, cuts inside a UTF-8 sequence included), and the RAW_UTF8
     chunks of one push may then have `max_push_bytes` bytes in all (the set's scratch is sized for them once)."""
+    _abi = "ucfp_text_streams"
 
     def __init__(self, max_streams: int, k: int = DEFAULT_K, ctx=None, utf8: bool = False, max_push_bytes: int = 1 << 20):
-        self._lib = _lib.load()
-        self.ctx = ctx or _lib.current_context()
-        h = C.c_void_p()
-        _lib.check(self._lib.ucfp_text_streams_create_ex(self.ctx.handle, k, max_streams, STREAMS_UTF8 if utf8 else 0,
-                                                         max_push_bytes if utf8 else 0, C.byref(h)))
-        self.handle = h
+        self._create(ctx, "create_ex", k, max_streams, STREAMS_UTF8 if utf8 else 0, max_push_bytes if utf8 else 0)
         self.max_streams, self.k = max_streams, k
         self.utf8, self.max_push_bytes = bool(utf8), int(max_push_bytes) if utf8 else 0
 
     def open(self, mode: int = RAW_ASCII) -> int:
-        slot = C.c_uint32(0)
-        _lib.check(self._lib.ucfp_text_streams_open(self.handle, mode, C.byref(slot)))
-        return int(slot.value)
-
-    def close(self, slot: int) -> None:
-        """Discards the stream; emits nothing."""
-        _lib.check(self._lib.ucfp_text_streams_close(self.handle, slot))
+        return super().open(mode)
 
     def push_dev(self, slots, counts, d_bytes, d_out, d_status, final=(), stream: int = 0) -> None:
         """Device variant (no sync): `d_bytes` the chunks of `slots` concatenated (uint8 tensor, any alignment), `d_out` a
         uint8 [len(slots), 1032] tensor (row i is written only when slots[i] is in `final`; None when nothing is final),
         `d_status` an int32 [len(slots)] tensor."""
-        final = set(final)
-        sl = np.ascontiguousarray(slots, dtype=np.uint32)
-        ns = np.ascontiguousarray(counts, dtype=np.uint64)
-        fi = np.array([1 if s in final else 0 for s in sl.tolist()], np.uint8)
+        sl, ns, fi = slot_arrays(slots, counts, final)
         _lib.check(self._lib.ucfp_text_streams_push_dev(
             self.handle, sl.ctypes.data, ns.ctypes.data, fi.ctypes.data, sl.size,
             d_bytes.data_ptr() if d_bytes is not None and d_bytes.numel() else None,
@@ -385,17 +373,6 @@ class MinHashStreams:
         st = d_st.cpu().numpy()
         out = d_out.cpu().numpy() if final else None
         return {s: (out[i].tobytes() if s in final else None, int(st[i])) for i, s in enumerate(slots)}
-
-    def destroy(self):
-        if getattr(self, "handle", None):
-            self._lib.ucfp_text_streams_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
 
 
 _CUT_AT = " \n\t\r"

@@ -390,12 +390,26 @@ int ucfp_audio_batcher_stats(ucfp_audio_batcher* b, uint64_t* batches, uint64_t*
  *     length.  The push path allocates nothing beyond growing the context's workspace to the largest push seen.
  *   - Errors are status codes: UCFP_E_INVALID for a slot out of range or not open, a slot twice in one push, a chunk
  *     above 2^29 samples, a stream that would pass 2^32 frames, cap_hashes below the bound; UCFP_E_MODALITY for a rate
- *     other than 8000 or a config outside the /v1/algorithms ranges.  A failed call changes no state. */
+ *     other than 8000 or a config outside the /v1/algorithms ranges.  A failed call changes no state.
+ *   - LIVE WINDOWS (the reference has no audio matcher): a set created by ucfp_wang_streams_create_ex
+ *     with window_frames = W (0 .. UCFP_WANG_STREAM_MAX_WINDOW_FRAMES; 0 = no windows, the set of
+ *     ucfp_wang_streams_create exactly) also keeps each stream's latest hashes for ucfp_landmark_index_query*.  The
+ *     window of an open stream at n samples is its emitted hashes with t_anchor >= w0 = max(0, F(n) - W), in emission
+ *     order, with w0 subtracted from t_anchor; at most ucfp_wang_streams_window_cap(cfg, W) = (ceil(2 W / 125) + 1) *
+ *     peaks_per_sec * fan_out hashes.  Nothing pushed or emitted yet, a final push or close: empty, origin 0.  A hit's
+ *     `offset` then says where stream frame w0 lies in the matched record.  W above the maximum, a misaligned
+ *     landmark buffer, a windows call on a set without windows: UCFP_E_INVALID. */
 typedef struct ucfp_wang_streams ucfp_wang_streams;
+#define UCFP_WANG_STREAM_MAX_WINDOW_FRAMES 8192u /* 131 s */
 /* sample_rate must be 8000 (audio.rs:425-431 -> UCFP_E_MODALITY); cfg as ucfp_audio_wang, NULL = defaults.  The rate and
  * the config are checked before anything else.  Fails with UCFP_E_INDEX without a gfx950 device (no CPU fallback). */
 int ucfp_wang_streams_create(ucfp_ctx* ctx, uint32_t sample_rate, const ucfp_wang_config* cfg, uint32_t max_streams,
                              ucfp_wang_streams** out);
+/* StreamingWangSession::new (audio.rs:413-431) for a set that also keeps live windows of window_frames frames (A20; the
+ * reference has no audio matcher).  window_frames = 0 is ucfp_wang_streams_create; above the maximum: UCFP_E_INVALID,
+ * after the rate and the config (UCFP_E_MODALITY). */
+int ucfp_wang_streams_create_ex(ucfp_ctx* ctx, uint32_t sample_rate, const ucfp_wang_config* cfg, uint32_t max_streams,
+                                uint32_t window_frames, ucfp_wang_streams** out);
 void ucfp_wang_streams_destroy(ucfp_wang_streams* s);
 int ucfp_wang_streams_open(ucfp_wang_streams* s, uint32_t* slot);      /* fresh stream, t = 0 (audio.rs:413-431) */
 int ucfp_wang_streams_close(ucfp_wang_streams* s, uint32_t slot);      /* discard, emit nothing */
@@ -404,6 +418,12 @@ int ucfp_wang_streams_close(ucfp_wang_streams* s, uint32_t slot);      /* discar
 uint64_t ucfp_wang_stream_frontier(uint64_t n_samples, const ucfp_wang_config* cfg);
 /* Host-only: device bytes a set holds per stream (0 for an out-of-range config). */
 size_t ucfp_wang_streams_state_bytes(const ucfp_wang_config* cfg);
+/* Host-only: the same with the ring of a window (A20; the reference has no audio matcher): state_bytes(cfg), plus
+ * (window_frames != 0) 8 bytes of ring header and 8 bytes per window hash.  0 for out-of-range arguments. */
+size_t ucfp_wang_streams_state_bytes_ex(const ucfp_wang_config* cfg, uint32_t window_frames);
+/* Host-only: hashes one stream's window can hold (A20; the reference has no audio matcher); 0 for window_frames = 0 or
+ * out-of-range arguments. */
+size_t ucfp_wang_streams_window_cap(const ucfp_wang_config* cfg, uint32_t window_frames);
 /* Upper bound on the hashes a push can emit; host-computable from the per-slot sample counts (0 for an invalid push). */
 size_t ucfp_wang_streams_max_hashes(ucfp_wang_streams* s, const uint32_t* slots, const uint64_t* n_samples,
                                     const uint8_t* final, size_t n);
@@ -419,6 +439,14 @@ int ucfp_wang_streams_push_dev(ucfp_wang_streams* s, const uint32_t* slots, cons
  * synchronous.  *n_hashes = hashes of this push. */
 int ucfp_wang_streams_push(ucfp_wang_streams* s, uint32_t slot, const float* pcm, size_t n, int final, uint8_t* out,
                            size_t cap_hashes, size_t* n_hashes);
+/* The live windows of n distinct open slots (A20; the hashes are those of StreamingWangSession::push, audio.rs:413-480,
+ * the window itself has no counterpart: the reference has no audio matcher).  Item i = d_landmarks[d_offsets[i] ..
+ * d_offsets[i+1]) with BYTE offsets (multiples of 8, n + 1 device u64) -- the query shape of
+ * ucfp_landmark_index_query_dev -- and d_origins[i] = w0 (device u32, may be NULL).  d_landmarks must be 8-byte aligned.
+ * cap_landmarks (8-byte hashes d_landmarks holds) below n * ucfp_wang_streams_window_cap -> UCFP_E_INVALID, as a closed
+ * slot, a slot out of range or named twice, and a set created with window_frames = 0.  No host synchronisation. */
+int ucfp_wang_streams_windows_dev(ucfp_wang_streams* s, const uint32_t* slots, size_t n, uint8_t* d_landmarks,
+                                  size_t cap_landmarks, uint64_t* d_offsets, uint32_t* d_origins, void* stream);
 
 /* STREAMING Panako (the reference has no streaming Panako): the stream set above with triplets behind
  * the same front end, plus a LIVE WINDOW per stream for ucfp_panako_index_query*.  A slot is one stream at 8 kHz.  After

@@ -323,16 +323,22 @@ SIGNATURES = {
     "ucfp_text_batcher_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "ucfp_wang_streams_create": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(WangConfig), C.c_uint32,
                                            C.POINTER(C.c_void_p)]),
+    "ucfp_wang_streams_create_ex": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(WangConfig), C.c_uint32, C.c_uint32,
+                                              C.POINTER(C.c_void_p)]),
     "ucfp_wang_streams_destroy": (None, [C.c_void_p]),
     "ucfp_wang_streams_open": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "ucfp_wang_streams_close": (C.c_int, [C.c_void_p, C.c_uint32]),
     "ucfp_wang_stream_frontier": (C.c_uint64, [C.c_uint64, C.POINTER(WangConfig)]),
     "ucfp_wang_streams_state_bytes": (C.c_size_t, [C.POINTER(WangConfig)]),
+    "ucfp_wang_streams_state_bytes_ex": (C.c_size_t, [C.POINTER(WangConfig), C.c_uint32]),
+    "ucfp_wang_streams_window_cap": (C.c_size_t, [C.POINTER(WangConfig), C.c_uint32]),
     "ucfp_wang_streams_max_hashes": (C.c_size_t, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "ucfp_wang_streams_push_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                              C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "ucfp_wang_streams_push": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p,
                                          C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ucfp_wang_streams_windows_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                C.c_void_p, C.c_void_p]),
     "ucfp_panako_streams_create": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(PanakoConfig), C.c_uint32, C.c_uint32,
                                              C.POINTER(C.c_void_p)]),
     "ucfp_panako_streams_destroy": (None, [C.c_void_p]),

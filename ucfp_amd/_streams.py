@@ -3,7 +3,7 @@ audio.PanakoStreams and text.MinHashStreams (the slot rules themselves live once
 
 A set's entries are `<_abi>_create*`, `_open`, `_close`, `_push_dev`, `_push`, `_destroy`.  The three audio kinds also
 share the shape of a push -- float32 chunks in, ragged int32 rows out -- and differ in the capacity entry and the
-trailing shape of a row.
+trailing shape of a row.  The two kinds that keep live windows (Wang, Panako) share `_windows_dev` / `_windows`.
 """
 import ctypes as C
 from typing import List
@@ -99,3 +99,23 @@ class AudioStreamSet(StreamSet):
                             lambda out, oo, cap, st: self._push_dev(slots, counts, d_pcm, out, oo, final, cap, st))
         return dict(zip(slots, rows))
 
+
+    def _windows_dev(self, slots, rows, offsets, origins, cap, stream) -> None:
+        """`<_abi>_windows_dev`: the live window of slots[i] -> the bytes rows[offsets[i]:offsets[i+1]] of an int32
+        [cap, *_row] tensor, `origins` an optional int32 [len(slots)] tensor; no sync."""
+        sl = np.ascontiguousarray(slots, dtype=np.uint32)
+        cap = rows.shape[0] if cap is None else cap
+        _lib.check(self._fn("windows_dev")(self.handle, sl.ctypes.data, sl.size, rows.data_ptr() if cap else None, cap,
+                                           offsets.data_ptr(), origins.data_ptr() if origins is not None else None,
+                                           stream or None))
+
+    def _windows(self, slots) -> dict:
+        """{slot: (uint32 [m, *_row] rows rebased to the window's origin, origin)}, oldest row first."""
+        import torch
+        slots = list(slots)
+        d_org = torch.zeros(max(len(slots), 1), dtype=torch.int32, device=f"cuda:{self.ctx.device}")
+        rows = self._ragged(len(slots), len(slots) * self.window_cap, self._row,
+                            lambda out, off, cap, st: self._windows_dev(slots, out, off, d_org, cap, st),
+                            unit=4 * int(np.prod(self._row)))
+        org = d_org.cpu().numpy().view(np.uint32)
+        return {s: (rows[i], int(org[i])) for i, s in enumerate(slots)}

@@ -320,13 +320,17 @@ def fingerprint_haitsma_with(samples, sample_rate: int, cfg: HaitsmaConfig, tena
 class WangStreams(AudioStreamSet):
     """A set of live Wang streams on the device (ucfp_wang_streams_*): `push` advances any subset of them
     by one chunk each with one launch sequence and returns the hashes each one emits now -- exactly the offline hashes
-    with t_anchor < frontier(n) so far, the rest on the final push (t_anchor = frames since `open`)."""
+    with t_anchor < frontier(n) so far, the rest on the final push (t_anchor = frames since `open`).  With
+    `window_frames` = W > 0, `windows` hands out each stream's latest W frames of hashes, rebased to the
+    window's origin, in the ragged shape `LandmarkIndex.query_dev` / ucfp_landmark_index_query_dev take."""
     _abi, _cap_entry, _row = "ucfp_wang_streams", "max_hashes", (2,)
 
-    def __init__(self, max_streams: int, cfg: Optional[WangConfig] = None, sample_rate: int = WANG_SR, ctx=None):
+    def __init__(self, max_streams: int, cfg: Optional[WangConfig] = None, sample_rate: int = WANG_SR, ctx=None, *,
+                 window_frames: int = 0):
         self._cfg = (cfg or WangConfig())._c()
-        self._create(ctx, "create", sample_rate, C.byref(self._cfg), max_streams)
-        self.max_streams = max_streams
+        self._create(ctx, "create_ex", sample_rate, C.byref(self._cfg), max_streams, window_frames)
+        self.max_streams, self.window_frames = max_streams, window_frames
+        self.window_cap = int(self._lib.ucfp_wang_streams_window_cap(C.byref(self._cfg), window_frames))
 
     def frontier(self, n_samples: int) -> int:
         """F(n): after a non-final push, every hash with t_anchor < F(n) has been emitted, and no other."""
@@ -343,6 +347,18 @@ class WangStreams(AudioStreamSet):
     def push(self, chunks: dict, final=()) -> dict:
         """{slot: samples} -> {slot: uint32 [n, 2]} of the hashes emitted now; slots in `final` end (and close)."""
         return self._push(chunks, final)
+
+    def windows_dev(self, slots, landmarks, offsets, origins=None, cap_landmarks: Optional[int] = None,
+                    stream: int = 0) -> None:
+        """Device variant (no sync): the live window of slots[i] -> the bytes landmarks[offsets[i]:offsets[i+1]]
+        (`landmarks` an int32 [cap, 2] tensor of at least len(slots) * window_cap hashes, `offsets` an int64
+        [len(slots) + 1] tensor of BYTE offsets, `origins` an optional int32 [len(slots)] tensor of the windows' first
+        frames)."""
+        self._windows_dev(slots, landmarks, offsets, origins, cap_landmarks, stream)
+
+    def windows(self, slots) -> dict:
+        """{slot: (uint32 [m, 2] hashes rebased to the window's origin, origin)}, oldest hash first."""
+        return self._windows(slots)
 
 
 class _StreamingSession:
@@ -507,22 +523,11 @@ class PanakoStreams(AudioStreamSet):
         """Device variant (no sync): the live window of slots[i] -> the bytes records[offsets[i]:offsets[i+1]] (`records`
         an int32 [cap, 4] tensor of at least len(slots) * window_cap records, `offsets` an int64 [len(slots) + 1] tensor
         of BYTE offsets, `origins` an optional int32 [len(slots)] tensor of the windows' first frames)."""
-        sl = np.ascontiguousarray(slots, dtype=np.uint32)
-        cap = records.shape[0] if cap_records is None else cap_records
-        _lib.check(self._lib.ucfp_panako_streams_windows_dev(self.handle, sl.ctypes.data, sl.size,
-                                                             records.data_ptr() if cap else None, cap, offsets.data_ptr(),
-                                                             origins.data_ptr() if origins is not None else None,
-                                                             stream or None))
+        self._windows_dev(slots, records, offsets, origins, cap_records, stream)
 
     def windows(self, slots) -> dict:
         """{slot: (uint32 [m, 4] records rebased to the window's origin, origin)}, oldest record first."""
-        import torch
-        slots = list(slots)
-        d_org = torch.zeros(max(len(slots), 1), dtype=torch.int32, device=f"cuda:{self.ctx.device}")
-        recs = self._ragged(len(slots), len(slots) * self.window_cap, (4,),
-                            lambda out, off, cap, st: self.windows_dev(slots, out, off, d_org, cap, st), unit=16)
-        org = d_org.cpu().numpy().view(np.uint32)
-        return {s: (recs[i], int(org[i])) for i, s in enumerate(slots)}
+        return self._windows(slots)
 
 
 class StreamingPanakoSession(_StreamingSession):

@@ -1511,8 +1511,7 @@ __global__ __launch_bounds__(256) void wang_streams_save_kernel(const WangStream
     }
 }
 
-// ---- streaming Panako (A19): the same push with triplets behind it, and a ring per stream that keeps the latest
-// window of emitted records in the shape the Panako index takes as a query.
+// ---- streaming Panako (A19): the same push with triplets behind it.
 
 // one thread per peak position of the push, as wang_streams_pair_kernel: the anchors inside the entry's emission window
 // walk their target zone (A13 P3-P5, panako_triplet_walk); the records carry frames since the stream was opened
@@ -1537,13 +1536,27 @@ __global__ void panako_streams_triplet_kernel(const WangStreamEntry* __restrict_
     if (!EMIT) counts[i] = taken;
 }
 
+// ---- live windows (A19 Panako, A20 Wang): one body per kernel, instantiated for the 16-byte record with three times
+// (uint4) and the 8-byte hash with one (uint2).  The first time of a record, its anchor's, orders the emission.
+__device__ __forceinline__ uint4 rec_rebased(uint4 r, uint32_t w0) {
+    r.y -= w0;
+    r.z -= w0;
+    r.w -= w0;
+    return r;
+}
+__device__ __forceinline__ uint2 rec_rebased(uint2 r, uint32_t w0) {
+    r.y -= w0;
+    return r;
+}
+
 // One workgroup per entry, behind the emit pass: the entry's new records out[a .. b) join the stream's ring and the
 // head moves past every record with t_a < w0 = max(0, F(n1) - W).  Records are emitted in anchor order, so those to
 // drop are a prefix of (ring, new).  What is kept fits the ring (A19's bound); if it ever did not, the oldest go.
-__global__ __launch_bounds__(256) void panako_streams_ring_kernel(const WangStreamEntry* __restrict__ ents,
-                                                                  const uint32_t* __restrict__ pk_base,
-                                                                  const uint32_t* __restrict__ rec_off,
-                                                                  const uint4* __restrict__ out, PanakoRingsDev rg) {
+template <class Rec>
+__global__ __launch_bounds__(256) void streams_ring_kernel(const WangStreamEntry* __restrict__ ents,
+                                                           const uint32_t* __restrict__ pk_base,
+                                                           const uint32_t* __restrict__ rec_off,
+                                                           const Rec* __restrict__ out, StreamRingsDev<Rec> rg) {
     __shared__ uint32_t s_old, s_new;
     const WangStreamEntry e = ents[blockIdx.x];
     const uint32_t tid = threadIdx.x;
@@ -1555,7 +1568,7 @@ __global__ __launch_bounds__(256) void panako_streams_ring_kernel(const WangStre
     const uint32_t a = rec_off[pk_base[blockIdx.x]], b = rec_off[pk_base[blockIdx.x + 1]];
     const uint32_t h = e.fresh ? 0u : rg.head[e.slot], c = e.fresh ? 0u : rg.count[e.slot];
     const uint32_t w0 = e.f_hi > rg.window ? e.f_hi - rg.window : 0u;
-    uint4* ring = rg.rec + (size_t)e.slot * R;
+    Rec* ring = rg.rec + (size_t)e.slot * R;
     if (tid == 0) s_old = s_new = 0;
     __syncthreads();
     uint32_t d_old = 0, d_new = 0;
@@ -1585,36 +1598,33 @@ __global__ __launch_bounds__(256) void panako_streams_ring_kernel(const WangStre
 }
 
 // the records in each item's ring (none for a stream that has not been pushed to since it was opened)
-__global__ void panako_streams_window_counts_kernel(const PanakoWindowItem* __restrict__ items, uint32_t n,
-                                                    PanakoRingsDev rg, uint32_t* __restrict__ cnt) {
+template <class Rec>
+__global__ void streams_window_counts_kernel(const StreamWindowItem* __restrict__ items, uint32_t n,
+                                             StreamRingsDev<Rec> rg, uint32_t* __restrict__ cnt) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) cnt[i] = items[i].live ? rg.count[items[i].slot] : 0u;
 }
 
-// One workgroup per item: the ring from its head on, the three times rebased to the window's origin w0; byte offsets
-// (the query shape of the Panako index) and origins
-__global__ __launch_bounds__(256) void panako_streams_windows_kernel(const PanakoWindowItem* __restrict__ items, uint32_t n,
-                                                                     const uint32_t* __restrict__ off, PanakoRingsDev rg,
-                                                                     uint4* __restrict__ out, size_t cap,
-                                                                     uint64_t* __restrict__ d_offsets,
-                                                                     uint32_t* __restrict__ d_origins) {
-    const PanakoWindowItem it = items[blockIdx.x];
+// One workgroup per item: the ring from its head on, every time rebased to the window's origin w0; byte offsets (the
+// query shape of the Panako and the landmark index) and origins
+template <class Rec>
+__global__ __launch_bounds__(256) void streams_windows_kernel(const StreamWindowItem* __restrict__ items, uint32_t n,
+                                                              const uint32_t* __restrict__ off, StreamRingsDev<Rec> rg,
+                                                              Rec* __restrict__ out, size_t cap,
+                                                              uint64_t* __restrict__ d_offsets,
+                                                              uint32_t* __restrict__ d_origins) {
+    const StreamWindowItem it = items[blockIdx.x];
     const uint32_t o0 = off[blockIdx.x], o1 = off[blockIdx.x + 1], tid = threadIdx.x;
     if (tid == 0) {
-        d_offsets[blockIdx.x] = (uint64_t)o0 * 16;
-        if (blockIdx.x + 1 == n) d_offsets[n] = (uint64_t)o1 * 16;
+        d_offsets[blockIdx.x] = (uint64_t)o0 * sizeof(Rec);
+        if (blockIdx.x + 1 == n) d_offsets[n] = (uint64_t)o1 * sizeof(Rec);
         if (d_origins) d_origins[blockIdx.x] = it.w0;
     }
     if (o1 == o0) return;
     const uint32_t R = rg.cap, h = rg.head[it.slot];
-    const uint4* ring = rg.rec + (size_t)it.slot * R;
-    for (uint32_t j = tid; j < o1 - o0; j += 256) {
-        uint4 r = ring[(h + j) % R];
-        r.y -= it.w0;
-        r.z -= it.w0;
-        r.w -= it.w0;
-        if ((size_t)o0 + j < cap) out[(size_t)o0 + j] = r;
-    }
+    const Rec* ring = rg.rec + (size_t)it.slot * R;
+    for (uint32_t j = tid; j < o1 - o0; j += 256)
+        if ((size_t)o0 + j < cap) out[(size_t)o0 + j] = rec_rebased(ring[(h + j) % R], it.w0);
 }
 
 // ---- streaming Haitsma (A18): the kernels around stft_power_kernel<2048, true> for one push of a stream set.
@@ -2077,10 +2087,11 @@ static void launch_wang_streams_back(const WangStreamsDev& st, uint8_t* ws, cons
                        (const uint32_t*)u32(w.pt), (const float*)f32(w.pp));
 }
 
-// Launches: the front end, pair count, scan (1 or 3), pair emit, offsets, save.
-int launch_wang_streams_push(const float* pcm, const WangStreamsDev& st, uint32_t fan_out, uint32_t zone_t,
-                             uint32_t zone_f, uint32_t pps, float floor_power, uint8_t* ws, const WangPushWs& w,
-                             uint32_t* out, size_t cap, uint64_t* d_out_off, hipStream_t stream) {
+// Launches: the front end, pair count, scan (1 or 3), pair emit, [ring,] offsets, save.  With a ring (rg.cap != 0)
+// every entry's new hashes join its stream's window (A20).
+int launch_wang_streams_push(const float* pcm, const WangStreamsDev& st, const WangRingsDev& rg, uint32_t fan_out,
+                             uint32_t zone_t, uint32_t zone_f, uint32_t pps, float floor_power, uint8_t* ws,
+                             const WangPushWs& w, uint32_t* out, size_t cap, uint64_t* d_out_off, hipStream_t stream) {
     const uint32_t n = (uint32_t)w.n;
     if (n == 0) {
         (void)hipMemsetAsync(d_out_off, 0, 8, stream);
@@ -2100,6 +2111,9 @@ int launch_wang_streams_push(const float* pcm, const WangStreamsDev& st, uint32_
                        n, (const uint32_t*)u32(w.np), (const uint32_t*)u32(w.pt), (const float*)f32(w.pp), fan_out,
                        zone_t, zone_f, floor_power, (uint32_t*)nullptr, (const uint32_t*)u32(w.pair_off),
                        reinterpret_cast<uint2*>(out), cap);
+    if (rg.cap)
+        hipLaunchKernelGGL(streams_ring_kernel<uint2>, dim3(n), dim3(256), 0, stream, ents, pk_base,
+                           (const uint32_t*)u32(w.pair_off), reinterpret_cast<const uint2*>(out), rg);
     launch_wang_streams_back(st, ws, w, d_out_off, stream);
     return 0;
 }
@@ -2131,18 +2145,19 @@ int launch_panako_streams_push(const float* pcm, const WangStreamsDev& st, const
                        fan_out, zone_t, zone_f, floor_power, (uint32_t*)nullptr, (const uint32_t*)u32(w.pair_off),
                        reinterpret_cast<uint4*>(out), cap);
     if (rg.cap)
-        hipLaunchKernelGGL(panako_streams_ring_kernel, dim3(n), dim3(256), 0, stream, ents, pk_base,
+        hipLaunchKernelGGL(streams_ring_kernel<uint4>, dim3(n), dim3(256), 0, stream, ents, pk_base,
                            (const uint32_t*)u32(w.pair_off), reinterpret_cast<const uint4*>(out), rg);
     launch_wang_streams_back(st, ws, w, d_out_off, stream);
     return 0;
 }
 
-PanakoWindowsWs panako_windows_layout(size_t n) {
+// ---- live windows orchestration (A19, A20) ----------------------------------------------------------
+StreamWindowsWs stream_windows_layout(size_t n) {
     auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    PanakoWindowsWs w;
+    StreamWindowsWs w;
     w.n = n;
     size_t off = 0;
-    w.items = off;    off += n * sizeof(PanakoWindowItem);
+    w.items = off;    off += n * sizeof(StreamWindowItem);
     w.tab_bytes = off; off = align(off);
     w.cnt = off;      off = align(off + (n + 1) * 4);
     w.off = off;      off = align(off + (n + 1) * 4);
@@ -2152,21 +2167,32 @@ PanakoWindowsWs panako_windows_layout(size_t n) {
 }
 
 // the items [ws + w.items, ws + w.tab_bytes) are on the device already.  Launches: counts, scan (1 or 3), copy.
-int launch_panako_streams_windows(const PanakoRingsDev& rg, uint8_t* ws, const PanakoWindowsWs& w, uint8_t* out,
-                                  size_t cap, uint64_t* d_offsets, uint32_t* d_origins, hipStream_t stream) {
+template <class Rec>
+static int launch_streams_windows_of(const StreamRingsDev<Rec>& rg, uint8_t* ws, const StreamWindowsWs& w, uint8_t* out,
+                                     size_t cap, uint64_t* d_offsets, uint32_t* d_origins, hipStream_t stream) {
     const uint32_t n = (uint32_t)w.n;
     if (n == 0) {
         (void)hipMemsetAsync(d_offsets, 0, 8, stream);
         return 0;
     }
     auto u32 = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
-    const PanakoWindowItem* items = reinterpret_cast<const PanakoWindowItem*>(ws + w.items);
-    hipLaunchKernelGGL(panako_streams_window_counts_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, stream, items, n, rg,
+    const StreamWindowItem* items = reinterpret_cast<const StreamWindowItem*>(ws + w.items);
+    hipLaunchKernelGGL(streams_window_counts_kernel<Rec>, dim3(blocks_for(n, 256)), dim3(256), 0, stream, items, n, rg,
                        u32(w.cnt));
     launch_exclusive_scan(u32(w.cnt), n, u32(w.off), u32(w.scan_tmp), stream);
-    hipLaunchKernelGGL(panako_streams_windows_kernel, dim3(n), dim3(256), 0, stream, items, n,
-                       (const uint32_t*)u32(w.off), rg, reinterpret_cast<uint4*>(out), cap, d_offsets, d_origins);
+    hipLaunchKernelGGL(streams_windows_kernel<Rec>, dim3(n), dim3(256), 0, stream, items, n,
+                       (const uint32_t*)u32(w.off), rg, reinterpret_cast<Rec*>(out), cap, d_offsets, d_origins);
     return 0;
+}
+
+int launch_streams_windows(const PanakoRingsDev& rg, uint8_t* ws, const StreamWindowsWs& w, uint8_t* out, size_t cap,
+                           uint64_t* d_offsets, uint32_t* d_origins, hipStream_t stream) {
+    return launch_streams_windows_of(rg, ws, w, out, cap, d_offsets, d_origins, stream);
+}
+
+int launch_streams_windows(const WangRingsDev& rg, uint8_t* ws, const StreamWindowsWs& w, uint8_t* out, size_t cap,
+                           uint64_t* d_offsets, uint32_t* d_origins, hipStream_t stream) {
+    return launch_streams_windows_of(rg, ws, w, out, cap, d_offsets, d_origins, stream);
 }
 
 // ---- streaming Haitsma orchestration (A18) ----------------------------------------------------------

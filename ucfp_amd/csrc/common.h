@@ -404,36 +404,46 @@ struct WangPushWs {
 };
 WangPushWs wang_push_layout(size_t n, size_t n_slots, size_t n_closed, size_t total_v, size_t total_cap,
                             size_t judged, uint32_t pps);
-int launch_wang_streams_push(const float* pcm, const WangStreamsDev& st, uint32_t fan_out, uint32_t zone_t,
-                             uint32_t zone_f, uint32_t pps, float floor_power, uint8_t* ws, const WangPushWs& w,
-                             uint32_t* out, size_t cap, uint64_t* d_out_off, hipStream_t stream);
-
-// ---- streaming Panako (A19): the Wang push with triplets behind it (panako_streams.hip plans it with the shared
-// wang_streams_core.h, audio.hip runs it), and a ring per stream that holds the latest window of emitted records ----
-struct PanakoRingsDev {
-    uint4* rec;           // [slots][cap] records with absolute times, in emission order from head on
+// ---- live windows (A19 Panako, A20 Wang): a ring per stream that holds the latest window of emitted records.  Rec is
+// the record of the set: uint4 (hash, t_a, t_b, t_c) for Panako, uint2 (hash, t_anchor) for Wang ----
+template <class Rec>
+struct StreamRingsDev {
+    Rec* rec;             // [slots][cap] records with absolute times, in emission order from head on
     uint32_t* head;       // [slots]
     uint32_t* count;      // [slots]
     uint32_t cap;         // records per ring (0: the set keeps no windows)
     uint32_t window;      // W in frames
 };
+using PanakoRingsDev = StreamRingsDev<uint4>;
+using WangRingsDev = StreamRingsDev<uint2>;
 // one item of a windows call, host-built
-struct PanakoWindowItem {
+struct StreamWindowItem {
     uint32_t slot;
     uint32_t w0;          // origin of the window: max(0, F(n) - W)
     uint32_t live;        // 0: nothing pushed since the slot was opened, whatever the ring holds
     uint32_t pad;
 };
-struct PanakoWindowsWs {
+struct StreamWindowsWs {
     size_t n = 0;
     size_t items, tab_bytes, cnt, off, scan_tmp, total = 0;
 };
+StreamWindowsWs stream_windows_layout(size_t n);
+// out: records of sizeof(Rec) bytes, aligned to it; d_offsets in BYTES
+int launch_streams_windows(const PanakoRingsDev& rg, uint8_t* ws, const StreamWindowsWs& w, uint8_t* out, size_t cap,
+                           uint64_t* d_offsets, uint32_t* d_origins, hipStream_t stream);
+int launch_streams_windows(const WangRingsDev& rg, uint8_t* ws, const StreamWindowsWs& w, uint8_t* out, size_t cap,
+                           uint64_t* d_offsets, uint32_t* d_origins, hipStream_t stream);
+
+// with a ring (rg.cap != 0) every entry's new hashes then join its stream's window (A20)
+int launch_wang_streams_push(const float* pcm, const WangStreamsDev& st, const WangRingsDev& rg, uint32_t fan_out,
+                             uint32_t zone_t, uint32_t zone_f, uint32_t pps, float floor_power, uint8_t* ws,
+                             const WangPushWs& w, uint32_t* out, size_t cap, uint64_t* d_out_off, hipStream_t stream);
+
+// ---- streaming Panako (A19): the Wang push with triplets behind it (panako_streams.hip plans it with the shared
+// wang_streams_core.h, audio.hip runs it) ----
 int launch_panako_streams_push(const float* pcm, const WangStreamsDev& st, const PanakoRingsDev& rg, uint32_t fan_out,
                                uint32_t zone_t, uint32_t zone_f, uint32_t pps, float floor_power, uint8_t* ws,
                                const WangPushWs& w, uint32_t* out, size_t cap, uint64_t* d_out_off, hipStream_t stream);
-PanakoWindowsWs panako_windows_layout(size_t n);
-int launch_panako_streams_windows(const PanakoRingsDev& rg, uint8_t* ws, const PanakoWindowsWs& w, uint8_t* out,
-                                  size_t cap, uint64_t* d_offsets, uint32_t* d_origins, hipStream_t stream);
 
 struct HaitsmaBatchWs {
     size_t n5_ub = 0, frames_ub = 0;      // upper bounds (the per-clip lengths of a batch live on the device)

@@ -1,7 +1,7 @@
 // stream_set.h -- what every device-resident stream set holds around its planner, beside the slot table
 // (stream_slots.h): two pinned host tables used in turn, each with the event of its last copy to the device, and the
 // event behind the set's last call.  One rotation per set: every call that fills a table (a push, Haitsma's blocks,
-// Panako's windows) takes the next one.  Which locks a call takes, whether it waits on the context's audio event and
+// Wang's and Panako's windows) takes the next one.  Which locks a call takes, whether it waits on the context's audio event and
 // where its table lands on the device stay with the planner that owns the call.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -2,6 +2,7 @@
 // built on it: wang_streams.hip (pairs, A9) and panako_streams.hip (triplets, A19).  The host tracks how many samples
 // each stream has seen, which fixes every frame range of a push: the host plans, the device keeps the data (carried
 // samples, the open second's candidates, the retained peaks).  What an anchor emits is the including file's business.
+// Either set may keep a live window per stream (A19, A20): the rings and the windows call are here too.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -22,6 +23,10 @@ namespace wstreams {
 constexpr uint64_t kMaxChunk = (uint64_t)1 << 29;     // samples of one stream in one push (18.6 h): t << 9 | k stays packable
 constexpr uint64_t kMaxPushSamples = (uint64_t)1 << 31;   // carried + new samples of one push (32-bit sample offsets)
 constexpr uint64_t kMaxFrames = ((uint64_t)1 << 32) - 1024;   // frames of a stream (u32 t_anchor, ~795 days)
+constexpr uint32_t kMaxWindowFrames = 8192;           // W of a live window (131 s)
+constexpr size_t kRingHeader = 8;                     // head and count
+static_assert(kMaxWindowFrames == UCFP_WANG_STREAM_MAX_WINDOW_FRAMES &&
+              kMaxWindowFrames == UCFP_PANAKO_STREAM_MAX_WINDOW_FRAMES, "");
 
 // ucfp_wang_config and ucfp_panako_config carry the same five fields with the same ranges
 struct Cfg {
@@ -57,7 +62,7 @@ struct Plan {
     uint64_t vbase, o, j0, j1, s0, n_closed, f_lo, f_hi, cap, bound;
 };
 
-// the slot table counts samples; the pinned tables hold a push (or, for Panako, the items of a windows call)
+// the slot table counts samples; the pinned tables hold a push or the items of a windows call
 struct Set : streams::Slots, streams::Tables {
     ucfp_ctx* ctx = nullptr;
     Cfg cfg{};
@@ -65,7 +70,15 @@ struct Set : streams::Slots, streams::Tables {
     std::vector<Plan> plan;
     WangStreamsDev dev{};
     uint8_t* dev_mem = nullptr;
+    uint32_t window = 0;                  // W in frames (0: the set keeps no windows)
+    uint8_t* ring_mem = nullptr;          // the rings of the including file's record type
 };
+
+// records a window of W frames can hold (A19, A20): the emitted anchors of [w0, F) lie in at most ceil(2 W / 125) + 1
+// seconds, a second holds at most peaks_per_sec anchors and an anchor emits at most fan_out records
+inline size_t window_cap_of(const Cfg& c, uint32_t w) {
+    return w ? ((size_t)(2 * w + 124) / 125 + 1) * c.peaks_per_sec * c.fan_out : 0;
+}
 
 inline size_t state_bytes_per_stream(uint32_t ret_cap) {
     return (size_t)kWangCarry * 4 + 4 + (size_t)kWangCandCap * 12 + 4 + (size_t)ret_cap * 12;
@@ -103,9 +116,25 @@ inline hipError_t set_init(Set* s, ucfp_ctx* ctx, const Cfg& c, uint32_t max_str
     return e == hipSuccess ? s->setup(tab_bytes_max(max_streams)) : e;
 }
 
+// one ring of window_cap records per slot behind set_init (window_frames != 0)
+template <class Rec>
+inline hipError_t rings_init(Set* s, uint32_t window_frames, StreamRingsDev<Rec>* rg) {
+    const size_t ms = s->max_streams, cap = window_cap_of(s->cfg, window_frames);
+    const size_t rec_bytes = (ms * cap * sizeof(Rec) + 255) & ~(size_t)255, idx_bytes = (ms * 4 + 255) & ~(size_t)255;
+    const hipError_t e = hipMalloc((void**)&s->ring_mem, rec_bytes + 2 * idx_bytes);
+    if (e != hipSuccess) return e;
+    rg->rec = reinterpret_cast<Rec*>(s->ring_mem);
+    rg->head = reinterpret_cast<uint32_t*>(s->ring_mem + rec_bytes);
+    rg->count = reinterpret_cast<uint32_t*>(s->ring_mem + rec_bytes + idx_bytes);
+    rg->cap = (uint32_t)cap;
+    rg->window = window_frames;
+    return hipSuccess;
+}
+
 inline void set_release(Set* s) {
     s->teardown();
     if (s->dev_mem) (void)hipFree(s->dev_mem);
+    if (s->ring_mem) (void)hipFree(s->ring_mem);
 }
 
 inline int set_open(Set* s, uint32_t* slot) {
@@ -360,6 +389,98 @@ int entry_push(typename K::set* s, uint32_t slot, const float* pcm, size_t n, in
     const size_t h = (size_t)(off[1] - off[0]);
     if (h) HIP_TRY(hipMemcpy(out, d_out + off[0] * K::rec_bytes, h * K::rec_bytes, hipMemcpyDeviceToHost));
     *n_hashes = h;
+    return UCFP_OK;
+}
+
+// Creation, for either back end: K also names the algorithm `name`, its default config `defaults()` and the set's rings
+// `rings(s)`.  The rate and the config are judged first (UCFP_E_MODALITY), whatever else is wrong.
+template <class K, class C>
+int entry_create(ucfp_ctx* ctx, uint32_t sample_rate, const C* cfg, uint32_t max_streams, uint32_t window_frames,
+                 typename K::set** out) {
+    if (sample_rate != 8000)
+        return capi_fail(UCFP_E_MODALITY, "%s requires 8 kHz mono input (got %u Hz); resample upstream", K::name, sample_rate);
+    const Cfg c = cfg ? cfg_of(*cfg) : K::defaults();
+    if (!cfg_ok(c)) return capi_fail(UCFP_E_MODALITY, "%sConfig outside the ranges of /v1/algorithms", K::name);
+    if (!ctx || !out) return capi_fail(UCFP_E_INVALID, "ctx / out is NULL");
+    *out = nullptr;
+    if (max_streams == 0 || max_streams > (1u << 20))
+        return capi_fail(UCFP_E_INVALID, "max_streams %u outside [1, 2^20]", max_streams);
+    if (window_frames > kMaxWindowFrames)
+        return capi_fail(UCFP_E_INVALID, "window_frames %u above %u", window_frames, kMaxWindowFrames);
+    HIP_TRY(hipSetDevice(ctx->device));
+    typename K::set* s = new (std::nothrow) typename K::set();
+    if (!s) return capi_fail(UCFP_E_INDEX, "out of host memory");
+    hipError_t e = set_init(s, ctx, c, max_streams);
+    s->window = window_frames;
+    if (e == hipSuccess && window_frames) e = rings_init(s, window_frames, &K::rings(s));
+    if (e != hipSuccess) {
+        set_release(s);
+        delete s;
+        return capi_fail(UCFP_E_INDEX, "stream set allocation failed: %s", hipGetErrorString(e));
+    }
+    *out = s;
+    return UCFP_OK;
+}
+
+// host-only: records of a window, device bytes per stream (0 for out-of-range arguments)
+template <class K, class C>
+size_t entry_window_cap(const C* cfg, uint32_t window_frames) {
+    const Cfg c = cfg ? cfg_of(*cfg) : K::defaults();
+    return cfg_ok(c) && window_frames <= kMaxWindowFrames ? window_cap_of(c, window_frames) : 0;
+}
+
+template <class K, class C>
+size_t entry_state_bytes(const C* cfg, uint32_t window_frames) {
+    const Cfg c = cfg ? cfg_of(*cfg) : K::defaults();
+    if (!cfg_ok(c) || window_frames > kMaxWindowFrames) return 0;
+    const size_t ring = window_frames ? kRingHeader + K::rec_bytes * window_cap_of(c, window_frames) : 0;
+    return state_bytes_per_stream(ret_cap_of(c)) + ring;
+}
+
+// The live windows of n distinct open slots in the ragged shape of the back end's index, rebased to their origins; K
+// also names the set's rings `rings(s)`, the argument that counts the caller's records `cap_arg` and its buffer
+// `buf_name`.  The items go through the set's pinned tables, in turn with the pushes'; no host synchronisation.
+template <class K>
+int entry_windows_dev(typename K::set* s, const uint32_t* slots, size_t n, uint8_t* d_out, size_t cap, uint64_t* d_offsets,
+                      uint32_t* d_origins, void* stream) {
+    if (!s) return capi_fail(UCFP_E_INVALID, "set is NULL");
+    if (!d_offsets || (n && !slots) || (cap && !d_out)) return capi_fail(UCFP_E_INVALID, "NULL buffer");
+    if (cap && ((uintptr_t)d_out & (K::align - 1))) return capi_fail(UCFP_E_INVALID, "%s", K::align_msg);
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (!s->window) return capi_fail(UCFP_E_INVALID, "the set was created with window_frames = 0: it keeps no windows");
+    int rc = s->check(slots, n, "items", "call");
+    if (rc) return rc;
+    const auto& rg = K::rings(s);
+    const size_t need = n * (size_t)rg.cap;
+    if (cap < need)
+        return capi_fail(UCFP_E_INVALID, "%s %zu below n * ucfp_%s_streams_window_cap = %zu", K::cap_arg, cap, K::abi, need);
+    if (need >= 0xffffffffu) return capi_fail(UCFP_E_INVALID, "too many windows for one call: split it");
+    ucfp_ctx* ctx = s->ctx;
+    hipStream_t st = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lk2(ctx->mu);
+    HIP_TRY(hipSetDevice(ctx->device));
+    const StreamWindowsWs w = stream_windows_layout(n);
+    rc = grow(&ctx->audio_ws, &ctx->audio_ws_cap, w.total);
+    if (rc) return rc;
+    int k = 0;
+    rc = s->next(&k);
+    if (rc) return rc;
+    auto* items = reinterpret_cast<StreamWindowItem*>(s->tab_h[k]);
+    for (size_t i = 0; i < n; i++) {
+        const uint64_t ns = s->n[slots[i]], f = frontier_of(judged_of(ns), s->cfg.target_zone_t);
+        items[i].slot = slots[i];
+        items[i].w0 = (uint32_t)(f > s->window ? f - s->window : 0);
+        items[i].live = ns ? 1u : 0u;
+        items[i].pad = 0;
+    }
+    HIP_TRY(hipStreamWaitEvent(st, ctx->audio_done, 0));
+    HIP_TRY(hipStreamWaitEvent(st, s->done, 0));
+    if (n) HIP_TRY(hipMemcpyAsync(ctx->audio_ws + w.items, items, w.tab_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(s->tab_copied[k], st));
+    launch_streams_windows(rg, ctx->audio_ws, w, d_out, cap, d_offsets, d_origins, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ctx->audio_done, st));
+    HIP_TRY(hipEventRecord(s->done, st));
     return UCFP_OK;
 }
 

@@ -10,6 +10,8 @@ path, backed by the GPU-resident shard behind the C ABI (ucfp_index_*).
                                       algorithm=ALGORITHM_PANAKO over Panako (hash, t_anchor) pairs (DESIGN A13)
     GpuIndex.identify_stretched(tenant, records, k)  the same over whole Panako triplets, by a (scale, offset) vote that
                                       survives a change of tempo (DESIGN A14; PanakoIndex)
+    GpuIndex.identify_live(tenant, streams, slots, k)  identify / identify_stretched over the live windows of a WangStreams
+                                      / PanakoStreams, windows and queries on the device (DESIGN A20)
     GpuIndex.identify_frames(tenant, frames, k)  the same over Haitsma sub-fingerprints (DESIGN A12; HaitsmaIndex)
     GpuIndex.nearest_tlsh(tenant, digest, k)  the `tlsh-128-1` records at the smallest TLSH distance (DESIGN A15; TlshIndex)
     GpuIndex.similar_images(tenant, record, k)  the image records that score highest with global and block hashes
@@ -29,7 +31,7 @@ from typing import Iterable, List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from .audio import ALGORITHM_HAITSMA, ALGORITHM_PANAKO, ALGORITHM_WANG, panako_landmarks
+from .audio import ALGORITHM_HAITSMA, ALGORITHM_PANAKO, ALGORITHM_WANG, PanakoStreams, WangStreams, panako_landmarks
 from .core import Hit, HitSource, Record, TermHit
 from .errors import InvalidArgument, UnsupportedError
 from .image import MultiHashConfig, match_algo
@@ -1136,6 +1138,53 @@ class GpuIndex:
         return [Hit(tenant_id=tenant_id, record_id=int(ids[0, i]), score=float(scores[0, i]), source=HitSource.Landmark,
                     votes=int(votes[0, i]), offset=int(offs[0, i]), scale=int(scales[0, i]) / 256.0)
                 for i in range(int(counts[0]))]
+
+    def identify_live(self, tenant_id: int, streams, slots, k: int, min_votes: int = 1, **match) -> dict:
+        """What are these live streams playing right now: {slot: (hits, origin)} for open `slots` of a `WangStreams` or a
+        `PanakoStreams` created with window_frames > 0 (DESIGN A20).  The windows go from the set to the index on the
+        device (`windows_dev` -> `LandmarkIndex.query_dev` / `PanakoIndex.query_dev`, one stream); only the answers
+        come back.  The hits of a slot are those of `identify` (Wang) / `identify_stretched` (Panako, with `match`) on
+        the host copy of its window, [] for an empty window; `offset` = frame `origin` of the stream in the record.  A
+        set without windows raises InvalidArgument.  Haitsma sets are left out on purpose: `blocks_dev` reports no
+        origin, so a hit's offset could not be placed in the stream."""
+        import torch
+        if isinstance(streams, WangStreams):
+            if match:
+                raise InvalidArgument(f"unknown match parameters: {sorted(match)}")
+            ix, width = self._lm, 2
+        elif isinstance(streams, PanakoStreams):
+            panako_match_config(**match)
+            ix, width = self._ps, 4
+        else:
+            raise InvalidArgument("identify_live takes a WangStreams or a PanakoStreams")
+        slots = [int(s) for s in slots]
+        nq, kk = len(slots), min(int(k), MAX_K)
+        dev = f"cuda:{streams.ctx.device}"
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream().cuda_stream
+            d_win = torch.zeros((max(nq * streams.window_cap, 1), width), dtype=torch.int32, device=dev)
+            d_off = torch.zeros(nq + 1, dtype=torch.int64, device=dev)
+            d_org = torch.zeros(max(nq, 1), dtype=torch.int32, device=dev)
+            streams.windows_dev(slots, d_win, d_off, d_org, nq * streams.window_cap, st)
+            answered = bool(nq and kk and ix is not None)
+            if answered:
+                o_ids = torch.zeros((nq, kk), dtype=torch.int64, device=dev)
+                o_v, o_o, o_c = (torch.zeros((nq, kk), dtype=torch.int32, device=dev) for _ in range(3))
+                o_f = torch.zeros((nq, kk), dtype=torch.float32, device=dev)
+                o_n = torch.zeros(nq, dtype=torch.int32, device=dev)
+                scales = (o_c.data_ptr(),) if width == 4 else ()
+                ix.query_dev(tenant_id, d_win.data_ptr(), d_off.data_ptr(), nq, kk, min_votes, o_ids.data_ptr(),
+                             o_v.data_ptr(), o_o.data_ptr(), *scales, o_f.data_ptr(), o_n.data_ptr(), st, **match)
+                ids, votes, offs = o_ids.cpu().numpy().view(np.uint64), o_v.cpu().numpy(), o_o.cpu().numpy()
+                sc, scores, counts = o_c.cpu().numpy(), o_f.cpu().numpy(), o_n.cpu().numpy()
+            org = d_org.cpu().numpy().view(np.uint32)
+        out = {}
+        for q, s in enumerate(slots):
+            out[s] = ([Hit(tenant_id=tenant_id, record_id=int(ids[q, i]), score=float(scores[q, i]),
+                           source=HitSource.Landmark, votes=int(votes[q, i]), offset=int(offs[q, i]),
+                           scale=int(sc[q, i]) / 256.0 if width == 4 else None)
+                       for i in range(int(counts[q]) if answered else 0)], int(org[q]))
+        return out
 
     def identify_frames(self, tenant_id: int, frames, k: int, flip_bits: int = 2, max_ber: float = 0.35) -> List[Hit]:
         """Which recording is this clip, and where in it: frames = Haitsma sub-fingerprints as bytes (4 per frame) or

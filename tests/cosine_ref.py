@@ -74,9 +74,15 @@ class CosineRef:
                 sc = dots[:, j] / np.where(self.bad, 1.0, rn * qn[q0 + j])
                 sc[self.bad] = -np.inf
                 thr = np.partition(sc, n - kk)[n - kk]      # the kk-th best score: everything at or above it competes
-                cand = np.nonzero(sc >= thr)[0]
-                order = cand[np.lexsort((self.ids[cand], -sc[cand]))][:kk]
-                self.best.append((order, sc[order]))
+                cand = np.nonzero(sc >= thr - 1e-12)[0]
+                # Bit-identical rows have ONE score.  The matrix product above may round their dots differently (its
+                # blocking depends on the row's position), which would order copies by that noise instead of by id --
+                # and drop a copy an ulp under the threshold, hence the slack above.  The first copy met lends its score.
+                sc_c, first = sc[cand], {}
+                for t, r in enumerate(cand):
+                    sc_c[t] = sc_c[first.setdefault(self.rows[r].tobytes(), t)]
+                by = np.lexsort((self.ids[cand], -sc_c))[:kk]
+                self.best.append((cand[by], sc_c[by]))
 
     def answer(self, k):
         """-> (ids [nq, k] u64, scores [nq, k] f32, counts [nq] u32): the reference's answer rounded to f32."""

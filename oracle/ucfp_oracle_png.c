@@ -183,8 +183,12 @@ static int inflate_raw(Bits* b, uint8_t* out, size_t cap, size_t* produced) {
             if (lens[256] == 0) return PNG_CORRUPT;
             int r = huff_build(&ll, lens, nlen);
             if (r < 0 || (r > 0 && nlen - ll.count[0] != 1)) return PNG_CORRUPT;   /* incomplete only with one code */
+            /* P5: a lone code that is not one bit long -- zlib refuses it ("invalid literal/lengths set", "invalid distances
+             * set"), other inflaters take it: decoders differ, the host's decoder decides */
+            int lone = r > 0 && ll.count[1] != 1;
             r = huff_build(&dd, lens + nlen, ndist);
             if (r < 0 || (r > 0 && ndist - dd.count[0] > 1)) return PNG_CORRUPT;   /* no distance code at all: a block of literals */
+            if (lone || (r > 0 && ndist - dd.count[0] == 1 && dd.count[1] != 1)) return PNG_NEEDS_HOST;
             int rc = inflate_codes(b, &ll, &dd, out, cap, &op);
             if (rc) return rc;
         } else {

@@ -130,6 +130,29 @@ def test_formats_handed_back_to_the_host(oracle):
     assert oracle.png_decode(b"GIF89a" + bytes(60))[0] == oracle.PNG_CORRUPT
 
 
+def test_lone_code_that_is_not_one_bit_long_is_the_hosts(oracle):
+    """P5: zlib takes an incomplete code of one symbol only when it is one bit long; other inflaters take any length.  The oracle
+    hands such a stream to the host's decoder, whichever of the two codes it is, and inflates the one-bit twin like zlib."""
+    import zlib
+    from deflate_writer import Stream
+    for bits in (1, 2, 7, 15):
+        for which in ("ll", "dist"):
+            S = Stream()
+            S.fixed([65, 66, 67])
+            if which == "ll":
+                S.dynamic([], {256: bits}, {})                                   # an empty block: only end-of-block has a code
+            else:
+                S.dynamic([68, (3, 1)], {68: 1, 256: 2, 257: 2}, {0: bits})
+            S.fixed([69], final=True)
+            z = S.finish()
+            if bits == 1:
+                assert zlib.decompress(z) == bytes(S.out) and oracle.inflate(z, 64) == (oracle.PNG_OK, bytes(S.out))
+            else:
+                with pytest.raises(zlib.error):
+                    zlib.decompress(z)
+                assert oracle.inflate(z, 64)[0] == oracle.PNG_NEEDS_HOST, (which, bits)
+
+
 def palette_png(rng, h, w, colours=256, **kw):
     """An 8-bit indexed-colour PNG with `colours` palette entries (PLTE shorter than 256 entries when colours < 256)."""
     idx = rng.integers(0, colours, (h, w), dtype=np.uint8)

@@ -10,6 +10,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 PIL = pytest.importorskip("PIL.Image")
 
+from deflate_writer import filter_rows                                       # noqa: E402
 from test_oracle_png import _png, config1_png, grey_alpha_png, palette_png   # noqa: E402
 
 
@@ -84,26 +85,7 @@ def test_every_filter_type_and_block_type(gpu_ctx, oracle):
     h, w, bpp = 70, 53, 3
     img = rng.integers(0, 256, (h, w * bpp), dtype=np.uint8).astype(np.int32)
     img[20:40] = (np.arange(w * bpp) * 3) & 255                      # compressible rows
-    rows = []
-    for y in range(h):
-        ft = y % 5
-        cur, up = img[y], (img[y - 1] if y else np.zeros_like(img[0]))
-        a = np.concatenate([np.zeros(bpp, np.int32), cur[:-bpp]])
-        c = np.concatenate([np.zeros(bpp, np.int32), up[:-bpp]])
-        if ft == 0:
-            pred = 0
-        elif ft == 1:
-            pred = a
-        elif ft == 2:
-            pred = up
-        elif ft == 3:
-            pred = (a + up) >> 1
-        else:
-            p = a + up - c
-            pa, pb, pc = abs(p - a), abs(p - up), abs(p - c)
-            pred = np.where((pa <= pb) & (pa <= pc), a, np.where(pb <= pc, up, c))
-        rows.append(bytes([ft]) + ((cur - pred) & 255).astype(np.uint8).tobytes())
-    raw = b"".join(rows)
+    raw = filter_rows(img, bpp, [y % 5 for y in range(h)])
 
     def fixed(d):
         co = zlib.compressobj(6, zlib.DEFLATED, 15, 8, zlib.Z_FIXED)

@@ -27,6 +27,8 @@
 // critical chunk is UCFP_E_MODALITY, while the checksum-ONLY failures decoders disagree on (Adler-32 of a stream that
 // otherwise inflated to the right length, the CRC of an ancillary chunk) are UCFP_IMAGE_NEEDS_HOST: the host's decoder
 // -- the reference's own, in a drop-in -- decides, so the device never rejects a file the reference would fingerprint.
+// Likewise a dynamic block whose literal/length or distance code is one lone symbol that is not one bit long: zlib refuses it,
+// other inflaters decode it (DESIGN P5).
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -116,9 +118,10 @@ __device__ uint32_t slow_code(uint64_t buf, const uint16_t* count, const uint16_
 }
 
 // Builds one code from lens[0 .. n): first-level table, canonical arrays for the slow path.  Lane j owns symbols
-// [5 j, 5 j + 5).  Returns 0 complete, 1 incomplete, -1 over-subscribed; *used = symbols with a code.
+// [5 j, 5 j + 5).  Returns 0 complete, 1 incomplete, -1 over-subscribed; *used = symbols with a code, *ones = those of one bit.
 template <bool DIST>
-__device__ int build_table(const uint8_t* lens, int n, uint32_t* tab, uint16_t* count, uint16_t* sorted, int lane, int* used) {
+__device__ int build_table(const uint8_t* lens, int n, uint32_t* tab, uint16_t* count, uint16_t* sorted, int lane, int* used,
+                           int* ones) {
     constexpr int R = DIST ? kDRoot : kRoot;
     for (int i = lane; i < (1 << R); i += 64) tab[i] = kInvalid;
     // per-lane histogram of the code lengths 1 .. 15, three 10-bit counters per word
@@ -159,6 +162,7 @@ __device__ int build_table(const uint8_t* lens, int n, uint32_t* tab, uint16_t* 
     }
     if (lane == 0) count[0] = 0;
     *used = total;
+    *ones = (int)(tot[0] & 1023u);
     if (left < 0) return -1;
 #pragma unroll
     for (int t = 0; t < 5; t++) {
@@ -665,7 +669,7 @@ __global__ __launch_bounds__(64) void png_inflate_kernel(const uint8_t* __restri
         bad = (cmf & 15) != 8 || (cmf >> 4) > 7 || ((cmf << 8 | flg) % 31) != 0 || (flg & 0x20);
     }
     uint32_t bp = 16, outpos = 0;
-    bool last = false, checksum_only = false;
+    bool last = false, checksum_only = false, lone = false;
     int B = C::kMaxB;
     Adler adler;
 #ifdef PNG_PROF
@@ -712,12 +716,12 @@ __global__ __launch_bounds__(64) void png_inflate_kernel(const uint8_t* __restri
             continue;
         }
         // ---- the block's two codes ----
-        int used = 0;
+        int used = 0, ones = 0;
         if (type == 1) {
             for (int s = lane; s < 320; s += 64) L.lens[s] = s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : s < 288 ? 8 : 5;
             wave_lds_sync();
-            build_table<false>(L.lens, 288, L.lit, L.ll_count, L.ll_sorted, lane, &used);
-            build_table<true>(L.lens + 288, 30, L.dst, L.d_count, L.d_sorted, lane, &used);
+            build_table<false>(L.lens, 288, L.lit, L.ll_count, L.ll_sorted, lane, &used, &ones);
+            build_table<true>(L.lens + 288, 30, L.dst, L.d_count, L.d_sorted, lane, &used, &ones);
         } else {
             const uint32_t nlen = peek_u(L.stage, rel, 5) + 257, ndist = peek_u(L.stage, rel + 5, 5) + 1,
                            ncode = peek_u(L.stage, rel + 10, 4) + 4;
@@ -827,16 +831,21 @@ __global__ __launch_bounds__(64) void png_inflate_kernel(const uint8_t* __restri
             if (lane < 32) L.lens[288 + lane] = (uint8_t)dl;
             for (int s = nlen + lane; s < 288; s += 64) L.lens[s] = 0;
             wave_lds_sync();
-            int r = build_table<false>(L.lens, 288, L.lit, L.ll_count, L.ll_sorted, lane, &used);
+            int r = build_table<false>(L.lens, 288, L.lit, L.ll_count, L.ll_sorted, lane, &used, &ones);
             if (r < 0 || (r > 0 && used != 1)) {
                 PNG_BAD(11);
                 break;
             }
-            r = build_table<true>(L.lens + 288, 30, L.dst, L.d_count, L.d_sorted, lane, &used);
+            // An incomplete code of exactly ONE symbol: zlib takes it only when that code is one bit long, other inflaters
+            // take any length -- decoders disagree, so the host's decoder decides (P5)
+            lone = r > 0 && ones != 1;
+            r = build_table<true>(L.lens + 288, 30, L.dst, L.d_count, L.d_sorted, lane, &used, &ones);
             if (r < 0 || (r > 0 && used > 1)) {
                 PNG_BAD(12);
                 break;
             }
+            lone = lone || (r > 0 && used == 1 && ones != 1);
+            if (lone) break;
         }
         wave_lds_sync();
         bp = s0 + rel;
@@ -961,8 +970,8 @@ __global__ __launch_bounds__(64) void png_inflate_kernel(const uint8_t* __restri
             if (take == 64 && add < C::kIterOut / 4 && B < C::kMaxB) B *= 2;
         }
     }
-    if (!bad && outpos != raw_n) PNG_BAD(16);
-    if (!bad) {
+    if (!bad && !lone && outpos != raw_n) PNG_BAD(16);
+    if (!bad && !lone) {
         // the Adler-32 of the output follows the deflate data at the next byte boundary, most significant byte first
         const uint32_t e = (bp + 7) / 8;
         // A stream that inflated to exactly the announced length but whose CHECKSUM is absent or wrong is not rejected
@@ -978,7 +987,7 @@ __global__ __launch_bounds__(64) void png_inflate_kernel(const uint8_t* __restri
 #endif
     if (lane == 0) {
         if (bad) info[img].status = UCFP_E_MODALITY;
-        else if (checksum_only) info[img].status = UCFP_IMAGE_NEEDS_HOST;
+        else if (checksum_only || lone) info[img].status = UCFP_IMAGE_NEEDS_HOST;
     }
 }
 
@@ -1171,7 +1180,8 @@ __global__ __launch_bounds__(64 * W) void png_huff_kernel(const uint8_t* __restr
         bad = (cmf & 15) != 8 || (cmf >> 4) > 7 || ((cmf << 8 | flg) % 31) != 0 || (flg & 0x20);
     }
     uint32_t bp = 16, outpos = 0, tpos = 0;
-    bool last = false;
+    bool last = false, lone = false;
+    constexpr uint32_t kHbadLone = 13;                  // not damage: the host's decoder decides (P5)
 #ifdef PNG_PROF
     unsigned long long _acc[16] = {0};
 #endif
@@ -1184,7 +1194,7 @@ __global__ __launch_bounds__(64 * W) void png_huff_kernel(const uint8_t* __restr
             uint32_t hbad = 0, stored_byte = 0, stored_len = 0;
             const uint32_t is_last = peek_u(L.stage, rel, 1), type = peek_u(L.stage, rel + 1, 2);
             rel += 3;
-            int used = 0;
+            int used = 0, ones = 0;
             if (type == 3 || bp + 3 > total_bits) {
                 hbad = 1;
             } else if (type == 0) {
@@ -1201,8 +1211,8 @@ __global__ __launch_bounds__(64 * W) void png_huff_kernel(const uint8_t* __restr
             } else if (type == 1) {
                 for (int s = lane; s < 320; s += 64) L.lens[s] = s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : s < 288 ? 8 : 5;
                 wave_lds_sync();
-                build_table<false>(L.lens, 288, L.lit, L.ll_count, L.ll_sorted, lane, &used);
-                build_table<true>(L.lens + 288, 30, L.dst, L.d_count, L.d_sorted, lane, &used);
+                build_table<false>(L.lens, 288, L.lit, L.ll_count, L.ll_sorted, lane, &used, &ones);
+                build_table<true>(L.lens + 288, 30, L.dst, L.d_count, L.d_sorted, lane, &used, &ones);
             } else {
                 const uint32_t nlen = peek_u(L.stage, rel, 5) + 257, ndist = peek_u(L.stage, rel + 5, 5) + 1,
                                ncode = peek_u(L.stage, rel + 10, 4) + 4;
@@ -1301,11 +1311,13 @@ __global__ __launch_bounds__(64 * W) void png_huff_kernel(const uint8_t* __restr
                     if (lane < 32) L.lens[288 + lane] = (uint8_t)dl;
                     for (int s = nlen + lane; s < 288; s += 64) L.lens[s] = 0;
                     wave_lds_sync();
-                    int r = build_table<false>(L.lens, 288, L.lit, L.ll_count, L.ll_sorted, lane, &used);
+                    int r = build_table<false>(L.lens, 288, L.lit, L.ll_count, L.ll_sorted, lane, &used, &ones);
                     if (r < 0 || (r > 0 && used != 1)) hbad = 11;
+                    const bool lone_ll = r > 0 && ones != 1;      // (a lone code that is not one bit long: see png_inflate_kernel)
                     if (!hbad) {
-                        r = build_table<true>(L.lens + 288, 30, L.dst, L.d_count, L.d_sorted, lane, &used);
+                        r = build_table<true>(L.lens + 288, 30, L.dst, L.d_count, L.d_sorted, lane, &used, &ones);
                         if (r < 0 || (r > 0 && used > 1)) hbad = 12;
+                        else if (lone_ll || (r > 0 && used == 1 && ones != 1)) hbad = kHbadLone;
                     }
                 }
             }
@@ -1325,7 +1337,8 @@ __global__ __launch_bounds__(64 * W) void png_huff_kernel(const uint8_t* __restr
         const uint32_t bp_sym = L.bc[3], st_byte = L.bc[4], st_len = L.bc[5];
         wg_sync();                                   // (bc is rewritten below)
         if (hbad) {
-            bad = true;
+            lone = hbad == kHbadLone;
+            bad = !lone;
             break;
         }
         if (type == 0) {
@@ -1462,13 +1475,14 @@ __global__ __launch_bounds__(64 * W) void png_huff_kernel(const uint8_t* __restr
             PROF_ADD(6);  // round end
         }
     }
-    if (!bad && outpos != raw_n) bad = true;
+    if (!bad && !lone && outpos != raw_n) bad = true;
 #if defined(PNG_PROF) && defined(PNG_PROF_HUFF)      // (the LZ pass reports into the same slots: one of the two per build)
     if (tid == 0)
         for (int i = 0; i < 12; i++) atomicAdd(&g_png_prof[i], _acc[i]);
 #endif
     if (tid == 0) {
         if (bad) info[img].status = UCFP_E_MODALITY;
+        else if (lone) info[img].status = UCFP_IMAGE_NEEDS_HOST;      // (damage in the blocks before it was found above: parse_tok checks every distance)
         tinfo[img].ntok = tpos;
         tinfo[img].end_bit = bp;
     }

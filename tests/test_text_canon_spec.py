@@ -122,3 +122,59 @@ def test_host_only_entry_points_need_no_gpu():
     assert lib.ucfp_text_utab_lookup(ord("A"), None, None, None) == 1        # every out pointer is optional
     assert lib.ucfp_text_utab_lookup(ord("A"), out, C.byref(n), C.byref(fl)) == 1 and (out[0], n.value, fl.value) == (97, 1, 1 | 16 | 32)
     assert lib.ucfp_text_utab_lookup(0xAD, out, C.byref(n), C.byref(fl)) == 1 and n.value == 0     # soft hyphen: Cf, deleted
+
+
+# ---- what tests/test_text_canon_sweep_gpu.py relies on, from the restatement alone ----
+def test_contexts_tell_every_pair_of_table_entries_apart():
+    """The contexts of the every-code-point sweep are not blind: any two (class, alnum, vowel) triples that occur among
+    the table's canonical code points give different tokens in at least one context."""
+    flags = ref.canonical_flags()
+    assert len(flags) >= 16 and {f & 15 for f in flags} == set(range(11))        # every class occurs
+    sig = {f: ref.context_signature(f) for f in flags}
+    same = [(a, b) for i, a in enumerate(flags) for b in flags[i + 1:] if sig[a] == sig[b]]
+    assert not same, same
+    doc = ref.context_document("é")
+    assert doc.count(b"  ") == len(ref.CONTEXTS) - 1 and ref.canon_bytes(doc)[1] == 0
+
+
+def test_expanders_are_found_in_the_table():
+    ex = ref.expanders()
+    assert {0x33AF, 0x2152, 0x00BC, 0x1F110, 0x2026} <= set(ex) and ex[0] == 0x33AF and ref.quiet_expander() == 0x2026
+    made = {cp: (len(chr(cp).encode()), len(ref.lookup(cp)[0])) for cp in ex}
+    assert made[0x33AF] == (3, 6) and made[0x2152] == (3, 4) and made[0xBC] == (2, 3) and made[0x1F110] == (4, 3) and made[0x2026] == (3, 3)
+    for cp in range(0x20000):                  # nothing in the table is denser than the densest of its width
+        r = ref.lookup(cp)
+        if r is not None and cp >= 0x80:
+            w = len(chr(cp).encode("utf-8", "surrogatepass"))
+            assert len(r[0]) <= max(n for c, (ww, n) in made.items() if ww == w), hex(cp)
+    assert not any(ref.lookup(x)[1] & 16 for x in ref.lookup(ref.quiet_expander())[0])
+    # 22 copies of the densest: three rounds of 64 in one step and the lead of the next
+    doc = (chr(ex[0]) * 22).encode()
+    assert len(doc) <= 66 and len(ref.canonical(map(ord, doc.decode()))) >= 129
+    m = ref.decide_map(doc)
+    assert len(m) == 132 and [v[:2] for v in m[:131]] == [(0, i) for i in range(131)] and m[131][:2] == (1, 0)
+    j = ref.joining_expander()
+    assert ref.tokens(chr(j) * 50) == ["".join(map(chr, ref.lookup(j)[0])) * 50]
+
+
+BOUND_BLOCK = 0x4000
+
+
+@pytest.mark.parametrize("b", range(0x20000 // BOUND_BLOCK))
+def test_token_bytes_stay_within_the_workspace_bound(b, capsys):
+    """ucfp_text_canon_bound sizes the workspace the emit pass writes into: every covered code point alone, between each
+    of four separators and eight times over stays within it."""
+    from ucfp_amd import _lib
+    bound = _lib.load().ucfp_text_canon_bound
+    worst = (0.0, "")
+    for cp in range(b * BOUND_BLOCK, (b + 1) * BOUND_BLOCK):
+        if ref.lookup(cp) is None:
+            continue
+        c = chr(cp)
+        for s in [c, c * 8] + [sep + c + sep for sep in (" ", "a", "1", "日")]:
+            src = s.encode("utf-8")
+            out, st = ref.canon_bytes(src)
+            assert st == 0 and len(out) <= bound(len(src)), (hex(cp), s)
+            worst = max(worst, (len(out) / len(src), s))
+    with capsys.disabled():
+        print(f"\ncanon bound, code points {b * BOUND_BLOCK:#x} ..: worst token bytes / source bytes = {worst[0]:.3f} for {worst[1]!r}")

@@ -437,3 +437,16 @@ def test_dedup_corpus_finds_a_one_character_edit(gpu_ctx):
     keep, labels, status = text.dedup_corpus(texts, 0.8, text.TextOpts(tokenizer="grapheme"), ctx=gpu_ctx)
     assert not status.any()
     assert labels[40] == 7 and not keep[40] and keep[:40].all() and list(labels[:40]) == list(range(40))
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_dense_steps(gpu_ctx, kind):
+    """Steps of more than 64 and more than 128 canonical code points (canon_whole's second and third round), at the leads
+    that put a sequence across the step edge: the dense documents of text_canon_ref."""
+    docs = []
+    for cp in canon_ref.expanders():
+        docs += [d for i, d in enumerate(canon_ref.dense_copies(cp)) if i % 64 in (0, 1, 2, 3, 61, 62, 63) and len(d) < 600]
+    docs += canon_ref.dense_mixed(16) + canon_ref.dense_dots()[::12] + canon_ref.dense_open_segments(1)[::401]
+    assert any(len(ref.device_clusters(d, U)) >= 129 and len(d) <= 66 for d in docs)
+    _check(gpu_ctx, kind, docs, U, 5, [0] * len(docs))
+    _check(gpu_ctx, kind, docs, U, 1, [0] * len(docs))

@@ -351,3 +351,27 @@ def test_session_routes(gpu_ctx):
     body = "\r\n".join(json.dumps(p, ensure_ascii=(i == 1)) for i, p in enumerate(parts)).encode("utf-8") + b"\n\n"
     got = T.ingest_stream_ndjson(body, T.TextOpts(), 3, 4)
     assert got.fingerprint == T.fingerprint_minhash_with("".join(parts), T.TextOpts(), 3, 4).fingerprint
+
+
+def test_dense_steps(gpu_ctx):
+    """Steps that make more than 64 and more than 128 canonical code points (text_canon_ref.dense_*: canon_decide's second
+    and third round, with the segment state of a slot carried into them), cut at every position and around the step.
+    The expected records are the PRETOKENIZED hash of the restatement's tokens, not the offline kernel's, which runs the
+    same rounds."""
+    def want(doc, k):
+        toks, st = ref.canon_bytes(doc)
+        assert st == 0
+        return T._run("minhash", [toks], PRETOK, k, gpu_ctx)
+
+    dense, quiet = chr(ref.expanders()[0]).encode(), chr(ref.quiet_expander()).encode()
+    every = [dense * 44, quiet * 22 + b"_" * 70 + b"a"]        # three rounds in a step; a segment kept across two steps
+    assert [max(i for _, i, *_ in ref.decide_map(d)) >= n for d, n in zip(every, (128, 64))] == [True, True]
+    for doc in every:
+        _, want_st = _check_cuts(gpu_ctx, doc, [[c] for c in range(len(doc) + 1)], 2, want=want(doc, 2))
+        assert want_st[0] == 0
+    docs = [chr(cp).encode() * 100 for cp in ref.expanders()] + ref.dense_mixed(12) + ref.dense_dots()[-4:]
+    docs += [d for d in ref.dense_open_segments(1) if len(d) == 3 * 22 + 1 + 70 + 1][:2]
+    docs += [d for d in ref.dense_open_segments(2) if d.startswith(dense * 10 + b"_" * 70)]      # a token's `_` tail fills a round
+    assert len(docs) == 6 + 12 + 4 + 2 + 3
+    for doc in docs:
+        _check_cuts(gpu_ctx, doc, [list(range(sz, len(doc), sz)) for sz in range(61, 69)], want=want(doc, 5))

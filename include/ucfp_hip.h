@@ -653,6 +653,77 @@ int ucfp_text_grapheme_covered(uint32_t cp);
  * doc_tokens[n]] non-decreasing.  UCFP_OK or UCFP_E_INVALID.  text.rs:194-219 (the tokens of one document are a sequence). */
 int ucfp_text_tokens_validate(const uint64_t* tok_offsets, const uint64_t* doc_tokens, size_t n);
 
+/* IDF: text::fingerprint_simhash_idf(text, opts, &IdfTable, ..) (src/modality/text.rs:344-362) with a table
+ * the caller supplies (the reference's own use; dto.rs:489-493 names server-side tables) or fits to a corpus on the GPU.
+ * txtfp's IdfTable and Weighting::IdfWeighted arithmetic are in a crate that is not available: every rule below is this
+ * library's own and "bit-exact" means against tests/simhash_idf_ref.py.
+ *   KEY (T9.1)      XXH3_64(canonical token bytes, seed 0), the value TF SimHash hashes: one table serves every tokeniser
+ *                   and input form.  Every u64 is a legal key, 0 and 2^64 - 1 included.
+ *   WEIGHT (T9.2)   u32 in Q16.16 (0x10000 = 1.0); all sums are 64-bit integers, so a record depends on neither the order of
+ *                   the tokens nor the device.  0 is legal and removes the token (a stop word).
+ *   RECORD (T9.3)   every token occurrence adds w(t) -- the table's weight of its key, else the table's default -- to tot,
+ *                   and to pos_b for every set bit b of its key; bit b of the record is set iff 2 pos_b > tot (a tie clears
+ *                   it).  Equal non-zero weights give the TF record.  Statuses are those of the TF entry over the same
+ *                   input, plus UCFP_E_MODALITY (-1) and a zero record for a document whose tot is 0.
+ *   FIT (T9.4)      a table counts N, the documents added with status 0, and per key df, those of them that hold the key
+ *                   at least once.  finalize gives weight(df) = 0x10000 + L(N + 1) - L(df + 1) and default = weight(0),
+ *                   L = ucfp_idf_log2_q16, an integer log2 in Q16 within (-1, 0] units of 65536 log2(x) (base 2 instead
+ *                   of ln only rescales the IDF term against the + 1).  A document with any other status adds nothing.
+ *   SUPPLIED (T9.5) set_weights REPLACES the table's contents by the given (key, weight) pairs and default and marks it
+ *                   final; N and every df are then 0.  A key given twice: UCFP_E_INVALID and nothing changes.
+ *   LIFECYCLE (T9.6) an add after finalize / set_weights makes the table not final; the weighted SimHash entries give
+ *                   UCFP_E_INVALID for a table that is not final; finalize of an empty table is legal (every token weighs
+ *                   1.0: TF records).  One thread mutates a table at a time; any number may read a final one.  finalize
+ *                   runs on `stream`, waits for it and frees the table's fit scratch: the weights are written when it
+ *                   returns.
+ *   TABLE           open addressing in device memory, at most half full (it grows by rehashing into twice the size or more
+ *                   before the inserts that need the room, behind a synchronisation of the stream: a fit step).
+ *   ADD             the forms, argument checks and statuses of ucfp_text_simhash_batch_ex / _simhash_tokens_batch.  The
+ *                   batch is worked off in pieces of at most piece_tokens slots (0: 2^22; a document owns one slot per byte
+ *                   -- per announced token in the token form -- and a larger document is a piece of its own); the scratch
+ *                   (12 bytes per slot, twice, plus the sort's) belongs to the table.  The _dev forms read d_offsets /
+ *                   d_doc_tokens back to plan the pieces and synchronise `stream` per piece; a decreasing doc_tokens is
+ *                   refused whole (UCFP_E_INVALID), tok_offsets is checked per document on the device as in the TF entry.
+ *                   d_status may be NULL.
+ *   EXPORT          unordered (key, df, weight) triples; weights are meaningful once the table is final.  With cap = 0 and
+ *                   NULL arrays it only reports *n and *default_q16; cap < *n otherwise is UCFP_E_INVALID. */
+typedef struct ucfp_idf_table ucfp_idf_table;
+/* text.rs:344-362 (the IdfTable argument) */
+int ucfp_idf_table_create(ucfp_ctx* ctx, size_t capacity_hint, size_t piece_tokens, uint32_t flags, ucfp_idf_table** out);
+void ucfp_idf_table_destroy(ucfp_idf_table* t);
+/* text.rs:344-362: the corpus side of the table, tokens as ucfp_text_simhash_batch_ex cuts them */
+int ucfp_idf_table_add_batch_dev(ucfp_idf_table* t, const uint8_t* d_utf8, const uint64_t* d_offsets, size_t n, int mode,
+                                 int tokenizer, int32_t* d_status, void* stream);
+int ucfp_idf_table_add_batch(ucfp_idf_table* t, const uint8_t* utf8, const uint64_t* offsets, size_t n, int mode, int tokenizer,
+                             int32_t* status);
+/* text.rs:344-362: the same behind a tokeniser the host ran */
+int ucfp_idf_table_add_tokens_batch_dev(ucfp_idf_table* t, const uint8_t* d_bytes, const uint64_t* d_tok_offsets,
+                                        const uint64_t* d_doc_tokens, size_t n, int32_t* d_status, void* stream);
+int ucfp_idf_table_add_tokens_batch(ucfp_idf_table* t, const uint8_t* bytes, const uint64_t* tok_offsets,
+                                    const uint64_t* doc_tokens, size_t n, int32_t* status);
+/* text.rs:344-362: a caller-made table */
+int ucfp_idf_table_set_weights(ucfp_idf_table* t, const uint64_t* keys, const uint32_t* weights_q16, size_t n,
+                               uint32_t default_q16);
+int ucfp_idf_table_finalize(ucfp_idf_table* t, void* stream);
+int ucfp_idf_table_size(ucfp_idf_table* t, uint64_t* n_docs, size_t* n_keys, int* is_final);
+int ucfp_idf_table_export(ucfp_idf_table* t, uint64_t* keys, uint32_t* dfs, uint32_t* weights_q16, size_t cap, size_t* n,
+                          uint32_t* default_q16);
+/* Host-only (no device, no context): T9.4's L and weight(df), T9.1's key.  text.rs:344-362. */
+uint32_t ucfp_idf_log2_q16(uint64_t x);
+uint32_t ucfp_idf_weight_q16(uint64_t n_docs, uint64_t df);
+uint64_t ucfp_text_token_key(const uint8_t* bytes, size_t len);
+/* text.rs:344-362: the weighted record; forms of ucfp_text_simhash_batch_ex and ucfp_text_simhash_tokens_batch */
+int ucfp_text_simhash_idf_batch_dev(ucfp_ctx* ctx, const ucfp_idf_table* table, const uint8_t* d_utf8, const uint64_t* d_offsets,
+                                    size_t n, int mode, int tokenizer, uint8_t* d_out, int32_t* d_status, void* stream);
+int ucfp_text_simhash_idf_batch(ucfp_ctx* ctx, const ucfp_idf_table* table, const uint8_t* utf8, const uint64_t* offsets, size_t n,
+                                int mode, int tokenizer, uint8_t* out, int32_t* status);
+int ucfp_text_simhash_idf_tokens_batch_dev(ucfp_ctx* ctx, const ucfp_idf_table* table, const uint8_t* d_bytes,
+                                           const uint64_t* d_tok_offsets, const uint64_t* d_doc_tokens, size_t n, uint8_t* d_out,
+                                           int32_t* d_status, void* stream);
+int ucfp_text_simhash_idf_tokens_batch(ucfp_ctx* ctx, const ucfp_idf_table* table, const uint8_t* bytes,
+                                       const uint64_t* tok_offsets, const uint64_t* doc_tokens, size_t n, uint8_t* out,
+                                       int32_t* status);
+
 /* STREAMING MinHash: text::StreamingMinHashSession::new / push / finalize (src/modality/text.rs:645-730)
  * behind POST /v1/ingest/text/{tid}/{rid}/stream (src/server/handlers.rs:590-626), with the state on the device and many
  * streams advanced by one push.  The reference buffers the document and hashes it at the end; here a stream keeps the 128

@@ -17,8 +17,9 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#if defined(__HIPCC__) || defined(__HIP__)
-/* device-only in HIP translation units: the secret lives in constant memory */
+#if (defined(__HIPCC__) || defined(__HIP__)) && !defined(UCFP_XXH3_HOST)
+/* device-only in HIP translation units: the secret lives in constant memory (a host-only translation unit that the HIP
+ * compiler builds defines UCFP_XXH3_HOST first and gets the plain functions) */
 #define UCFP_XXH3_FN __device__ static inline __attribute__((always_inline))
 #define UCFP_XXH3_CONST __constant__ const
 #else

@@ -141,6 +141,30 @@ SIGNATURES = {
                                                  C.c_void_p, C.c_void_p]),
     "ucfp_text_grapheme_covered": (C.c_int, [C.c_uint32]),
     "ucfp_text_tokens_validate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "ucfp_idf_table_create": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "ucfp_idf_table_destroy": (None, [C.c_void_p]),
+    "ucfp_idf_table_add_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p,
+                                               C.c_void_p]),
+    "ucfp_idf_table_add_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p]),
+    "ucfp_idf_table_add_tokens_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                      C.c_void_p]),
+    "ucfp_idf_table_add_tokens_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ucfp_idf_table_set_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32]),
+    "ucfp_idf_table_finalize": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ucfp_idf_table_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
+    "ucfp_idf_table_export": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+                                        C.POINTER(C.c_uint32)]),
+    "ucfp_idf_log2_q16": (C.c_uint32, [C.c_uint64]),
+    "ucfp_idf_weight_q16": (C.c_uint32, [C.c_uint64, C.c_uint64]),
+    "ucfp_text_token_key": (C.c_uint64, [C.c_char_p, C.c_size_t]),
+    "ucfp_text_simhash_idf_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ucfp_text_simhash_idf_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int,
+                                              C.c_void_p, C.c_void_p]),
+    "ucfp_text_simhash_idf_tokens_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ucfp_text_simhash_idf_tokens_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                     C.c_void_p, C.c_void_p]),
     "ucfp_text_streams_create": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
     "ucfp_text_streams_create_ex": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
                                               C.POINTER(C.c_void_p)]),

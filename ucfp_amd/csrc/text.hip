@@ -32,11 +32,12 @@
 
 namespace ucfp {
 
-// MODE_SIM = false: MinHash (out 1032 B/doc); true: SimHash (out 8 B/doc)
-template <bool MODE_SIM>
+// MODE = T_MIN (false): MinHash (out 1032 B/doc); T_SIM (true): SimHash (out 8 B/doc); T_IDF: weighted SimHash against the
+// table in `aux` (out 8 B/doc); T_KEYS: no record, the tokens' keys go to aux.key_out (text_core.h)
+template <int MODE>
 __global__ __launch_bounds__(64 * kWavesPerBlock) void text_hash_kernel(
     const uint8_t* __restrict__ utf8, const uint64_t* __restrict__ offsets, size_t n, int pretok_i, uint32_t k,
-    uint8_t* __restrict__ out, int32_t* __restrict__ status) {
+    uint8_t* __restrict__ out, int32_t* __restrict__ status, TextIdfAux aux) {
     __shared__ WaveLds lds[kWavesPerBlock];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const size_t doc = (size_t)blockIdx.x * kWavesPerBlock + wave;
@@ -49,6 +50,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void text_hash_kernel(
 
     TextWave W;
     bool nonascii = false, too_long = false;
+    if (MODE == T_KEYS) text_keys_doc(aux, offsets[doc], len, doc);
 
     // ---- stream the document, 256 bytes per outer iteration, 64 per step ----
     auto load_chunk = [&](size_t base) -> uint32_t {  // this lane's 4 bytes of [base, base + 256)
@@ -73,7 +75,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void text_hash_kernel(
             const size_t pos = base + 64 * sub + lane;
             if (base + 64 * sub >= len) break;
             if (text_batch_full(W)) {   // make room
-                text_flush<MODE_SIM>(L, W, k, lane, false);
+                text_flush<MODE>(L, W, k, lane, false, &aux);
                 if (text_batch_full(W)) too_long = true;
                 if (too_long) break;
             }
@@ -83,9 +85,9 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void text_hash_kernel(
     }
     // close a token that runs to the end of the document, then the final flush
     if (W.carry && W.ntok > 0 && lane == 0) L.cend[W.ntok - 1] = (uint16_t)(W.cbase + W.ntok - 1);
-    if (!too_long) text_flush<MODE_SIM>(L, W, k, lane, true);
+    if (!too_long) text_flush<MODE>(L, W, k, lane, true, &aux);
     // ---- emit ----
-    const int32_t stv = text_emit<MODE_SIM>(out + doc * (MODE_SIM ? 8 : 1032), W, __ballot(nonascii) != 0, too_long, lane);
+    const int32_t stv = text_emit<MODE>(out + doc * (MODE != T_MIN ? 8 : 1032), W, __ballot(nonascii) != 0, too_long, lane);
     if (status && lane == 0) status[doc] = stv;
 }
 
@@ -93,8 +95,8 @@ int launch_text_minhash(const uint8_t* utf8, const uint64_t* offsets, size_t n, 
                         uint8_t* out, int32_t* status, hipStream_t stream) {
     if (n == 0) return 0;
     const unsigned grid = (unsigned)((n + kWavesPerBlock - 1) / kWavesPerBlock);
-    hipLaunchKernelGGL(text_hash_kernel<false>, dim3(grid), dim3(64 * kWavesPerBlock), 0, stream, utf8, offsets, n,
-                       mode, k, out, status);
+    hipLaunchKernelGGL(text_hash_kernel<T_MIN>, dim3(grid), dim3(64 * kWavesPerBlock), 0, stream, utf8, offsets, n,
+                       mode, k, out, status, TextIdfAux{});
     return 0;
 }
 
@@ -102,8 +104,22 @@ int launch_text_simhash(const uint8_t* utf8, const uint64_t* offsets, size_t n, 
                         int32_t* status, hipStream_t stream) {
     if (n == 0) return 0;
     const unsigned grid = (unsigned)((n + kWavesPerBlock - 1) / kWavesPerBlock);
-    hipLaunchKernelGGL(text_hash_kernel<true>, dim3(grid), dim3(64 * kWavesPerBlock), 0, stream, utf8, offsets, n,
-                       mode, 1u, out, status);
+    hipLaunchKernelGGL(text_hash_kernel<T_SIM>, dim3(grid), dim3(64 * kWavesPerBlock), 0, stream, utf8, offsets, n,
+                       mode, 1u, out, status, TextIdfAux{});
+    return 0;
+}
+
+// the word tokeniser in the two modes of DESIGN.md T9 (text_idf.hip): idf = true the weighted record, false the keys
+int launch_text_idf_words(bool idf, const TextIdfAux& aux, const uint8_t* utf8, const uint64_t* offsets, size_t n, int mode,
+                          uint8_t* out, int32_t* status, hipStream_t stream) {
+    if (n == 0) return 0;
+    const unsigned grid = (unsigned)((n + kWavesPerBlock - 1) / kWavesPerBlock);
+    if (idf)
+        hipLaunchKernelGGL(text_hash_kernel<T_IDF>, dim3(grid), dim3(64 * kWavesPerBlock), 0, stream, utf8, offsets, n, mode, 1u,
+                           out, status, aux);
+    else
+        hipLaunchKernelGGL(text_hash_kernel<T_KEYS>, dim3(grid), dim3(64 * kWavesPerBlock), 0, stream, utf8, offsets, n, mode, 1u,
+                           out, status, aux);
     return 0;
 }
 

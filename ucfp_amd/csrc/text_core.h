@@ -4,7 +4,8 @@
 // wave state (TextWave), the 64-byte tokeniser step (text_step), the flush of a batch (text_flush) and the record and
 // status of a finished document (text_emit).  The canon stage in front of it is text_canon_core.h.  text_marked_kernel
 // (text_grapheme.hip: graphemes, caller-segmented tokens) runs the same flush and record behind text_step_marked, the step
-// whose token starts are a mask.
+// whose token starts are a mask.  Flush and record come in four modes (T_MIN .. T_KEYS below): MinHash, SimHash, and for
+// TF.IDF SimHash (text_idf.hip) the weighted SimHash against a table and the emission of the tokens' keys.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -12,6 +13,7 @@
 #include "../../include/ucfp_hip.h"
 #include "../../include/ucfp_xxh3.h"
 #include "common.h"
+#include "text_idf.h"
 
 namespace ucfp {
 
@@ -89,10 +91,39 @@ __device__ __forceinline__ uint32_t popc_below(uint64_t m, int lane) {  // bits 
 
 __device__ __forceinline__ void wave_sync() { wave_lds_sync(); }
 
+// What a kernel makes of a document's tokens.  T_MIN and T_SIM are the records of T5 and T6 (the values of the former
+// `bool MODE_SIM`, so text_flush<false> / <true> mean what they meant); T_IDF is the weighted SimHash of DESIGN.md T9.3;
+// T_KEYS writes every token's key (T9.1) and the document's ordinal out for the fit of an IDF table (T9.4).
+enum { T_MIN = 0, T_SIM = 1, T_IDF = 2, T_KEYS = 3 };
+
+// the table probe of T_IDF (TextIdfAux, text_idf.h): one lane, one probe sequence
+__device__ __forceinline__ uint32_t idf_lookup(const TextIdfAux& A, uint64_t key) {
+    if (key == 0) return A.tab_wts[(size_t)A.mask + 1];
+    uint32_t i = (uint32_t)((key * kIdfMul) >> A.shift);
+    for (;;) {
+        const uint64_t k = A.tab_keys[i];
+        if (k == key) return A.tab_wts[i];
+        if (k == 0) return A.default_w;
+        i = (i + 1) & A.mask;
+    }
+}
+
+// T_KEYS: where the tokens of this wave's document go -- its slots begin at its byte offset within the piece and there are
+// as many as it has bytes, cut at the end of the piece's arrays whatever the offsets say
+__device__ __forceinline__ void text_keys_doc(TextIdfAux& A, uint64_t byte0, size_t len, size_t doc) {
+    const bool in = byte0 >= A.slot_base && byte0 - A.slot_base <= A.slot_cap;
+    A.slot0 = in ? byte0 - A.slot_base : 0;
+    uint64_t room = in ? A.slot_cap - A.slot0 : 0;
+    room = room < (uint64_t)len ? room : (uint64_t)len;
+    A.doc_cap = (uint32_t)(room < 0x7fffffffull ? room : 0x7fffffffull);
+    A.ord = (uint32_t)doc;
+}
+
 // what one wave carries through a document: between two steps offline, from one push to the next in a stream
 struct TextWave {
     uint64_t m0 = ~0ull, m1 = ~0ull;  // MinHash running minima: slots lane, lane + 64
     uint32_t ones = 0;                // SimHash: count of bit `lane`
+    uint64_t pos = 0, tot = 0;        // T_IDF: weight of the tokens with bit `lane` set, weight of all tokens (Q16.16 sums)
     uint32_t total_tok = 0;           // complete tokens consumed by flushes (net of carried ones)
     bool any_shingle = false;
     // wave-uniform tokenizer state of the current LDS batch
@@ -108,8 +139,10 @@ __device__ __forceinline__ bool text_batch_full(const TextWave& W) {
 }
 
 // consume the batch: hash complete items, fold them in, carry the tail to the front
-template <bool MODE_SIM>
-__device__ __forceinline__ void text_flush(WaveLds& L, TextWave& W, uint32_t k, int lane, bool final) {
+template <int MODE>
+__device__ __forceinline__ void text_flush(WaveLds& L, TextWave& W, uint32_t k, int lane, bool final,
+                                           const TextIdfAux* A = nullptr) {
+    constexpr bool MODE_SIM = MODE != T_MIN;   // the items are single tokens
     wave_sync();
     const uint32_t ncomplete = W.ntok - (W.carry && !final ? 1u : 0u);
     uint32_t nitems, keep_from;
@@ -134,14 +167,28 @@ __device__ __forceinline__ void text_flush(WaveLds& L, TextWave& W, uint32_t k, 
             else e = ncomplete >= k ? s + k - 1 : ncomplete - 1;
             const uint32_t a = L.cstart[s], b = L.cend[e];
             const uint64_t h = xxh3_lds(L.canon + a, (size_t)(b - a));
-            L.h1[s] = h;
-            if (!MODE_SIM) L.h2[s] = mix_h2(h);
+            if (MODE != T_KEYS) L.h1[s] = h;
+            if (MODE == T_MIN) L.h2[s] = mix_h2(h);
+            if (MODE == T_IDF) L.h2[s] = idf_lookup(*A, h);   // one probe sequence per lane: 64 independent gathers
+            if (MODE == T_KEYS) {
+                const uint32_t t = W.total_tok + s;
+                if (t < A->doc_cap) {
+                    A->key_out[A->slot0 + t] = h;
+                    A->ord_out[A->slot0 + t] = A->ord;
+                }
+            }
         }
     }
     wave_sync();
-    if (MODE_SIM) {
+    if (MODE == T_SIM) {
         for (uint32_t s = 0; s < nitems; s++) W.ones += (uint32_t)((L.h1[s] >> lane) & 1ull);
-    } else {
+    } else if (MODE == T_IDF) {
+        for (uint32_t s = 0; s < nitems; s++) {
+            const uint64_t w = L.h2[s];   // < 2^32; at most 2^31 tokens, so neither sum wraps
+            W.pos += ((L.h1[s] >> lane) & 1ull) ? w : 0ull;
+            W.tot += w;
+        }
+    } else if (MODE == T_MIN) {
 #pragma unroll 4
         for (uint32_t s = 0; s < nitems; s++) {
             const uint64_t h = L.h1[s], g = L.h2[s];
@@ -265,14 +312,17 @@ __device__ __forceinline__ void text_step_marked(WaveLds& L, TextWave& W, uint32
 }
 
 // The end of a document: its status, and its record at `rec` (MinHash: 1032 bytes; SimHash: 8), zero unless the status is 0.
-template <bool MODE_SIM>
+template <int MODE>
 __device__ __forceinline__ int32_t text_emit(uint8_t* rec, const TextWave& W, bool nonascii, bool too_long, int lane) {
+    constexpr bool MODE_SIM = MODE != T_MIN;
     int32_t stv = 0;
     if (nonascii) stv = 1;                    // non-ASCII in raw mode: host must pre-tokenise
     else if (too_long) stv = -2;              // UCFP_E_UNSUPPORTED: a token / k-token run exceeds the LDS batch
     else if (W.total_tok == 0 || (!MODE_SIM && !W.any_shingle)) stv = -1;   // UCFP_E_MODALITY: no tokens
+    else if (MODE == T_IDF && W.tot == 0) stv = -1;   // every token weighs 0 (T9.3)
+    if (MODE == T_KEYS) return stv;   // no record: the keys went out in the flushes
     if (MODE_SIM) {
-        const uint64_t bits = __ballot(2u * W.ones > W.total_tok);
+        const uint64_t bits = MODE == T_IDF ? __ballot(2ull * W.pos > W.tot) : __ballot(2u * W.ones > W.total_tok);
         if (lane == 0) {
             const uint64_t v = stv == 0 ? bits : 0ull;
             for (int b = 0; b < 8; b++) rec[b] = (uint8_t)(v >> (8 * b));

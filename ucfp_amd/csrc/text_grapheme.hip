@@ -97,12 +97,12 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void text_gcanon_kernel(
     }
 }
 
-// MODE_SIM = false: MinHash (out 1032 B/doc); true: SimHash (out 8 B/doc).  G_ASCII / G_CANON: document i is
+// MODE = T_MIN (false): MinHash (out 1032 B/doc); T_SIM (true): SimHash (out 8 B/doc); T_IDF / T_KEYS as text_hash_kernel.  G_ASCII / G_CANON: document i is
 // bytes[offsets[i], offsets[i + 1]).  G_TOKENS: `offsets` is doc_tokens, token t is bytes[tok_off[t], tok_off[t + 1]).
-template <bool MODE_SIM, int SRC>
+template <int MODE, int SRC>
 __global__ __launch_bounds__(64 * kWavesPerBlock) void text_marked_kernel(
     const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ offsets, const uint64_t* __restrict__ tok_off, size_t n,
-    uint32_t k, uint8_t* __restrict__ out, int32_t* __restrict__ status) {
+    uint32_t k, uint8_t* __restrict__ out, int32_t* __restrict__ status, TextIdfAux aux) {
     __shared__ WaveLds lds[kWavesPerBlock];
     __shared__ uint8_t marks[SRC == G_TOKENS ? kWavesPerBlock : 1][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -143,6 +143,10 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void text_marked_kernel(
     TextWave W;
     bool nonascii = false, too_long = false;
     uint32_t prev_last = 0;   // the byte before the step's first (CR LF across a step)
+    if (MODE == T_KEYS) {   // slots by bytes; by announced tokens for a token table (empty tokens merge: never more are cut)
+        if (SRC == G_TOKENS) text_keys_doc(aux, tcur, invalid ? 0 : (size_t)(t1 - tcur), doc);
+        else text_keys_doc(aux, b0, len, doc);
+    }
 
     // ---- stream the document, 256 bytes per outer iteration, 64 per step (the reader of text_hash_kernel) ----
     auto load_chunk = [&](size_t base) -> uint32_t {  // this lane's 4 bytes of [base, base + 256)
@@ -166,7 +170,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void text_marked_kernel(
             const size_t pos = base + 64 * sub + lane;
             if (base + 64 * sub >= len) break;
             if (text_batch_full_marked(W)) {   // make room
-                text_flush<MODE_SIM>(L, W, k, lane, false);
+                text_flush<MODE>(L, W, k, lane, false, &aux);
                 if (text_batch_full_marked(W)) too_long = true;
                 if (too_long) break;
             }
@@ -204,9 +208,9 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void text_marked_kernel(
     }
     // close the token that runs to the end of the document, then the final flush
     if (W.carry && W.ntok > 0 && lane == 0) L.cend[W.ntok - 1] = (uint16_t)(W.cbase + W.ntok - 1);
-    if (!too_long) text_flush<MODE_SIM>(L, W, k, lane, true);
+    if (!too_long) text_flush<MODE>(L, W, k, lane, true, &aux);
     // ---- emit ----
-    int32_t stv = text_emit<MODE_SIM>(out + doc * (MODE_SIM ? 8 : 1032), W, __ballot(nonascii) != 0, too_long || invalid, lane);
+    int32_t stv = text_emit<MODE>(out + doc * (MODE != T_MIN ? 8 : 1032), W, __ballot(nonascii) != 0, too_long || invalid, lane);
     if (invalid) stv = UCFP_E_INVALID;
     if (status && lane == 0) status[doc] = stv;
 }
@@ -219,11 +223,24 @@ void launch_marked(bool sim, const uint8_t* bytes, const uint64_t* offsets, cons
     if (n == 0) return;
     const unsigned grid = (unsigned)((n + kWavesPerBlock - 1) / kWavesPerBlock);
     if (sim)
-        hipLaunchKernelGGL((text_marked_kernel<true, SRC>), dim3(grid), dim3(64 * kWavesPerBlock), 0, stream, bytes, offsets, tok_off,
-                           n, 1u, out, status);
+        hipLaunchKernelGGL((text_marked_kernel<T_SIM, SRC>), dim3(grid), dim3(64 * kWavesPerBlock), 0, stream, bytes, offsets, tok_off,
+                           n, 1u, out, status, TextIdfAux{});
     else
-        hipLaunchKernelGGL((text_marked_kernel<false, SRC>), dim3(grid), dim3(64 * kWavesPerBlock), 0, stream, bytes, offsets, tok_off,
-                           n, k, out, status);
+        hipLaunchKernelGGL((text_marked_kernel<T_MIN, SRC>), dim3(grid), dim3(64 * kWavesPerBlock), 0, stream, bytes, offsets, tok_off,
+                           n, k, out, status, TextIdfAux{});
+}
+
+template <int SRC>
+void launch_marked_idf(bool idf, const TextIdfAux& aux, const uint8_t* bytes, const uint64_t* offsets, const uint64_t* tok_off,
+                       size_t n, uint8_t* out, int32_t* status, hipStream_t stream) {
+    if (n == 0) return;
+    const unsigned grid = (unsigned)((n + kWavesPerBlock - 1) / kWavesPerBlock);
+    if (idf)
+        hipLaunchKernelGGL((text_marked_kernel<T_IDF, SRC>), dim3(grid), dim3(64 * kWavesPerBlock), 0, stream, bytes, offsets, tok_off,
+                           n, 1u, out, status, aux);
+    else
+        hipLaunchKernelGGL((text_marked_kernel<T_KEYS, SRC>), dim3(grid), dim3(64 * kWavesPerBlock), 0, stream, bytes, offsets, tok_off,
+                           n, 1u, out, status, aux);
 }
 
 // Mode UCFP_TEXT_RAW_UTF8 of the grapheme calls: the canon pass into the context's scratch (shared with the word route,
@@ -388,6 +405,33 @@ int tokenizer_check(int tokenizer) {
 }
 
 }  // namespace
+
+// the marked kernel in the two modes of DESIGN.md T9 (text_idf.hip): src 0 = ASCII graphemes, 1 = graphemes of a canonical
+// stream, 2 = the caller's token table (`offsets` = doc_tokens); idf = true the weighted record, false the keys
+int launch_text_idf_marked(int src, bool idf, const TextIdfAux& aux, const uint8_t* bytes, const uint64_t* offsets,
+                           const uint64_t* tok_off, size_t n, uint8_t* out, int32_t* status, hipStream_t stream) {
+    if (src == G_ASCII) launch_marked_idf<G_ASCII>(idf, aux, bytes, offsets, tok_off, n, out, status, stream);
+    else if (src == G_CANON) launch_marked_idf<G_CANON>(idf, aux, bytes, offsets, tok_off, n, out, status, stream);
+    else launch_marked_idf<G_TOKENS>(idf, aux, bytes, offsets, tok_off, n, out, status, stream);
+    return 0;
+}
+
+// the grapheme canon pass on its own (count, scan, emit): the whole U3 stream of every document, can_off n + 1 words
+int launch_text_gcanon(ucfp_ctx* ctx, const uint8_t* d_utf8, const uint64_t* d_offsets, size_t n, uint8_t* canon, uint64_t* can_off,
+                       int32_t* cstatus, hipStream_t stream) {
+    if (n == 0) return UCFP_OK;
+    const uint16_t* s1 = nullptr;
+    const uint32_t *s2 = nullptr, *pool = nullptr;
+    const int rc = text_canon_tables(ctx->device, &s1, &s2, &pool);
+    if (rc) return rc;
+    const unsigned grid = (unsigned)((n + kWavesPerBlock - 1) / kWavesPerBlock);
+    hipLaunchKernelGGL(text_gcanon_kernel<false>, dim3(grid), dim3(64 * kWavesPerBlock), 0, stream, d_utf8, d_offsets, n, can_off,
+                       canon, cstatus, s1, s2, pool);
+    launch_text_canon_scan(can_off, n, stream);
+    hipLaunchKernelGGL(text_gcanon_kernel<true>, dim3(grid), dim3(64 * kWavesPerBlock), 0, stream, d_utf8, d_offsets, n, can_off,
+                       canon, cstatus, s1, s2, pool);
+    return UCFP_OK;
+}
 
 }  // namespace ucfp
 

@@ -23,6 +23,10 @@ UAX#29 extended grapheme cluster of the canonical text is a token, found on the 
 set of UTF-8; what the device hands back and every other canonicaliser is cut into clusters here (`regex`, \\X) and
 hashed through the token entries, which `minhash_tokens` / `simhash_tokens` also open to any tokeniser the caller runs
 itself (the reference's cjk-jp / cjk-ko).  Streams and the micro-batcher are built for the `word` tokeniser only.
+
+`IdfTable` is the table `fingerprint_simhash_idf` takes: token key -> Q16.16 weight in device memory,
+supplied (`from_weights`, `load`) or fitted to a corpus on the GPU (`fit`), applied by `simhash_batch(.., idf=)` and
+`simhash_tokens(.., idf=)` through the same routes.  Streams and the micro-batcher take no table.
 """
 import ctypes as C
 import math
@@ -254,8 +258,11 @@ def minhash_tokens(docs: Sequence[Sequence[bytes]], k: int = DEFAULT_K, ctx=None
     return _run_tokens("minhash", docs, k, ctx)
 
 
-def simhash_tokens(docs: Sequence[Sequence[bytes]], ctx=None):
-    """SimHash-64 of caller-tokenised documents (see `minhash_tokens`).  -> (records uint8 [n, 8], status int32 [n])."""
+def simhash_tokens(docs: Sequence[Sequence[bytes]], ctx=None, idf: Optional["IdfTable"] = None):
+    """SimHash-64 of caller-tokenised documents (see `minhash_tokens`).  -> (records uint8 [n, 8], status int32 [n]).
+    With `idf` (a final `IdfTable`) every token weighs what the table says."""
+    if idf is not None:
+        return idf._simhash_tokens(docs, ctx)
     return _run_tokens("simhash", docs, 1, ctx)
 
 
@@ -323,8 +330,242 @@ def minhash_batch(texts: Sequence[str], opts: Optional[TextOpts] = None, ctx=Non
     return _batch("minhash", texts, opts or TextOpts(), ctx)
 
 
-def simhash_batch(texts: Sequence[str], opts: Optional[TextOpts] = None, ctx=None):
+def simhash_batch(texts: Sequence[str], opts: Optional[TextOpts] = None, ctx=None, idf: Optional["IdfTable"] = None):
+    """-> (records uint8 [n, 8], status int32 [n]).  With `idf` (a final `IdfTable`) the TF.IDF record of DESIGN.md T9."""
+    if idf is not None:
+        return idf._simhash(texts, opts or TextOpts(), ctx)
     return _batch("simhash", texts, opts or TextOpts(), ctx)
+
+
+def _route(texts: Sequence[str], opts: TextOpts, run, run_tokens, rec_bytes: int):
+    """The routing of `_batch` / `_batch_grapheme` around other runners (the IDF table's): ASCII documents raw, other
+    documents as UTF-8 under the default canonicaliser, what the device hands back and every other canonicaliser through
+    the host (PRETOKENIZED for `word`, the token form for `grapheme`).  run(docs, mode, tokenizer) and run_tokens(docs)
+    return (records or None, status)."""
+    if opts.tokenizer not in ("word", "grapheme"):
+        raise _unsupported_tokenizer(opts)
+    grapheme = opts.tokenizer == "grapheme"
+    tok = TOK_GRAPHEME if grapheme else TOK_WORD
+    out = np.zeros((len(texts), rec_bytes), np.uint8)
+    status = np.zeros(len(texts), np.int32)
+    c = opts.canonicalizer
+    host = []
+    groups = {RAW_ASCII: [], RAW_UTF8: []}
+    for i, t in enumerate(texts):
+        if t.isascii() and c.case_fold:
+            groups[RAW_ASCII].append(i)
+        elif not t.isascii() and c.is_default():
+            groups[RAW_UTF8].append(i)
+        else:
+            host.append(i)
+
+    def put(idx, o, s):
+        if o is not None:
+            out[idx] = o
+        status[idx] = s
+
+    for mode, idx in groups.items():
+        if idx:
+            o, s = run([texts[i].encode("utf-8", "surrogatepass") for i in idx], mode, tok)
+            put(idx, o, s)
+            host += [i for i, st in zip(idx, s) if st == NEEDS_HOST]
+    if host:
+        host.sort()
+        if grapheme:
+            o, s = run_tokens([[g.encode("utf-8", "surrogatepass") for g in _host_graphemes(c.apply(texts[i]))] for i in host])
+        else:
+            o, s = run([" ".join(_host_tokens(c.apply(texts[i]))).encode("utf-8") for i in host], PRETOKENIZED, TOK_WORD)
+        put(host, o, s)
+    return out, status
+
+
+def _quantize_weight(w) -> int:
+    """a float weight -> Q16.16, floor(w * 65536 + 0.5) in float64."""
+    w = float(w)
+    if not (w >= 0.0) or w >= 65536.0:          # NaN fails the first comparison
+        raise InvalidArgument(f"an IDF weight must be in [0, 65536) (got {w!r})")
+    q = int(math.floor(w * 65536.0 + 0.5))
+    if q > 0xFFFFFFFF:
+        raise InvalidArgument(f"an IDF weight must quantise below 2^32 (got {w!r})")
+    return q
+
+
+class IdfTable:
+    """A device-resident IDF table (ucfp_idf_table_*): token key -> Q16.16 weight, fitted to a corpus on
+    the GPU (`add` / `add_tokens`, then `finalize`; `fit` does both) or supplied (`from_weights`, `load`).  A final table
+    goes to `simhash_batch(.., idf=table)`, `simhash_tokens(.., idf=table)` and `fingerprint_simhash_idf`.  A token's key
+    is XXH3-64 of its canonical bytes, so one table serves every tokeniser and route.  One thread mutates a table at a
+    time; a final one may be read by any number."""
+
+    def __init__(self, opts: Optional[TextOpts] = None, ctx=None, capacity_hint: int = 1 << 16, piece_tokens: int = 0):
+        self.opts = opts or TextOpts()
+        self.ctx = ctx or _lib.current_context()
+        self._lib = _lib.load()
+        h = C.c_void_p()
+        _lib.check(self._lib.ucfp_idf_table_create(self.ctx.handle, int(capacity_hint), int(piece_tokens), 0, C.byref(h)))
+        self.handle = h
+
+    # ---- the corpus side
+    def _add_docs(self, docs: Sequence[bytes], mode: int, tokenizer: int):
+        blob, offs = _pack(docs)
+        status = np.zeros(len(docs), np.int32)
+        _lib.check(self._lib.ucfp_idf_table_add_batch(self.handle, blob.ctypes.data, offs.ctypes.data, len(docs), mode, tokenizer,
+                                                      status.ctypes.data))
+        return None, status
+
+    def _add_tokens(self, docs: Sequence[Sequence[bytes]]):
+        blob, tok_offs, doc_toks = _pack_tokens(docs)
+        status = np.zeros(len(docs), np.int32)
+        _lib.check(self._lib.ucfp_idf_table_add_tokens_batch(self.handle, blob.ctypes.data, tok_offs.ctypes.data,
+                                                             doc_toks.ctypes.data, len(docs), status.ctypes.data))
+        return None, status
+
+    def add(self, texts: Sequence[str]) -> np.ndarray:
+        """Count the documents' tokens (routed as `simhash_batch` routes them: raw ASCII, UTF-8 on the device, the host's
+        tokens for what the device hands back; `cjk-*` has no segmenter here -- pass its tokens to `add_tokens`).
+        -> status int32 [n]; a document whose final status is not 0 adds nothing.  The table is not final afterwards."""
+        return _route(texts, self.opts, self._add_docs, self._add_tokens, 0)[1]
+
+    def add_tokens(self, docs: Sequence[Sequence[bytes]]) -> np.ndarray:
+        return self._add_tokens(docs)[1]
+
+    def finalize(self) -> "IdfTable":
+        """Weights from the counts (T9.4); the call waits for them, so a SimHash call on any stream sees them.  The fit
+        scratch is given back."""
+        _lib.check(self._lib.ucfp_idf_table_finalize(self.handle, None))
+        return self
+
+    def fit(self, texts: Sequence[str]) -> "IdfTable":
+        self.add(texts)
+        return self.finalize()
+
+    # ---- supplied weights
+    def key(self, token) -> int:
+        """T9.1: a `str` is canonicalised with opts.canonicalizer first, `bytes` are keyed as they are, an `int` is a key."""
+        if isinstance(token, (int, np.integer)):
+            k = int(token)
+            if not 0 <= k < 1 << 64:
+                raise InvalidArgument(f"a raw key is a u64 (got {k})")
+            return k
+        if isinstance(token, str):
+            token = self.opts.canonicalizer.apply(token).encode("utf-8", "surrogatepass")
+        b = bytes(token)
+        return int(self._lib.ucfp_text_token_key(b, len(b)))
+
+    def set_weights(self, mapping_or_pairs, default: float = 1.0) -> "IdfTable":
+        pairs = list(mapping_or_pairs.items()) if hasattr(mapping_or_pairs, "items") else list(mapping_or_pairs)
+        keys = np.array([self.key(k) for k, _ in pairs], np.uint64)
+        wts = np.array([_quantize_weight(w) for _, w in pairs], np.uint32)
+        return self._set_q16(keys, wts, _quantize_weight(default))
+
+    def _set_q16(self, keys: np.ndarray, wts: np.ndarray, default_q16: int) -> "IdfTable":
+        keys = np.ascontiguousarray(keys, np.uint64)
+        wts = np.ascontiguousarray(wts, np.uint32)
+        _lib.check(self._lib.ucfp_idf_table_set_weights(self.handle, keys.ctypes.data if keys.size else None,
+                                                        wts.ctypes.data if wts.size else None, keys.size, int(default_q16)))
+        return self
+
+    @classmethod
+    def from_weights(cls, mapping_or_pairs, default: float = 1.0, opts: Optional[TextOpts] = None, ctx=None) -> "IdfTable":
+        pairs = mapping_or_pairs.items() if hasattr(mapping_or_pairs, "items") else mapping_or_pairs
+        pairs = list(pairs)
+        t = cls(opts, ctx, capacity_hint=max(16, len(pairs)))
+        try:
+            return t.set_weights(pairs, default)
+        except Exception:
+            t.close()
+            raise
+
+    # ---- reading
+    def _size(self):
+        nd, nk, fin = C.c_uint64(0), C.c_size_t(0), C.c_int(0)
+        _lib.check(self._lib.ucfp_idf_table_size(self.handle, C.byref(nd), C.byref(nk), C.byref(fin)))
+        return int(nd.value), int(nk.value), bool(fin.value)
+
+    @property
+    def n_docs(self) -> int:
+        return self._size()[0]
+
+    @property
+    def is_final(self) -> bool:
+        return self._size()[2]
+
+    def __len__(self) -> int:
+        return self._size()[1]
+
+    def __bool__(self) -> bool:
+        nd, nk, _ = self._size()
+        return nk > 0 or nd > 0
+
+    def export(self) -> dict:
+        """-> {"keys" u64, "dfs" u32, "weights" u32 (Q16.16), "default" int, "n_docs" int}, sorted by key: what a host
+        persists.  `IdfTable.load` makes a supplied table of it (weights and default; counts are not restored)."""
+        nd, nk, _ = self._size()
+        keys, dfs, wts = np.zeros(nk, np.uint64), np.zeros(nk, np.uint32), np.zeros(nk, np.uint32)
+        n, dq = C.c_size_t(0), C.c_uint32(0)
+        _lib.check(self._lib.ucfp_idf_table_export(self.handle, keys.ctypes.data if nk else None, dfs.ctypes.data if nk else None,
+                                                   wts.ctypes.data if nk else None, nk, C.byref(n), C.byref(dq)))
+        order = np.argsort(keys[:n.value], kind="stable")
+        return {"keys": keys[order], "dfs": dfs[order], "weights": wts[order], "default": int(dq.value), "n_docs": nd}
+
+    @classmethod
+    def load(cls, arrays: dict, opts: Optional[TextOpts] = None, ctx=None) -> "IdfTable":
+        t = cls(opts, ctx, capacity_hint=max(16, len(arrays["keys"])))
+        try:
+            return t._set_q16(np.asarray(arrays["keys"]), np.asarray(arrays["weights"]), int(arrays["default"]))
+        except Exception:
+            t.close()
+            raise
+
+    def weight(self, token) -> float:
+        """The weight a token has in the final table (the default when its key is absent)."""
+        e = self.export()
+        k = np.uint64(self.key(token))
+        i = int(np.searchsorted(e["keys"], k))
+        q = int(e["weights"][i]) if i < e["keys"].size and e["keys"][i] == k else e["default"]
+        return q / 65536.0
+
+    @property
+    def digest(self) -> int:
+        """XXH3-64 over the key-sorted (key, weight) pairs and the default, little-endian: names the table that made a record."""
+        e = self.export()
+        body = b"".join(int(k).to_bytes(8, "little") + int(w).to_bytes(4, "little") for k, w in zip(e["keys"], e["weights"]))
+        body += int(e["default"]).to_bytes(4, "little")
+        return int(self._lib.ucfp_text_token_key(body, len(body)))
+
+    # ---- the record side
+    def _simhash_docs(self, ctx, docs: Sequence[bytes], mode: int, tokenizer: int):
+        blob, offs = _pack(docs)
+        out = np.zeros((len(docs), SIMHASH_BYTES), np.uint8)
+        status = np.zeros(len(docs), np.int32)
+        _lib.check(self._lib.ucfp_text_simhash_idf_batch(ctx.handle, self.handle, blob.ctypes.data, offs.ctypes.data, len(docs), mode,
+                                                         tokenizer, out.ctypes.data, status.ctypes.data))
+        return out, status
+
+    def _simhash_tokens(self, docs: Sequence[Sequence[bytes]], ctx=None):
+        ctx = ctx or self.ctx
+        blob, tok_offs, doc_toks = _pack_tokens(docs)
+        out = np.zeros((len(docs), SIMHASH_BYTES), np.uint8)
+        status = np.zeros(len(docs), np.int32)
+        _lib.check(self._lib.ucfp_text_simhash_idf_tokens_batch(ctx.handle, self.handle, blob.ctypes.data, tok_offs.ctypes.data,
+                                                                doc_toks.ctypes.data, len(docs), out.ctypes.data, status.ctypes.data))
+        return out, status
+
+    def _simhash(self, texts: Sequence[str], opts: TextOpts, ctx=None):
+        ctx = ctx or self.ctx
+        return _route(texts, opts, lambda d, m, t: self._simhash_docs(ctx, d, m, t), lambda d: self._simhash_tokens(d, ctx),
+                      SIMHASH_BYTES)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self._lib.ucfp_idf_table_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class MinHashStreams(StreamSet):
@@ -672,11 +913,20 @@ def fingerprint_simhash_tf(text: str, opts: TextOpts, tenant_id: int, record_id:
 
 def fingerprint_simhash_idf(text: str, opts: TextOpts, idf, tenant_id: int, record_id: int,
                             config_hash_value: Optional[int] = None) -> Record:
-    """The server always passes IdfTable::default() (handlers.rs:410): an empty table weights every
-    token 1.0, i.e. TF weighting; a non-empty table is not supported on the HIP path."""
-    if idf:
-        raise UnsupportedError("non-empty IdfTable is not built into the HIP path")
-    return _simhash(text, opts, ALGORITHM_SIMHASH_IDF, tenant_id, record_id, config_hash_value)
+    """text.rs:344-362.  The server always passes IdfTable::default() (handlers.rs:410): an empty table weights every
+    token 1.0, i.e. TF weighting, and so does a falsy `idf` here.  A final `IdfTable` (fitted on the GPU or supplied)
+    gives the weighted record of DESIGN.md T9 under the same tag; its arithmetic is this library's own (txtfp's is
+    not available), bit-exact against tests/simhash_idf_ref.py.  Any other table object is refused."""
+    if not idf:
+        return _simhash(text, opts, ALGORITHM_SIMHASH_IDF, tenant_id, record_id, config_hash_value)
+    if not isinstance(idf, IdfTable):
+        raise UnsupportedError("only a ucfp_amd.text.IdfTable is built into the HIP path")
+    recs, status = simhash_batch([text], opts, idf=idf)
+    _raise_for(int(status[0]))
+    tok_tag = {"word": "word-uax29", "grapheme": "grapheme-uax29", "cjk-jp": "cjk-jp", "cjk-ko": "cjk-ko"}[opts.tokenizer]
+    return Record(tenant_id=tenant_id, record_id=record_id, modality=Modality.Text, format_version=FORMAT_VERSION,
+                  algorithm=ALGORITHM_SIMHASH_IDF, config_hash=_record_config_hash(opts, tok_tag, ALGORITHM_SIMHASH_IDF, config_hash_value),
+                  fingerprint=recs[0].tobytes(), embedding=None, model_id=None, metadata=b"", text=text)
 
 
 def fingerprint_lsh(text: str, opts: TextOpts, tenant_id: int, record_id: int,

@@ -647,6 +647,33 @@ int ucfp_text_simhash_tokens_batch_dev(ucfp_ctx* ctx, const uint8_t* d_bytes, co
                                        const uint64_t* d_doc_tokens, size_t n, uint8_t* d_out, int32_t* d_status, void* stream);
 int ucfp_text_simhash_tokens_batch(ucfp_ctx* ctx, const uint8_t* bytes, const uint64_t* tok_offsets, const uint64_t* doc_tokens,
                                    size_t n, uint8_t* out, int32_t* status);
+
+/* MINHASH WITH ANY SLOT COUNT.  The reference's entry point is generic over the slot count,
+ * fingerprint_minhash_with::<const H> (src/modality/text.rs:182-236); its manifest offers h from 16 to 1024 in steps of 16
+ * and the presets (k = 3, h = 256) and (k = 7, h = 64) (src/server/algorithms_manifest.rs:280-328).
+ *   h        a multiple of UCFP_MINHASH_H_STEP in [UCFP_MINHASH_H_MIN, UCFP_MINHASH_H_MAX]; anything else UCFP_E_INVALID
+ *   record   UCFP_MINHASH_RECORD_BYTES(h) = 8 + 8 h bytes: u16 LE schema = 1, six zero bytes, h u64 LE slots;
+ *            slot i = min over the document's shingles of h1 + i * h2 mod 2^64 (T5 continued to i < h), so the slots of
+ *            h' < h are the first h' slots of h over the same text
+ *   out      rows 8 + 8 h bytes apart, 4-byte alignment; a document whose status is not 0 gets a zero record
+ * Modes, tokenisers, statuses, shingle_k's range, UCFP_TEXT_MAX_WINDOW_BYTES and the validation order are those of the _ex
+ * and token entries above; h is checked after the tokeniser.  h = 128 writes what those entries write, byte for byte.
+ * COMPATIBILITY as for UCFP_MINHASH_BYTES: layout txtfp's, slot values ours (UCFP_MINHASH_FORMAT_VERSION). */
+#define UCFP_MINHASH_H_MIN 16
+#define UCFP_MINHASH_H_MAX 1024
+#define UCFP_MINHASH_H_STEP 16
+#define UCFP_MINHASH_RECORD_BYTES(h) (8 + 8 * (size_t)(h))
+/* text.rs:182-236 (fingerprint_minhash_with::<H>) behind the tokeniser named by `tokenizer` */
+int ucfp_text_minhash_h_batch_dev(ucfp_ctx* ctx, const uint8_t* d_utf8, const uint64_t* d_offsets, size_t n, int mode, int tokenizer,
+                                  uint32_t shingle_k, uint32_t h, uint8_t* d_out, int32_t* d_status, void* stream);
+int ucfp_text_minhash_h_batch(ucfp_ctx* ctx, const uint8_t* utf8, const uint64_t* offsets, size_t n, int mode, int tokenizer,
+                              uint32_t shingle_k, uint32_t h, uint8_t* out, int32_t* status);
+/* text.rs:182-236 behind a tokeniser the host ran */
+int ucfp_text_minhash_tokens_h_batch_dev(ucfp_ctx* ctx, const uint8_t* d_bytes, const uint64_t* d_tok_offsets,
+                                         const uint64_t* d_doc_tokens, size_t n, uint32_t shingle_k, uint32_t h, uint8_t* d_out,
+                                         int32_t* d_status, void* stream);
+int ucfp_text_minhash_tokens_h_batch(ucfp_ctx* ctx, const uint8_t* bytes, const uint64_t* tok_offsets, const uint64_t* doc_tokens,
+                                     size_t n, uint32_t shingle_k, uint32_t h, uint8_t* out, int32_t* status);
 /* Host-only (no device, no context): 1 iff the grapheme set (G3) covers cp.  text.rs:66-83 (Grapheme). */
 int ucfp_text_grapheme_covered(uint32_t cp);
 /* Host-only: the check the host token entries make of their tables -- doc_tokens[0 .. n] and tok_offsets[doc_tokens[0] ..
@@ -922,6 +949,15 @@ int ucfp_minhash_index_query_dev(ucfp_minhash_index* ix, uint32_t tenant, const 
                                  uint32_t* d_out_n, void* stream);
 /* DESIGN.md A17; host-only (no device needed): agree of two records, 0 .. 128 (a NULL argument gives 0) */
 uint32_t ucfp_minhash_agree(const uint8_t* a, const uint8_t* b);
+/* Records of h slots (the records of text.rs:182-236 at any H).  An index holds records of ONE h, fixed
+ * at creation: rows and queries are UCFP_MINHASH_RECORD_BYTES(h) bytes, agree counts the i < h, min_agree above h is
+ * UCFP_E_INVALID and score = (float)agree / (float)h (one f32 division; at h = 128 the agree / 128.0f above, bit for bit).
+ * ucfp_minhash_index_create is create_h with h = 128; every other ucfp_minhash_index_* call takes either handle. */
+int ucfp_minhash_index_create_h(ucfp_ctx* ctx, uint32_t flags, uint32_t h, ucfp_minhash_index** out);
+/* the h of a handle (0 for NULL) */
+uint32_t ucfp_minhash_index_slots(ucfp_minhash_index* ix);
+/* host-only: agree of two records of h slots, 0 .. h (a NULL argument or an invalid h gives 0); text.rs:182-236 */
+uint32_t ucfp_minhash_agree_h(const uint8_t* a, const uint8_t* b, uint32_t h);
 
 /* ---- image search over whole records: global and block hashes scored together ----
  * The reference threads a compare-time MultiHashConfig through its adapter and its DTO (src/modality/image.rs:90-104,

@@ -139,6 +139,14 @@ SIGNATURES = {
                                                      C.c_void_p, C.c_void_p, C.c_void_p]),
     "ucfp_text_simhash_tokens_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                                  C.c_void_p, C.c_void_p]),
+    "ucfp_text_minhash_h_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_uint32,
+                                                C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ucfp_text_minhash_h_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_uint32,
+                                            C.c_uint32, C.c_void_p, C.c_void_p]),
+    "ucfp_text_minhash_tokens_h_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32,
+                                                       C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ucfp_text_minhash_tokens_h_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32,
+                                                   C.c_uint32, C.c_void_p, C.c_void_p]),
     "ucfp_text_grapheme_covered": (C.c_int, [C.c_uint32]),
     "ucfp_text_tokens_validate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "ucfp_idf_table_create": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32, C.POINTER(C.c_void_p)]),
@@ -211,6 +219,9 @@ SIGNATURES = {
     "ucfp_minhash_index_query_dev": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ucfp_minhash_agree": (C.c_uint32, [C.c_void_p, C.c_void_p]),
+    "ucfp_minhash_agree_h": (C.c_uint32, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    "ucfp_minhash_index_create_h": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "ucfp_minhash_index_slots": (C.c_uint32, [C.c_void_p]),
     "ucfp_image_match_config_default": (None, [C.POINTER(ImageMatchConfig)]),
     "ucfp_image_match_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ImageMatchConfig), C.POINTER(C.c_float)]),
     "ucfp_image_match_index_create": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),

@@ -87,8 +87,8 @@ FORMAT_VERSION = 1  # src/lib.rs:62
 # the bundle, as a list of integers, a hex string or bytes; `algorithm`, when given, must name the tag that goes with the
 # length.  `multi_hash` is the reference's MultiHashConfigDto object (kebab-case keys, dto.rs:462-480) and `min_score` a
 # number; both are optional and are checked when the query runs.
-# MinHash search adds `minhash` (DESIGN A17): the 1032 bytes of a MinHash-128 record as a hex string of 2064 digits, a list
-# of 1032 integers or bytes; `algorithm`, when given, names the tag of the records searched ("minhash-h128" or
+# MinHash search adds `minhash` (DESIGN A17): the bytes of a MinHash record (8 + 8 H; 1032 at the default H = 128) as a hex
+# string, a list of integers or bytes -- its length tells H, and records of that H are searched (DESIGN T10); `algorithm`, when given, names the tag of the records searched ("minhash-h128" or
 # "minhash-lsh-h128").  `min_similarity` in (0, 1] is optional and valid only with `minhash`: hits need that Jaccard estimate.
 # A body the reference accepts parses to the same query here.
 
@@ -110,8 +110,8 @@ class QueryRequest:
     image_record: Optional[bytes] = None   # a whole image record, 168 or 536 bytes (DESIGN A16)
     multi_hash: Optional[dict] = None   # MultiHashConfigDto of an `image_record` query (dto.rs:462-480)
     min_score: Optional[float] = None   # hits of an `image_record` query need at least this score
-    minhash: Optional[bytes] = None     # the 1032 bytes of a MinHash-128 record (DESIGN A17)
-    min_similarity: Optional[float] = None   # hits of a `minhash` query need agree / 128 >= this, in (0, 1]
+    minhash: Optional[bytes] = None     # the 8 + 8 H bytes of a MinHash record (DESIGN A17, T10)
+    min_similarity: Optional[float] = None   # hits of a `minhash` query need agree / H >= this, in (0, 1]
     terms: List[str] = field(default_factory=list)
     explain: bool = False
 
@@ -248,15 +248,15 @@ def _tlsh_bytes(tl) -> bytes:
 
 
 _MINHASH_TAGS = ("minhash-h128", "minhash-lsh-h128")
-_MINHASH_BYTES = 1032
+_MINHASH_SIZES = tuple(8 + 8 * h for h in range(16, 1025, 16))   # a record of H slots, H a multiple of 16 in [16, 1024] (DESIGN T10)
 
 
 def _minhash_bytes(rec) -> bytes:
-    """`minhash` of a query body -> the 1032 record bytes."""
+    """`minhash` of a query body -> the record bytes: 8 + 8 H of them (1032 at the default H = 128)."""
     from .errors import InvalidArgument
     if isinstance(rec, list):
-        if len(rec) != _MINHASH_BYTES or not all(isinstance(x, int) and not isinstance(x, bool) and 0 <= x < 256 for x in rec):
-            raise InvalidArgument("`minhash` as a list must be 1032 integers below 256")
+        if len(rec) not in _MINHASH_SIZES or not all(isinstance(x, int) and not isinstance(x, bool) and 0 <= x < 256 for x in rec):
+            raise InvalidArgument("`minhash` as a list must be 8 + 8 H integers below 256 (1032 at H = 128)")
         return bytes(rec)
     if isinstance(rec, (bytes, bytearray)):
         raw = bytes(rec)
@@ -267,8 +267,9 @@ def _minhash_bytes(rec) -> bytes:
             raise InvalidArgument("`minhash` as a string must be hexadecimal") from None
     else:
         raise InvalidArgument("`minhash` must be a hex string, a list of integers or bytes")
-    if len(raw) != _MINHASH_BYTES:
-        raise InvalidArgument(f"`minhash` must be 1032 bytes (2064 hex digits), not {len(raw)}")
+    if len(raw) not in _MINHASH_SIZES:
+        raise InvalidArgument(f"`minhash` must be 8 + 8 H bytes, H a multiple of 16 in [16, 1024] (1032 bytes, 2064 hex digits, at "
+                              f"H = 128), not {len(raw)}")
     return raw
 
 

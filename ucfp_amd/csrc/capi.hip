@@ -844,14 +844,14 @@ static int text_check(ucfp_ctx* ctx, const void* utf8, const void* offsets, size
 // Mode UCFP_TEXT_RAW_UTF8 of the _dev calls: the scratch is sized by the batch's bytes, which only the device knows --
 // d_offsets[0] and d_offsets[n] are read back behind the work already on `stream` (the one place these calls wait).
 static int text_utf8_dev(ucfp_ctx* ctx, bool sim, const uint8_t* d_utf8, const uint64_t* d_offsets, size_t n, uint32_t k,
-                         uint8_t* d_out, int32_t* d_status, hipStream_t stream) {
+                         uint8_t* d_out, int32_t* d_status, hipStream_t stream, uint32_t h = 128) {
     if (n == 0) return UCFP_OK;
     uint64_t ends[2] = {0, 0};
     HIP_TRY(hipMemcpyAsync(&ends[0], d_offsets, 8, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipMemcpyAsync(&ends[1], d_offsets + n, 8, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     if (ends[1] < ends[0]) return fail(UCFP_E_INVALID, "offsets must be non-decreasing");
-    return ucfp::text_utf8_hash(ctx, sim, d_utf8, d_offsets, n, (size_t)(ends[1] - ends[0]), k, d_out, d_status, stream);
+    return ucfp::text_utf8_hash(ctx, sim, d_utf8, d_offsets, n, (size_t)(ends[1] - ends[0]), k, d_out, d_status, stream, h);
 }
 
 int ucfp_text_minhash_batch_dev(ucfp_ctx* ctx, const uint8_t* d_utf8, const uint64_t* d_offsets, size_t n,
@@ -876,7 +876,7 @@ int ucfp_text_simhash_batch_dev(ucfp_ctx* ctx, const uint8_t* d_utf8, const uint
 }
 
 static int text_host(ucfp_ctx* ctx, bool sim, const uint8_t* utf8, const uint64_t* offsets, size_t n, int mode,
-                     uint32_t k, uint8_t* out, int32_t* status) {
+                     uint32_t k, uint8_t* out, int32_t* status, uint32_t h = 128) {
     int rc = text_check(ctx, utf8, offsets, n, mode, out);
     if (rc) return rc;
     if (n == 0) return UCFP_OK;
@@ -884,7 +884,7 @@ static int text_host(ucfp_ctx* ctx, bool sim, const uint8_t* utf8, const uint64_
     const size_t base = offsets[0], total = offsets[n] - offsets[0];
     for (size_t i = 0; i < n; i++)
         if (offsets[i + 1] < offsets[i]) return fail(UCFP_E_INVALID, "offsets must be non-decreasing");
-    const size_t rec = sim ? UCFP_SIMHASH_BYTES : UCFP_MINHASH_BYTES;
+    const size_t rec = sim ? UCFP_SIMHASH_BYTES : UCFP_MINHASH_RECORD_BYTES(h);
     const size_t o_off = (total + 16 + 255) & ~(size_t)255;
     const size_t in_bytes = o_off + (n + 1) * 8;
     const size_t o_st = (n * rec + 255) & ~(size_t)255;
@@ -903,10 +903,10 @@ static int text_host(ucfp_ctx* ctx, bool sim, const uint8_t* utf8, const uint64_
     const uint64_t* d_off = reinterpret_cast<const uint64_t*>(ctx->stage_in + o_off);
     int32_t* d_st = reinterpret_cast<int32_t*>(ctx->stage_out + o_st);
     if (mode == UCFP_TEXT_RAW_UTF8) {
-        rc = ucfp::text_utf8_hash(ctx, sim, ctx->stage_in, d_off, n, total, k, ctx->stage_out, d_st, st);
+        rc = ucfp::text_utf8_hash(ctx, sim, ctx->stage_in, d_off, n, total, k, ctx->stage_out, d_st, st, h);
         if (rc) return rc;
     } else if (sim) ucfp::launch_text_simhash(ctx->stage_in, d_off, n, mode, ctx->stage_out, d_st, st);
-    else ucfp::launch_text_minhash(ctx->stage_in, d_off, n, mode, k, ctx->stage_out, d_st, st);
+    else ucfp::launch_text_minhash(ctx->stage_in, d_off, n, mode, k, ctx->stage_out, d_st, st, h);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out, ctx->stage_out, n * rec, hipMemcpyDeviceToHost, st));
     if (status) HIP_TRY(hipMemcpyAsync(status, d_st, n * 4, hipMemcpyDeviceToHost, st));
@@ -922,6 +922,33 @@ int ucfp_text_minhash_batch(ucfp_ctx* ctx, const uint8_t* utf8, const uint64_t* 
 int ucfp_text_simhash_batch(ucfp_ctx* ctx, const uint8_t* utf8, const uint64_t* offsets, size_t n, int mode,
                             uint8_t* out, int32_t* status) {
     return text_host(ctx, true, utf8, offsets, n, mode, 1, out, status);
+}
+
+// MinHash with h slots (the reference's fingerprint_minhash_with::<H>, text.rs:182-236): validation in the
+// order of the _ex entries, then the slot count, then what the 128-slot entries check
+int ucfp_text_minhash_h_batch_dev(ucfp_ctx* ctx, const uint8_t* d_utf8, const uint64_t* d_offsets, size_t n, int mode, int tokenizer,
+                                  uint32_t shingle_k, uint32_t h, uint8_t* d_out, int32_t* d_status, void* stream) {
+    if (!ctx) return fail(UCFP_E_INVALID, "ctx is NULL");
+    if (tokenizer != UCFP_TEXT_TOK_WORD && tokenizer != UCFP_TEXT_TOK_GRAPHEME) return fail(UCFP_E_INVALID, "unknown tokenizer %d", tokenizer);
+    if (int rc = ucfp::minhash_h_check(h)) return rc;
+    if (tokenizer == UCFP_TEXT_TOK_GRAPHEME)
+        return ucfp::text_grapheme_minhash_h_dev(ctx, d_utf8, d_offsets, n, mode, shingle_k, h, d_out, d_status, (hipStream_t)stream);
+    int rc = text_check(ctx, d_utf8, d_offsets, n, mode, d_out);
+    if (rc) return rc;
+    if (shingle_k == 0 || shingle_k > 64) return fail(UCFP_E_MODALITY, "shingle k must be in [1, 64] (got %u)", shingle_k);
+    if (mode == UCFP_TEXT_RAW_UTF8) return text_utf8_dev(ctx, false, d_utf8, d_offsets, n, shingle_k, d_out, d_status, (hipStream_t)stream, h);
+    ucfp::launch_text_minhash(d_utf8, d_offsets, n, mode, shingle_k, d_out, d_status, (hipStream_t)stream, h);
+    HIP_TRY(hipGetLastError());
+    return UCFP_OK;
+}
+
+int ucfp_text_minhash_h_batch(ucfp_ctx* ctx, const uint8_t* utf8, const uint64_t* offsets, size_t n, int mode, int tokenizer,
+                              uint32_t shingle_k, uint32_t h, uint8_t* out, int32_t* status) {
+    if (!ctx) return fail(UCFP_E_INVALID, "ctx is NULL");
+    if (tokenizer != UCFP_TEXT_TOK_WORD && tokenizer != UCFP_TEXT_TOK_GRAPHEME) return fail(UCFP_E_INVALID, "unknown tokenizer %d", tokenizer);
+    if (int rc = ucfp::minhash_h_check(h)) return rc;
+    if (tokenizer == UCFP_TEXT_TOK_GRAPHEME) return ucfp::text_grapheme_minhash_h(ctx, utf8, offsets, n, mode, shingle_k, h, out, status);
+    return text_host(ctx, false, utf8, offsets, n, mode, shingle_k, out, status, h);
 }
 
 int ucfp_image_record_codes_dev(ucfp_ctx* ctx, const uint8_t* d_records, size_t n, uint32_t algo, uint32_t which,

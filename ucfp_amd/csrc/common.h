@@ -317,8 +317,22 @@ int launch_cosine_keys_filtered(const float* rows, const float* norms, size_t n,
 int launch_cosine_scores_from_keys(const uint32_t* keys, size_t total, float* scores, hipStream_t stream);
 
 // text.hip
+// MinHash with h slots.  minhash_h_check: UCFP_E_INVALID unless h is a multiple of 16 in [16, 1024].
+// text_minhash_nr: the minima per lane of the kernel that serves h -- ceil(h / 64), rounded up to an instantiated count
+// (1, 2, 3, 4, 6, 8, 12, 16: the presets' 1, 2 and 4 are exact and no h folds more than a third in vain).
+inline int minhash_h_check(uint32_t h) {
+    if (h < UCFP_MINHASH_H_MIN || h > UCFP_MINHASH_H_MAX || h % UCFP_MINHASH_H_STEP != 0)
+        return capi_fail(UCFP_E_INVALID, "MinHash slot count h must be a multiple of %d in [%d, %d] (got %u)", UCFP_MINHASH_H_STEP,
+                         UCFP_MINHASH_H_MIN, UCFP_MINHASH_H_MAX, h);
+    return 0;
+}
+constexpr uint32_t text_minhash_nr(uint32_t h) {
+    const uint32_t r = (h + 63) / 64;
+    return r <= 4 ? r : r <= 6 ? 6 : r <= 8 ? 8 : r <= 12 ? 12 : 16;
+}
+// out: 8 + 8 h bytes per document; h = 128 launches the kernel of the 128-slot entries
 int launch_text_minhash(const uint8_t* utf8, const uint64_t* offsets, size_t n, int mode, uint32_t k,
-                        uint8_t* out, int32_t* status, hipStream_t stream);
+                        uint8_t* out, int32_t* status, hipStream_t stream, uint32_t h = 128);
 int launch_text_simhash(const uint8_t* utf8, const uint64_t* offsets, size_t n, int mode, uint8_t* out,
                         int32_t* status, hipStream_t stream);
 
@@ -330,7 +344,12 @@ void launch_text_canon_scan(uint64_t* tok_off, size_t n, hipStream_t stream);   
 void launch_text_canon_merge(const int32_t* cstatus, size_t n, int32_t* status, hipStream_t stream);   // a nonzero cstatus wins
 int text_canon_tables(int device, const uint16_t** stage1, const uint32_t** stage2, const uint32_t** pool);   // device addresses
 int text_utf8_hash(ucfp_ctx* ctx, bool sim, const uint8_t* d_utf8, const uint64_t* d_offsets, size_t n, size_t total_bytes,
-                   uint32_t k, uint8_t* d_out, int32_t* d_status, hipStream_t stream);
+                   uint32_t k, uint8_t* d_out, int32_t* d_status, hipStream_t stream, uint32_t h = 128);
+// text_grapheme.hip: the grapheme tokeniser and the caller's tokens behind the MinHash entries with a slot count (capi.hip)
+int text_grapheme_minhash_h_dev(ucfp_ctx* ctx, const uint8_t* d_utf8, const uint64_t* d_offsets, size_t n, int mode, uint32_t k,
+                                uint32_t h, uint8_t* d_out, int32_t* d_status, hipStream_t stream);
+int text_grapheme_minhash_h(ucfp_ctx* ctx, const uint8_t* utf8, const uint64_t* offsets, size_t n, int mode, uint32_t k, uint32_t h,
+                            uint8_t* out, int32_t* status);
 
 // audio.hip
 struct WangWs {

@@ -1,14 +1,15 @@
-// minhash_index.hip -- GPU index over MinHash-128 records: "the k stored records that agree with this one
-// in the most slots", exact.
+// minhash_index.hip -- GPU index over MinHash records of H slots: "the k stored records that agree
+// with this one in the most slots", exact.  H is fixed when the index is created (128 by ucfp_minhash_index_create).
 //
 // Spec (ours; the quantity is the score numerator of ucfp_lsh_query_dev and the `agree` of ucfp_lsh_dedup_dev, lsh.hip):
-// a row and a query are UCFP_MINHASH_BYTES = 1032 bytes, 8 header bytes (neither compared nor validated, as lsh.hip:44)
-// and 128 u64 LE slots;
-//   agree(q, r) = #{ i < 128 : slot_i(q) == slot_i(r) }      all 64 bits, the same index only
-// hits: agree >= min_agree (0 .. 128), ordered (agree desc, id asc), first k; score = (float)agree / 128.0f, exact.
+// a row and a query are 8 + 8 H bytes (UCFP_MINHASH_BYTES = 1032 at H = 128), 8 header bytes (neither compared nor
+// validated, as lsh.hip:44) and H u64 LE slots;
+//   agree(q, r) = #{ i < H : slot_i(q) == slot_i(r) }      all 64 bits, the same index only
+// hits: agree >= min_agree (0 .. H), ordered (agree desc, id asc), first k; score = (float)agree / (float)H, one division.
 //
-// Layout of a tenant after a (lazy) rebuild: rows in ascending id order, each row its 1024 slot bytes as they are (the
-// header is dropped on the host, so a row starts on a 16-byte boundary); no repack into planes.
+// Layout of a tenant after a (lazy) rebuild: rows in ascending id order, each row its 8 H slot bytes as they are (the
+// header is dropped on the host, so a row starts on a 16-byte boundary), padded with ~0 slots to C = ceil(H / 128) chunks
+// of 128 slots; no repack into planes.  A query's registers hold 0 at the pad positions, so a pad never agrees.
 //
 // Query, in passes whose key matrix stays below 1 GiB:
 //   mh_keys   lanes = slots: a wave reads a row as one 16-byte load per lane (slots 2 lane, 2 lane + 1) and keeps the same
@@ -20,16 +21,21 @@
 //             size of the pass).  Up to 32: two waves read the same rows against 16 queries each, two ways over the rows.
 //             More: the four waves read the same rows against 16 queries each, so a row comes from memory once per 64
 //             queries and the other reads hit the cache.
+//             H slots: the kernel is templated on C as well; a lane loads one 16-byte vector per chunk and the C pairs of
+//             ballots of a (query, row) are summed before the one v_writelane.  The query tile shrinks so that QT C stays
+//             at or under the 16 query-slot pairs a lane holds at C = 1, and fewer rows are in flight (kUnroll rows of C
+//             vectors).  Dispatched (C, QT, WQ), with T = 16, 8, 4, 4, 2, 2, 2, 2 for C = 1 .. 8:
+//               1 query (C, 1, 1); up to min(4, T) (C, min(4, T), 1); up to T (C, T, 1); up to 2 T (C, T, 2); more (C, T, 4).
+//             C = 1 is the dispatch H = 128 has always had; its key is H - agree.
 //   topk.hip  select_topk_u32 + the merge tree, the selector of the cosine search: exact by (key, id)
 // and mh_scores turns the selected keys into agree and score.  One query is bound by the 1024 bytes per row; a large
 // batch by instructions: 3 VALU + 3 SALU per (query, row) against 16 bytes per (query, row) at 64 queries.
-// Not here: a compact filter plane (the low 16 bits of every slot bound agree from above and would prune exactly at a
+// Not here: packing two H = 64 rows into one wave load (an H = 64 row is half pad); a compact filter plane (the low 16 bits of every slot bound agree from above and would prune exactly at a
 // quarter of the bytes), device-resident appends, sharding over GPUs, a search micro-batcher, save / load.
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <array>
 #include <cstdlib>
 #include <map>
 #include <unordered_map>
@@ -39,22 +45,22 @@
 
 namespace {
 
-constexpr uint32_t kRecBytes = UCFP_MINHASH_BYTES;
 constexpr uint32_t kHeaderBytes = 8;
-constexpr uint32_t kSlots = 128;
-constexpr uint32_t kRowBytes = kSlots * 8;        // a stored row: the slots alone
-constexpr uint32_t kRowVec = kRowBytes / 16;      // uint4 per row = lanes per wave
-constexpr uint32_t kTile = 16;                    // queries a wave keeps in registers (the largest QT)
+constexpr uint32_t kChunkSlots = 128;             // slots a wave compares per load: two per lane
+constexpr uint32_t kChunkBytes = kChunkSlots * 8;
+constexpr uint32_t kChunkVec = kChunkBytes / 16;  // uint4 per chunk = lanes per wave
+constexpr uint32_t kTile = 16;                    // query-slot pairs a lane keeps in registers: QT C at the most
 constexpr uint32_t kWaves = kThreads / 64;
 constexpr uint32_t kGroupRows = 64;               // rows whose counts one key register collects, one per lane
 constexpr uint32_t kGroups = 8;                   // groups of a block
 constexpr uint32_t kBlockRows = kGroupRows * kGroups;
-constexpr uint32_t kUnroll = 4;                   // rows in flight per wave
+constexpr uint32_t kUnroll = 4;                   // 16-byte vectors in flight per lane: 4 / C rows, one at the least
 constexpr size_t kKeyBytes = (size_t)1 << 30;     // key matrix of one pass (UCFP_MINHASH_KEY_BYTES at creation overrides it)
 constexpr size_t kMaxRows = (size_t)1 << 31;
 
-// records: 1032 bytes each, only 4-byte alignment guaranteed (lsh.hip:42)
-__device__ __forceinline__ uint64_t load_slot(const uint8_t* rec, uint32_t i) {
+// records: 8 + 8 h bytes each, only 4-byte alignment guaranteed (lsh.hip:42); a slot at or past h reads as 0
+__device__ __forceinline__ uint64_t load_slot(const uint8_t* rec, uint32_t i, uint32_t h) {
+    if (i >= h) return 0;
     const uint32_t* p = reinterpret_cast<const uint32_t*>(rec + kHeaderBytes + 8 * (size_t)i);
     return (uint64_t)p[0] | ((uint64_t)p[1] << 32);
 }
@@ -62,25 +68,31 @@ __device__ __forceinline__ uint64_t load_slot(const uint8_t* rec, uint32_t i) {
 // v_writelane_b32: clang has no builtin for it, so the LLVM intrinsic is bound by name (as hip's own headers bind theirs)
 extern "C" __device__ int mh_writelane(int src, int lane, int old) __asm("llvm.amdgcn.writelane.i32");
 
-// keys[q][row] for the nq queries of a pass.  QT queries per wave; WQ of the block's four waves take different queries
-// (the other 4 / WQ ways split the block's row groups).  Block b: query group b % nqg, rows [b / nqg * kBlockRows, ...).
-template <int QT, int WQ>
+// keys[q][row] for the nq queries of a pass.  Rows of C chunks (h slots, the rest pad); QT queries per wave; WQ of the
+// block's four waves take different queries (the other 4 / WQ ways split the block's row groups).  Block b: query group
+// b % nqg, rows [b / nqg * kBlockRows, ...).
+template <int C, int QT, int WQ>
 __global__ __launch_bounds__(kThreads) void mh_keys(const uint4* __restrict__ rows, size_t n, const uint8_t* __restrict__ q,
-                                                     uint32_t nq, uint32_t nqg, uint32_t min_agree,
+                                                     uint32_t nq, uint32_t nqg, uint32_t min_agree, uint32_t h,
                                                      uint32_t* __restrict__ keys) {
+    constexpr uint32_t U = kUnroll / C ? kUnroll / C : 1;   // rows in flight
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint32_t qg = blockIdx.x % nqg;
     const size_t row_base = (size_t)(blockIdx.x / nqg) * kBlockRows;
     const uint32_t q0 = (qg * WQ + wave % WQ) * QT;
     if (q0 >= nq) return;   // wave-uniform
-    uint64_t qa[QT], qb[QT];
+    const size_t rec_bytes = kHeaderBytes + 8 * (size_t)h;
+    uint64_t qa[QT][C], qb[QT][C];
 #pragma unroll
     for (int t = 0; t < QT; t++) {
         const uint32_t qi = q0 + t < nq ? q0 + t : nq - 1;   // a short tile repeats the last query; it is not stored
-        const uint8_t* rec = q + (size_t)qi * kRecBytes;
-        qa[t] = load_slot(rec, 2 * lane);
-        qb[t] = load_slot(rec, 2 * lane + 1);
+        const uint8_t* rec = q + (size_t)qi * rec_bytes;
+#pragma unroll
+        for (int c = 0; c < C; c++) {
+            qa[t][c] = load_slot(rec, kChunkSlots * c + 2 * lane, h);
+            qb[t][c] = load_slot(rec, kChunkSlots * c + 2 * lane + 1, h);
+        }
     }
     for (uint32_t g = wave / WQ; g < kGroups; g += kWaves / WQ) {
         const size_t r0 = row_base + (size_t)g * kGroupRows;
@@ -89,20 +101,26 @@ __global__ __launch_bounds__(kThreads) void mh_keys(const uint4* __restrict__ ro
 #pragma unroll
         for (int t = 0; t < QT; t++) acc[t] = 0;
 #pragma unroll 1
-        for (uint32_t j = 0; j < kGroupRows; j += kUnroll) {
+        for (uint32_t j = 0; j < kGroupRows; j += U) {
             if (r0 + j >= n) break;
-            uint4 v[kUnroll];
+            uint4 v[U][C];
 #pragma unroll
-            for (uint32_t u = 0; u < kUnroll; u++) {
+            for (uint32_t u = 0; u < U; u++) {
                 const size_t r = r0 + j + u < n ? r0 + j + u : n - 1;   // past the end: a row that exists; its lane is not stored
-                v[u] = rows[r * kRowVec + lane];
+#pragma unroll
+                for (int c = 0; c < C; c++) v[u][c] = rows[(r * C + c) * kChunkVec + lane];
             }
 #pragma unroll
-            for (uint32_t u = 0; u < kUnroll; u++) {
-                const uint64_t ra = (uint64_t)v[u].x | ((uint64_t)v[u].y << 32), rb = (uint64_t)v[u].z | ((uint64_t)v[u].w << 32);
+            for (uint32_t u = 0; u < U; u++) {
 #pragma unroll
                 for (int t = 0; t < QT; t++) {
-                    const uint32_t cnt = (uint32_t)__popcll(__ballot(ra == qa[t])) + (uint32_t)__popcll(__ballot(rb == qb[t]));
+                    uint32_t cnt = 0;
+#pragma unroll
+                    for (int c = 0; c < C; c++) {
+                        const uint64_t ra = (uint64_t)v[u][c].x | ((uint64_t)v[u][c].y << 32);
+                        const uint64_t rb = (uint64_t)v[u][c].z | ((uint64_t)v[u][c].w << 32);
+                        cnt += (uint32_t)__popcll(__ballot(ra == qa[t][c])) + (uint32_t)__popcll(__ballot(rb == qb[t][c]));
+                    }
                     acc[t] = (uint32_t)mh_writelane((int)cnt, (int)(j + u), (int)acc[t]);
                 }
             }
@@ -111,21 +129,21 @@ __global__ __launch_bounds__(kThreads) void mh_keys(const uint4* __restrict__ ro
         if (row < n) {
 #pragma unroll
             for (int t = 0; t < QT; t++)
-                if (q0 + t < nq) keys[(size_t)(q0 + t) * n + row] = acc[t] >= min_agree ? kSlots - acc[t] : kEmpty32;
+                if (q0 + t < nq) keys[(size_t)(q0 + t) * n + row] = acc[t] >= min_agree ? h - acc[t] : kEmpty32;
         }
     }
 }
 
 // the selected keys -> agree (in place) and score
-__global__ void mh_scores(uint32_t* __restrict__ agree, size_t total, float* __restrict__ scores) {
+__global__ void mh_scores(uint32_t* __restrict__ agree, size_t total, uint32_t h, float* __restrict__ scores) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
     const uint32_t key = agree[i];
     if (key == kEmpty32) {
         scores[i] = -1.0f;
     } else {
-        agree[i] = kSlots - key;
-        scores[i] = (float)(kSlots - key) / 128.0f;
+        agree[i] = h - key;
+        scores[i] = (float)(h - key) / (float)h;
     }
 }
 
@@ -141,7 +159,7 @@ __global__ void mh_empty(size_t nq, uint32_t k, uint64_t* __restrict__ out_ids, 
     if (i < nq) out_n[i] = 0;
 }
 
-using Row = std::array<uint8_t, kRowBytes>;
+using Row = std::vector<uint8_t>;   // the 8 h slot bytes of a record
 
 struct Tenant {
     std::map<uint64_t, Row> recs;   // id -> slots; ascending id = row order, so ties by row are ties by id
@@ -155,6 +173,10 @@ inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 }  // namespace
 
 struct ucfp_minhash_index : ucfp::IndexCore {
+    uint32_t h = 128;               // slots of a record
+    uint32_t chunks = 1;            // C = ceil(h / 128): a device row is chunks * 1024 bytes
+    size_t rec_bytes() const { return kHeaderBytes + 8 * (size_t)h; }
+    size_t row_bytes() const { return (size_t)chunks * kChunkBytes; }
     std::unordered_map<uint32_t, Tenant> tenants;
     size_t key_bytes = kKeyBytes;
     DevArr q_in, q_ws, q_out;       // host-pointer queries, the pass workspace, host-pointer answers
@@ -162,22 +184,23 @@ struct ucfp_minhash_index : ucfp::IndexCore {
 
 namespace {
 
-int rebuild(ucfp_minhash_index*, Tenant& T, hipStream_t st) {
+int rebuild(ucfp_minhash_index* ix, Tenant& T, hipStream_t st) {
     const size_t n = T.recs.size();
     if (n >= kMaxRows) return capi_fail(UCFP_E_INVALID, "too many rows in one tenant (%zu)", n);
-    std::vector<uint8_t> h_rows(n * kRowBytes);
+    const size_t row_bytes = ix->row_bytes();
+    std::vector<uint8_t> h_rows(n * row_bytes, 0xff);   // pad slots are ~0
     std::vector<uint64_t> h_ids(n);
     size_t i = 0;
     for (auto& kv : T.recs) {
         h_ids[i] = kv.first;
-        memcpy(h_rows.data() + i * kRowBytes, kv.second.data(), kRowBytes);
+        memcpy(h_rows.data() + i * row_bytes, kv.second.data(), kv.second.size());
         i++;
     }
     int rc;
-    if ((rc = T.ids.ensure(n * 8)) || (rc = T.rows.ensure(n * kRowBytes))) return rc;
+    if ((rc = T.ids.ensure(n * 8)) || (rc = T.rows.ensure(n * row_bytes))) return rc;
     if (n) {
         HIP_TRY(hipMemcpyAsync(T.ids.p, h_ids.data(), n * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(T.rows.p, h_rows.data(), n * kRowBytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(T.rows.p, h_rows.data(), n * row_bytes, hipMemcpyHostToDevice, st));
     }
     HIP_TRY(hipStreamSynchronize(st));   // the host vectors above go out of scope
     T.n = n;
@@ -189,22 +212,38 @@ int do_upsert(ucfp_minhash_index* ix, uint32_t tenant, const uint64_t* ids, cons
     if (!n) return UCFP_OK;
     if (!ids || !records) return capi_fail(UCFP_E_INVALID, "ids/records is NULL");
     Tenant& T = ix->tenants[tenant];
+    const size_t rec_bytes = ix->rec_bytes();
     for (size_t i = 0; i < n; i++) {
-        Row r;
-        memcpy(r.data(), records + i * kRecBytes + kHeaderBytes, kRowBytes);
-        T.recs.insert_or_assign(T.recs.end(), ids[i], r);   // the hint: ascending ids append in constant time
+        const uint8_t* slots = records + i * rec_bytes + kHeaderBytes;
+        T.recs.insert_or_assign(T.recs.end(), ids[i], Row(slots, slots + 8 * (size_t)ix->h));   // the hint: ascending ids append in constant time
     }
     T.dirty = true;
     return UCFP_OK;
 }
 
-template <int QT, int WQ>
-void launch_keys(const Tenant& T, const uint8_t* d_q, uint32_t cnt, uint32_t min_agree, uint32_t* keymat, hipStream_t st) {
+template <int C, int QT, int WQ>
+void launch_keys(const Tenant& T, const uint8_t* d_q, uint32_t cnt, uint32_t min_agree, uint32_t h, uint32_t* keymat,
+                 hipStream_t st) {
     const uint32_t per = QT * WQ;   // queries of a block
     const uint32_t nqg = (cnt + per - 1) / per;
     const size_t blocks = (size_t)nqg * ((T.n + kBlockRows - 1) / kBlockRows);
-    hipLaunchKernelGGL((mh_keys<QT, WQ>), dim3((unsigned)blocks), dim3(kThreads), 0, st, T.rows.as<uint4>(), T.n, d_q, cnt, nqg,
-                       min_agree, keymat);
+    hipLaunchKernelGGL((mh_keys<C, QT, WQ>), dim3((unsigned)blocks), dim3(kThreads), 0, st, T.rows.as<uint4>(), T.n, d_q, cnt, nqg,
+                       min_agree, h, keymat);
+}
+
+// the query tile of C chunks: QT C <= kTile (C = 3 and 5 .. 7 round down to a power of two)
+constexpr uint32_t tile_of(uint32_t c) { return c == 1 ? kTile : c == 2 ? kTile / 2 : c <= 4 ? kTile / 4 : kTile / 8; }
+
+// the arm of a pass of cnt queries (file header)
+template <int C>
+void dispatch_keys(const Tenant& T, const uint8_t* qp, uint32_t cnt, uint32_t min_agree, uint32_t h, uint32_t* keymat,
+                   hipStream_t st) {
+    constexpr int QT = (int)tile_of(C), QS = QT < 4 ? QT : 4;
+    if (cnt == 1) launch_keys<C, 1, 1>(T, qp, cnt, min_agree, h, keymat, st);
+    else if (cnt <= (uint32_t)QS) launch_keys<C, QS, 1>(T, qp, cnt, min_agree, h, keymat, st);
+    else if (cnt <= (uint32_t)QT) launch_keys<C, QT, 1>(T, qp, cnt, min_agree, h, keymat, st);
+    else if (cnt <= 2u * QT) launch_keys<C, QT, 2>(T, qp, cnt, min_agree, h, keymat, st);   // 26 queries fit a pass over 10 M rows
+    else launch_keys<C, QT, kWaves>(T, qp, cnt, min_agree, h, keymat, st);
 }
 
 int query_impl(ucfp_minhash_index* ix, uint32_t tenant, const uint8_t* d_q, size_t nq, uint32_t k, uint32_t min_agree,
@@ -227,7 +266,8 @@ int query_impl(ucfp_minhash_index* ix, uint32_t tenant, const uint8_t* d_q, size
     size_t chunk = std::max<size_t>(1, ix->key_bytes / (4 * n));
     chunk = std::min<size_t>(std::min<size_t>(chunk, 32768), nq);
     // mh_keys numbers its blocks (query group, row block) in one dimension
-    if (((chunk + kTile - 1) / kTile) * ((n + kBlockRows - 1) / kBlockRows) > 0x7fffffffu)
+    const uint32_t h = ix->h, tile = tile_of(ix->chunks);
+    if (((chunk + tile - 1) / tile) * ((n + kBlockRows - 1) / kBlockRows) > 0x7fffffffu)
         return capi_fail(UCFP_E_INVALID, "too many rows for one launch (%zu)", n);
     const ucfp::SelectPlan sp = ucfp::select_plan(n, (uint32_t)chunk);
     const size_t tmp_e = 2 * ucfp::topk_merge_tmp_entries(sp.slices, (uint32_t)chunk, k);   // both tree levels
@@ -249,12 +289,17 @@ int query_impl(ucfp_minhash_index* ix, uint32_t tenant, const uint8_t* d_q, size
     uint32_t* keymat = reinterpret_cast<uint32_t*>(w + o_keys);
     for (size_t q0 = 0; q0 < nq; q0 += chunk) {
         const uint32_t cnt = (uint32_t)std::min(chunk, nq - q0);
-        const uint8_t* qp = d_q + q0 * kRecBytes;
-        if (cnt == 1) launch_keys<1, 1>(T, qp, cnt, min_agree, keymat, st);
-        else if (cnt <= 4) launch_keys<4, 1>(T, qp, cnt, min_agree, keymat, st);
-        else if (cnt <= kTile) launch_keys<kTile, 1>(T, qp, cnt, min_agree, keymat, st);
-        else if (cnt <= 2 * kTile) launch_keys<kTile, 2>(T, qp, cnt, min_agree, keymat, st);   // 26 queries fit a pass over 10 M rows
-        else launch_keys<kTile, kWaves>(T, qp, cnt, min_agree, keymat, st);
+        const uint8_t* qp = d_q + q0 * ix->rec_bytes();
+        switch (ix->chunks) {
+            case 1: dispatch_keys<1>(T, qp, cnt, min_agree, h, keymat, st); break;
+            case 2: dispatch_keys<2>(T, qp, cnt, min_agree, h, keymat, st); break;
+            case 3: dispatch_keys<3>(T, qp, cnt, min_agree, h, keymat, st); break;
+            case 4: dispatch_keys<4>(T, qp, cnt, min_agree, h, keymat, st); break;
+            case 5: dispatch_keys<5>(T, qp, cnt, min_agree, h, keymat, st); break;
+            case 6: dispatch_keys<6>(T, qp, cnt, min_agree, h, keymat, st); break;
+            case 7: dispatch_keys<7>(T, qp, cnt, min_agree, h, keymat, st); break;
+            default: dispatch_keys<8>(T, qp, cnt, min_agree, h, keymat, st); break;
+        }
         HIP_TRY(hipGetLastError());
         ucfp::SelectPlan pl = ucfp::select_plan(n, cnt);
         if (pl.slices > sp.slices) {   // the partial lists were sized for the full pass
@@ -268,7 +313,7 @@ int query_impl(ucfp_minhash_index* ix, uint32_t tenant, const uint8_t* d_q, size
                                          d_ids + q0 * k, d_agree + q0 * k, d_n + q0, st);
         HIP_TRY(hipGetLastError());
     }
-    hipLaunchKernelGGL(mh_scores, dim3((unsigned)((nq * k + 255) / 256)), dim3(256), 0, st, d_agree, nq * k, d_scores);
+    hipLaunchKernelGGL(mh_scores, dim3((unsigned)((nq * k + 255) / 256)), dim3(256), 0, st, d_agree, nq * k, h, d_scores);
     HIP_TRY(hipGetLastError());
     return UCFP_OK;
 }
@@ -277,7 +322,7 @@ int query_args(ucfp_minhash_index* ix, const void* records, size_t nq, uint32_t 
                const void* out_agree, const void* out_scores, const void* out_n) {
     if (!ix) return capi_fail(UCFP_E_INVALID, "index is NULL");
     if (k > UCFP_INDEX_MAX_K) return capi_fail(UCFP_E_INVALID, "k = %u exceeds UCFP_INDEX_MAX_K = %u", k, UCFP_INDEX_MAX_K);
-    if (min_agree > kSlots) return capi_fail(UCFP_E_INVALID, "min_agree = %u exceeds the %u slots of a record", min_agree, kSlots);
+    if (min_agree > ix->h) return capi_fail(UCFP_E_INVALID, "min_agree = %u exceeds the %u slots of a record", min_agree, ix->h);
     if (nq > 0x7fffffffu) return capi_fail(UCFP_E_INVALID, "too many queries");
     if (nq && (!records || !out_n)) return capi_fail(UCFP_E_INVALID, "records/out_n is NULL");
     if (nq && k && (!out_ids || !out_agree || !out_scores)) return capi_fail(UCFP_E_INVALID, "an output buffer is NULL");
@@ -288,22 +333,34 @@ int query_args(ucfp_minhash_index* ix, const void* records, size_t nq, uint32_t 
 
 extern "C" {
 
-uint32_t ucfp_minhash_agree(const uint8_t* a, const uint8_t* b) {
-    if (!a || !b) return 0;
+uint32_t ucfp_minhash_agree_h(const uint8_t* a, const uint8_t* b, uint32_t h) {
+    if (!a || !b || h < UCFP_MINHASH_H_MIN || h > UCFP_MINHASH_H_MAX || h % UCFP_MINHASH_H_STEP != 0) return 0;
     uint32_t agree = 0;
-    for (uint32_t i = 0; i < kSlots; i++) agree += memcmp(a + kHeaderBytes + 8 * i, b + kHeaderBytes + 8 * i, 8) == 0 ? 1u : 0u;
+    for (uint32_t i = 0; i < h; i++) agree += memcmp(a + kHeaderBytes + 8 * i, b + kHeaderBytes + 8 * i, 8) == 0 ? 1u : 0u;
     return agree;
 }
 
-int ucfp_minhash_index_create(ucfp_ctx* ctx, uint32_t flags, ucfp_minhash_index** out) {
+uint32_t ucfp_minhash_agree(const uint8_t* a, const uint8_t* b) { return ucfp_minhash_agree_h(a, b, 128); }
+
+int ucfp_minhash_index_create_h(ucfp_ctx* ctx, uint32_t flags, uint32_t h, ucfp_minhash_index** out) {
     if (!ctx || !out) return capi_fail(UCFP_E_INVALID, "ctx/out is NULL");
     *out = nullptr;
     if (flags != 0) return capi_fail(UCFP_E_INVALID, "no MinHash index flags are defined (got %u)", flags);
+    if (int rc = ucfp::minhash_h_check(h)) return rc;
     const int rc = ucfp::create_index(ctx, "MinHash index", out);
+    if (rc) return rc;
+    (*out)->h = h;
+    (*out)->chunks = (h + kChunkSlots - 1) / kChunkSlots;
     // a smaller key matrix means more passes over the rows: for tuning, and for tests of the pass loop at small sizes
-    if (const char* e = rc ? nullptr : getenv("UCFP_MINHASH_KEY_BYTES")) (*out)->key_bytes = std::max<size_t>(4096, strtoull(e, nullptr, 10));
+    if (const char* e = getenv("UCFP_MINHASH_KEY_BYTES")) (*out)->key_bytes = std::max<size_t>(4096, strtoull(e, nullptr, 10));
     return rc;
 }
+
+int ucfp_minhash_index_create(ucfp_ctx* ctx, uint32_t flags, ucfp_minhash_index** out) {
+    return ucfp_minhash_index_create_h(ctx, flags, 128, out);
+}
+
+uint32_t ucfp_minhash_index_slots(ucfp_minhash_index* ix) { return ix ? ix->h : 0; }
 
 void ucfp_minhash_index_destroy(ucfp_minhash_index* ix) {
     if (!ix) return;
@@ -330,9 +387,10 @@ int ucfp_minhash_index_upsert_dev(ucfp_minhash_index* ix, uint32_t tenant, const
     hipStream_t st = (hipStream_t)stream;
     // the row table lives on the host (mutations are bookkeeping; the device rows are rebuilt at the next query)
     std::vector<uint64_t> ids(n);
-    std::vector<uint8_t> rows(n * kRecBytes);
+    const size_t rec_bytes = ix->rec_bytes();
+    std::vector<uint8_t> rows(n * rec_bytes);
     HIP_TRY(hipMemcpyAsync(ids.data(), d_ids, n * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(rows.data(), d_records, n * kRecBytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(rows.data(), d_records, n * rec_bytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return do_upsert(ix, tenant, ids.data(), rows.data(), n);
 }
@@ -380,10 +438,10 @@ int ucfp_minhash_index_query(ucfp_minhash_index* ix, uint32_t tenant, const uint
     std::lock_guard<std::mutex> lk(ix->mu);
     if ((rc = ix->begin())) return rc;
     hipStream_t st = ix->own;
-    const size_t nk = nq * k;
+    const size_t nk = nq * k, rec_bytes = ix->rec_bytes();
     const size_t o_agree = align256(nk * 8), o_sc = align256(o_agree + nk * 4), o_n = align256(o_sc + nk * 4);
-    if ((rc = ix->q_in.ensure(nq * kRecBytes)) || (rc = ix->q_out.ensure(o_n + nq * 4))) return rc;
-    HIP_TRY(hipMemcpyAsync(ix->q_in.p, records, nq * kRecBytes, hipMemcpyHostToDevice, st));
+    if ((rc = ix->q_in.ensure(nq * rec_bytes)) || (rc = ix->q_out.ensure(o_n + nq * 4))) return rc;
+    HIP_TRY(hipMemcpyAsync(ix->q_in.p, records, nq * rec_bytes, hipMemcpyHostToDevice, st));
     uint8_t* ob = ix->q_out.as<uint8_t>();
     rc = query_impl(ix, tenant, ix->q_in.as<uint8_t>(), nq, k, min_agree, (uint64_t*)ob, (uint32_t*)(ob + o_agree),
                     (float*)(ob + o_sc), (uint32_t*)(ob + o_n), st);

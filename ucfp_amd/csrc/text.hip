@@ -20,6 +20,7 @@
 //      keeps running minima of h1 + i*h2 for its slots i and i + 64 (a wave = all 128 permutations);
 //      SimHash: lane = output bit, each token hash is broadcast and lane b counts bit b.
 //      The last k-1 complete tokens (and an unfinished one) are carried to the front of the batch.
+//      MinHash with H slots: lane = ceil(H / 64) of the H slots, i, i + 64, i + 128, ...
 // ALU-bound: ~16 integer ops per shingle per lane in D; HBM traffic is 4 KiB + 1 KiB per document.
 //
 // A, B (text_step), C, D (text_flush) and the record (text_emit) live in text_core.h, which text_stream_kernel
@@ -33,11 +34,14 @@
 namespace ucfp {
 
 // MODE = T_MIN (false): MinHash (out 1032 B/doc); T_SIM (true): SimHash (out 8 B/doc); T_IDF: weighted SimHash against the
-// table in `aux` (out 8 B/doc); T_KEYS: no record, the tokens' keys go to aux.key_out (text_core.h)
-template <int MODE>
+// table in `aux` (out 8 B/doc); T_KEYS: no record, the tokens' keys go to aux.key_out (text_core.h).  NR = 0: the 128-slot
+// record, `h` unused; NR >= 1 (T_MIN only): h slots, 64 (NR - 1) < h <= 64 NR, out 8 + 8 h B/doc.
+template <int MODE, int NR = 0>
 __global__ __launch_bounds__(64 * kWavesPerBlock) void text_hash_kernel(
     const uint8_t* __restrict__ utf8, const uint64_t* __restrict__ offsets, size_t n, int pretok_i, uint32_t k,
-    uint8_t* __restrict__ out, int32_t* __restrict__ status, TextIdfAux aux) {
+    uint8_t* __restrict__ out, int32_t* __restrict__ status, TextIdfAux aux, uint32_t h) {
+    constexpr int R = NR ? NR : 2;
+    const uint32_t slots = NR ? h : 128u;
     __shared__ WaveLds lds[kWavesPerBlock];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const size_t doc = (size_t)blockIdx.x * kWavesPerBlock + wave;
@@ -49,6 +53,9 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void text_hash_kernel(
     const bool aligned4 = (reinterpret_cast<uintptr_t>(text) & 3u) == 0;
 
     TextWave W;
+    uint64_t mx[text_mx_len(R)];
+#pragma unroll
+    for (int r = 0; r < text_mx_len(R); r++) mx[r] = ~0ull;
     bool nonascii = false, too_long = false;
     if (MODE == T_KEYS) text_keys_doc(aux, offsets[doc], len, doc);
 
@@ -75,7 +82,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void text_hash_kernel(
             const size_t pos = base + 64 * sub + lane;
             if (base + 64 * sub >= len) break;
             if (text_batch_full(W)) {   // make room
-                text_flush<MODE>(L, W, k, lane, false, &aux);
+                text_flush<MODE, R>(L, W, k, lane, false, &aux, mx);
                 if (text_batch_full(W)) too_long = true;
                 if (too_long) break;
             }
@@ -85,18 +92,42 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void text_hash_kernel(
     }
     // close a token that runs to the end of the document, then the final flush
     if (W.carry && W.ntok > 0 && lane == 0) L.cend[W.ntok - 1] = (uint16_t)(W.cbase + W.ntok - 1);
-    if (!too_long) text_flush<MODE>(L, W, k, lane, true, &aux);
+    if (!too_long) text_flush<MODE, R>(L, W, k, lane, true, &aux, mx);
     // ---- emit ----
-    const int32_t stv = text_emit<MODE>(out + doc * (MODE != T_MIN ? 8 : 1032), W, __ballot(nonascii) != 0, too_long, lane);
+    const int32_t stv = text_emit<MODE, R>(out + doc * (MODE != T_MIN ? 8 : 8 + 8 * (size_t)slots), W, __ballot(nonascii) != 0,
+                                           too_long, lane, slots, mx);
     if (status && lane == 0) status[doc] = stv;
 }
 
-int launch_text_minhash(const uint8_t* utf8, const uint64_t* offsets, size_t n, int mode, uint32_t k,
-                        uint8_t* out, int32_t* status, hipStream_t stream) {
-    if (n == 0) return 0;
+namespace {
+template <int NR>
+void launch_minhash_nr(const uint8_t* utf8, const uint64_t* offsets, size_t n, int mode, uint32_t k, uint32_t h, uint8_t* out,
+                       int32_t* status, hipStream_t stream) {
     const unsigned grid = (unsigned)((n + kWavesPerBlock - 1) / kWavesPerBlock);
-    hipLaunchKernelGGL(text_hash_kernel<T_MIN>, dim3(grid), dim3(64 * kWavesPerBlock), 0, stream, utf8, offsets, n,
-                       mode, k, out, status, TextIdfAux{});
+    hipLaunchKernelGGL((text_hash_kernel<T_MIN, NR>), dim3(grid), dim3(64 * kWavesPerBlock), 0, stream, utf8, offsets, n, mode, k,
+                       out, status, TextIdfAux{}, h);
+}
+}  // namespace
+
+// h = 128 is the kernel this call has always launched; any other h (validated by the caller, minhash_h_check) goes to
+// the instantiation of text_minhash_nr(h) minima per lane
+int launch_text_minhash(const uint8_t* utf8, const uint64_t* offsets, size_t n, int mode, uint32_t k,
+                        uint8_t* out, int32_t* status, hipStream_t stream, uint32_t h) {
+    if (n == 0) return 0;
+    if (h == 128) {
+        launch_minhash_nr<0>(utf8, offsets, n, mode, k, h, out, status, stream);
+        return 0;
+    }
+    switch (text_minhash_nr(h)) {
+        case 1: launch_minhash_nr<1>(utf8, offsets, n, mode, k, h, out, status, stream); break;
+        case 2: launch_minhash_nr<2>(utf8, offsets, n, mode, k, h, out, status, stream); break;
+        case 3: launch_minhash_nr<3>(utf8, offsets, n, mode, k, h, out, status, stream); break;
+        case 4: launch_minhash_nr<4>(utf8, offsets, n, mode, k, h, out, status, stream); break;
+        case 6: launch_minhash_nr<6>(utf8, offsets, n, mode, k, h, out, status, stream); break;
+        case 8: launch_minhash_nr<8>(utf8, offsets, n, mode, k, h, out, status, stream); break;
+        case 12: launch_minhash_nr<12>(utf8, offsets, n, mode, k, h, out, status, stream); break;
+        default: launch_minhash_nr<16>(utf8, offsets, n, mode, k, h, out, status, stream); break;
+    }
     return 0;
 }
 
@@ -105,7 +136,7 @@ int launch_text_simhash(const uint8_t* utf8, const uint64_t* offsets, size_t n, 
     if (n == 0) return 0;
     const unsigned grid = (unsigned)((n + kWavesPerBlock - 1) / kWavesPerBlock);
     hipLaunchKernelGGL(text_hash_kernel<T_SIM>, dim3(grid), dim3(64 * kWavesPerBlock), 0, stream, utf8, offsets, n,
-                       mode, 1u, out, status, TextIdfAux{});
+                       mode, 1u, out, status, TextIdfAux{}, 0u);
     return 0;
 }
 
@@ -116,10 +147,10 @@ int launch_text_idf_words(bool idf, const TextIdfAux& aux, const uint8_t* utf8, 
     const unsigned grid = (unsigned)((n + kWavesPerBlock - 1) / kWavesPerBlock);
     if (idf)
         hipLaunchKernelGGL(text_hash_kernel<T_IDF>, dim3(grid), dim3(64 * kWavesPerBlock), 0, stream, utf8, offsets, n, mode, 1u,
-                           out, status, aux);
+                           out, status, aux, 0u);
     else
         hipLaunchKernelGGL(text_hash_kernel<T_KEYS>, dim3(grid), dim3(64 * kWavesPerBlock), 0, stream, utf8, offsets, n, mode, 1u,
-                           out, status, aux);
+                           out, status, aux, 0u);
     return 0;
 }
 

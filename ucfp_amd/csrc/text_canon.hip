@@ -201,10 +201,10 @@ int text_canon_tables(int device, const uint16_t** stage1, const uint32_t** stag
 }
 
 // Mode UCFP_TEXT_RAW_UTF8 of the MinHash / SimHash calls: canon pass into the context's scratch, the hash pass over it
-// PRETOKENIZED, statuses merged.  total_bytes = d_offsets[n] - d_offsets[0].  Everything is enqueued on `stream`; users
+// PRETOKENIZED (MinHash: records of h slots), statuses merged.  total_bytes = d_offsets[n] - d_offsets[0].  Everything is enqueued on `stream`; users
 // of the scratch on other streams are ordered by canon_done, as the users of norm_ws are.
 int text_utf8_hash(ucfp_ctx* ctx, bool sim, const uint8_t* d_utf8, const uint64_t* d_offsets, size_t n, size_t total_bytes,
-                   uint32_t k, uint8_t* d_out, int32_t* d_status, hipStream_t stream) {
+                   uint32_t k, uint8_t* d_out, int32_t* d_status, hipStream_t stream, uint32_t h) {
     if (n == 0) return UCFP_OK;
     const size_t o_st = ((n + 1) * 8 + 255) & ~(size_t)255;
     const size_t o_tok = o_st + ((n * 4 + 255) & ~(size_t)255);
@@ -218,7 +218,7 @@ int text_utf8_hash(ucfp_ctx* ctx, bool sim, const uint8_t* d_utf8, const uint64_
     uint8_t* tokens = ctx->canon_ws + o_tok;
     launch_text_canon(d_utf8, d_offsets, n, tokens, tok_off, cstatus, stream);
     if (sim) launch_text_simhash(tokens, tok_off, n, UCFP_TEXT_PRETOKENIZED, d_out, d_status, stream);
-    else launch_text_minhash(tokens, tok_off, n, UCFP_TEXT_PRETOKENIZED, k, d_out, d_status, stream);
+    else launch_text_minhash(tokens, tok_off, n, UCFP_TEXT_PRETOKENIZED, k, d_out, d_status, stream, h);
     if (d_status)
         hipLaunchKernelGGL(text_canon_merge_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, cstatus, n, d_status);
     HIP_TRY(hipGetLastError());

@@ -138,10 +138,15 @@ __device__ __forceinline__ bool text_batch_full(const TextWave& W) {
     return W.ntok + kStepTok > (uint32_t)kTokCap || W.cbase + W.ntok + kStepRoom > (uint32_t)kCanonCap;
 }
 
+// MinHash with H slots: a lane keeps NR = ceil(H / 64) running minima, slots lane + 64 r.  The first two
+// are TextWave's m0 and m1 (what a stream saves and restores); the others live in an array of the kernel's, `mx`, that
+// only constant indices touch, so it stays in registers.  NR = 1 leaves m1 alone.
+constexpr int text_mx_len(int NR) { return NR > 2 ? NR - 2 : 1; }
+
 // consume the batch: hash complete items, fold them in, carry the tail to the front
-template <int MODE>
+template <int MODE, int NR = 2>
 __device__ __forceinline__ void text_flush(WaveLds& L, TextWave& W, uint32_t k, int lane, bool final,
-                                           const TextIdfAux* A = nullptr) {
+                                           const TextIdfAux* A = nullptr, uint64_t* mx = nullptr) {
     constexpr bool MODE_SIM = MODE != T_MIN;   // the items are single tokens
     wave_sync();
     const uint32_t ncomplete = W.ntok - (W.carry && !final ? 1u : 0u);
@@ -189,13 +194,20 @@ __device__ __forceinline__ void text_flush(WaveLds& L, TextWave& W, uint32_t k, 
             W.tot += w;
         }
     } else if (MODE == T_MIN) {
-#pragma unroll 4
+        constexpr int kUnroll = NR <= 2 ? 4 : NR <= 4 ? 2 : 1;
+#pragma unroll kUnroll
         for (uint32_t s = 0; s < nitems; s++) {
             const uint64_t h = L.h1[s], g = L.h2[s];
             const uint64_t v0 = h + (uint64_t)lane * g;
             const uint64_t v1 = v0 + (g << 6);
             W.m0 = v0 < W.m0 ? v0 : W.m0;
-            W.m1 = v1 < W.m1 ? v1 : W.m1;
+            if (NR >= 2) W.m1 = v1 < W.m1 ? v1 : W.m1;
+            uint64_t v = v1;
+#pragma unroll
+            for (int r = 2; r < NR; r++) {
+                v += g << 6;
+                mx[r - 2] = v < mx[r - 2] ? v : mx[r - 2];
+            }
         }
     }
     if (nitems) W.any_shingle = true;
@@ -311,9 +323,11 @@ __device__ __forceinline__ void text_step_marked(WaveLds& L, TextWave& W, uint32
     W.carry = W.carry || inw != 0;
 }
 
-// The end of a document: its status, and its record at `rec` (MinHash: 1032 bytes; SimHash: 8), zero unless the status is 0.
-template <int MODE>
-__device__ __forceinline__ int32_t text_emit(uint8_t* rec, const TextWave& W, bool nonascii, bool too_long, int lane) {
+// The end of a document: its status, and its record at `rec` (MinHash: 8 + 8 h bytes; SimHash: 8), zero unless the status
+// is 0.  h <= 64 NR; a lane whose slot lane + 64 r is not below h stores nothing.
+template <int MODE, int NR = 2>
+__device__ __forceinline__ int32_t text_emit(uint8_t* rec, const TextWave& W, bool nonascii, bool too_long, int lane,
+                                             uint32_t h = 128, const uint64_t* mx = nullptr) {
     constexpr bool MODE_SIM = MODE != T_MIN;
     int32_t stv = 0;
     if (nonascii) stv = 1;                    // non-ASCII in raw mode: host must pre-tokenise
@@ -328,14 +342,27 @@ __device__ __forceinline__ int32_t text_emit(uint8_t* rec, const TextWave& W, bo
             for (int b = 0; b < 8; b++) rec[b] = (uint8_t)(v >> (8 * b));
         }
     } else {
+        // the records are only 8-byte aligned when the base is: write dwords
         const uint64_t a = stv == 0 ? W.m0 : 0ull, b = stv == 0 ? W.m1 : 0ull;
-        // 1032-byte records are only 8-byte aligned when the base is: write dwords
         uint32_t* o0 = reinterpret_cast<uint32_t*>(rec + 8 + 8 * lane);
         uint32_t* o1 = reinterpret_cast<uint32_t*>(rec + 8 + 8 * (lane + 64));
-        o0[0] = (uint32_t)a;
-        o0[1] = (uint32_t)(a >> 32);
-        o1[0] = (uint32_t)b;
-        o1[1] = (uint32_t)(b >> 32);
+        if ((uint32_t)lane < h) {
+            o0[0] = (uint32_t)a;
+            o0[1] = (uint32_t)(a >> 32);
+        }
+        if (NR >= 2 && (uint32_t)lane + 64u < h) {
+            o1[0] = (uint32_t)b;
+            o1[1] = (uint32_t)(b >> 32);
+        }
+#pragma unroll
+        for (int r = 2; r < NR; r++) {
+            const uint64_t c = stv == 0 ? mx[r - 2] : 0ull;
+            if ((uint32_t)lane + 64u * (uint32_t)r < h) {
+                uint32_t* o = reinterpret_cast<uint32_t*>(rec + 8 + 8 * (lane + 64 * r));
+                o[0] = (uint32_t)c;
+                o[1] = (uint32_t)(c >> 32);
+            }
+        }
         if (lane == 0) {
             uint32_t* o32 = reinterpret_cast<uint32_t*>(rec);
             o32[0] = stv == 0 ? 1u : 0u;  // schema: u16 = 1, pad

@@ -99,10 +99,13 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void text_gcanon_kernel(
 
 // MODE = T_MIN (false): MinHash (out 1032 B/doc); T_SIM (true): SimHash (out 8 B/doc); T_IDF / T_KEYS as text_hash_kernel.  G_ASCII / G_CANON: document i is
 // bytes[offsets[i], offsets[i + 1]).  G_TOKENS: `offsets` is doc_tokens, token t is bytes[tok_off[t], tok_off[t + 1]).
-template <int MODE, int SRC>
+// NR and h as in text_hash_kernel: NR = 0 the 128-slot record, NR >= 1 MinHash with h slots (out 8 + 8 h B/doc).
+template <int MODE, int SRC, int NR = 0>
 __global__ __launch_bounds__(64 * kWavesPerBlock) void text_marked_kernel(
     const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ offsets, const uint64_t* __restrict__ tok_off, size_t n,
-    uint32_t k, uint8_t* __restrict__ out, int32_t* __restrict__ status, TextIdfAux aux) {
+    uint32_t k, uint8_t* __restrict__ out, int32_t* __restrict__ status, TextIdfAux aux, uint32_t h) {
+    constexpr int R = NR ? NR : 2;
+    const uint32_t slots = NR ? h : 128u;
     __shared__ WaveLds lds[kWavesPerBlock];
     __shared__ uint8_t marks[SRC == G_TOKENS ? kWavesPerBlock : 1][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -141,6 +144,9 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void text_marked_kernel(
     const bool aligned4 = (reinterpret_cast<uintptr_t>(text) & 3u) == 0;
 
     TextWave W;
+    uint64_t mx[text_mx_len(R)];
+#pragma unroll
+    for (int r = 0; r < text_mx_len(R); r++) mx[r] = ~0ull;
     bool nonascii = false, too_long = false;
     uint32_t prev_last = 0;   // the byte before the step's first (CR LF across a step)
     if (MODE == T_KEYS) {   // slots by bytes; by announced tokens for a token table (empty tokens merge: never more are cut)
@@ -170,7 +176,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void text_marked_kernel(
             const size_t pos = base + 64 * sub + lane;
             if (base + 64 * sub >= len) break;
             if (text_batch_full_marked(W)) {   // make room
-                text_flush<MODE>(L, W, k, lane, false, &aux);
+                text_flush<MODE, R>(L, W, k, lane, false, &aux, mx);
                 if (text_batch_full_marked(W)) too_long = true;
                 if (too_long) break;
             }
@@ -208,26 +214,49 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void text_marked_kernel(
     }
     // close the token that runs to the end of the document, then the final flush
     if (W.carry && W.ntok > 0 && lane == 0) L.cend[W.ntok - 1] = (uint16_t)(W.cbase + W.ntok - 1);
-    if (!too_long) text_flush<MODE>(L, W, k, lane, true, &aux);
+    if (!too_long) text_flush<MODE, R>(L, W, k, lane, true, &aux, mx);
     // ---- emit ----
-    int32_t stv = text_emit<MODE>(out + doc * (MODE != T_MIN ? 8 : 1032), W, __ballot(nonascii) != 0, too_long || invalid, lane);
+    int32_t stv = text_emit<MODE, R>(out + doc * (MODE != T_MIN ? 8 : 8 + 8 * (size_t)slots), W, __ballot(nonascii) != 0,
+                                     too_long || invalid, lane, slots, mx);
     if (invalid) stv = UCFP_E_INVALID;
     if (status && lane == 0) status[doc] = stv;
 }
 
 namespace {
 
+template <int SRC, int NR>
+void launch_marked_nr(const uint8_t* bytes, const uint64_t* offsets, const uint64_t* tok_off, size_t n, uint32_t k, uint32_t h,
+                      uint8_t* out, int32_t* status, hipStream_t stream) {
+    const unsigned grid = (unsigned)((n + kWavesPerBlock - 1) / kWavesPerBlock);
+    hipLaunchKernelGGL((text_marked_kernel<T_MIN, SRC, NR>), dim3(grid), dim3(64 * kWavesPerBlock), 0, stream, bytes, offsets,
+                       tok_off, n, k, out, status, TextIdfAux{}, h);
+}
+
+// MinHash: h = 128 is the kernel of the 128-slot entries; any other h the instantiation of text_minhash_nr(h) minima per lane
 template <int SRC>
 void launch_marked(bool sim, const uint8_t* bytes, const uint64_t* offsets, const uint64_t* tok_off, size_t n, uint32_t k,
-                   uint8_t* out, int32_t* status, hipStream_t stream) {
+                   uint8_t* out, int32_t* status, hipStream_t stream, uint32_t h = 128) {
     if (n == 0) return;
     const unsigned grid = (unsigned)((n + kWavesPerBlock - 1) / kWavesPerBlock);
-    if (sim)
+    if (sim) {
         hipLaunchKernelGGL((text_marked_kernel<T_SIM, SRC>), dim3(grid), dim3(64 * kWavesPerBlock), 0, stream, bytes, offsets, tok_off,
-                           n, 1u, out, status, TextIdfAux{});
-    else
-        hipLaunchKernelGGL((text_marked_kernel<T_MIN, SRC>), dim3(grid), dim3(64 * kWavesPerBlock), 0, stream, bytes, offsets, tok_off,
-                           n, k, out, status, TextIdfAux{});
+                           n, 1u, out, status, TextIdfAux{}, 0u);
+        return;
+    }
+    if (h == 128) {
+        launch_marked_nr<SRC, 0>(bytes, offsets, tok_off, n, k, h, out, status, stream);
+        return;
+    }
+    switch (text_minhash_nr(h)) {
+        case 1: launch_marked_nr<SRC, 1>(bytes, offsets, tok_off, n, k, h, out, status, stream); break;
+        case 2: launch_marked_nr<SRC, 2>(bytes, offsets, tok_off, n, k, h, out, status, stream); break;
+        case 3: launch_marked_nr<SRC, 3>(bytes, offsets, tok_off, n, k, h, out, status, stream); break;
+        case 4: launch_marked_nr<SRC, 4>(bytes, offsets, tok_off, n, k, h, out, status, stream); break;
+        case 6: launch_marked_nr<SRC, 6>(bytes, offsets, tok_off, n, k, h, out, status, stream); break;
+        case 8: launch_marked_nr<SRC, 8>(bytes, offsets, tok_off, n, k, h, out, status, stream); break;
+        case 12: launch_marked_nr<SRC, 12>(bytes, offsets, tok_off, n, k, h, out, status, stream); break;
+        default: launch_marked_nr<SRC, 16>(bytes, offsets, tok_off, n, k, h, out, status, stream); break;
+    }
 }
 
 template <int SRC>
@@ -237,16 +266,16 @@ void launch_marked_idf(bool idf, const TextIdfAux& aux, const uint8_t* bytes, co
     const unsigned grid = (unsigned)((n + kWavesPerBlock - 1) / kWavesPerBlock);
     if (idf)
         hipLaunchKernelGGL((text_marked_kernel<T_IDF, SRC>), dim3(grid), dim3(64 * kWavesPerBlock), 0, stream, bytes, offsets, tok_off,
-                           n, 1u, out, status, aux);
+                           n, 1u, out, status, aux, 0u);
     else
         hipLaunchKernelGGL((text_marked_kernel<T_KEYS, SRC>), dim3(grid), dim3(64 * kWavesPerBlock), 0, stream, bytes, offsets, tok_off,
-                           n, 1u, out, status, aux);
+                           n, 1u, out, status, aux, 0u);
 }
 
 // Mode UCFP_TEXT_RAW_UTF8 of the grapheme calls: the canon pass into the context's scratch (shared with the word route,
 // ordered by canon_done), the hash pass over the canonical bytes, statuses merged.
 int grapheme_utf8_hash(ucfp_ctx* ctx, bool sim, const uint8_t* d_utf8, const uint64_t* d_offsets, size_t n, size_t total_bytes,
-                       uint32_t k, uint8_t* d_out, int32_t* d_status, hipStream_t stream) {
+                       uint32_t k, uint8_t* d_out, int32_t* d_status, hipStream_t stream, uint32_t h = 128) {
     if (n == 0) return UCFP_OK;
     const uint16_t* s1 = nullptr;
     const uint32_t *s2 = nullptr, *pool = nullptr;
@@ -268,7 +297,7 @@ int grapheme_utf8_hash(ucfp_ctx* ctx, bool sim, const uint8_t* d_utf8, const uin
     launch_text_canon_scan(can_off, n, stream);
     hipLaunchKernelGGL(text_gcanon_kernel<true>, dim3(grid), dim3(64 * kWavesPerBlock), 0, stream, d_utf8, d_offsets, n, can_off,
                        canon, cstatus, s1, s2, pool);
-    launch_marked<G_CANON>(sim, canon, can_off, nullptr, n, k, d_out, d_status, stream);
+    launch_marked<G_CANON>(sim, canon, can_off, nullptr, n, k, d_out, d_status, stream, h);
     if (d_status) launch_text_canon_merge(cstatus, n, d_status, stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ctx->canon_done, stream));
@@ -287,11 +316,11 @@ int grapheme_check(ucfp_ctx* ctx, const void* offsets, size_t n, int mode, uint3
 }
 
 int grapheme_dev(ucfp_ctx* ctx, bool sim, const uint8_t* d_utf8, const uint64_t* d_offsets, size_t n, int mode, uint32_t k,
-                 uint8_t* d_out, int32_t* d_status, hipStream_t stream) {
+                 uint8_t* d_out, int32_t* d_status, hipStream_t stream, uint32_t h = 128) {
     int rc = grapheme_check(ctx, d_offsets, n, mode, k, d_out);
     if (rc || n == 0) return rc;
     if (mode == UCFP_TEXT_RAW_ASCII) {
-        launch_marked<G_ASCII>(sim, d_utf8, d_offsets, nullptr, n, k, d_out, d_status, stream);
+        launch_marked<G_ASCII>(sim, d_utf8, d_offsets, nullptr, n, k, d_out, d_status, stream, h);
         HIP_TRY(hipGetLastError());
         return UCFP_OK;
     }
@@ -301,18 +330,18 @@ int grapheme_dev(ucfp_ctx* ctx, bool sim, const uint8_t* d_utf8, const uint64_t*
     HIP_TRY(hipMemcpyAsync(&ends[1], d_offsets + n, 8, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     if (ends[1] < ends[0]) return capi_fail(UCFP_E_INVALID, "offsets must be non-decreasing");
-    return grapheme_utf8_hash(ctx, sim, d_utf8, d_offsets, n, (size_t)(ends[1] - ends[0]), k, d_out, d_status, stream);
+    return grapheme_utf8_hash(ctx, sim, d_utf8, d_offsets, n, (size_t)(ends[1] - ends[0]), k, d_out, d_status, stream, h);
 }
 
 int grapheme_host(ucfp_ctx* ctx, bool sim, const uint8_t* utf8, const uint64_t* offsets, size_t n, int mode, uint32_t k,
-                  uint8_t* out, int32_t* status) {
+                  uint8_t* out, int32_t* status, uint32_t h = 128) {
     int rc = grapheme_check(ctx, offsets, n, mode, k, out);
     if (rc || n == 0) return rc;
     for (size_t i = 0; i < n; i++)
         if (offsets[i + 1] < offsets[i]) return capi_fail(UCFP_E_INVALID, "offsets must be non-decreasing");
     const size_t base = offsets[0], total = offsets[n] - offsets[0];
     if (total && !utf8) return capi_fail(UCFP_E_INVALID, "utf8 is NULL");
-    const size_t rec = sim ? UCFP_SIMHASH_BYTES : UCFP_MINHASH_BYTES;
+    const size_t rec = sim ? UCFP_SIMHASH_BYTES : UCFP_MINHASH_RECORD_BYTES(h);
     const size_t o_off = (total + 16 + 255) & ~(size_t)255;
     const size_t in_bytes = o_off + (n + 1) * 8;
     const size_t o_st = (n * rec + 255) & ~(size_t)255;
@@ -331,10 +360,10 @@ int grapheme_host(ucfp_ctx* ctx, bool sim, const uint8_t* utf8, const uint64_t* 
     const uint64_t* d_off = reinterpret_cast<const uint64_t*>(ctx->stage_in + o_off);
     int32_t* d_st = reinterpret_cast<int32_t*>(ctx->stage_out + o_st);
     if (mode == UCFP_TEXT_RAW_UTF8) {
-        rc = grapheme_utf8_hash(ctx, sim, ctx->stage_in, d_off, n, total, k, ctx->stage_out, d_st, st);
+        rc = grapheme_utf8_hash(ctx, sim, ctx->stage_in, d_off, n, total, k, ctx->stage_out, d_st, st, h);
         if (rc) return rc;
     } else {
-        launch_marked<G_ASCII>(sim, ctx->stage_in, d_off, nullptr, n, k, ctx->stage_out, d_st, st);
+        launch_marked<G_ASCII>(sim, ctx->stage_in, d_off, nullptr, n, k, ctx->stage_out, d_st, st, h);
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out, ctx->stage_out, n * rec, hipMemcpyDeviceToHost, st));
@@ -352,16 +381,16 @@ int tokens_check(ucfp_ctx* ctx, const void* tok_offsets, const void* doc_tokens,
 }
 
 int tokens_dev(ucfp_ctx* ctx, bool sim, const uint8_t* d_bytes, const uint64_t* d_tok_offsets, const uint64_t* d_doc_tokens,
-               size_t n, uint32_t k, uint8_t* d_out, int32_t* d_status, hipStream_t stream) {
+               size_t n, uint32_t k, uint8_t* d_out, int32_t* d_status, hipStream_t stream, uint32_t h = 128) {
     int rc = tokens_check(ctx, d_tok_offsets, d_doc_tokens, n, k, d_out);
     if (rc || n == 0) return rc;
-    launch_marked<G_TOKENS>(sim, d_bytes, d_doc_tokens, d_tok_offsets, n, k, d_out, d_status, stream);
+    launch_marked<G_TOKENS>(sim, d_bytes, d_doc_tokens, d_tok_offsets, n, k, d_out, d_status, stream, h);
     HIP_TRY(hipGetLastError());
     return UCFP_OK;
 }
 
 int tokens_host(ucfp_ctx* ctx, bool sim, const uint8_t* bytes, const uint64_t* tok_offsets, const uint64_t* doc_tokens, size_t n,
-                uint32_t k, uint8_t* out, int32_t* status) {
+                uint32_t k, uint8_t* out, int32_t* status, uint32_t h = 128) {
     int rc = tokens_check(ctx, tok_offsets, doc_tokens, n, k, out);
     if (rc || n == 0) return rc;
     rc = ucfp_text_tokens_validate(tok_offsets, doc_tokens, n);
@@ -369,7 +398,7 @@ int tokens_host(ucfp_ctx* ctx, bool sim, const uint8_t* bytes, const uint64_t* t
     const uint64_t T0 = doc_tokens[0], nt = doc_tokens[n] - T0;
     const uint64_t base = tok_offsets[T0], total = tok_offsets[T0 + nt] - base;
     if (total && !bytes) return capi_fail(UCFP_E_INVALID, "bytes is NULL");
-    const size_t rec = sim ? UCFP_SIMHASH_BYTES : UCFP_MINHASH_BYTES;
+    const size_t rec = sim ? UCFP_SIMHASH_BYTES : UCFP_MINHASH_RECORD_BYTES(h);
     const size_t o_tok = ((size_t)total + 16 + 255) & ~(size_t)255;
     const size_t o_doc = o_tok + ((((size_t)nt + 1) * 8 + 255) & ~(size_t)255);
     const size_t in_bytes = o_doc + (n + 1) * 8;
@@ -390,7 +419,7 @@ int tokens_host(ucfp_ctx* ctx, bool sim, const uint8_t* bytes, const uint64_t* t
     HIP_TRY(hipMemcpyAsync(ctx->stage_in + o_doc, rel_doc.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
     int32_t* d_st = reinterpret_cast<int32_t*>(ctx->stage_out + o_st);
     launch_marked<G_TOKENS>(sim, ctx->stage_in, reinterpret_cast<const uint64_t*>(ctx->stage_in + o_doc),
-                            reinterpret_cast<const uint64_t*>(ctx->stage_in + o_tok), n, k, ctx->stage_out, d_st, st);
+                            reinterpret_cast<const uint64_t*>(ctx->stage_in + o_tok), n, k, ctx->stage_out, d_st, st, h);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out, ctx->stage_out, n * rec, hipMemcpyDeviceToHost, st));
     if (status) HIP_TRY(hipMemcpyAsync(status, d_st, n * 4, hipMemcpyDeviceToHost, st));
@@ -414,6 +443,16 @@ int launch_text_idf_marked(int src, bool idf, const TextIdfAux& aux, const uint8
     else if (src == G_CANON) launch_marked_idf<G_CANON>(idf, aux, bytes, offsets, tok_off, n, out, status, stream);
     else launch_marked_idf<G_TOKENS>(idf, aux, bytes, offsets, tok_off, n, out, status, stream);
     return 0;
+}
+
+// the grapheme tokeniser behind ucfp_text_minhash_h_batch[_dev] (capi.hip); h was validated there
+int text_grapheme_minhash_h_dev(ucfp_ctx* ctx, const uint8_t* d_utf8, const uint64_t* d_offsets, size_t n, int mode, uint32_t k,
+                                uint32_t h, uint8_t* d_out, int32_t* d_status, hipStream_t stream) {
+    return grapheme_dev(ctx, false, d_utf8, d_offsets, n, mode, k, d_out, d_status, stream, h);
+}
+int text_grapheme_minhash_h(ucfp_ctx* ctx, const uint8_t* utf8, const uint64_t* offsets, size_t n, int mode, uint32_t k, uint32_t h,
+                            uint8_t* out, int32_t* status) {
+    return grapheme_host(ctx, false, utf8, offsets, n, mode, k, out, status, h);
 }
 
 // the grapheme canon pass on its own (count, scan, emit): the whole U3 stream of every document, can_off n + 1 words
@@ -496,6 +535,21 @@ int ucfp_text_minhash_tokens_batch_dev(ucfp_ctx* ctx, const uint8_t* d_bytes, co
 int ucfp_text_minhash_tokens_batch(ucfp_ctx* ctx, const uint8_t* bytes, const uint64_t* tok_offsets, const uint64_t* doc_tokens,
                                    size_t n, uint32_t shingle_k, uint8_t* out, int32_t* status) {
     return ucfp::tokens_host(ctx, false, bytes, tok_offsets, doc_tokens, n, shingle_k, out, status);
+}
+
+int ucfp_text_minhash_tokens_h_batch_dev(ucfp_ctx* ctx, const uint8_t* d_bytes, const uint64_t* d_tok_offsets,
+                                         const uint64_t* d_doc_tokens, size_t n, uint32_t shingle_k, uint32_t h, uint8_t* d_out,
+                                         int32_t* d_status, void* stream) {
+    if (!ctx) return ucfp::capi_fail(UCFP_E_INVALID, "ctx is NULL");
+    if (int rc = ucfp::minhash_h_check(h)) return rc;
+    return ucfp::tokens_dev(ctx, false, d_bytes, d_tok_offsets, d_doc_tokens, n, shingle_k, d_out, d_status, (hipStream_t)stream, h);
+}
+
+int ucfp_text_minhash_tokens_h_batch(ucfp_ctx* ctx, const uint8_t* bytes, const uint64_t* tok_offsets, const uint64_t* doc_tokens,
+                                     size_t n, uint32_t shingle_k, uint32_t h, uint8_t* out, int32_t* status) {
+    if (!ctx) return ucfp::capi_fail(UCFP_E_INVALID, "ctx is NULL");
+    if (int rc = ucfp::minhash_h_check(h)) return rc;
+    return ucfp::tokens_host(ctx, false, bytes, tok_offsets, doc_tokens, n, shingle_k, out, status, h);
 }
 
 int ucfp_text_simhash_tokens_batch_dev(ucfp_ctx* ctx, const uint8_t* d_bytes, const uint64_t* d_tok_offsets,

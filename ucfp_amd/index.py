@@ -16,7 +16,7 @@ path, backed by the GPU-resident shard behind the C ABI (ucfp_index_*).
     GpuIndex.nearest_tlsh(tenant, digest, k)  the `tlsh-128-1` records at the smallest TLSH distance (DESIGN A15; TlshIndex)
     GpuIndex.similar_images(tenant, record, k)  the image records that score highest with global and block hashes
                                       together (DESIGN A16; ImageMatchIndex)
-    GpuIndex.similar_text(tenant, record_or_text, k)  the MinHash-128 records that agree with a record (or a text's
+    GpuIndex.similar_text(tenant, record_or_text, k)  the MinHash records of the same slot count that agree with a record (or a text's
                                       record) in the most slots (DESIGN A17; MinHashIndex)
     GpuIndex.bm25(tenant, terms, k)   IndexBackend::bm25 / bm25_explain :37-50 over Record.text (DESIGN A11; Bm25Index)
     GpuIndex.flush()                  IndexBackend::flush    :63
@@ -37,7 +37,7 @@ from .errors import InvalidArgument, UnsupportedError
 from .image import MultiHashConfig, match_algo
 from .image import _TAG as _IMAGE_TAG
 from .terms import query_terms, tokenize
-from .text import ALGORITHM_LSH, ALGORITHM_MINHASH_128, ALGORITHM_TLSH, MINHASH_BYTES
+from .text import ALGORITHM_LSH, ALGORITHM_MINHASH_128, ALGORITHM_TLSH, DEFAULT_H, MINHASH_BYTES, _check_h, minhash_slots
 
 HAMMING64, COSINE_F32 = 1, 2
 APPEND_ONLY = 1
@@ -565,15 +565,18 @@ def _pack_digests(digests) -> np.ndarray:
 
 
 class MinHashIndex:
-    """Thin RAII wrapper over one ucfp_minhash_index (DESIGN A17): rows and queries are MinHash-128 records (1032 bytes
-    each); a query answers the k rows that agree with it in the most slots, exactly."""
+    """Thin RAII wrapper over one ucfp_minhash_index (DESIGN A17, T10): rows and queries are MinHash records of `h`
+    slots (8 + 8 h bytes each; 1032 at the default 128); a query answers the k rows that agree with it in the most slots,
+    exactly, with score = agree / h."""
 
-    def __init__(self, flags: int = 0, ctx=None):
+    def __init__(self, flags: int = 0, ctx=None, h: int = DEFAULT_H):
         self._lib = _lib.load()
         self.ctx = ctx or _lib.current_context()
-        h = C.c_void_p()
-        _lib.check(self._lib.ucfp_minhash_index_create(self.ctx.handle, flags, C.byref(h)))
-        self.handle = h
+        self.h = _check_h(h)
+        self.rec_bytes = 8 + 8 * self.h
+        handle = C.c_void_p()
+        _lib.check(self._lib.ucfp_minhash_index_create_h(self.ctx.handle, flags, self.h, C.byref(handle)))
+        self.handle = handle
 
     def close(self):
         if getattr(self, "handle", None):
@@ -587,9 +590,9 @@ class MinHashIndex:
             pass
 
     def upsert(self, tenant: int, ids, records) -> None:
-        """ids [n]; records: uint8 [n, 1032], or n records as bytes."""
+        """ids [n]; records: uint8 [n, 8 + 8 h], or n records as bytes."""
         ids = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
-        rows = _pack_minhash(records)
+        rows = _pack_minhash(records, self.rec_bytes)
         if rows.shape[0] != ids.shape[0]:
             raise InvalidArgument("ids and records disagree on the number of rows")
         _lib.check(self._lib.ucfp_minhash_index_upsert(self.handle, tenant, ids.ctypes.data, rows.ctypes.data, ids.shape[0]))
@@ -614,7 +617,9 @@ class MinHashIndex:
     def query(self, tenant: int, records, k: int, min_agree: int = 1):
         """-> (ids [nq,k] u64, agree [nq,k] u32, scores [nq,k] f32, counts [nq] u32); rows that agree in fewer than
         `min_agree` slots are left out (0: every row is a hit)."""
-        q = _pack_minhash(records)
+        if not 0 <= int(min_agree) <= self.h:
+            raise InvalidArgument(f"min_agree must be in [0, {self.h}] (got {min_agree!r})")
+        q = _pack_minhash(records, self.rec_bytes)
         nq = q.shape[0]
         kk = max(int(k), 1)
         ids = np.full((nq, kk), INVALID_ID, np.uint64)
@@ -633,21 +638,21 @@ class MinHashIndex:
                                                           out_n_ptr, stream or None))
 
 
-def _pack_minhash(records) -> np.ndarray:
-    """uint8 [n, 1032], bytes (one record or several back to back) or a list of bytes -> uint8 [n, 1032] (one spare row
-    behind it, so the pointer is never to an empty buffer)."""
+def _pack_minhash(records, rec_bytes: int = MINHASH_BYTES) -> np.ndarray:
+    """uint8 [n, rec_bytes], bytes (one record or several back to back) or a list of bytes -> uint8 [n, rec_bytes] (one
+    spare row behind it, so the pointer is never to an empty buffer)."""
     if isinstance(records, (bytes, bytearray)):
         records = np.frombuffer(bytes(records), np.uint8)
     if isinstance(records, np.ndarray) and records.dtype == np.uint8:
-        if records.size % MINHASH_BYTES:
-            raise InvalidArgument(f"records must be {MINHASH_BYTES} bytes each")
-        rows = records.reshape(-1, MINHASH_BYTES)
+        if records.size % rec_bytes or (records.ndim == 2 and records.shape[1] != rec_bytes):
+            raise InvalidArgument(f"records must be {rec_bytes} bytes each")
+        rows = records.reshape(-1, rec_bytes)
     else:
         records = [bytes(r) for r in records]
-        if any(len(r) != MINHASH_BYTES for r in records):
-            raise InvalidArgument(f"records must be {MINHASH_BYTES} bytes each")
-        rows = np.frombuffer(b"".join(records), np.uint8).reshape(-1, MINHASH_BYTES)
-    buf = np.zeros((rows.shape[0] + 1, MINHASH_BYTES), np.uint8)
+        if any(len(r) != rec_bytes for r in records):
+            raise InvalidArgument(f"records must be {rec_bytes} bytes each")
+        rows = np.frombuffer(b"".join(records), np.uint8).reshape(-1, rec_bytes)
+    buf = np.zeros((rows.shape[0] + 1, rec_bytes), np.uint8)
     buf[:rows.shape[0]] = rows
     return buf[:rows.shape[0]]
 
@@ -898,6 +903,7 @@ class GpuIndex:
         self._tl = None       # TlshIndex of the tlsh-128-1 records (DESIGN A15)
         self._im = {}         # image algorithm tag -> ImageMatchIndex of its whole records (DESIGN A16)
         self._mh = {}         # MinHash algorithm tag -> MinHashIndex of its 1032-byte records (DESIGN A17)
+        self._mh_h = {}       # (tag, H) -> MinHashIndex of the tag's records of H != 128 slots (DESIGN T10): one index per (tag, H)
         self._sidecar = sidecar   # ucfp_amd.store.Sidecar: the stored-table mirror written at upsert
 
     def attach_sidecar(self, sidecar) -> None:
@@ -946,11 +952,20 @@ class GpuIndex:
             ix = self._im[tag] = ImageMatchIndex(_IMAGE_ALGO[tag], 0, self.ctx)
         return ix
 
-    def _minhash(self, tag: str) -> MinHashIndex:
-        ix = self._mh.get(tag)
+    def _minhash(self, tag: str, h: int = DEFAULT_H) -> MinHashIndex:
+        """The MinHash index of (tag, H), made on first use: every H carries the tag `minhash-h128`, so H is part of the key."""
+        table, key = (self._mh, tag) if h == DEFAULT_H else (self._mh_h, (tag, h))
+        ix = table.get(key)
         if ix is None:
-            ix = self._mh[tag] = MinHashIndex(0, self.ctx)
+            ix = table[key] = MinHashIndex(0, self.ctx, h)
         return ix
+
+    def _minhash_get(self, tag: str, h: int) -> Optional[MinHashIndex]:
+        return self._mh.get(tag) if h == DEFAULT_H else self._mh_h.get((tag, h))
+
+    def _minhash_keys(self):
+        """(tag, H) of every MinHash index present."""
+        return [(tag, DEFAULT_H) for tag in self._mh] + list(self._mh_h)
 
     def _bm25(self) -> Bm25Index:
         if self._bm is None:
@@ -963,14 +978,16 @@ class GpuIndex:
                 + ([self._ps] if self._ps is not None else [])
                 + ([self._hx] if self._hx is not None else [])
                 + ([self._bm] if self._bm is not None else [])
-                + ([self._tl] if self._tl is not None else []) + list(self._im.values()) + list(self._mh.values()))
+                + ([self._tl] if self._tl is not None else []) + list(self._im.values()) + list(self._mh.values())
+                + list(self._mh_h.values()))
 
     def upsert(self, records: Sequence[Record]) -> None:
         """Embeddings go to the cosine index of their dimension; image records also feed the
         Hamming spaces `<algorithm>` with their 64-bit global hashes (SURVEY 8f N2 offsets) and, whole, the image match
-        index of their algorithm tag (DESIGN A16); `minhash-h128` and `minhash-lsh-h128` records of 1032 bytes feed the
-        MinHash index of their tag (DESIGN A17: the two tags carry the same bytes and mean different things to the index
-        layer, so they are never searched together);
+        index of their algorithm tag (DESIGN A16); `minhash-h128` and `minhash-lsh-h128` records of 8 + 8 H bytes feed the
+        MinHash index of their tag and slot count H, told by the fingerprint's length (DESIGN A17, T10: the two tags carry
+        the same bytes and mean different things to the index layer, so they are never searched together; records of
+        different H cannot be compared);
         `audiofp-wang-v1` records feed the landmark index with their landmarks, `audiofp-panako-v1` records a second
         landmark index with their (hash, t_anchor) pairs (the two never share postings) and `audiofp-haitsma-v1` records
         the sub-fingerprint index with their frames; every record with `text`, whatever its
@@ -1016,12 +1033,12 @@ class GpuIndex:
             for tag in self._im:
                 if tag != im_tag:
                     stale_im.setdefault((r.tenant_id, tag), []).append(r.record_id)
-            mh_tag = r.algorithm if _feeds_minhash(r) else None
-            if mh_tag is not None:
-                by_mh.setdefault((r.tenant_id, mh_tag), []).append(r)
-            for tag in self._mh:
-                if tag != mh_tag:
-                    stale_mh.setdefault((r.tenant_id, tag), []).append(r.record_id)
+            mh_key = (r.algorithm, minhash_slots(r.fingerprint)) if _feeds_minhash(r) else None
+            if mh_key is not None:
+                by_mh.setdefault((r.tenant_id, mh_key), []).append(r)
+            for key in self._minhash_keys():
+                if key != mh_key:
+                    stale_mh.setdefault((r.tenant_id, key), []).append(r.record_id)
             dim = len(r.embedding) if r.embedding is not None else 0
             if dim > 0:
                 by_cos.setdefault((r.tenant_id, dim), []).append(r)
@@ -1050,8 +1067,8 @@ class GpuIndex:
             self._tl.delete(tenant, np.array(ids, np.uint64))
         for (tenant, tag), ids in stale_im.items():
             self._im[tag].delete(tenant, np.array(ids, np.uint64))
-        for (tenant, tag), ids in stale_mh.items():
-            self._mh[tag].delete(tenant, np.array(ids, np.uint64))
+        for (tenant, (tag, h)), ids in stale_mh.items():
+            self._minhash_get(tag, h).delete(tenant, np.array(ids, np.uint64))
         for tenant, ids in stale_bm.items():
             self._bm.delete(tenant, np.array(ids, np.uint64))
         for tenant, recs in by_bm.items():
@@ -1073,8 +1090,8 @@ class GpuIndex:
         for (tenant, tag), recs in by_im.items():
             self._image_match(tag).upsert(tenant, np.array([r.record_id for r in recs], np.uint64),
                                           [bytes(r.fingerprint) for r in recs])
-        for (tenant, tag), recs in by_mh.items():
-            self._minhash(tag).upsert(tenant, np.array([r.record_id for r in recs], np.uint64),
+        for (tenant, (tag, h)), recs in by_mh.items():
+            self._minhash(tag, h).upsert(tenant, np.array([r.record_id for r in recs], np.uint64),
                                       [bytes(r.fingerprint) for r in recs])
         for (tenant, dim), recs in by_cos.items():
             ids = np.array([r.record_id for r in recs], np.uint64)
@@ -1237,20 +1254,14 @@ class GpuIndex:
 
     def similar_text(self, tenant_id: int, record_or_text, k: int, *, algorithm: Optional[str] = None,
                      min_agree: Optional[int] = None, threshold: Optional[float] = None) -> List[Hit]:
-        """The MinHash-128 records that agree with a record in the most slots (DESIGN A17): `record_or_text` is the 1032
-        record bytes, or a `str` that is fingerprinted with the default TextOpts first.  Hits need `min_agree` equal slots
-        (default 1), or the Jaccard estimate `threshold` (text.min_agree_for); score = agree / 128, `distance` =
-        128 - agree.  `algorithm` names the tag of the records searched (`minhash-h128` or `minhash-lsh-h128`); with
-        none, the only MinHash index present."""
+        """The MinHash records that agree with a record in the most slots (DESIGN A17): `record_or_text` is the 8 + 8 H
+        record bytes, or a `str` that is fingerprinted with the default TextOpts first.  The record's length tells H, and
+        only stored records of that H are searched (none stored: no hits).  Hits need `min_agree` equal slots
+        (default 1), or the Jaccard estimate `threshold` (text.min_agree_for); score = agree / H, `distance` =
+        H - agree.  `algorithm` names the tag of the records searched (`minhash-h128` or `minhash-lsh-h128`); with
+        none, the only tag with a MinHash index."""
         if min_agree is not None and threshold is not None:
             raise InvalidArgument("give `min_agree` or `threshold`, not both")
-        if threshold is not None:
-            from .text import min_agree_for
-            min_agree = min_agree_for(threshold)
-        elif min_agree is None:
-            min_agree = 1
-        if not 0 <= int(min_agree) <= 128:
-            raise InvalidArgument(f"min_agree must be in [0, 128] (got {min_agree!r})")
         if algorithm is not None and algorithm not in _MINHASH_TAGS:
             raise InvalidArgument(f"no MinHash index for algorithm {algorithm!r}")
         if isinstance(record_or_text, str):
@@ -1260,19 +1271,26 @@ class GpuIndex:
             rec = recs[0].tobytes()
         else:
             rec = bytes(record_or_text)
-            if len(rec) != MINHASH_BYTES:
-                raise InvalidArgument(f"a MinHash record is {MINHASH_BYTES} bytes, not {len(rec)}")
+        h = minhash_slots(rec)
+        if threshold is not None:
+            from .text import min_agree_for
+            min_agree = min_agree_for(threshold, h)
+        elif min_agree is None:
+            min_agree = 1
+        if not 0 <= int(min_agree) <= h:
+            raise InvalidArgument(f"min_agree must be in [0, {h}] (got {min_agree!r})")
         tag = algorithm
         if tag is None:
-            if len(self._mh) > 1:
+            tags = {t for t, _ in self._minhash_keys()}
+            if len(tags) > 1:
                 raise InvalidArgument("`algorithm` is required when MinHash records of several algorithms are indexed")
-            tag = next(iter(self._mh), None)
-        ix = self._mh.get(tag)
+            tag = next(iter(tags), None)
+        ix = self._minhash_get(tag, h)
         if ix is None or k == 0:
             return []
         ids, agree, scores, counts = ix.query(tenant_id, [rec], min(k, MAX_K), int(min_agree))
         return [Hit(tenant_id=tenant_id, record_id=int(ids[0, i]), score=float(scores[0, i]), source=HitSource.MinHash,
-                    distance=128 - int(agree[0, i])) for i in range(int(counts[0]))]
+                    distance=h - int(agree[0, i])) for i in range(int(counts[0]))]
 
     def bm25(self, tenant_id: int, terms: Sequence[str], k: int, filter: Optional[bytes] = None,
              explain: bool = False) -> List[Hit]:
@@ -1358,8 +1376,14 @@ _MINHASH_TAGS = (ALGORITHM_MINHASH_128, ALGORITHM_LSH)
 
 
 def _feeds_minhash(r: Record) -> bool:
-    """A `minhash-h128` or `minhash-lsh-h128` record that is one whole MinHash-128 signature."""
-    return r.algorithm in _MINHASH_TAGS and len(r.fingerprint) == MINHASH_BYTES
+    """A `minhash-h128` or `minhash-lsh-h128` record that is one whole MinHash signature of a valid slot count."""
+    if r.algorithm not in _MINHASH_TAGS:
+        return False
+    try:
+        minhash_slots(r.fingerprint)
+    except InvalidArgument:
+        return False
+    return True
 
 
 def _hash_spaces(r: Record):

@@ -167,8 +167,8 @@ def rebuild(path: str, ctx=None, sidecar: bool = False):
     `sidecar=True` keeps the log attached, so later upserts / deletes are appended to it."""
     import torch
     from .audio import ALGORITHM_HAITSMA, ALGORITHM_PANAKO, ALGORITHM_WANG, panako_landmarks
-    from .text import ALGORITHM_TLSH
-    from .index import GpuIndex
+    from .text import ALGORITHM_TLSH, minhash_slots
+    from .index import GpuIndex, _feeds_minhash
     ctx = ctx or _lib.current_context()
     lib = _lib.load()
     dev = f"cuda:{ctx.device}"
@@ -191,7 +191,9 @@ def rebuild(path: str, ctx=None, sidecar: bool = False):
                     gi._hamming(space).upsert(int(tenant), ids[sel], d_codes.cpu().numpy().view(np.uint64))
                 # the whole records refill the image match index of their tag, whose row table lives on the host (A16)
                 gi._image_match(algorithm).upsert(int(tenant), ids[sel], np.ascontiguousarray(blobs[sel]))
-        for algorithm in _MINHASH:     # whole records: the MinHash index keeps its row table on the host (A17)
+        # whole records: the MinHash index keeps its row table on the host (A17).  The records of the default 128 slots are
+        # gathered at once; those of any other slot count (T10) are picked up by the walk below, one index per (tag, H)
+        for algorithm in _MINHASH:
             tenants, ids, blobs = snap.gather_fingerprints(algorithm, 1032)
             for tenant in np.unique(tenants):
                 sel = tenants == tenant
@@ -203,7 +205,7 @@ def rebuild(path: str, ctx=None, sidecar: bool = False):
                 gi._hamming(algorithm).upsert(int(tenant), ids[sel], np.ascontiguousarray(blobs[sel]).view(np.uint64).reshape(-1))
         # Wang records are variable length: walk the rows (the landmark index keeps its record table on the host)
         # (so are Haitsma records: the sub-fingerprint index does the same)
-        wang, haitsma, panako, tlsh = {}, {}, {}, {}
+        wang, haitsma, panako, tlsh, minhash_h = {}, {}, {}, {}, {}
         for r in snap:
             if r.algorithm == ALGORITHM_WANG:
                 wang.setdefault(r.tenant_id, []).append(r)
@@ -213,6 +215,11 @@ def rebuild(path: str, ctx=None, sidecar: bool = False):
                 panako.setdefault(r.tenant_id, []).append(r)
             elif r.algorithm == ALGORITHM_TLSH:
                 tlsh.setdefault(r.tenant_id, []).append(r)
+            elif r.algorithm in _MINHASH and len(r.fingerprint) != 1032 and _feeds_minhash(r):
+                minhash_h.setdefault((r.tenant_id, r.algorithm, minhash_slots(r.fingerprint)), []).append(r)
+        for (tenant, algorithm, h), recs in minhash_h.items():
+            gi._minhash(algorithm, h).upsert(tenant, np.array([r.record_id for r in recs], np.uint64),
+                                             [bytes(r.fingerprint) for r in recs])
         for tenant, recs in wang.items():
             gi._landmarks().upsert(tenant, np.array([r.record_id for r in recs], np.uint64), [r.fingerprint for r in recs])
         for tenant, recs in panako.items():     # their (hash, t_anchor) pairs, in a landmark index of their own (A13)

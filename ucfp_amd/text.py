@@ -1,7 +1,7 @@
 """Text fingerprinting -- host-side mirror of src/modality/text.rs.
 
     fingerprint_minhash(text, tenant_id, record_id)                 text.rs:172-174
-    fingerprint_minhash_with(text, opts, tenant_id, record_id)      text.rs:182-236  (H = 128)
+    fingerprint_minhash_with(text, opts, tenant_id, record_id)      text.rs:182-236  (any opts.h)
     fingerprint_simhash_tf / fingerprint_simhash_idf                text.rs:328-362
     fingerprint_lsh                                                 text.rs:437-446
     fingerprint_tlsh                                                text.rs:452-484  (TLSH 128/1, DESIGN A15)
@@ -60,6 +60,7 @@ RAW_ASCII, PRETOKENIZED, RAW_UTF8 = 0, 1, 2
 TOK_WORD, TOK_GRAPHEME = 0, 1        # UCFP_TEXT_TOK_*: the tokeniser of the ucfp_text_*_batch_ex entries
 NEEDS_HOST = 1
 MINHASH_BYTES, SIMHASH_BYTES = 1032, 8
+MINHASH_H_MIN, MINHASH_H_MAX, MINHASH_H_STEP = 16, 1024, 16   # UCFP_MINHASH_H_*: the slot counts built
 TLSH_BYTES = 35             # UCFP_TLSH_BYTES: swap(checksum), swap(L), Q1 << 4 | Q2, code[31] .. code[0]
 TLSH_MAX_DISTANCE = 2473    # UCFP_TLSH_MAX_DISTANCE
 TLSH_MIN_BYTES = 50         # shorter documents are refused (the reference's README.md:96)
@@ -158,6 +159,31 @@ def _prepare(text: str, opts: TextOpts) -> Tuple[bytes, int]:
     return " ".join(toks).encode("utf-8"), PRETOKENIZED
 
 
+def minhash_bytes(h: int = DEFAULT_H) -> int:
+    """The bytes of a MinHash record of `h` slots (UCFP_MINHASH_RECORD_BYTES): 8 + 8 h."""
+    return 8 + 8 * _check_h(h)
+
+
+def _check_h(h) -> int:
+    """the manifest's range (algorithms_manifest.rs:280-328), a multiple of 16 in [16, 1024]."""
+    if isinstance(h, bool) or not isinstance(h, (int, np.integer)) or h < MINHASH_H_MIN or h > MINHASH_H_MAX or h % MINHASH_H_STEP:
+        raise InvalidArgument(f"MinHash slot count h must be a multiple of {MINHASH_H_STEP} in [{MINHASH_H_MIN}, {MINHASH_H_MAX}] "
+                              f"(got {h!r})")
+    return int(h)
+
+
+def minhash_slots(record) -> int:
+    """The slot count of a MinHash record, told by its length (every H carries the tag `minhash-h128`, text.rs:221-228)."""
+    n = len(record)
+    if n < 8 or (n - 8) % 8:
+        raise InvalidArgument(f"{n} bytes are not a MinHash record (8 + 8 h)")
+    return _check_h((n - 8) // 8)
+
+
+def _rec_bytes(kind: str, h: int) -> int:
+    return SIMHASH_BYTES if kind == "simhash" else 8 + 8 * h
+
+
 def _pack(docs: Sequence[bytes]):
     offs = np.zeros(len(docs) + 1, np.uint64)
     np.cumsum([len(d) for d in docs], out=offs[1:])
@@ -165,17 +191,20 @@ def _pack(docs: Sequence[bytes]):
     return blob, offs
 
 
-def _run(kind: str, docs: Sequence[bytes], mode: int, k: int, ctx=None):
+def _run(kind: str, docs: Sequence[bytes], mode: int, k: int, ctx=None, h: int = DEFAULT_H):
+    """MinHash with h != 128 slots goes through the entries that take a slot count."""
     ctx = ctx or _lib.current_context()
     lib = _lib.load()
     blob, offs = _pack(docs)
     n = len(docs)
-    rec = SIMHASH_BYTES if kind == "simhash" else MINHASH_BYTES
-    out = np.zeros((n, rec), np.uint8)
+    out = np.zeros((n, _rec_bytes(kind, h)), np.uint8)
     status = np.zeros(n, np.int32)
     if kind == "simhash":
         _lib.check(lib.ucfp_text_simhash_batch(ctx.handle, blob.ctypes.data, offs.ctypes.data, n, mode,
                                                out.ctypes.data, status.ctypes.data))
+    elif h != DEFAULT_H:
+        _lib.check(lib.ucfp_text_minhash_h_batch(ctx.handle, blob.ctypes.data, offs.ctypes.data, n, mode, TOK_WORD, k, h,
+                                                 out.ctypes.data, status.ctypes.data))
     else:
         _lib.check(lib.ucfp_text_minhash_batch(ctx.handle, blob.ctypes.data, offs.ctypes.data, n, mode, k,
                                                out.ctypes.data, status.ctypes.data))
@@ -207,17 +236,20 @@ def canon_batch(docs: Sequence[bytes], ctx=None) -> Tuple[List[bytes], np.ndarra
     return [toks[int(toff[i]):int(toff[i + 1])].tobytes() for i in range(n)], status
 
 
-def _run_ex(kind: str, docs: Sequence[bytes], mode: int, tokenizer: int, k: int, ctx=None):
-    """`_run` through the entries that take a tokeniser (ucfp_text_*_batch_ex)."""
+def _run_ex(kind: str, docs: Sequence[bytes], mode: int, tokenizer: int, k: int, ctx=None, h: int = DEFAULT_H):
+    """`_run` through the entries that take a tokeniser (ucfp_text_*_batch_ex; ucfp_text_minhash_h_batch for h != 128)."""
     ctx = ctx or _lib.current_context()
     lib = _lib.load()
     blob, offs = _pack(docs)
     n = len(docs)
-    out = np.zeros((n, SIMHASH_BYTES if kind == "simhash" else MINHASH_BYTES), np.uint8)
+    out = np.zeros((n, _rec_bytes(kind, h)), np.uint8)
     status = np.zeros(n, np.int32)
     if kind == "simhash":
         _lib.check(lib.ucfp_text_simhash_batch_ex(ctx.handle, blob.ctypes.data, offs.ctypes.data, n, mode, tokenizer,
                                                   out.ctypes.data, status.ctypes.data))
+    elif h != DEFAULT_H:
+        _lib.check(lib.ucfp_text_minhash_h_batch(ctx.handle, blob.ctypes.data, offs.ctypes.data, n, mode, tokenizer, k, h,
+                                                 out.ctypes.data, status.ctypes.data))
     else:
         _lib.check(lib.ucfp_text_minhash_batch_ex(ctx.handle, blob.ctypes.data, offs.ctypes.data, n, mode, tokenizer, k,
                                                   out.ctypes.data, status.ctypes.data))
@@ -235,27 +267,31 @@ def _pack_tokens(docs: Sequence[Sequence[bytes]]):
     return blob, tok_offs, doc_toks
 
 
-def _run_tokens(kind: str, docs: Sequence[Sequence[bytes]], k: int, ctx=None):
+def _run_tokens(kind: str, docs: Sequence[Sequence[bytes]], k: int, ctx=None, h: int = DEFAULT_H):
     ctx = ctx or _lib.current_context()
     lib = _lib.load()
     blob, tok_offs, doc_toks = _pack_tokens(docs)
     n = len(docs)
-    out = np.zeros((n, SIMHASH_BYTES if kind == "simhash" else MINHASH_BYTES), np.uint8)
+    out = np.zeros((n, _rec_bytes(kind, h)), np.uint8)
     status = np.zeros(n, np.int32)
     if kind == "simhash":
         _lib.check(lib.ucfp_text_simhash_tokens_batch(ctx.handle, blob.ctypes.data, tok_offs.ctypes.data, doc_toks.ctypes.data, n,
                                                       out.ctypes.data, status.ctypes.data))
+    elif h != DEFAULT_H:
+        _lib.check(lib.ucfp_text_minhash_tokens_h_batch(ctx.handle, blob.ctypes.data, tok_offs.ctypes.data, doc_toks.ctypes.data, n,
+                                                        k, h, out.ctypes.data, status.ctypes.data))
     else:
         _lib.check(lib.ucfp_text_minhash_tokens_batch(ctx.handle, blob.ctypes.data, tok_offs.ctypes.data, doc_toks.ctypes.data, n,
                                                       k, out.ctypes.data, status.ctypes.data))
     return out, status
 
 
-def minhash_tokens(docs: Sequence[Sequence[bytes]], k: int = DEFAULT_K, ctx=None):
-    """MinHash-128 of documents the caller has tokenised: `docs` is a sequence of token sequences, a
+def minhash_tokens(docs: Sequence[Sequence[bytes]], k: int = DEFAULT_K, ctx=None, h: int = DEFAULT_H):
+    """MinHash of documents the caller has tokenised: `docs` is a sequence of token sequences, a
     token any `bytes`, spaces and NULs included, hashed as it is; an empty token is not a token.  The route for any
-    tokeniser the caller runs itself (the reference's cjk-jp / cjk-ko).  -> (records uint8 [n, 1032], status int32 [n])."""
-    return _run_tokens("minhash", docs, k, ctx)
+    tokeniser the caller runs itself (the reference's cjk-jp / cjk-ko).  `h` is the slot count.
+    -> (records uint8 [n, 8 + 8 h], status int32 [n])."""
+    return _run_tokens("minhash", docs, k, ctx, _check_h(h))
 
 
 def simhash_tokens(docs: Sequence[Sequence[bytes]], ctx=None, idf: Optional["IdfTable"] = None):
@@ -271,8 +307,8 @@ def _batch_grapheme(kind: str, texts: Sequence[str], opts: TextOpts, ctx=None):
     other documents as UTF-8 when the canonicaliser is the default one (RAW_UTF8); what the device hands back and every
     other canonicaliser is canonicalised and cut into clusters here (`Canonicalizer.apply`, then \\X) and goes to the
     token entries.  All three routes give the same record."""
-    rec = SIMHASH_BYTES if kind == "simhash" else MINHASH_BYTES
-    out = np.zeros((len(texts), rec), np.uint8)
+    h = _check_h(opts.h) if kind == "minhash" else DEFAULT_H
+    out = np.zeros((len(texts), _rec_bytes(kind, h)), np.uint8)
     status = np.zeros(len(texts), np.int32)
     c = opts.canonicalizer
     host = []
@@ -287,14 +323,14 @@ def _batch_grapheme(kind: str, texts: Sequence[str], opts: TextOpts, ctx=None):
     for mode, idx in groups.items():
         if not idx:
             continue
-        o, s = _run_ex(kind, [texts[i].encode("utf-8", "surrogatepass") for i in idx], mode, TOK_GRAPHEME, opts.k, ctx)
+        o, s = _run_ex(kind, [texts[i].encode("utf-8", "surrogatepass") for i in idx], mode, TOK_GRAPHEME, opts.k, ctx, h)
         out[idx] = o
         status[idx] = s
         host += [i for i, st in zip(idx, s) if st == NEEDS_HOST]
     if host:
         host.sort()
         docs = [[g.encode("utf-8", "surrogatepass") for g in _host_graphemes(c.apply(texts[i]))] for i in host]
-        o, s = _run_tokens(kind, docs, opts.k, ctx)
+        o, s = _run_tokens(kind, docs, opts.k, ctx, h)
         out[host] = o
         status[host] = s
     return out, status
@@ -305,12 +341,12 @@ def _batch(kind: str, texts: Sequence[str], opts: TextOpts, ctx=None):
     UTF-8 launch hands back join the host group."""
     if opts.tokenizer == "grapheme":
         return _batch_grapheme(kind, texts, opts, ctx)
-    rec = SIMHASH_BYTES if kind == "simhash" else MINHASH_BYTES
-    out = np.zeros((len(texts), rec), np.uint8)
+    h = _check_h(opts.h) if kind == "minhash" else DEFAULT_H
+    out = np.zeros((len(texts), _rec_bytes(kind, h)), np.uint8)
     status = np.zeros(len(texts), np.int32)
     dev = [i for i, t in enumerate(texts) if _device_utf8(t, opts)]
     if dev:
-        o, s = _run(kind, [texts[i].encode("utf-8", "surrogatepass") for i in dev], RAW_UTF8, opts.k, ctx)
+        o, s = _run(kind, [texts[i].encode("utf-8", "surrogatepass") for i in dev], RAW_UTF8, opts.k, ctx, h)
         out[dev] = o
         status[dev] = s
     done = {i for i, st in zip(dev, status[dev]) if st != NEEDS_HOST}
@@ -319,14 +355,15 @@ def _batch(kind: str, texts: Sequence[str], opts: TextOpts, ctx=None):
         idx = [i for i, p in enumerate(prepared) if p is not None and p[1] == mode]
         if not idx:
             continue
-        o, s = _run(kind, [prepared[i][0] for i in idx], mode, opts.k, ctx)
+        o, s = _run(kind, [prepared[i][0] for i in idx], mode, opts.k, ctx, h)
         out[idx] = o
         status[idx] = s
     return out, status
 
 
 def minhash_batch(texts: Sequence[str], opts: Optional[TextOpts] = None, ctx=None):
-    """-> (records uint8 [n, 1032], status int32 [n])."""
+    """-> (records uint8 [n, 8 + 8 opts.h], status int32 [n]); opts.h is the slot count (1032 bytes at the
+    default 128)."""
     return _batch("minhash", texts, opts or TextOpts(), ctx)
 
 
@@ -654,7 +691,8 @@ class StreamingMinHashSession:
         if self.opts.tokenizer != "word":
             raise UnsupportedError(f"tokenizer `{self.opts.tokenizer}` is not built into the HIP path")
         if self.opts.h != DEFAULT_H:
-            raise UnsupportedError("only H = 128 is built (the reference's public entry point, text.rs:172-174)")
+            raise UnsupportedError(f"streaming MinHash is built for H = {DEFAULT_H} only, as the reference's session is (got "
+                                   f"H = {self.opts.h}); minhash_batch takes any H")
         self.tenant_id, self.record_id = tenant_id, record_id
         self._config_hash_value = config_hash_value
         self._utf8_ok = self.opts.canonicalizer.is_default()
@@ -806,6 +844,9 @@ class TextBatcher:
         self._lib = _lib.load()
         self.ctx = ctx or _lib.current_context()
         self.opts = opts or TextOpts()
+        if kind == "minhash" and self.opts.h != DEFAULT_H:
+            raise UnsupportedError(f"the text micro-batcher is built for H = {DEFAULT_H} only (got H = {self.opts.h}); "
+                                   "minhash_batch takes any H")
         self.kind = kind
         self.rec = MINHASH_BYTES if kind == "minhash" else SIMHASH_BYTES
         algo = ALGO_MINHASH if kind == "minhash" else ALGO_SIMHASH
@@ -886,8 +927,8 @@ def fingerprint_minhash(text: str, tenant_id: int, record_id: int) -> Record:
 
 def fingerprint_minhash_with(text: str, opts: TextOpts, tenant_id: int, record_id: int,
                              config_hash_value: Optional[int] = None) -> Record:
-    if opts.h != DEFAULT_H:
-        raise UnsupportedError("only H = 128 is built (the reference's public entry point, text.rs:172-174)")
+    """text.rs:182-236 at any slot count opts.h.  Every H carries the tag `minhash-h128`, as in the
+    reference (text.rs:221-228): the fingerprint's length, 8 + 8 h, tells H."""
     recs, status = minhash_batch([text], opts)
     _raise_for(int(status[0]))
     return Record(tenant_id=tenant_id, record_id=record_id, modality=Modality.Text,
@@ -1022,10 +1063,14 @@ def _dev(a: np.ndarray):
 
 
 def _records(records) -> np.ndarray:
+    """MinHash-128 records for the band index, which is built for H = 128 only (`minhash-lsh-h128`, 16 x 8 bands)."""
     if isinstance(records, (bytes, bytearray)):
         records = np.frombuffer(bytes(records), np.uint8)
-    r = np.ascontiguousarray(records, dtype=np.uint8).reshape(-1, MINHASH_BYTES)
-    return r
+    r = np.ascontiguousarray(records, dtype=np.uint8)
+    if (r.ndim == 2 and r.shape[1] != MINHASH_BYTES) or r.size % MINHASH_BYTES:
+        raise UnsupportedError(f"the LSH index is built for H = {DEFAULT_H} only ({MINHASH_BYTES}-byte records); these are rows of "
+                               f"{r.shape[-1] if r.ndim == 2 else r.size} bytes")
+    return r.reshape(-1, MINHASH_BYTES)
 
 
 def lsh_band_keys(records, bands: int = 16, rows: int = 8, ctx=None) -> np.ndarray:
@@ -1043,22 +1088,23 @@ def lsh_band_keys(records, bands: int = 16, rows: int = 8, ctx=None) -> np.ndarr
     return d_k[:, :n].t().contiguous().cpu().numpy().view(np.uint64)
 
 
-def min_agree_for(threshold: float) -> int:
-    """Smallest slot agreement whose Jaccard estimate (agree / 128) reaches `threshold`, 0 < threshold <= 1:
-    max(1, ceil(threshold * 128)); the product by 128 is exact in binary floating point."""
+def min_agree_for(threshold: float, h: int = DEFAULT_H) -> int:
+    """Smallest slot agreement whose Jaccard estimate (agree / h) reaches `threshold`, 0 < threshold <= 1:
+    max(1, ceil(threshold * h)); the product is exact in binary floating point when h is a power of two (the default 128)
+    and correctly rounded otherwise."""
     t = float(threshold)
     if not 0.0 < t <= 1.0:      # also rejects NaN
         raise InvalidArgument(f"threshold must be in (0, 1] (got {threshold!r})")
-    return max(1, math.ceil(t * 128.0))
+    return max(1, math.ceil(t * _check_h(h)))
 
 
 def minhash_agree(a, b) -> int:
-    """The number of equal slots of two MinHash-128 records, 0 .. 128 (host code: ucfp_minhash_agree needs no device;
-    the headers are not compared)."""
+    """The number of equal slots of two MinHash records of the same slot count H, 0 .. H; H is told by the records'
+    length (host code: ucfp_minhash_agree_h needs no device; the headers are not compared)."""
     a, b = bytes(a), bytes(b)
-    if len(a) != MINHASH_BYTES or len(b) != MINHASH_BYTES:
-        raise InvalidArgument(f"a MinHash record is {MINHASH_BYTES} bytes")
-    return int(_lib.load().ucfp_minhash_agree(a, b))
+    if len(a) != len(b):
+        raise InvalidArgument(f"MinHash records of {len(a)} and {len(b)} bytes have different slot counts")
+    return int(_lib.load().ucfp_minhash_agree_h(a, b, minhash_slots(a)))
 
 
 SPAN_ALL = 0xFFFFFFFF   # dedup: every pair of a run of equal band keys
@@ -1170,6 +1216,8 @@ def dedup_corpus(texts: Sequence[str], threshold: float = 0.8, opts: Optional[Te
     A document whose status is not 0 (no tokens, oversized token) is its own cluster: kept, its own label, never
     the representative of another."""
     min_agree = min_agree_for(threshold)
+    if opts is not None and opts.h != DEFAULT_H:
+        raise UnsupportedError(f"de-duplication runs on the LSH index, which is built for H = {DEFAULT_H} only (got H = {opts.h})")
     n = len(texts)
     keep = np.ones(n, bool)
     labels = np.arange(n, dtype=np.int64)

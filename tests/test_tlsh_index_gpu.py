@@ -88,6 +88,23 @@ def test_pass_loop(gpu_ctx, pool, monkeypatch):
     ix.close()
 
 
+def test_short_last_pass(gpu_ctx, pool, monkeypatch):
+    """A last pass that wants more slices than the partial lists were sized for: 65 queries over 33 000 rows in passes of
+    64 and 1.  select_plan(33000, 64) asks for 4096 / 64 = 64 slices, 516 rows each, rounded up to 576: 58 slices, and the
+    partial lists are reserved for those.  select_plan(33000, 1) is capped at ceil(33000 / 512) = 65 slices of 512 rows;
+    65 > 58, so the pass loop has to bring the one-query pass back to 58 slices of 576 rows."""
+    from ucfp_amd.index import TlshIndex
+    rows, ids, queries, big, small = pool
+    n, nq = 33_000, 65
+    monkeypatch.setenv("UCFP_TLSH_KEY_BYTES", str(64 * 4 * n))
+    ix = TlshIndex(ctx=gpu_ctx)
+    monkeypatch.delenv("UCFP_TLSH_KEY_BYTES")
+    ix.upsert(0, ids[:n], rows[:n])
+    for k in (10, 128):
+        _check(ix.query(0, queries[:nq], k), ref.topk_from_distances(ids[:n], big[:nq, :n], k), k)
+    ix.close()
+
+
 def test_identical_rows_return_the_smallest_ids(gpu_ctx):
     from ucfp_amd.index import TlshIndex
     rng = np.random.default_rng(12)

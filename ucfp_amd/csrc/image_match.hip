@@ -21,25 +21,20 @@
 // and im_scores turns the selected keys back into the scores' bit patterns.  ALU-bound once a pass carries more than a
 // few queries: about 400 vector instructions per (query, row) on a bundle against 408 bytes per row.
 // Not here: sharding over GPUs, a search micro-batcher, save / load (ucfp_hip.h says so).
+// The tenant table, its mutations, the head of the rebuild, the pass loop and the call protocol are scan_index.h's
+// (UCFP_IMAGE_MATCH_KEY_BYTES at creation overrides the size of a pass's key matrix).
 
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cmath>
-#include <cstdlib>
-#include <map>
-#include <unordered_map>
-#include <vector>
 
-#include "postings.h"
+#include "scan_index.h"
 
 namespace {
 
 constexpr uint32_t kCodes = 17;                  // u64 codes of one algorithm: global, 16 blocks
 constexpr uint32_t kRecBytes = 168;              // one algorithm's record: exact[32] | global | 16 blocks
 constexpr uint32_t kBundleBytes = 536;           // 32-byte header, then the ahash, phash and dhash records
-constexpr size_t kKeyBytes = (size_t)1 << 30;    // key matrix of one pass (UCFP_IMAGE_MATCH_KEY_BYTES at creation overrides it)
-constexpr size_t kMaxRows = (size_t)1 << 31;
 constexpr uint32_t kKeyZero = 0x7f800000u;       // the key of score +0; a larger score has a smaller key
 
 // What one pair costs, on the host and on the device alike.  c points to the 17 or 51 codes of each side.
@@ -117,26 +112,6 @@ __global__ void im_scores(const uint32_t* __restrict__ key, size_t total, float*
     scores[i] = k == kEmpty32 ? -1.0f : __uint_as_float(kKeyZero - k);
 }
 
-// empty answers for every query (unknown tenant / no rows)
-__global__ void im_empty(size_t nq, uint32_t k, uint64_t* __restrict__ out_ids, float* __restrict__ out_scores,
-                         uint32_t* __restrict__ out_n) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < nq * k) {
-        out_ids[i] = kEmpty64;
-        out_scores[i] = -1.0f;
-    }
-    if (i < nq) out_n[i] = 0;
-}
-
-struct Tenant {
-    std::map<uint64_t, std::vector<uint64_t>> recs;   // id -> codes; ascending id = row order, so ties by row are ties by id
-    bool dirty = true;
-    size_t n = 0, stride = 0;                         // valid when !dirty
-    DevArr rows, ids;
-};
-
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 inline bool unit(float x) { return std::isfinite(x) && x >= 0.0f && x <= 1.0f; }
 
 // M4; `bundle`: the three algorithm weights count.  -0.0f is taken as +0.0f, so no product is ever negative zero.
@@ -181,133 +156,58 @@ inline void record_codes(const uint8_t* rec, bool bundle, uint64_t* out) {
 
 }  // namespace
 
-struct ucfp_image_match_index : ucfp::IndexCore {
-    std::unordered_map<uint32_t, Tenant> tenants;
+struct ucfp_image_match_index : ucfp::ScanIndex<std::vector<uint64_t>> {
+    static constexpr uint64_t kPad = 0;
     bool bundle = false;            // 536-byte bundles (51 codes) or 168-byte records (17)
-    size_t key_bytes = kKeyBytes;
-    DevArr b_packed;                // rebuild staging
-    DevArr q_in, q_ws, q_out;       // host-pointer queries, the pass workspace, host-pointer answers
 
     uint32_t words() const { return bundle ? 3 * kCodes : kCodes; }
-    uint32_t rec_bytes() const { return bundle ? kBundleBytes : kRecBytes; }
+    size_t rec_bytes() const { return bundle ? kBundleBytes : kRecBytes; }
+    size_t row_len() const { return words(); }
+    Row to_row(const uint8_t* rec) const {
+        Row c(words());
+        record_codes(rec, bundle, c.data());
+        return c;
+    }
+    // n rows of W codes -> W planes of `stride` rows
+    int upload(DevArr& rows, const uint64_t* h_rows, size_t n, size_t stride, hipStream_t st) {
+        const uint32_t W = words();
+        int rc;
+        if ((rc = rows.ensure(stride * W * 8)) || (rc = b_packed.ensure(n * W * 8))) return rc;
+        if (!n) return UCFP_OK;
+        HIP_TRY(hipMemcpyAsync(b_packed.p, h_rows, n * W * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(rows.p, 0, stride * W * 8, st));
+        hipLaunchKernelGGL(im_pack, dim3((unsigned)((n * W + 255) / 256)), dim3(256), 0, st, b_packed.as<uint8_t>(), n, W, W * 8u, 0u,
+                           kCodes * 8u, rows.as<uint64_t>(), stride, (size_t)1);
+        HIP_TRY(hipGetLastError());
+        return UCFP_OK;
+    }
 };
 
 namespace {
 
-int rebuild(ucfp_image_match_index* ix, Tenant& T, hipStream_t st) {
-    const size_t n = T.recs.size();
-    if (n >= kMaxRows) return capi_fail(UCFP_E_INVALID, "too many rows in one tenant (%zu)", n);
-    const uint32_t W = ix->words();
-    const size_t stride = (n + 63) & ~(size_t)63;
-    std::vector<uint64_t> h_rows(n * W);
-    std::vector<uint64_t> h_ids(n);
-    size_t i = 0;
-    for (auto& kv : T.recs) {
-        h_ids[i] = kv.first;
-        memcpy(h_rows.data() + i * W, kv.second.data(), (size_t)W * 8);
-        i++;
-    }
-    int rc;
-    if ((rc = T.ids.ensure(n * 8)) || (rc = T.rows.ensure(stride * W * 8)) || (rc = ix->b_packed.ensure(n * W * 8))) return rc;
-    if (n) {
-        HIP_TRY(hipMemcpyAsync(T.ids.p, h_ids.data(), n * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(ix->b_packed.p, h_rows.data(), n * W * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemsetAsync(T.rows.p, 0, stride * W * 8, st));
-        hipLaunchKernelGGL(im_pack, dim3((unsigned)((n * W + 255) / 256)), dim3(256), 0, st, ix->b_packed.as<uint8_t>(), n, W,
-                           W * 8u, 0u, kCodes * 8u, T.rows.as<uint64_t>(), stride, (size_t)1);
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipStreamSynchronize(st));   // the host vectors above go out of scope
-    T.n = n;
-    T.stride = stride;
-    T.dirty = false;
-    return UCFP_OK;
-}
-
-int do_upsert(ucfp_image_match_index* ix, uint32_t tenant, const uint64_t* ids, const uint8_t* records, size_t n) {
-    if (!n) return UCFP_OK;
-    if (!ids || !records) return capi_fail(UCFP_E_INVALID, "ids/records is NULL");
-    Tenant& T = ix->tenants[tenant];
-    const uint32_t W = ix->words(), rb = ix->rec_bytes();
-    for (size_t i = 0; i < n; i++) {
-        std::vector<uint64_t> c(W);
-        record_codes(records + i * rb, ix->bundle, c.data());
-        T.recs.insert_or_assign(T.recs.end(), ids[i], std::move(c));   // the hint: ascending ids append in constant time
-    }
-    T.dirty = true;
-    return UCFP_OK;
-}
-
 int query_impl(ucfp_image_match_index* ix, uint32_t tenant, const uint8_t* d_q, size_t nq, uint32_t k, const Weights& wt,
-               float min_score, uint64_t* d_ids, float* d_scores, uint32_t* d_n, hipStream_t st) {
-    int rc;
-    if (k == 0) {
-        HIP_TRY(hipMemsetAsync(d_n, 0, nq * 4, st));
-        return UCFP_OK;
-    }
-    auto it = ix->tenants.find(tenant);
-    if (it != ix->tenants.end() && it->second.dirty && (rc = rebuild(ix, it->second, st))) return rc;
-    if (it == ix->tenants.end() || it->second.n == 0) {
-        hipLaunchKernelGGL(im_empty, dim3((unsigned)((nq * k + 255) / 256)), dim3(256), 0, st, nq, k, d_ids, d_scores, d_n);
-        HIP_TRY(hipGetLastError());
-        return UCFP_OK;
-    }
-    Tenant& T = it->second;
-    const size_t n = T.n;
+               float min_score, const ucfp::ScanOut& o, hipStream_t st) {
     const uint32_t W = ix->words();
-    // queries per pass: the key matrix stays below key_bytes; queries ride on gridDim.y of the select kernel
-    size_t chunk = std::max<size_t>(1, ix->key_bytes / (4 * n));
-    chunk = std::min<size_t>(std::min<size_t>(chunk, 32768), nq);
-    const ucfp::SelectPlan sp = ucfp::select_plan(n, (uint32_t)chunk);
-    const size_t tmp_e = 2 * ucfp::topk_merge_tmp_entries(sp.slices, (uint32_t)chunk, k);   // both tree levels
-    size_t off = 0;
-    const size_t o_qw = off;
-    off = align256(off + nq * W * 8);
-    const size_t o_keys = off;
-    off = align256(off + chunk * n * 4 + 64);
-    const size_t o_pid = off;
-    off = align256(off + (size_t)sp.slices * chunk * k * 8);
-    const size_t o_pk = off;
-    off = align256(off + (size_t)sp.slices * chunk * k * 4);
-    const size_t o_pc = off;
-    off = align256(off + (size_t)sp.slices * chunk * 4);
-    const size_t o_tid = off;
-    off = align256(off + tmp_e * 8);
-    const size_t o_tk = off;
-    off = align256(off + tmp_e * 4);
-    const size_t o_ok = off;   // the selected keys of every query
-    off = align256(off + nq * k * 4);
-    if ((rc = ix->q_ws.ensure(off))) return rc;
-    uint8_t* w = ix->q_ws.as<uint8_t>();
-    uint64_t* qw = reinterpret_cast<uint64_t*>(w + o_qw);
-    uint32_t* keymat = reinterpret_cast<uint32_t*>(w + o_keys);
-    uint32_t* okeys = reinterpret_cast<uint32_t*>(w + o_ok);
-    hipLaunchKernelGGL(im_pack, dim3((unsigned)((nq * W + 255) / 256)), dim3(256), 0, st, d_q, nq, W, ix->rec_bytes(),
-                       ix->bundle ? 64u : 32u, kRecBytes, qw, (size_t)1, (size_t)W);
-    HIP_TRY(hipGetLastError());
-    for (size_t q0 = 0; q0 < nq; q0 += chunk) {
-        const uint32_t cnt = (uint32_t)std::min(chunk, nq - q0);
-        const dim3 grid((unsigned)((n + kThreads - 1) / kThreads));
-        if (ix->bundle)
-            hipLaunchKernelGGL(im_keys<3>, grid, dim3(kThreads), 0, st, T.rows.as<uint64_t>(), n, T.stride, qw + q0 * W, cnt, wt,
-                               min_score, keymat);
-        else
-            hipLaunchKernelGGL(im_keys<1>, grid, dim3(kThreads), 0, st, T.rows.as<uint64_t>(), n, T.stride, qw + q0 * W, cnt, wt,
-                               min_score, keymat);
-        HIP_TRY(hipGetLastError());
-        ucfp::SelectPlan pl = ucfp::select_plan(n, cnt);
-        if (pl.slices > sp.slices) {   // the partial lists were sized for the full pass
-            pl.per_slice = (((n + sp.slices - 1) / sp.slices) + 63) & ~(size_t)63;
-            pl.slices = (uint32_t)((n + pl.per_slice - 1) / pl.per_slice);
-        }
-        ucfp::launch_select_topk_u32(keymat, T.ids.as<uint64_t>(), n, pl, cnt, k, reinterpret_cast<uint64_t*>(w + o_pid),
-                                     reinterpret_cast<uint32_t*>(w + o_pk), reinterpret_cast<uint32_t*>(w + o_pc), st);
-        ucfp::launch_topk_merge_tree_u32(reinterpret_cast<uint64_t*>(w + o_pid), reinterpret_cast<uint32_t*>(w + o_pk), pl.slices,
-                                         cnt, k, reinterpret_cast<uint64_t*>(w + o_tid), reinterpret_cast<uint32_t*>(w + o_tk),
-                                         d_ids + q0 * k, okeys + q0 * k, d_n + q0, st);
-        HIP_TRY(hipGetLastError());
-    }
-    hipLaunchKernelGGL(im_scores, dim3((unsigned)((nq * k + 255) / 256)), dim3(256), 0, st, okeys, nq * k, d_scores);
+    uint64_t* qw = nullptr;   // the queries in code order, in the workspace
+    uint32_t* okeys = nullptr;
+    const int rc = ucfp::scan_query(
+        ix, tenant, nq, k, nq * W * 8, o, st, &okeys,
+        [&](uint8_t* q_area) {
+            qw = reinterpret_cast<uint64_t*>(q_area);
+            hipLaunchKernelGGL(im_pack, dim3((unsigned)((nq * W + 255) / 256)), dim3(256), 0, st, d_q, nq, W, (uint32_t)ix->rec_bytes(),
+                               ix->bundle ? 64u : 32u, kRecBytes, qw, (size_t)1, (size_t)W);
+        },
+        [&](const ucfp_image_match_index::Tenant& T, size_t q0, uint32_t cnt, uint32_t* keymat) {
+            const dim3 grid((unsigned)((T.n + kThreads - 1) / kThreads));
+            if (ix->bundle)
+                hipLaunchKernelGGL(im_keys<3>, grid, dim3(kThreads), 0, st, T.rows.as<uint64_t>(), T.n, T.stride, qw + q0 * W, cnt, wt,
+                                   min_score, keymat);
+            else
+                hipLaunchKernelGGL(im_keys<1>, grid, dim3(kThreads), 0, st, T.rows.as<uint64_t>(), T.n, T.stride, qw + q0 * W, cnt, wt,
+                                   min_score, keymat);
+        });
+    if (rc || !okeys) return rc;
+    hipLaunchKernelGGL(im_scores, dim3((unsigned)((nq * k + 255) / 256)), dim3(256), 0, st, okeys, nq * k, o.scores);
     HIP_TRY(hipGetLastError());
     return UCFP_OK;
 }
@@ -360,67 +260,31 @@ int ucfp_image_match_index_create(ucfp_ctx* ctx, uint32_t algo, uint32_t flags, 
     const int rc = ucfp::create_index(ctx, "image match index", out);
     if (rc) return rc;
     (*out)->bundle = algo == UCFP_IMG_MULTI;
-    // a smaller key matrix means more passes over the rows: for tuning, and for tests of the pass loop at small sizes
-    if (const char* e = getenv("UCFP_IMAGE_MATCH_KEY_BYTES")) (*out)->key_bytes = std::max<size_t>(4096, strtoull(e, nullptr, 10));
+    ucfp::scan_key_bytes_env(*out, "UCFP_IMAGE_MATCH_KEY_BYTES");
     return UCFP_OK;
 }
 
-void ucfp_image_match_index_destroy(ucfp_image_match_index* ix) {
-    if (!ix) return;
-    ix->quiesce();
-    for (auto& kv : ix->tenants)
-        for (DevArr* a : {&kv.second.rows, &kv.second.ids}) a->release();
-    for (DevArr* a : {&ix->b_packed, &ix->q_in, &ix->q_ws, &ix->q_out}) a->release();
-    delete ix;
-}
+void ucfp_image_match_index_destroy(ucfp_image_match_index* ix) { ucfp::scan_destroy(ix); }
 
 int ucfp_image_match_index_upsert(ucfp_image_match_index* ix, uint32_t tenant, const uint64_t* ids, const uint8_t* records,
                                   size_t n) {
-    if (!ix) return capi_fail(UCFP_E_INVALID, "index is NULL");
-    std::lock_guard<std::mutex> lk(ix->mu);
-    return do_upsert(ix, tenant, ids, records, n);
+    return ucfp::scan_upsert(ix, tenant, ids, records, n, "records");
 }
 
 int ucfp_image_match_index_upsert_dev(ucfp_image_match_index* ix, uint32_t tenant, const uint64_t* d_ids,
                                       const uint8_t* d_records, size_t n, void* stream) {
-    if (!ix) return capi_fail(UCFP_E_INVALID, "index is NULL");
-    if (!n) return UCFP_OK;
-    if (!d_ids || !d_records) return capi_fail(UCFP_E_INVALID, "ids/records is NULL");
-    std::lock_guard<std::mutex> lk(ix->mu);
-    HIP_TRY(hipSetDevice(ix->device));
-    hipStream_t st = (hipStream_t)stream;
-    // the row table lives on the host (mutations are bookkeeping; the planes are rebuilt at the next query)
-    std::vector<uint64_t> ids(n);
-    std::vector<uint8_t> rows(n * ix->rec_bytes());
-    HIP_TRY(hipMemcpyAsync(ids.data(), d_ids, n * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(rows.data(), d_records, n * ix->rec_bytes(), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return do_upsert(ix, tenant, ids.data(), rows.data(), n);
+    return ucfp::scan_upsert_dev(ix, tenant, d_ids, d_records, n, "records", stream);
 }
 
 int ucfp_image_match_index_delete(ucfp_image_match_index* ix, uint32_t tenant, const uint64_t* ids, size_t n, size_t* n_removed) {
-    if (!ix) return capi_fail(UCFP_E_INVALID, "index is NULL");
-    if (n && !ids) return capi_fail(UCFP_E_INVALID, "ids is NULL");
-    std::lock_guard<std::mutex> lk(ix->mu);
-    size_t removed = 0;
-    auto it = ix->tenants.find(tenant);
-    if (it != ix->tenants.end()) {
-        for (size_t i = 0; i < n; i++) removed += it->second.recs.erase(ids[i]);
-        if (removed) it->second.dirty = true;
-    }
-    if (n_removed) *n_removed = removed;
-    return UCFP_OK;
+    return ucfp::scan_delete(ix, tenant, ids, n, n_removed);
 }
 
 int ucfp_image_match_index_size(ucfp_image_match_index* ix, uint32_t tenant, size_t* rows) {
-    if (!ix) return capi_fail(UCFP_E_INVALID, "index is NULL");
-    std::lock_guard<std::mutex> lk(ix->mu);
-    auto it = ix->tenants.find(tenant);
-    if (rows) *rows = it == ix->tenants.end() ? 0 : it->second.recs.size();
-    return UCFP_OK;
+    return ucfp::scan_size(ix, tenant, rows);
 }
 
-int ucfp_image_match_index_flush(ucfp_image_match_index* ix) { return ucfp::flush_dirty(ix, rebuild); }
+int ucfp_image_match_index_flush(ucfp_image_match_index* ix) { return ucfp::scan_flush(ix); }
 
 int ucfp_image_match_index_query_dev(ucfp_image_match_index* ix, uint32_t tenant, const uint8_t* d_records, size_t nq, uint32_t k,
                                      const ucfp_image_match_config* cfg, uint64_t* d_out_ids, float* d_out_scores,
@@ -430,11 +294,9 @@ int ucfp_image_match_index_query_dev(ucfp_image_match_index* ix, uint32_t tenant
     Weights wt;
     float min_score;
     if ((rc = check_config(cfg, ix->bundle, &wt, &min_score)) || nq == 0) return rc;
-    std::lock_guard<std::mutex> lk(ix->mu);
-    if ((rc = ix->begin())) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    rc = query_impl(ix, tenant, d_records, nq, k, wt, min_score, d_out_ids, d_out_scores, d_out_n, st);
-    return ix->end(st, rc);
+    return ucfp::scan_query_dev(ix, stream, [&](hipStream_t st) {
+        return query_impl(ix, tenant, d_records, nq, k, wt, min_score, {d_out_ids, nullptr, d_out_scores, d_out_n}, st);
+    });
 }
 
 int ucfp_image_match_index_query(ucfp_image_match_index* ix, uint32_t tenant, const uint8_t* records, size_t nq, uint32_t k,
@@ -444,23 +306,10 @@ int ucfp_image_match_index_query(ucfp_image_match_index* ix, uint32_t tenant, co
     Weights wt;
     float min_score;
     if ((rc = check_config(cfg, ix->bundle, &wt, &min_score)) || nq == 0) return rc;
-    std::lock_guard<std::mutex> lk(ix->mu);
-    if ((rc = ix->begin())) return rc;
-    hipStream_t st = ix->own;
-    const size_t nk = nq * k, rb = ix->rec_bytes();
-    const size_t o_sc = align256(nk * 8), o_n = align256(o_sc + nk * 4);
-    if ((rc = ix->q_in.ensure(nq * rb)) || (rc = ix->q_out.ensure(o_n + nq * 4))) return rc;
-    HIP_TRY(hipMemcpyAsync(ix->q_in.p, records, nq * rb, hipMemcpyHostToDevice, st));
-    uint8_t* ob = ix->q_out.as<uint8_t>();
-    rc = query_impl(ix, tenant, ix->q_in.as<uint8_t>(), nq, k, wt, min_score, (uint64_t*)ob, (float*)(ob + o_sc),
-                    (uint32_t*)(ob + o_n), st);
-    if (rc) return ix->end_sync(rc);
-    if (nk) {
-        HIP_TRY(hipMemcpyAsync(out_ids, ob, nk * 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(out_scores, ob + o_sc, nk * 4, hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(hipMemcpyAsync(out_n, ob + o_n, nq * 4, hipMemcpyDeviceToHost, st));
-    return ix->end_sync(UCFP_OK);
+    return ucfp::scan_query_host(ix, records, nq, k, out_ids, nullptr, out_scores, out_n,
+                                 [&](const uint8_t* d_q, const ucfp::ScanOut& o, hipStream_t st) {
+                                     return query_impl(ix, tenant, d_q, nq, k, wt, min_score, o, st);
+                                 });
 }
 
 }  // extern "C"

@@ -33,15 +33,12 @@
 // Not here: packing two H = 64 rows into one wave load (an H = 64 row is half pad); a compact filter plane (the low 16 bits of every slot bound agree from above and would prune exactly at a
 // quarter of the bytes), device-resident appends, sharding over GPUs, a search micro-batcher, save / load.
 
+// The tenant table, its mutations, the head of the rebuild, the pass loop and the call protocol are scan_index.h's
+// (UCFP_MINHASH_KEY_BYTES at creation overrides the size of a pass's key matrix).
+
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <cstdlib>
-#include <map>
-#include <unordered_map>
-#include <vector>
-
-#include "postings.h"
+#include "scan_index.h"
 
 namespace {
 
@@ -55,8 +52,6 @@ constexpr uint32_t kGroupRows = 64;               // rows whose counts one key r
 constexpr uint32_t kGroups = 8;                   // groups of a block
 constexpr uint32_t kBlockRows = kGroupRows * kGroups;
 constexpr uint32_t kUnroll = 4;                   // 16-byte vectors in flight per lane: 4 / C rows, one at the least
-constexpr size_t kKeyBytes = (size_t)1 << 30;     // key matrix of one pass (UCFP_MINHASH_KEY_BYTES at creation overrides it)
-constexpr size_t kMaxRows = (size_t)1 << 31;
 
 // records: 8 + 8 h bytes each, only 4-byte alignment guaranteed (lsh.hip:42); a slot at or past h reads as 0
 __device__ __forceinline__ uint64_t load_slot(const uint8_t* rec, uint32_t i, uint32_t h) {
@@ -147,79 +142,27 @@ __global__ void mh_scores(uint32_t* __restrict__ agree, size_t total, uint32_t h
     }
 }
 
-// empty answers for every query (unknown tenant / no rows)
-__global__ void mh_empty(size_t nq, uint32_t k, uint64_t* __restrict__ out_ids, uint32_t* __restrict__ out_agree,
-                         float* __restrict__ out_scores, uint32_t* __restrict__ out_n) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < nq * k) {
-        out_ids[i] = kEmpty64;
-        out_agree[i] = kEmpty32;
-        out_scores[i] = -1.0f;
-    }
-    if (i < nq) out_n[i] = 0;
-}
-
-using Row = std::vector<uint8_t>;   // the 8 h slot bytes of a record
-
-struct Tenant {
-    std::map<uint64_t, Row> recs;   // id -> slots; ascending id = row order, so ties by row are ties by id
-    bool dirty = true;
-    size_t n = 0;                   // valid when !dirty
-    DevArr rows, ids;
-};
-
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace
 
-struct ucfp_minhash_index : ucfp::IndexCore {
+struct ucfp_minhash_index : ucfp::ScanIndex<std::vector<uint8_t>> {   // a row: the 8 h slot bytes of a record
+    static constexpr uint8_t kPad = 0xff;   // pad slots are ~0
     uint32_t h = 128;               // slots of a record
     uint32_t chunks = 1;            // C = ceil(h / 128): a device row is chunks * 1024 bytes
+
     size_t rec_bytes() const { return kHeaderBytes + 8 * (size_t)h; }
-    size_t row_bytes() const { return (size_t)chunks * kChunkBytes; }
-    std::unordered_map<uint32_t, Tenant> tenants;
-    size_t key_bytes = kKeyBytes;
-    DevArr q_in, q_ws, q_out;       // host-pointer queries, the pass workspace, host-pointer answers
+    size_t row_len() const { return (size_t)chunks * kChunkBytes; }
+    Row to_row(const uint8_t* rec) const { return Row(rec + kHeaderBytes, rec + kHeaderBytes + 8 * (size_t)h); }
+    // the padded rows as they are
+    int upload(DevArr& rows, const uint8_t* h_rows, size_t n, size_t, hipStream_t st) {
+        if (int rc = rows.ensure(n * row_len())) return rc;
+        if (n) HIP_TRY(hipMemcpyAsync(rows.p, h_rows, n * row_len(), hipMemcpyHostToDevice, st));
+        return UCFP_OK;
+    }
 };
 
 namespace {
 
-int rebuild(ucfp_minhash_index* ix, Tenant& T, hipStream_t st) {
-    const size_t n = T.recs.size();
-    if (n >= kMaxRows) return capi_fail(UCFP_E_INVALID, "too many rows in one tenant (%zu)", n);
-    const size_t row_bytes = ix->row_bytes();
-    std::vector<uint8_t> h_rows(n * row_bytes, 0xff);   // pad slots are ~0
-    std::vector<uint64_t> h_ids(n);
-    size_t i = 0;
-    for (auto& kv : T.recs) {
-        h_ids[i] = kv.first;
-        memcpy(h_rows.data() + i * row_bytes, kv.second.data(), kv.second.size());
-        i++;
-    }
-    int rc;
-    if ((rc = T.ids.ensure(n * 8)) || (rc = T.rows.ensure(n * row_bytes))) return rc;
-    if (n) {
-        HIP_TRY(hipMemcpyAsync(T.ids.p, h_ids.data(), n * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(T.rows.p, h_rows.data(), n * row_bytes, hipMemcpyHostToDevice, st));
-    }
-    HIP_TRY(hipStreamSynchronize(st));   // the host vectors above go out of scope
-    T.n = n;
-    T.dirty = false;
-    return UCFP_OK;
-}
-
-int do_upsert(ucfp_minhash_index* ix, uint32_t tenant, const uint64_t* ids, const uint8_t* records, size_t n) {
-    if (!n) return UCFP_OK;
-    if (!ids || !records) return capi_fail(UCFP_E_INVALID, "ids/records is NULL");
-    Tenant& T = ix->tenants[tenant];
-    const size_t rec_bytes = ix->rec_bytes();
-    for (size_t i = 0; i < n; i++) {
-        const uint8_t* slots = records + i * rec_bytes + kHeaderBytes;
-        T.recs.insert_or_assign(T.recs.end(), ids[i], Row(slots, slots + 8 * (size_t)ix->h));   // the hint: ascending ids append in constant time
-    }
-    T.dirty = true;
-    return UCFP_OK;
-}
+using Tenant = ucfp_minhash_index::Tenant;
 
 template <int C, int QT, int WQ>
 void launch_keys(const Tenant& T, const uint8_t* d_q, uint32_t cnt, uint32_t min_agree, uint32_t h, uint32_t* keymat,
@@ -247,73 +190,31 @@ void dispatch_keys(const Tenant& T, const uint8_t* qp, uint32_t cnt, uint32_t mi
 }
 
 int query_impl(ucfp_minhash_index* ix, uint32_t tenant, const uint8_t* d_q, size_t nq, uint32_t k, uint32_t min_agree,
-               uint64_t* d_ids, uint32_t* d_agree, float* d_scores, uint32_t* d_n, hipStream_t st) {
-    int rc;
-    if (k == 0) {
-        HIP_TRY(hipMemsetAsync(d_n, 0, nq * 4, st));
-        return UCFP_OK;
-    }
-    auto it = ix->tenants.find(tenant);
-    if (it != ix->tenants.end() && it->second.dirty && (rc = rebuild(ix, it->second, st))) return rc;
-    if (it == ix->tenants.end() || it->second.n == 0) {
-        hipLaunchKernelGGL(mh_empty, dim3((unsigned)((nq * k + 255) / 256)), dim3(256), 0, st, nq, k, d_ids, d_agree, d_scores, d_n);
-        HIP_TRY(hipGetLastError());
-        return UCFP_OK;
-    }
-    Tenant& T = it->second;
-    const size_t n = T.n;
-    // queries per pass: the key matrix stays below key_bytes; queries ride on gridDim.y of the select kernel
-    size_t chunk = std::max<size_t>(1, ix->key_bytes / (4 * n));
-    chunk = std::min<size_t>(std::min<size_t>(chunk, 32768), nq);
-    // mh_keys numbers its blocks (query group, row block) in one dimension
+               const ucfp::ScanOut& o, hipStream_t st) {
     const uint32_t h = ix->h, tile = tile_of(ix->chunks);
-    if (((chunk + tile - 1) / tile) * ((n + kBlockRows - 1) / kBlockRows) > 0x7fffffffu)
-        return capi_fail(UCFP_E_INVALID, "too many rows for one launch (%zu)", n);
-    const ucfp::SelectPlan sp = ucfp::select_plan(n, (uint32_t)chunk);
-    const size_t tmp_e = 2 * ucfp::topk_merge_tmp_entries(sp.slices, (uint32_t)chunk, k);   // both tree levels
-    size_t off = 0;
-    const size_t o_keys = off;
-    off = align256(off + chunk * n * 4 + 64);
-    const size_t o_pid = off;
-    off = align256(off + (size_t)sp.slices * chunk * k * 8);
-    const size_t o_pk = off;
-    off = align256(off + (size_t)sp.slices * chunk * k * 4);
-    const size_t o_pc = off;
-    off = align256(off + (size_t)sp.slices * chunk * 4);
-    const size_t o_tid = off;
-    off = align256(off + tmp_e * 8);
-    const size_t o_tk = off;
-    off = align256(off + tmp_e * 4);
-    if ((rc = ix->q_ws.ensure(off))) return rc;
-    uint8_t* w = ix->q_ws.as<uint8_t>();
-    uint32_t* keymat = reinterpret_cast<uint32_t*>(w + o_keys);
-    for (size_t q0 = 0; q0 < nq; q0 += chunk) {
-        const uint32_t cnt = (uint32_t)std::min(chunk, nq - q0);
-        const uint8_t* qp = d_q + q0 * ix->rec_bytes();
-        switch (ix->chunks) {
-            case 1: dispatch_keys<1>(T, qp, cnt, min_agree, h, keymat, st); break;
-            case 2: dispatch_keys<2>(T, qp, cnt, min_agree, h, keymat, st); break;
-            case 3: dispatch_keys<3>(T, qp, cnt, min_agree, h, keymat, st); break;
-            case 4: dispatch_keys<4>(T, qp, cnt, min_agree, h, keymat, st); break;
-            case 5: dispatch_keys<5>(T, qp, cnt, min_agree, h, keymat, st); break;
-            case 6: dispatch_keys<6>(T, qp, cnt, min_agree, h, keymat, st); break;
-            case 7: dispatch_keys<7>(T, qp, cnt, min_agree, h, keymat, st); break;
-            default: dispatch_keys<8>(T, qp, cnt, min_agree, h, keymat, st); break;
-        }
-        HIP_TRY(hipGetLastError());
-        ucfp::SelectPlan pl = ucfp::select_plan(n, cnt);
-        if (pl.slices > sp.slices) {   // the partial lists were sized for the full pass
-            pl.per_slice = (((n + sp.slices - 1) / sp.slices) + 63) & ~(size_t)63;
-            pl.slices = (uint32_t)((n + pl.per_slice - 1) / pl.per_slice);
-        }
-        ucfp::launch_select_topk_u32(keymat, T.ids.as<uint64_t>(), n, pl, cnt, k, reinterpret_cast<uint64_t*>(w + o_pid),
-                                     reinterpret_cast<uint32_t*>(w + o_pk), reinterpret_cast<uint32_t*>(w + o_pc), st);
-        ucfp::launch_topk_merge_tree_u32(reinterpret_cast<uint64_t*>(w + o_pid), reinterpret_cast<uint32_t*>(w + o_pk), pl.slices,
-                                         cnt, k, reinterpret_cast<uint64_t*>(w + o_tid), reinterpret_cast<uint32_t*>(w + o_tk),
-                                         d_ids + q0 * k, d_agree + q0 * k, d_n + q0, st);
-        HIP_TRY(hipGetLastError());
-    }
-    hipLaunchKernelGGL(mh_scores, dim3((unsigned)((nq * k + 255) / 256)), dim3(256), 0, st, d_agree, nq * k, h, d_scores);
+    uint32_t* agree = nullptr;
+    const int rc = ucfp::scan_query(
+        ix, tenant, nq, k, 0, o, st, &agree, [](uint8_t*) {},   // the kernel reads the records as they are
+        [&](const Tenant& T, size_t q0, uint32_t cnt, uint32_t* keymat) {
+            const uint8_t* qp = d_q + q0 * ix->rec_bytes();
+            switch (ix->chunks) {
+                case 1: dispatch_keys<1>(T, qp, cnt, min_agree, h, keymat, st); break;
+                case 2: dispatch_keys<2>(T, qp, cnt, min_agree, h, keymat, st); break;
+                case 3: dispatch_keys<3>(T, qp, cnt, min_agree, h, keymat, st); break;
+                case 4: dispatch_keys<4>(T, qp, cnt, min_agree, h, keymat, st); break;
+                case 5: dispatch_keys<5>(T, qp, cnt, min_agree, h, keymat, st); break;
+                case 6: dispatch_keys<6>(T, qp, cnt, min_agree, h, keymat, st); break;
+                case 7: dispatch_keys<7>(T, qp, cnt, min_agree, h, keymat, st); break;
+                default: dispatch_keys<8>(T, qp, cnt, min_agree, h, keymat, st); break;
+            }
+        },
+        [&](size_t n, size_t chunk) {   // mh_keys numbers its blocks (query group, row block) in one dimension
+            if (((chunk + tile - 1) / tile) * ((n + kBlockRows - 1) / kBlockRows) > 0x7fffffffu)
+                return capi_fail(UCFP_E_INVALID, "too many rows for one launch (%zu)", n);
+            return (int)UCFP_OK;
+        });
+    if (rc || !agree) return rc;
+    hipLaunchKernelGGL(mh_scores, dim3((unsigned)((nq * k + 255) / 256)), dim3(256), 0, st, agree, nq * k, h, o.scores);
     HIP_TRY(hipGetLastError());
     return UCFP_OK;
 }
@@ -351,8 +252,7 @@ int ucfp_minhash_index_create_h(ucfp_ctx* ctx, uint32_t flags, uint32_t h, ucfp_
     if (rc) return rc;
     (*out)->h = h;
     (*out)->chunks = (h + kChunkSlots - 1) / kChunkSlots;
-    // a smaller key matrix means more passes over the rows: for tuning, and for tests of the pass loop at small sizes
-    if (const char* e = getenv("UCFP_MINHASH_KEY_BYTES")) (*out)->key_bytes = std::max<size_t>(4096, strtoull(e, nullptr, 10));
+    ucfp::scan_key_bytes_env(*out, "UCFP_MINHASH_KEY_BYTES");
     return rc;
 }
 
@@ -362,97 +262,43 @@ int ucfp_minhash_index_create(ucfp_ctx* ctx, uint32_t flags, ucfp_minhash_index*
 
 uint32_t ucfp_minhash_index_slots(ucfp_minhash_index* ix) { return ix ? ix->h : 0; }
 
-void ucfp_minhash_index_destroy(ucfp_minhash_index* ix) {
-    if (!ix) return;
-    ix->quiesce();
-    for (auto& kv : ix->tenants)
-        for (DevArr* a : {&kv.second.rows, &kv.second.ids}) a->release();
-    for (DevArr* a : {&ix->q_in, &ix->q_ws, &ix->q_out}) a->release();
-    delete ix;
-}
+void ucfp_minhash_index_destroy(ucfp_minhash_index* ix) { ucfp::scan_destroy(ix); }
 
 int ucfp_minhash_index_upsert(ucfp_minhash_index* ix, uint32_t tenant, const uint64_t* ids, const uint8_t* records, size_t n) {
-    if (!ix) return capi_fail(UCFP_E_INVALID, "index is NULL");
-    std::lock_guard<std::mutex> lk(ix->mu);
-    return do_upsert(ix, tenant, ids, records, n);
+    return ucfp::scan_upsert(ix, tenant, ids, records, n, "records");
 }
 
 int ucfp_minhash_index_upsert_dev(ucfp_minhash_index* ix, uint32_t tenant, const uint64_t* d_ids, const uint8_t* d_records,
                                   size_t n, void* stream) {
-    if (!ix) return capi_fail(UCFP_E_INVALID, "index is NULL");
-    if (!n) return UCFP_OK;
-    if (!d_ids || !d_records) return capi_fail(UCFP_E_INVALID, "ids/records is NULL");
-    std::lock_guard<std::mutex> lk(ix->mu);
-    HIP_TRY(hipSetDevice(ix->device));
-    hipStream_t st = (hipStream_t)stream;
-    // the row table lives on the host (mutations are bookkeeping; the device rows are rebuilt at the next query)
-    std::vector<uint64_t> ids(n);
-    const size_t rec_bytes = ix->rec_bytes();
-    std::vector<uint8_t> rows(n * rec_bytes);
-    HIP_TRY(hipMemcpyAsync(ids.data(), d_ids, n * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(rows.data(), d_records, n * rec_bytes, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return do_upsert(ix, tenant, ids.data(), rows.data(), n);
+    return ucfp::scan_upsert_dev(ix, tenant, d_ids, d_records, n, "records", stream);
 }
 
 int ucfp_minhash_index_delete(ucfp_minhash_index* ix, uint32_t tenant, const uint64_t* ids, size_t n, size_t* n_removed) {
-    if (!ix) return capi_fail(UCFP_E_INVALID, "index is NULL");
-    if (n && !ids) return capi_fail(UCFP_E_INVALID, "ids is NULL");
-    std::lock_guard<std::mutex> lk(ix->mu);
-    size_t removed = 0;
-    auto it = ix->tenants.find(tenant);
-    if (it != ix->tenants.end()) {
-        for (size_t i = 0; i < n; i++) removed += it->second.recs.erase(ids[i]);
-        if (removed) it->second.dirty = true;
-    }
-    if (n_removed) *n_removed = removed;
-    return UCFP_OK;
+    return ucfp::scan_delete(ix, tenant, ids, n, n_removed);
 }
 
-int ucfp_minhash_index_size(ucfp_minhash_index* ix, uint32_t tenant, size_t* rows) {
-    if (!ix) return capi_fail(UCFP_E_INVALID, "index is NULL");
-    std::lock_guard<std::mutex> lk(ix->mu);
-    auto it = ix->tenants.find(tenant);
-    if (rows) *rows = it == ix->tenants.end() ? 0 : it->second.recs.size();
-    return UCFP_OK;
-}
+int ucfp_minhash_index_size(ucfp_minhash_index* ix, uint32_t tenant, size_t* rows) { return ucfp::scan_size(ix, tenant, rows); }
 
-int ucfp_minhash_index_flush(ucfp_minhash_index* ix) { return ucfp::flush_dirty(ix, rebuild); }
+int ucfp_minhash_index_flush(ucfp_minhash_index* ix) { return ucfp::scan_flush(ix); }
 
 int ucfp_minhash_index_query_dev(ucfp_minhash_index* ix, uint32_t tenant, const uint8_t* d_records, size_t nq, uint32_t k,
                                  uint32_t min_agree, uint64_t* d_out_ids, uint32_t* d_out_agree, float* d_out_scores,
                                  uint32_t* d_out_n, void* stream) {
-    int rc = query_args(ix, d_records, nq, k, min_agree, d_out_ids, d_out_agree, d_out_scores, d_out_n);
+    const int rc = query_args(ix, d_records, nq, k, min_agree, d_out_ids, d_out_agree, d_out_scores, d_out_n);
     if (rc || nq == 0) return rc;
-    std::lock_guard<std::mutex> lk(ix->mu);
-    if ((rc = ix->begin())) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    rc = query_impl(ix, tenant, d_records, nq, k, min_agree, d_out_ids, d_out_agree, d_out_scores, d_out_n, st);
-    return ix->end(st, rc);
+    return ucfp::scan_query_dev(ix, stream, [&](hipStream_t st) {
+        return query_impl(ix, tenant, d_records, nq, k, min_agree, {d_out_ids, d_out_agree, d_out_scores, d_out_n}, st);
+    });
 }
 
 int ucfp_minhash_index_query(ucfp_minhash_index* ix, uint32_t tenant, const uint8_t* records, size_t nq, uint32_t k,
                              uint32_t min_agree, uint64_t* out_ids, uint32_t* out_agree, float* out_scores, uint32_t* out_n) {
-    int rc = query_args(ix, records, nq, k, min_agree, out_ids, out_agree, out_scores, out_n);
+    const int rc = query_args(ix, records, nq, k, min_agree, out_ids, out_agree, out_scores, out_n);
     if (rc || nq == 0) return rc;
-    std::lock_guard<std::mutex> lk(ix->mu);
-    if ((rc = ix->begin())) return rc;
-    hipStream_t st = ix->own;
-    const size_t nk = nq * k, rec_bytes = ix->rec_bytes();
-    const size_t o_agree = align256(nk * 8), o_sc = align256(o_agree + nk * 4), o_n = align256(o_sc + nk * 4);
-    if ((rc = ix->q_in.ensure(nq * rec_bytes)) || (rc = ix->q_out.ensure(o_n + nq * 4))) return rc;
-    HIP_TRY(hipMemcpyAsync(ix->q_in.p, records, nq * rec_bytes, hipMemcpyHostToDevice, st));
-    uint8_t* ob = ix->q_out.as<uint8_t>();
-    rc = query_impl(ix, tenant, ix->q_in.as<uint8_t>(), nq, k, min_agree, (uint64_t*)ob, (uint32_t*)(ob + o_agree),
-                    (float*)(ob + o_sc), (uint32_t*)(ob + o_n), st);
-    if (rc) return ix->end_sync(rc);
-    if (nk) {
-        HIP_TRY(hipMemcpyAsync(out_ids, ob, nk * 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(out_agree, ob + o_agree, nk * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(out_scores, ob + o_sc, nk * 4, hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(hipMemcpyAsync(out_n, ob + o_n, nq * 4, hipMemcpyDeviceToHost, st));
-    return ix->end_sync(UCFP_OK);
+    return ucfp::scan_query_host(ix, records, nq, k, out_ids, out_agree, out_scores, out_n,
+                                 [&](const uint8_t* d_q, const ucfp::ScanOut& o, hipStream_t st) {
+                                     return query_impl(ix, tenant, d_q, nq, k, min_agree, o, st);
+                                 });
 }
 
 }  // extern "C"

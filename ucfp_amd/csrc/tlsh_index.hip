@@ -20,25 +20,20 @@
 // and tl_scores turns the selected distances into scores.  ALU-bound once a pass carries more than a few queries: about
 // 60 integer instructions per (query, row) against 52 bytes per row.
 // Not here: sharding over GPUs, a search micro-batcher, save / load (ucfp_hip.h says so).
+// The tenant table, its mutations, the head of the rebuild, the pass loop and the call protocol are scan_index.h's
+// (UCFP_TLSH_KEY_BYTES at creation overrides the size of a pass's key matrix).
 
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <array>
-#include <cstdlib>
-#include <map>
-#include <unordered_map>
-#include <vector>
 
-#include "postings.h"
+#include "scan_index.h"
 
 namespace {
 
 constexpr uint32_t kRowBytes = UCFP_TLSH_BYTES;
 constexpr uint32_t kPlanes = 13;                 // dwords per stored row
 constexpr uint32_t kQueryWords = 16;             // dwords per packed query
-constexpr size_t kKeyBytes = (size_t)1 << 30;    // key matrix of one pass (UCFP_TLSH_KEY_BYTES at creation overrides it)
-constexpr size_t kMaxRows = (size_t)1 << 31;
 
 // packed 35-byte digests -> planes; word w of item i goes to out[w * stride_w + i * stride_i]
 __global__ void tl_pack(const uint8_t* __restrict__ in, size_t n, uint32_t* __restrict__ out, size_t stride_w, size_t stride_i) {
@@ -107,143 +102,51 @@ __global__ void tl_scores(const uint32_t* __restrict__ dist, size_t total, float
     scores[i] = d == kEmpty32 ? -1.0f : (float)(UCFP_TLSH_MAX_DISTANCE - d) / (float)UCFP_TLSH_MAX_DISTANCE;
 }
 
-// empty answers for every query (unknown tenant / no rows)
-__global__ void tl_empty(size_t nq, uint32_t k, uint64_t* __restrict__ out_ids, uint32_t* __restrict__ out_dist,
-                         float* __restrict__ out_scores, uint32_t* __restrict__ out_n) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < nq * k) {
-        out_ids[i] = kEmpty64;
-        out_dist[i] = kEmpty32;
-        out_scores[i] = -1.0f;
-    }
-    if (i < nq) out_n[i] = 0;
-}
-
-using Row = std::array<uint8_t, kRowBytes>;
-
-struct Tenant {
-    std::map<uint64_t, Row> recs;   // id -> digest; ascending id = row order, so ties by row are ties by id
-    bool dirty = true;
-    size_t n = 0, stride = 0;       // valid when !dirty
-    DevArr rows, ids;
-};
-
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+using Row = std::array<uint8_t, kRowBytes>;   // the digest: no allocation per row
 
 }  // namespace
 
-struct ucfp_tlsh_index : ucfp::IndexCore {
-    std::unordered_map<uint32_t, Tenant> tenants;
-    size_t key_bytes = kKeyBytes;
-    DevArr b_packed;                // rebuild staging
-    DevArr q_in, q_ws, q_out;       // host-pointer queries, the pass workspace, host-pointer answers
+struct ucfp_tlsh_index : ucfp::ScanIndex<Row> {
+    static constexpr uint8_t kPad = 0;
+    size_t rec_bytes() const { return kRowBytes; }
+    size_t row_len() const { return kRowBytes; }
+    Row to_row(const uint8_t* rec) const {
+        Row r;
+        memcpy(r.data(), rec, kRowBytes);
+        return r;
+    }
+    // n digests -> 13 planes of `stride` rows
+    int upload(DevArr& rows, const uint8_t* h_rows, size_t n, size_t stride, hipStream_t st) {
+        int rc;
+        if ((rc = rows.ensure(stride * kPlanes * 4)) || (rc = b_packed.ensure(n * kRowBytes))) return rc;
+        if (!n) return UCFP_OK;
+        HIP_TRY(hipMemcpyAsync(b_packed.p, h_rows, n * kRowBytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(rows.p, 0, stride * kPlanes * 4, st));
+        hipLaunchKernelGGL(tl_pack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, b_packed.as<uint8_t>(), n,
+                           rows.as<uint32_t>(), stride, (size_t)1);
+        HIP_TRY(hipGetLastError());
+        return UCFP_OK;
+    }
 };
 
 namespace {
 
-int rebuild(ucfp_tlsh_index* ix, Tenant& T, hipStream_t st) {
-    const size_t n = T.recs.size();
-    if (n >= kMaxRows) return capi_fail(UCFP_E_INVALID, "too many rows in one tenant (%zu)", n);
-    const size_t stride = (n + 63) & ~(size_t)63;
-    std::vector<uint8_t> h_rows(n * kRowBytes);
-    std::vector<uint64_t> h_ids(n);
-    size_t i = 0;
-    for (auto& kv : T.recs) {
-        h_ids[i] = kv.first;
-        memcpy(h_rows.data() + i * kRowBytes, kv.second.data(), kRowBytes);
-        i++;
-    }
-    int rc;
-    if ((rc = T.ids.ensure(n * 8)) || (rc = T.rows.ensure(stride * kPlanes * 4)) || (rc = ix->b_packed.ensure(n * kRowBytes)))
-        return rc;
-    if (n) {
-        HIP_TRY(hipMemcpyAsync(T.ids.p, h_ids.data(), n * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(ix->b_packed.p, h_rows.data(), n * kRowBytes, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemsetAsync(T.rows.p, 0, stride * kPlanes * 4, st));
-        hipLaunchKernelGGL(tl_pack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ix->b_packed.as<uint8_t>(), n,
-                           T.rows.as<uint32_t>(), stride, (size_t)1);
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipStreamSynchronize(st));   // the host vectors above go out of scope
-    T.n = n;
-    T.stride = stride;
-    T.dirty = false;
-    return UCFP_OK;
-}
-
-int do_upsert(ucfp_tlsh_index* ix, uint32_t tenant, const uint64_t* ids, const uint8_t* digests, size_t n) {
-    if (!n) return UCFP_OK;
-    if (!ids || !digests) return capi_fail(UCFP_E_INVALID, "ids/digests is NULL");
-    Tenant& T = ix->tenants[tenant];
-    for (size_t i = 0; i < n; i++) {
-        Row r;
-        memcpy(r.data(), digests + i * kRowBytes, kRowBytes);
-        T.recs.insert_or_assign(T.recs.end(), ids[i], r);   // the hint: ascending ids append in constant time
-    }
-    T.dirty = true;
-    return UCFP_OK;
-}
-
 int query_impl(ucfp_tlsh_index* ix, uint32_t tenant, const uint8_t* d_q, size_t nq, uint32_t k, uint32_t max_distance,
-               uint64_t* d_ids, uint32_t* d_dist, float* d_scores, uint32_t* d_n, hipStream_t st) {
-    int rc;
-    if (k == 0) {
-        HIP_TRY(hipMemsetAsync(d_n, 0, nq * 4, st));
-        return UCFP_OK;
-    }
-    auto it = ix->tenants.find(tenant);
-    if (it != ix->tenants.end() && it->second.dirty && (rc = rebuild(ix, it->second, st))) return rc;
-    if (it == ix->tenants.end() || it->second.n == 0) {
-        hipLaunchKernelGGL(tl_empty, dim3((unsigned)((nq * k + 255) / 256)), dim3(256), 0, st, nq, k, d_ids, d_dist, d_scores, d_n);
-        HIP_TRY(hipGetLastError());
-        return UCFP_OK;
-    }
-    Tenant& T = it->second;
-    const size_t n = T.n;
-    // queries per pass: the key matrix stays below key_bytes; queries ride on gridDim.y of the select kernel
-    size_t chunk = std::max<size_t>(1, ix->key_bytes / (4 * n));
-    chunk = std::min<size_t>(std::min<size_t>(chunk, 32768), nq);
-    const ucfp::SelectPlan sp = ucfp::select_plan(n, (uint32_t)chunk);
-    const size_t tmp_e = 2 * ucfp::topk_merge_tmp_entries(sp.slices, (uint32_t)chunk, k);   // both tree levels
-    size_t off = 0;
-    const size_t o_qw = off;
-    off = align256(off + nq * kQueryWords * 4);
-    const size_t o_keys = off;
-    off = align256(off + chunk * n * 4 + 64);
-    const size_t o_pid = off;
-    off = align256(off + (size_t)sp.slices * chunk * k * 8);
-    const size_t o_pk = off;
-    off = align256(off + (size_t)sp.slices * chunk * k * 4);
-    const size_t o_pc = off;
-    off = align256(off + (size_t)sp.slices * chunk * 4);
-    const size_t o_tid = off;
-    off = align256(off + tmp_e * 8);
-    const size_t o_tk = off;
-    off = align256(off + tmp_e * 4);
-    if ((rc = ix->q_ws.ensure(off))) return rc;
-    uint8_t* w = ix->q_ws.as<uint8_t>();
-    uint32_t* qw = reinterpret_cast<uint32_t*>(w + o_qw);
-    uint32_t* keymat = reinterpret_cast<uint32_t*>(w + o_keys);
-    hipLaunchKernelGGL(tl_pack, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, d_q, nq, qw, (size_t)1, (size_t)kQueryWords);
-    HIP_TRY(hipGetLastError());
-    for (size_t q0 = 0; q0 < nq; q0 += chunk) {
-        const uint32_t cnt = (uint32_t)std::min(chunk, nq - q0);
-        hipLaunchKernelGGL(tl_keys, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, T.rows.as<uint32_t>(), n,
-                           T.stride, qw + q0 * kQueryWords, cnt, max_distance, keymat);
-        HIP_TRY(hipGetLastError());
-        ucfp::SelectPlan pl = ucfp::select_plan(n, cnt);
-        if (pl.slices > sp.slices) {   // the partial lists were sized for the full pass
-            pl.per_slice = (((n + sp.slices - 1) / sp.slices) + 63) & ~(size_t)63;
-            pl.slices = (uint32_t)((n + pl.per_slice - 1) / pl.per_slice);
-        }
-        ucfp::launch_select_topk_u32(keymat, T.ids.as<uint64_t>(), n, pl, cnt, k, reinterpret_cast<uint64_t*>(w + o_pid),
-                                     reinterpret_cast<uint32_t*>(w + o_pk), reinterpret_cast<uint32_t*>(w + o_pc), st);
-        ucfp::launch_topk_merge_tree_u32(reinterpret_cast<uint64_t*>(w + o_pid), reinterpret_cast<uint32_t*>(w + o_pk), pl.slices,
-                                         cnt, k, reinterpret_cast<uint64_t*>(w + o_tid), reinterpret_cast<uint32_t*>(w + o_tk),
-                                         d_ids + q0 * k, d_dist + q0 * k, d_n + q0, st);
-        HIP_TRY(hipGetLastError());
-    }
-    hipLaunchKernelGGL(tl_scores, dim3((unsigned)((nq * k + 255) / 256)), dim3(256), 0, st, d_dist, nq * k, d_scores);
+               const ucfp::ScanOut& o, hipStream_t st) {
+    uint32_t* qw = nullptr;   // the packed queries, in the workspace
+    uint32_t* dist = nullptr;
+    const int rc = ucfp::scan_query(
+        ix, tenant, nq, k, nq * kQueryWords * 4, o, st, &dist,
+        [&](uint8_t* q_area) {
+            qw = reinterpret_cast<uint32_t*>(q_area);
+            hipLaunchKernelGGL(tl_pack, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, d_q, nq, qw, (size_t)1, (size_t)kQueryWords);
+        },
+        [&](const ucfp_tlsh_index::Tenant& T, size_t q0, uint32_t cnt, uint32_t* keymat) {
+            hipLaunchKernelGGL(tl_keys, dim3((unsigned)((T.n + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, T.rows.as<uint32_t>(),
+                               T.n, T.stride, qw + q0 * kQueryWords, cnt, max_distance, keymat);
+        });
+    if (rc || !dist) return rc;
+    hipLaunchKernelGGL(tl_scores, dim3((unsigned)((nq * k + 255) / 256)), dim3(256), 0, st, dist, nq * k, o.scores);
     HIP_TRY(hipGetLastError());
     return UCFP_OK;
 }
@@ -267,101 +170,47 @@ int ucfp_tlsh_index_create(ucfp_ctx* ctx, uint32_t flags, ucfp_tlsh_index** out)
     *out = nullptr;
     if (flags != 0) return capi_fail(UCFP_E_INVALID, "no TLSH index flags are defined (got %u)", flags);
     const int rc = ucfp::create_index(ctx, "TLSH index", out);
-    // a smaller key matrix means more passes over the rows: for tuning, and for tests of the pass loop at small sizes
-    if (const char* e = rc ? nullptr : getenv("UCFP_TLSH_KEY_BYTES")) (*out)->key_bytes = std::max<size_t>(4096, strtoull(e, nullptr, 10));
+    if (!rc) ucfp::scan_key_bytes_env(*out, "UCFP_TLSH_KEY_BYTES");
     return rc;
 }
 
-void ucfp_tlsh_index_destroy(ucfp_tlsh_index* ix) {
-    if (!ix) return;
-    ix->quiesce();
-    for (auto& kv : ix->tenants)
-        for (DevArr* a : {&kv.second.rows, &kv.second.ids}) a->release();
-    for (DevArr* a : {&ix->b_packed, &ix->q_in, &ix->q_ws, &ix->q_out}) a->release();
-    delete ix;
-}
+void ucfp_tlsh_index_destroy(ucfp_tlsh_index* ix) { ucfp::scan_destroy(ix); }
 
 int ucfp_tlsh_index_upsert(ucfp_tlsh_index* ix, uint32_t tenant, const uint64_t* ids, const uint8_t* digests, size_t n) {
-    if (!ix) return capi_fail(UCFP_E_INVALID, "index is NULL");
-    std::lock_guard<std::mutex> lk(ix->mu);
-    return do_upsert(ix, tenant, ids, digests, n);
+    return ucfp::scan_upsert(ix, tenant, ids, digests, n, "digests");
 }
 
 int ucfp_tlsh_index_upsert_dev(ucfp_tlsh_index* ix, uint32_t tenant, const uint64_t* d_ids, const uint8_t* d_digests, size_t n,
                                void* stream) {
-    if (!ix) return capi_fail(UCFP_E_INVALID, "index is NULL");
-    if (!n) return UCFP_OK;
-    if (!d_ids || !d_digests) return capi_fail(UCFP_E_INVALID, "ids/digests is NULL");
-    std::lock_guard<std::mutex> lk(ix->mu);
-    HIP_TRY(hipSetDevice(ix->device));
-    hipStream_t st = (hipStream_t)stream;
-    // the row table lives on the host (mutations are bookkeeping; the planes are rebuilt at the next query)
-    std::vector<uint64_t> ids(n);
-    std::vector<uint8_t> rows(n * kRowBytes);
-    HIP_TRY(hipMemcpyAsync(ids.data(), d_ids, n * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(rows.data(), d_digests, n * kRowBytes, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return do_upsert(ix, tenant, ids.data(), rows.data(), n);
+    return ucfp::scan_upsert_dev(ix, tenant, d_ids, d_digests, n, "digests", stream);
 }
 
 int ucfp_tlsh_index_delete(ucfp_tlsh_index* ix, uint32_t tenant, const uint64_t* ids, size_t n, size_t* n_removed) {
-    if (!ix) return capi_fail(UCFP_E_INVALID, "index is NULL");
-    if (n && !ids) return capi_fail(UCFP_E_INVALID, "ids is NULL");
-    std::lock_guard<std::mutex> lk(ix->mu);
-    size_t removed = 0;
-    auto it = ix->tenants.find(tenant);
-    if (it != ix->tenants.end()) {
-        for (size_t i = 0; i < n; i++) removed += it->second.recs.erase(ids[i]);
-        if (removed) it->second.dirty = true;
-    }
-    if (n_removed) *n_removed = removed;
-    return UCFP_OK;
+    return ucfp::scan_delete(ix, tenant, ids, n, n_removed);
 }
 
-int ucfp_tlsh_index_size(ucfp_tlsh_index* ix, uint32_t tenant, size_t* rows) {
-    if (!ix) return capi_fail(UCFP_E_INVALID, "index is NULL");
-    std::lock_guard<std::mutex> lk(ix->mu);
-    auto it = ix->tenants.find(tenant);
-    if (rows) *rows = it == ix->tenants.end() ? 0 : it->second.recs.size();
-    return UCFP_OK;
-}
+int ucfp_tlsh_index_size(ucfp_tlsh_index* ix, uint32_t tenant, size_t* rows) { return ucfp::scan_size(ix, tenant, rows); }
 
-int ucfp_tlsh_index_flush(ucfp_tlsh_index* ix) { return ucfp::flush_dirty(ix, rebuild); }
+int ucfp_tlsh_index_flush(ucfp_tlsh_index* ix) { return ucfp::scan_flush(ix); }
 
 int ucfp_tlsh_index_query_dev(ucfp_tlsh_index* ix, uint32_t tenant, const uint8_t* d_digests, size_t nq, uint32_t k,
                               uint32_t max_distance, uint64_t* d_out_ids, uint32_t* d_out_dist, float* d_out_scores,
                               uint32_t* d_out_n, void* stream) {
-    int rc = query_args(ix, d_digests, nq, k, d_out_ids, d_out_dist, d_out_scores, d_out_n);
+    const int rc = query_args(ix, d_digests, nq, k, d_out_ids, d_out_dist, d_out_scores, d_out_n);
     if (rc || nq == 0) return rc;
-    std::lock_guard<std::mutex> lk(ix->mu);
-    if ((rc = ix->begin())) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    rc = query_impl(ix, tenant, d_digests, nq, k, max_distance, d_out_ids, d_out_dist, d_out_scores, d_out_n, st);
-    return ix->end(st, rc);
+    return ucfp::scan_query_dev(ix, stream, [&](hipStream_t st) {
+        return query_impl(ix, tenant, d_digests, nq, k, max_distance, {d_out_ids, d_out_dist, d_out_scores, d_out_n}, st);
+    });
 }
 
 int ucfp_tlsh_index_query(ucfp_tlsh_index* ix, uint32_t tenant, const uint8_t* digests, size_t nq, uint32_t k,
                           uint32_t max_distance, uint64_t* out_ids, uint32_t* out_dist, float* out_scores, uint32_t* out_n) {
-    int rc = query_args(ix, digests, nq, k, out_ids, out_dist, out_scores, out_n);
+    const int rc = query_args(ix, digests, nq, k, out_ids, out_dist, out_scores, out_n);
     if (rc || nq == 0) return rc;
-    std::lock_guard<std::mutex> lk(ix->mu);
-    if ((rc = ix->begin())) return rc;
-    hipStream_t st = ix->own;
-    const size_t nk = nq * k;
-    const size_t o_dist = align256(nk * 8), o_sc = align256(o_dist + nk * 4), o_n = align256(o_sc + nk * 4);
-    if ((rc = ix->q_in.ensure(nq * kRowBytes)) || (rc = ix->q_out.ensure(o_n + nq * 4))) return rc;
-    HIP_TRY(hipMemcpyAsync(ix->q_in.p, digests, nq * kRowBytes, hipMemcpyHostToDevice, st));
-    uint8_t* ob = ix->q_out.as<uint8_t>();
-    rc = query_impl(ix, tenant, ix->q_in.as<uint8_t>(), nq, k, max_distance, (uint64_t*)ob, (uint32_t*)(ob + o_dist),
-                    (float*)(ob + o_sc), (uint32_t*)(ob + o_n), st);
-    if (rc) return ix->end_sync(rc);
-    if (nk) {
-        HIP_TRY(hipMemcpyAsync(out_ids, ob, nk * 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(out_dist, ob + o_dist, nk * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(out_scores, ob + o_sc, nk * 4, hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(hipMemcpyAsync(out_n, ob + o_n, nq * 4, hipMemcpyDeviceToHost, st));
-    return ix->end_sync(UCFP_OK);
+    return ucfp::scan_query_host(ix, digests, nq, k, out_ids, out_dist, out_scores, out_n,
+                                 [&](const uint8_t* d_q, const ucfp::ScanOut& o, hipStream_t st) {
+                                     return query_impl(ix, tenant, d_q, nq, k, max_distance, o, st);
+                                 });
 }
 
 }  // extern "C"

@@ -481,20 +481,36 @@ class HaitsmaIndex:
                                                           stream or None))
 
 
-class TlshIndex:
-    """Thin RAII wrapper over one ucfp_tlsh_index (DESIGN A15): rows and queries are TLSH digests (35 bytes each, or
-    any form text.tlsh_digest_bytes takes); a query answers the k rows at the smallest TLSH distance, exactly."""
+def _pack_rows(rows, rec_bytes: int, to_bytes=None) -> np.ndarray:
+    """A uint8 array of whole records, or a list of records, -> uint8 [n, rec_bytes] (one spare row behind it, so the
+    pointer is never to an empty buffer).  A list item goes through `to_bytes`, which checks it; without one every item
+    (and an array) must be rec_bytes bytes each."""
+    if isinstance(rows, np.ndarray) and rows.dtype == np.uint8:
+        if to_bytes is None and rows.size % rec_bytes:
+            raise InvalidArgument(f"records must be {rec_bytes} bytes each")
+        rows = rows.reshape(-1, rec_bytes)
+    else:
+        rows = [(to_bytes or bytes)(r) for r in rows]
+        if to_bytes is None and any(len(r) != rec_bytes for r in rows):
+            raise InvalidArgument(f"records must be {rec_bytes} bytes each")
+        rows = np.frombuffer(b"".join(rows), np.uint8).reshape(-1, rec_bytes)
+    buf = np.zeros((rows.shape[0] + 1, rec_bytes), np.uint8)
+    buf[:rows.shape[0]] = rows
+    return buf[:rows.shape[0]]
 
-    def __init__(self, flags: int = 0, ctx=None):
-        self._lib = _lib.load()
-        self.ctx = ctx or _lib.current_context()
-        h = C.c_void_p()
-        _lib.check(self._lib.ucfp_tlsh_index_create(self.ctx.handle, flags, C.byref(h)))
-        self.handle = h
+
+class _ScanIndex:
+    """What TlshIndex, MinHashIndex and ImageMatchIndex share, as their C side does (scan_index.h): the calls
+    ucfp_<_name>_index_* that do not depend on what a row is.  A subclass creates `handle` and packs rows in `_pack`."""
+    _name = ""              # the C symbol prefix
+    _what = "records"       # how messages call the rows
+
+    def _call(self, fn: str, *args) -> None:
+        _lib.check(getattr(self._lib, f"ucfp_{self._name}_index_{fn}")(self.handle, *args))
 
     def close(self):
         if getattr(self, "handle", None):
-            self._lib.ucfp_tlsh_index_destroy(self.handle)
+            getattr(self._lib, f"ucfp_{self._name}_index_destroy")(self.handle)
             self.handle = None
 
     def __del__(self):
@@ -503,30 +519,53 @@ class TlshIndex:
         except Exception:
             pass
 
-    def upsert(self, tenant: int, ids, digests) -> None:
-        """ids [n]; digests: uint8 [n, 35], or n digests as bytes / strings."""
+    def upsert(self, tenant: int, ids, records) -> None:
+        """ids [n]; records: uint8 [n, bytes of a record], or n records as bytes."""
         ids = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
-        rows = _pack_digests(digests)
+        rows = self._pack(records)
         if rows.shape[0] != ids.shape[0]:
-            raise InvalidArgument("ids and digests disagree on the number of rows")
-        _lib.check(self._lib.ucfp_tlsh_index_upsert(self.handle, tenant, ids.ctypes.data, rows.ctypes.data, ids.shape[0]))
+            raise InvalidArgument(f"ids and {self._what} disagree on the number of rows")
+        self._call("upsert", tenant, ids.ctypes.data, rows.ctypes.data, ids.shape[0])
 
-    def upsert_dev(self, tenant: int, ids_ptr: int, digests_ptr: int, n: int, stream: int = 0) -> None:
-        _lib.check(self._lib.ucfp_tlsh_index_upsert_dev(self.handle, tenant, ids_ptr, digests_ptr, n, stream or None))
+    def upsert_dev(self, tenant: int, ids_ptr: int, records_ptr: int, n: int, stream: int = 0) -> None:
+        self._call("upsert_dev", tenant, ids_ptr, records_ptr, n, stream or None)
 
     def delete(self, tenant: int, ids) -> int:
         ids = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
         removed = C.c_size_t(0)
-        _lib.check(self._lib.ucfp_tlsh_index_delete(self.handle, tenant, ids.ctypes.data, ids.shape[0], C.byref(removed)))
+        self._call("delete", tenant, ids.ctypes.data, ids.shape[0], C.byref(removed))
         return int(removed.value)
 
     def size(self, tenant: int) -> int:
         r = C.c_size_t(0)
-        _lib.check(self._lib.ucfp_tlsh_index_size(self.handle, tenant, C.byref(r)))
+        self._call("size", tenant, C.byref(r))
         return int(r.value)
 
     def flush(self) -> None:
-        _lib.check(self._lib.ucfp_tlsh_index_flush(self.handle))
+        self._call("flush")
+
+
+class TlshIndex(_ScanIndex):
+    """Thin RAII wrapper over one ucfp_tlsh_index (DESIGN A15): rows and queries are TLSH digests (35 bytes each, or
+    any form text.tlsh_digest_bytes takes); a query answers the k rows at the smallest TLSH distance, exactly."""
+    _name, _what = "tlsh", "digests"
+
+    def __init__(self, flags: int = 0, ctx=None):
+        self._lib = _lib.load()
+        self.ctx = ctx or _lib.current_context()
+        h = C.c_void_p()
+        _lib.check(self._lib.ucfp_tlsh_index_create(self.ctx.handle, flags, C.byref(h)))
+        self.handle = h
+
+    def _pack(self, digests) -> np.ndarray:
+        return _pack_digests(digests)
+
+    def upsert(self, tenant: int, ids, digests) -> None:
+        """ids [n]; digests: uint8 [n, 35], or n digests as bytes / strings."""
+        super().upsert(tenant, ids, digests)
+
+    def upsert_dev(self, tenant: int, ids_ptr: int, digests_ptr: int, n: int, stream: int = 0) -> None:
+        super().upsert_dev(tenant, ids_ptr, digests_ptr, n, stream)
 
     def query(self, tenant: int, digests, k: int, max_distance: Optional[int] = None):
         """-> (ids [nq,k] u64, dist [nq,k] u32, scores [nq,k] f32, counts [nq] u32); rows farther than `max_distance`
@@ -551,23 +590,18 @@ class TlshIndex:
 
 
 def _pack_digests(digests) -> np.ndarray:
-    """-> uint8 [n, 35] (one spare row behind it, so the pointer is never to an empty buffer)."""
+    """-> uint8 [n, 35]; a single bytes or str is one digest."""
     from .text import TLSH_BYTES, tlsh_digest_bytes
-    if isinstance(digests, np.ndarray) and digests.dtype == np.uint8:
-        rows = digests.reshape(-1, TLSH_BYTES)
-    else:
-        if isinstance(digests, (bytes, bytearray, str)):
-            digests = [digests]
-        rows = np.frombuffer(b"".join(tlsh_digest_bytes(d) for d in digests), np.uint8).reshape(-1, TLSH_BYTES)
-    buf = np.zeros((rows.shape[0] + 1, TLSH_BYTES), np.uint8)
-    buf[:rows.shape[0]] = rows
-    return buf[:rows.shape[0]]
+    if isinstance(digests, (bytes, bytearray, str)):
+        digests = [digests]
+    return _pack_rows(digests, TLSH_BYTES, tlsh_digest_bytes)
 
 
-class MinHashIndex:
+class MinHashIndex(_ScanIndex):
     """Thin RAII wrapper over one ucfp_minhash_index (DESIGN A17, T10): rows and queries are MinHash records of `h`
     slots (8 + 8 h bytes each; 1032 at the default 128); a query answers the k rows that agree with it in the most slots,
     exactly, with score = agree / h."""
+    _name = "minhash"
 
     def __init__(self, flags: int = 0, ctx=None, h: int = DEFAULT_H):
         self._lib = _lib.load()
@@ -578,48 +612,15 @@ class MinHashIndex:
         _lib.check(self._lib.ucfp_minhash_index_create_h(self.ctx.handle, flags, self.h, C.byref(handle)))
         self.handle = handle
 
-    def close(self):
-        if getattr(self, "handle", None):
-            self._lib.ucfp_minhash_index_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def upsert(self, tenant: int, ids, records) -> None:
-        """ids [n]; records: uint8 [n, 8 + 8 h], or n records as bytes."""
-        ids = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
-        rows = _pack_minhash(records, self.rec_bytes)
-        if rows.shape[0] != ids.shape[0]:
-            raise InvalidArgument("ids and records disagree on the number of rows")
-        _lib.check(self._lib.ucfp_minhash_index_upsert(self.handle, tenant, ids.ctypes.data, rows.ctypes.data, ids.shape[0]))
-
-    def upsert_dev(self, tenant: int, ids_ptr: int, records_ptr: int, n: int, stream: int = 0) -> None:
-        _lib.check(self._lib.ucfp_minhash_index_upsert_dev(self.handle, tenant, ids_ptr, records_ptr, n, stream or None))
-
-    def delete(self, tenant: int, ids) -> int:
-        ids = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
-        removed = C.c_size_t(0)
-        _lib.check(self._lib.ucfp_minhash_index_delete(self.handle, tenant, ids.ctypes.data, ids.shape[0], C.byref(removed)))
-        return int(removed.value)
-
-    def size(self, tenant: int) -> int:
-        r = C.c_size_t(0)
-        _lib.check(self._lib.ucfp_minhash_index_size(self.handle, tenant, C.byref(r)))
-        return int(r.value)
-
-    def flush(self) -> None:
-        _lib.check(self._lib.ucfp_minhash_index_flush(self.handle))
+    def _pack(self, records) -> np.ndarray:
+        return _pack_minhash(records, self.rec_bytes)
 
     def query(self, tenant: int, records, k: int, min_agree: int = 1):
         """-> (ids [nq,k] u64, agree [nq,k] u32, scores [nq,k] f32, counts [nq] u32); rows that agree in fewer than
         `min_agree` slots are left out (0: every row is a hit)."""
         if not 0 <= int(min_agree) <= self.h:
             raise InvalidArgument(f"min_agree must be in [0, {self.h}] (got {min_agree!r})")
-        q = _pack_minhash(records, self.rec_bytes)
+        q = self._pack(records)
         nq = q.shape[0]
         kk = max(int(k), 1)
         ids = np.full((nq, kk), INVALID_ID, np.uint64)
@@ -639,28 +640,19 @@ class MinHashIndex:
 
 
 def _pack_minhash(records, rec_bytes: int = MINHASH_BYTES) -> np.ndarray:
-    """uint8 [n, rec_bytes], bytes (one record or several back to back) or a list of bytes -> uint8 [n, rec_bytes] (one
-    spare row behind it, so the pointer is never to an empty buffer)."""
+    """-> uint8 [n, rec_bytes]; bytes are one record or several back to back."""
     if isinstance(records, (bytes, bytearray)):
         records = np.frombuffer(bytes(records), np.uint8)
-    if isinstance(records, np.ndarray) and records.dtype == np.uint8:
-        if records.size % rec_bytes or (records.ndim == 2 and records.shape[1] != rec_bytes):
-            raise InvalidArgument(f"records must be {rec_bytes} bytes each")
-        rows = records.reshape(-1, rec_bytes)
-    else:
-        records = [bytes(r) for r in records]
-        if any(len(r) != rec_bytes for r in records):
-            raise InvalidArgument(f"records must be {rec_bytes} bytes each")
-        rows = np.frombuffer(b"".join(records), np.uint8).reshape(-1, rec_bytes)
-    buf = np.zeros((rows.shape[0] + 1, rec_bytes), np.uint8)
-    buf[:rows.shape[0]] = rows
-    return buf[:rows.shape[0]]
+    if isinstance(records, np.ndarray) and records.dtype == np.uint8 and records.ndim == 2 and records.shape[1] != rec_bytes:
+        raise InvalidArgument(f"records must be {rec_bytes} bytes each")
+    return _pack_rows(records, rec_bytes)
 
 
-class ImageMatchIndex:
+class ImageMatchIndex(_ScanIndex):
     """Thin RAII wrapper over one ucfp_image_match_index (DESIGN A16): rows and queries are whole image records of one
     size -- 168 bytes (`algo` AHASH, PHASH or DHASH) or the 536-byte bundle (MULTI); a query answers the k rows that score
     highest with global and block hashes together, exactly.  The MultiHashConfig is passed per query."""
+    _name = "image_match"
 
     def __init__(self, algo: int, flags: int = 0, ctx=None):
         self._lib = _lib.load()
@@ -671,59 +663,11 @@ class ImageMatchIndex:
         _lib.check(self._lib.ucfp_image_match_index_create(self.ctx.handle, self.algo, flags, C.byref(h)))
         self.handle = h
 
-    def close(self):
-        if getattr(self, "handle", None):
-            self._lib.ucfp_image_match_index_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def _pack(self, records) -> np.ndarray:
-        """-> uint8 [n, record_bytes] (one spare row behind it, so the pointer is never to an empty buffer)."""
-        rb = self.record_bytes
-        if isinstance(records, np.ndarray) and records.dtype == np.uint8:
-            if records.size % rb:
-                raise InvalidArgument(f"records must be {rb} bytes each")
-            rows = records.reshape(-1, rb)
-        else:
-            if isinstance(records, (bytes, bytearray)):
-                records = [records]
-            records = [bytes(r) for r in records]
-            if any(len(r) != rb for r in records):
-                raise InvalidArgument(f"records must be {rb} bytes each")
-            rows = np.frombuffer(b"".join(records), np.uint8).reshape(-1, rb)
-        buf = np.zeros((rows.shape[0] + 1, rb), np.uint8)
-        buf[:rows.shape[0]] = rows
-        return buf[:rows.shape[0]]
-
-    def upsert(self, tenant: int, ids, records) -> None:
-        """ids [n]; records: uint8 [n, record_bytes], or n records as bytes."""
-        ids = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
-        rows = self._pack(records)
-        if rows.shape[0] != ids.shape[0]:
-            raise InvalidArgument("ids and records disagree on the number of rows")
-        _lib.check(self._lib.ucfp_image_match_index_upsert(self.handle, tenant, ids.ctypes.data, rows.ctypes.data, ids.shape[0]))
-
-    def upsert_dev(self, tenant: int, ids_ptr: int, records_ptr: int, n: int, stream: int = 0) -> None:
-        _lib.check(self._lib.ucfp_image_match_index_upsert_dev(self.handle, tenant, ids_ptr, records_ptr, n, stream or None))
-
-    def delete(self, tenant: int, ids) -> int:
-        ids = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
-        removed = C.c_size_t(0)
-        _lib.check(self._lib.ucfp_image_match_index_delete(self.handle, tenant, ids.ctypes.data, ids.shape[0], C.byref(removed)))
-        return int(removed.value)
-
-    def size(self, tenant: int) -> int:
-        r = C.c_size_t(0)
-        _lib.check(self._lib.ucfp_image_match_index_size(self.handle, tenant, C.byref(r)))
-        return int(r.value)
-
-    def flush(self) -> None:
-        _lib.check(self._lib.ucfp_image_match_index_flush(self.handle))
+        """-> uint8 [n, record_bytes]; bytes are exactly one record."""
+        if isinstance(records, (bytes, bytearray)):
+            records = [records]
+        return _pack_rows(records, self.record_bytes)
 
     def query(self, tenant: int, records, k: int, config: Optional[MultiHashConfig] = None):
         """-> (ids [nq,k] u64, scores [nq,k] f32, counts [nq] u32); rows scoring below config.min_score are left out."""

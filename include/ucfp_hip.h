@@ -410,17 +410,39 @@ int ucfp_wang_streams_create(ucfp_ctx* ctx, uint32_t sample_rate, const ucfp_wan
  * after the rate and the config (UCFP_E_MODALITY). */
 int ucfp_wang_streams_create_ex(ucfp_ctx* ctx, uint32_t sample_rate, const ucfp_wang_config* cfg, uint32_t max_streams,
                                 uint32_t window_frames, ucfp_wang_streams** out);
+/* A set that takes its feed at ANY rate from 1 000 to 384 000 Hz and resamples it on the device (the
+ * reference resamples upstream of the session).  A stream that has received n input samples holds S(n) final 8 kHz
+ * samples (ucfp_wang_stream_samples); everything above then holds with S(n) in n's place: the hashes emitted so far
+ * are the offline hashes at that rate (ucfp_audio_wang_batch_dev over the one clip) with t_anchor <
+ * ucfp_wang_stream_frontier(S(n)), and the concatenation over all pushes equals that offline record byte for byte,
+ * however the feed is cut -- empty chunks, one-sample chunks and chunks that release no 8 kHz sample included.
+ * n_samples of open / push / push_dev / max_hashes count INPUT samples; t_anchor, the window origins and W stay in
+ * 8 kHz frames.  On top of the state above a slot carries the <= ceil(sample_rate / 8000) + 1 input samples the next
+ * 8 kHz sample needs.  A rate outside the range: UCFP_E_MODALITY ("sample rate"), judged with the config before
+ * anything else.  At 8000 this is ucfp_wang_streams_create_ex exactly.  A chunk is at most 2^29 input samples and may
+ * release at most 2^29 samples at 8 kHz: UCFP_E_INVALID otherwise, before any state changes. */
+int ucfp_wang_streams_create_sr(ucfp_ctx* ctx, uint32_t sample_rate, const ucfp_wang_config* cfg, uint32_t max_streams,
+                                uint32_t window_frames, ucfp_wang_streams** out);
 void ucfp_wang_streams_destroy(ucfp_wang_streams* s);
 int ucfp_wang_streams_open(ucfp_wang_streams* s, uint32_t* slot);      /* fresh stream, t = 0 (audio.rs:413-431) */
 int ucfp_wang_streams_close(ucfp_wang_streams* s, uint32_t slot);      /* discard, emit nothing */
 /* Host-only, no GPU: F(n) of A9 -- frames(n) = n < 1024 ? 0 : (n - 1024) / 128 + 1, J = max(0, frames - 7),
  * C = the first frame of the second holding frame J, F = max(0, C - target_zone_t). */
 uint64_t ucfp_wang_stream_frontier(uint64_t n_samples, const ucfp_wang_config* cfg);
+/* Host-only, no GPU: S(n) of A21, the final 8 kHz samples of a stream after n_samples input samples at sample_rate --
+ * n at 8000; otherwise S(0) = 0 and S(n) = min(ceil((n - 1) 8000 / sr), floor(n 8000 / sr)): the outputs whose right
+ * neighbour has arrived, capped at the offline length.  final != 0: floor(n 8000 / sr), the offline length.  0 for a
+ * rate outside [1000, 384000].  The frontier of such a stream is ucfp_wang_stream_frontier(S, cfg) (Panako:
+ * ucfp_panako_stream_frontier(S, cfg)). */
+uint64_t ucfp_wang_stream_samples(uint64_t n_samples, uint32_t sample_rate, int final);
 /* Host-only: device bytes a set holds per stream (0 for an out-of-range config). */
 size_t ucfp_wang_streams_state_bytes(const ucfp_wang_config* cfg);
 /* Host-only: the same with the ring of a window (A20; the reference has no audio matcher): state_bytes(cfg), plus
  * (window_frames != 0) 8 bytes of ring header and 8 bytes per window hash.  0 for out-of-range arguments. */
 size_t ucfp_wang_streams_state_bytes_ex(const ucfp_wang_config* cfg, uint32_t window_frames);
+/* Host-only: the same for a set of ucfp_wang_streams_create_sr (A21): state_bytes_ex(cfg, window_frames), plus
+ * 4 * (ceil(sample_rate / 8000) + 1) bytes of carried input for sample_rate != 8000.  0 for out-of-range arguments. */
+size_t ucfp_wang_streams_state_bytes_sr(const ucfp_wang_config* cfg, uint32_t window_frames, uint32_t sample_rate);
 /* Host-only: hashes one stream's window can hold (A20; the reference has no audio matcher); 0 for window_frames = 0 or
  * out-of-range arguments. */
 size_t ucfp_wang_streams_window_cap(const ucfp_wang_config* cfg, uint32_t window_frames);
@@ -470,6 +492,12 @@ typedef struct ucfp_panako_streams ucfp_panako_streams;
  * checked before anything else. */
 int ucfp_panako_streams_create(ucfp_ctx* ctx, uint32_t sample_rate, const ucfp_panako_config* cfg, uint32_t max_streams,
                                uint32_t window_frames, ucfp_panako_streams** out);
+/* As ucfp_wang_streams_create_sr (A21): a feed at any rate from 1 000 to 384 000 Hz, resampled on the device; the
+ * concatenation over all pushes equals ucfp_audio_panako_batch_dev over the one clip at that rate byte for byte.
+ * n_samples count input samples, S(n) = ucfp_wang_stream_samples; times and W stay in 8 kHz frames.  At 8000 this is
+ * ucfp_panako_streams_create exactly. */
+int ucfp_panako_streams_create_sr(ucfp_ctx* ctx, uint32_t sample_rate, const ucfp_panako_config* cfg,
+                                  uint32_t max_streams, uint32_t window_frames, ucfp_panako_streams** out);
 void ucfp_panako_streams_destroy(ucfp_panako_streams* s);
 int ucfp_panako_streams_open(ucfp_panako_streams* s, uint32_t* slot);     /* fresh stream, t = 0, empty window */
 int ucfp_panako_streams_close(ucfp_panako_streams* s, uint32_t slot);     /* discard, emit nothing */
@@ -477,6 +505,9 @@ int ucfp_panako_streams_close(ucfp_panako_streams* s, uint32_t slot);     /* dis
 uint64_t ucfp_panako_stream_frontier(uint64_t n_samples, const ucfp_panako_config* cfg);
 /* Host-only: device bytes a set holds per stream (0 for an out-of-range config or window). */
 size_t ucfp_panako_streams_state_bytes(const ucfp_panako_config* cfg, uint32_t window_frames);
+/* Host-only: the same for a set of ucfp_panako_streams_create_sr (A21): plus 4 * (ceil(sample_rate / 8000) + 1) bytes
+ * of carried input for sample_rate != 8000.  0 for out-of-range arguments. */
+size_t ucfp_panako_streams_state_bytes_sr(const ucfp_panako_config* cfg, uint32_t window_frames, uint32_t sample_rate);
 /* Host-only: records one stream's window can hold (0 for window_frames = 0 or out-of-range arguments). */
 size_t ucfp_panako_streams_window_cap(const ucfp_panako_config* cfg, uint32_t window_frames);
 /* Upper bound on the records a push can emit (0 for an invalid push). */

@@ -360,6 +360,10 @@ SIGNATURES = {
                                            C.POINTER(C.c_void_p)]),
     "ucfp_wang_streams_create_ex": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(WangConfig), C.c_uint32, C.c_uint32,
                                               C.POINTER(C.c_void_p)]),
+    "ucfp_wang_streams_create_sr": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(WangConfig), C.c_uint32, C.c_uint32,
+                                              C.POINTER(C.c_void_p)]),
+    "ucfp_wang_stream_samples": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_int]),
+    "ucfp_wang_streams_state_bytes_sr": (C.c_size_t, [C.POINTER(WangConfig), C.c_uint32, C.c_uint32]),
     "ucfp_wang_streams_destroy": (None, [C.c_void_p]),
     "ucfp_wang_streams_open": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "ucfp_wang_streams_close": (C.c_int, [C.c_void_p, C.c_uint32]),
@@ -376,6 +380,9 @@ SIGNATURES = {
                                                 C.c_void_p, C.c_void_p]),
     "ucfp_panako_streams_create": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(PanakoConfig), C.c_uint32, C.c_uint32,
                                              C.POINTER(C.c_void_p)]),
+    "ucfp_panako_streams_create_sr": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(PanakoConfig), C.c_uint32, C.c_uint32,
+                                                C.POINTER(C.c_void_p)]),
+    "ucfp_panako_streams_state_bytes_sr": (C.c_size_t, [C.POINTER(PanakoConfig), C.c_uint32, C.c_uint32]),
     "ucfp_panako_streams_destroy": (None, [C.c_void_p]),
     "ucfp_panako_streams_open": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "ucfp_panako_streams_close": (C.c_int, [C.c_void_p, C.c_uint32]),

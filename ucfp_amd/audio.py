@@ -322,19 +322,29 @@ class WangStreams(AudioStreamSet):
     by one chunk each with one launch sequence and returns the hashes each one emits now -- exactly the offline hashes
     with t_anchor < frontier(n) so far, the rest on the final push (t_anchor = frames since `open`).  With
     `window_frames` = W > 0, `windows` hands out each stream's latest W frames of hashes, rebased to the
-    window's origin, in the ragged shape `LandmarkIndex.query_dev` / ucfp_landmark_index_query_dev take."""
+    window's origin, in the ragged shape `LandmarkIndex.query_dev` / ucfp_landmark_index_query_dev take.  With
+    `resample=True` the set takes its feed at any `sample_rate` from 1 to 384 kHz and resamples it on
+    the device: counts are input samples, the pushes add up to `wang_hashes_batch` of the feed at that rate, and times
+    and windows stay in 8 kHz frames."""
     _abi, _cap_entry, _row = "ucfp_wang_streams", "max_hashes", (2,)
 
     def __init__(self, max_streams: int, cfg: Optional[WangConfig] = None, sample_rate: int = WANG_SR, ctx=None, *,
-                 window_frames: int = 0):
+                 window_frames: int = 0, resample: bool = False):
         self._cfg = (cfg or WangConfig())._c()
-        self._create(ctx, "create_ex", sample_rate, C.byref(self._cfg), max_streams, window_frames)
+        self._create(ctx, "create_sr" if resample else "create_ex", sample_rate, C.byref(self._cfg), max_streams,
+                     window_frames)
         self.max_streams, self.window_frames = max_streams, window_frames
+        self.sample_rate = sample_rate
         self.window_cap = int(self._lib.ucfp_wang_streams_window_cap(C.byref(self._cfg), window_frames))
 
+    def final_samples(self, n_samples: int, final: bool = False) -> int:
+        """S(n): the 8 kHz samples of a stream that are final once it has received n samples at the set's rate."""
+        return int(self._lib.ucfp_wang_stream_samples(n_samples, self.sample_rate, 1 if final else 0))
+
     def frontier(self, n_samples: int) -> int:
-        """F(n): after a non-final push, every hash with t_anchor < F(n) has been emitted, and no other."""
-        return int(self._lib.ucfp_wang_stream_frontier(n_samples, C.byref(self._cfg)))
+        """F(n), n in samples at the set's rate: after a non-final push, every hash with t_anchor < F(n) has been
+        emitted, and no other."""
+        return int(self._lib.ucfp_wang_stream_frontier(self.final_samples(n_samples), C.byref(self._cfg)))
 
     max_hashes = AudioStreamSet._max_rows
 
@@ -411,10 +421,12 @@ class StreamingWangSession(_StreamingSession):
     `finalize` returns one record with every hash (the offline hashes of the whole stream, byte for byte)."""
     _algorithm = ALGORITHM_WANG
 
-    def __init__(self, sample_rate: int, tenant_id: int, record_id: int):
-        if sample_rate != WANG_SR:
+    def __init__(self, sample_rate: int, tenant_id: int, record_id: int, *, resample: bool = False):
+        """`resample=True` (A21): any rate from 1 to 384 kHz, resampled on the device; `finalize` then returns the
+        record of `wang_hashes_batch` at that rate."""
+        if sample_rate != WANG_SR and not resample:
             raise ModalityError(f"Wang requires 8 kHz mono input (got {sample_rate} Hz); resample upstream")
-        self._start(WangStreams(1), tenant_id, record_id)
+        self._start(WangStreams(1, sample_rate=sample_rate, resample=resample), tenant_id, record_id)
 
 
 class HaitsmaStreams(AudioStreamSet):
@@ -487,23 +499,33 @@ class PanakoStreams(AudioStreamSet):
     them by one chunk each with one launch sequence and returns the records each one emits now -- exactly the offline
     records with t_a < frontier(n) so far, the rest on the final push (times = frames since `open`).  With
     `window_frames` = W > 0, `windows` hands out each stream's latest W frames of records, rebased to the window's
-    origin, in the ragged shape `PanakoIndex.query_dev` / ucfp_panako_index_query_dev take."""
+    origin, in the ragged shape `PanakoIndex.query_dev` / ucfp_panako_index_query_dev take.  With `resample=True`
+     the set takes its feed at any `sample_rate` from 1 to 384 kHz and resamples it on the device: counts
+    are input samples, the pushes add up to `panako_hashes_batch` of the feed at that rate, and times and windows stay
+    in 8 kHz frames."""
     _abi, _cap_entry, _row = "ucfp_panako_streams", "max_hashes", (4,)
 
     def __init__(self, max_streams: int, cfg: Optional[PanakoConfig] = None, window_frames: int = 0,
-                 sample_rate: int = WANG_SR, ctx=None):
+                 sample_rate: int = WANG_SR, ctx=None, *, resample: bool = False):
         self._cfg = (cfg or PanakoConfig())._c()
-        self._create(ctx, "create", sample_rate, C.byref(self._cfg), max_streams, window_frames)
+        self._create(ctx, "create_sr" if resample else "create", sample_rate, C.byref(self._cfg), max_streams,
+                     window_frames)
         self.max_streams, self.window_frames = max_streams, window_frames
+        self.sample_rate = sample_rate
         self.window_cap = int(self._lib.ucfp_panako_streams_window_cap(C.byref(self._cfg), window_frames))
 
     def close(self, slot: int) -> None:
         """Discards the stream and its window; emits nothing."""
         super().close(slot)
 
+    def final_samples(self, n_samples: int, final: bool = False) -> int:
+        """S(n): the 8 kHz samples of a stream that are final once it has received n samples at the set's rate."""
+        return int(self._lib.ucfp_wang_stream_samples(n_samples, self.sample_rate, 1 if final else 0))
+
     def frontier(self, n_samples: int) -> int:
-        """F(n): after a non-final push, every record with t_a < F(n) has been emitted, and no other."""
-        return int(self._lib.ucfp_panako_stream_frontier(n_samples, C.byref(self._cfg)))
+        """F(n), n in samples at the set's rate: after a non-final push, every record with t_a < F(n) has been emitted,
+        and no other."""
+        return int(self._lib.ucfp_panako_stream_frontier(self.final_samples(n_samples), C.byref(self._cfg)))
 
     max_hashes = AudioStreamSet._max_rows
 
@@ -536,10 +558,13 @@ class StreamingPanakoSession(_StreamingSession):
     no records; `finalize` returns one record equal to `fingerprint_panako_with` of the whole stream byte for byte."""
     _algorithm = ALGORITHM_PANAKO
 
-    def __init__(self, sample_rate: int, tenant_id: int, record_id: int, cfg: Optional[PanakoConfig] = None):
-        if sample_rate != WANG_SR:
+    def __init__(self, sample_rate: int, tenant_id: int, record_id: int, cfg: Optional[PanakoConfig] = None, *,
+                 resample: bool = False):
+        """`resample=True` (A21): any rate from 1 to 384 kHz, resampled on the device; `finalize` then returns the
+        record of `panako_hashes_batch` at that rate."""
+        if sample_rate != WANG_SR and not resample:
             raise ModalityError(f"Panako requires 8 kHz mono input (got {sample_rate} Hz); resample upstream")
-        self._start(PanakoStreams(1, cfg), tenant_id, record_id)
+        self._start(PanakoStreams(1, cfg, sample_rate=sample_rate, resample=resample), tenant_id, record_id)
 
     def _buffer(self, rows: int) -> np.ndarray:
         return _aligned_records(rows)

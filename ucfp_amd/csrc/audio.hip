@@ -60,6 +60,27 @@ __device__ __forceinline__ float resample_mix(float x0, float x1, float frac) {
     return x0 + mm;
 }
 
+// A stream set that resamples (A18 Haitsma, A21 Wang / Panako) keeps, per slot, the input samples the next output
+// still needs.  E is the set's push entry: the state carries inputs [c_in, n0), the chunk holds [n0, n1).
+// input sample a of the entry's stream, a in [c_in, n1)
+// (`carry` is not __restrict__: the save kernels write the buffer they read it from, behind a barrier)
+template <class E>
+__device__ __forceinline__ float stream_input(const E& e, const float* carry, uint32_t carry_cap,
+                                              const float* __restrict__ pcm, uint64_t a) {
+    return a < e.n0 ? carry[(size_t)e.slot * carry_cap + (a - e.c_in)] : pcm[e.chunk_off + (a - e.n0)];
+}
+// output sample o (ABSOLUTE, since `open`) of the entry's stream, final by the set's emission rule: idx + 1 < n1,
+// except on the final push, which clamps as A1 does at the end of a clip
+template <class E>
+__device__ __forceinline__ float stream_resampled(const E& e, const float* carry, uint32_t carry_cap,
+                                                  const float* __restrict__ pcm, uint64_t o, uint32_t sr_in,
+                                                  uint32_t sr_out) {
+    const ResamplePos p = resample_pos(o, sr_in, sr_out);
+    uint64_t a1 = p.idx + 1;
+    if (e.fin && a1 >= e.n1) a1 = e.n1 - 1;
+    return resample_mix(stream_input(e, carry, carry_cap, pcm, p.idx), stream_input(e, carry, carry_cap, pcm, a1), p.frac);
+}
+
 __global__ void resample_linear_kernel(const float* __restrict__ in, size_t n, uint32_t sr_in, uint32_t sr_out,
                                        float* __restrict__ out, size_t m) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1382,6 +1403,26 @@ __global__ void wang_streams_gather_kernel(const float* __restrict__ pcm, const 
     vbuf[g] = r < e.carry_in ? smp[(size_t)e.slot * kWangCarry + r] : pcm[e.chunk_off + (r - e.carry_in)];
 }
 
+// A21, in the gather's place on a set whose rate is not 8 kHz: virtual clip i = the carried 8 kHz samples of its stream,
+// then the 8 kHz samples that became final in this push (A1 at the absolute index, from the carried inputs and the chunk)
+__global__ void wang_streams_assemble_kernel(const float* __restrict__ pcm, const WangStreamEntry* __restrict__ ents,
+                                             const WangStreamRsEntry* __restrict__ rs_ents,
+                                             const uint32_t* __restrict__ v_base, uint32_t n,
+                                             const float* __restrict__ smp, WangStreamsRsDev rs,
+                                             float* __restrict__ vbuf) {
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= v_base[n]) return;
+    const uint32_t i = clip_of(v_base, n, g);
+    const uint32_t carry_in = ents[i].carry_in;
+    const uint32_t r = g - v_base[i];
+    if (r < carry_in) {
+        vbuf[g] = smp[(size_t)ents[i].slot * kWangCarry + r];
+        return;
+    }
+    const WangStreamRsEntry e = rs_ents[i];
+    vbuf[g] = stream_resampled(e, rs.carry, rs.carry_cap, pcm, e.s0 + (r - carry_in), rs.sr, (uint32_t)kWangSr);
+}
+
 // one wave per entry: its peak list = the retained peaks, then the selected peaks of its closed seconds (in order)
 __global__ __launch_bounds__(64) void wang_streams_peaks_kernel(const WangStreamClip* __restrict__ clips,
                                                                 const WangStreamEntry* __restrict__ ents,
@@ -1451,7 +1492,10 @@ __global__ void wang_streams_offsets_kernel(const uint32_t* __restrict__ pk_base
     if (i <= n) out_off[i] = pair_off[pk_base[i]];
 }
 
-// one workgroup per entry: what the next push needs goes back into the stream's state (a final push leaves it empty)
+// one workgroup per entry: what the next push needs goes back into the stream's state (a final push leaves it empty).
+// RESAMPLE (A21): the carried inputs too, which may move inside the slot's own buffer: each is read by the thread that
+// writes it, with a barrier in between (carry_cap <= 50 < the workgroup).
+template <bool RESAMPLE>
 __global__ __launch_bounds__(256) void wang_streams_save_kernel(const WangStreamClip* __restrict__ clips,
                                                                 const WangStreamEntry* __restrict__ ents,
                                                                 const uint32_t* __restrict__ pk_base,
@@ -1462,7 +1506,10 @@ __global__ __launch_bounds__(256) void wang_streams_save_kernel(const WangStream
                                                                 const uint32_t* __restrict__ cand_k,
                                                                 const float* __restrict__ cand_p,
                                                                 const uint32_t* __restrict__ ptk,
-                                                                const float* __restrict__ pp) {
+                                                                const float* __restrict__ pp,
+                                                                const float* __restrict__ pcm,
+                                                                const WangStreamRsEntry* __restrict__ rs_ents,
+                                                                WangStreamsRsDev rs) {
     __shared__ uint32_t first;
     const WangStreamClip cl = clips[blockIdx.x];
     const WangStreamEntry e = ents[blockIdx.x];
@@ -1473,6 +1520,13 @@ __global__ __launch_bounds__(256) void wang_streams_save_kernel(const WangStream
             st.ret_n[e.slot] = 0;
         }
         return;
+    }
+    if (RESAMPLE) {
+        const WangStreamRsEntry re = rs_ents[blockIdx.x];
+        const uint32_t n_carry = (uint32_t)(re.n1 - re.c_out);        // <= carry_cap
+        const float v = tid < n_carry ? stream_input(re, rs.carry, rs.carry_cap, pcm, re.c_out + tid) : 0.0f;
+        __syncthreads();
+        if (tid < n_carry) rs.carry[(size_t)e.slot * rs.carry_cap + tid] = v;
     }
     // samples from frame J - 7's first one on
     for (uint32_t i = tid; i < e.carry_out; i += 256)
@@ -1633,7 +1687,7 @@ __global__ __launch_bounds__(256) void streams_windows_kernel(const StreamWindow
 // input sample a of the entry's stream, a in [c_in, n1): carried in the state or in the chunk
 __device__ __forceinline__ float haitsma_stream_input(const HaitsmaStreamEntry& e, const HaitsmaStreamsDev& st,
                                                       const float* __restrict__ pcm, uint64_t a) {
-    return a < e.n0 ? st.carry[(size_t)e.slot * st.carry_cap + (a - e.c_in)] : pcm[e.chunk_off + (a - e.n0)];
+    return stream_input(e, st.carry, st.carry_cap, pcm, a);
 }
 
 // Assemble: run i = the carried tail of its stream, then the 5 kHz samples that became final (A1 at the absolute index)
@@ -1654,10 +1708,7 @@ __global__ void haitsma_streams_assemble_kernel(const float* __restrict__ pcm, c
         run[g] = haitsma_stream_input(e, st, pcm, o);
         return;
     }
-    const ResamplePos p = resample_pos(o, sr, (uint32_t)kHkSr);
-    uint64_t a1 = p.idx + 1;                     // < n1 by the emission rule, except on the final push
-    if (e.fin && a1 >= e.n1) a1 = e.n1 - 1;
-    run[g] = resample_mix(haitsma_stream_input(e, st, pcm, p.idx), haitsma_stream_input(e, st, pcm, a1), p.frac);
+    run[g] = stream_resampled(e, st.carry, st.carry_cap, pcm, o, sr, (uint32_t)kHkSr);
 }
 
 // frame g of the push -> where its 2048 samples start in `run`; fr_base is also the caller's output offset table
@@ -1998,7 +2049,7 @@ int launch_haitsma_batch(const float* pcm, const uint64_t* d_offsets, size_t n_t
 static_assert(kWangCandCap == (uint32_t)kCandCap, "");
 
 WangPushWs wang_push_layout(size_t n, size_t n_slots, size_t n_closed, size_t total_v, size_t total_cap,
-                            size_t judged, uint32_t pps) {
+                            size_t judged, uint32_t pps, bool resample) {
     auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
     WangPushWs w;
     w.n = n;
@@ -2015,6 +2066,8 @@ WangPushWs wang_push_layout(size_t n, size_t n_slots, size_t n_closed, size_t to
     w.seg_base = off;   off += (n + 1) * 4;
     w.pk_base = off;    off += (n + 1) * 4;
     w.n_closed_w = off; off += 4;
+    w.rs = off = (off + 7) & ~(size_t)7;
+    if (resample) off += n * sizeof(WangStreamRsEntry);
     w.tab_bytes = off;  off = align(off);
     w.vbuf = off;       off = align(off + total_v * 4);
     w.cand_cnt = off;   off = align(off + n_slots * 4);
@@ -2036,9 +2089,10 @@ WangPushWs wang_push_layout(size_t n, size_t n_slots, size_t n_closed, size_t to
 }
 
 // The table [ws + w.clips, ws + w.tab_bytes) is on the device already (the caller copies it in front of this).
-// The front end of a push, shared by Wang (A9) and Panako (A19): load, gather, stream, select, peaks -- whatever n is.
-static void launch_wang_streams_front(const float* pcm, const WangStreamsDev& st, uint32_t pps, uint8_t* ws,
-                                      const WangPushWs& w, hipStream_t stream) {
+// The front end of a push, shared by Wang (A9) and Panako (A19): load, gather (A21: assemble on a resampling set),
+// stream, select, peaks -- whatever n is.
+static void launch_wang_streams_front(const float* pcm, const WangStreamsDev& st, const WangStreamsRsDev& rs, uint32_t pps,
+                                      uint8_t* ws, const WangPushWs& w, hipStream_t stream) {
     const uint32_t n = (uint32_t)w.n;
     auto f32 = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
     auto u32 = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
@@ -2049,7 +2103,11 @@ static void launch_wang_streams_front(const float* pcm, const WangStreamsDev& st
     const uint32_t* pk_base = u32(w.pk_base);
     hipLaunchKernelGGL(wang_streams_load_kernel, dim3(n), dim3(64), 0, stream, clips, ents, st, u32(w.cand_cnt),
                        u32(w.cand_t), u32(w.cand_k), f32(w.cand_p));
-    if (w.total_v)
+    if (w.total_v && rs.sr != (uint32_t)kWangSr)
+        hipLaunchKernelGGL(wang_streams_assemble_kernel, dim3(blocks_for(w.total_v, 256)), dim3(256), 0, stream, pcm, ents,
+                           reinterpret_cast<const WangStreamRsEntry*>(ws + w.rs), v_base, n, (const float*)st.smp, rs,
+                           f32(w.vbuf));
+    else if (w.total_v)
         hipLaunchKernelGGL(wang_streams_gather_kernel, dim3(blocks_for(w.total_v, 256)), dim3(256), 0, stream, pcm, ents,
                            v_base, n, (const float*)st.smp, f32(w.vbuf));
     if (w.n_seg) {
@@ -2071,8 +2129,8 @@ static void launch_wang_streams_front(const float* pcm, const WangStreamsDev& st
 }
 
 // the end of a push, behind either back end: per-entry output offsets, then the streams' state for the next push
-static void launch_wang_streams_back(const WangStreamsDev& st, uint8_t* ws, const WangPushWs& w, uint64_t* d_out_off,
-                                     hipStream_t stream) {
+static void launch_wang_streams_back(const float* pcm, const WangStreamsDev& st, const WangStreamsRsDev& rs, uint8_t* ws,
+                                     const WangPushWs& w, uint64_t* d_out_off, hipStream_t stream) {
     const uint32_t n = (uint32_t)w.n;
     auto f32 = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
     auto u32 = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
@@ -2081,15 +2139,17 @@ static void launch_wang_streams_back(const WangStreamsDev& st, uint8_t* ws, cons
     const uint32_t* pk_base = u32(w.pk_base);
     hipLaunchKernelGGL(wang_streams_offsets_kernel, dim3(blocks_for(n + 1, 256)), dim3(256), 0, stream, pk_base, n,
                        (const uint32_t*)u32(w.pair_off), d_out_off);
-    hipLaunchKernelGGL(wang_streams_save_kernel, dim3(n), dim3(256), 0, stream, clips, ents, pk_base,
-                       (const uint32_t*)u32(w.np), st, (const float*)f32(w.vbuf), (const uint32_t*)u32(w.cand_cnt),
-                       (const uint32_t*)u32(w.cand_t), (const uint32_t*)u32(w.cand_k), (const float*)f32(w.cand_p),
-                       (const uint32_t*)u32(w.pt), (const float*)f32(w.pp));
+    const auto save = rs.sr != (uint32_t)kWangSr ? wang_streams_save_kernel<true> : wang_streams_save_kernel<false>;
+    hipLaunchKernelGGL(save, dim3(n), dim3(256), 0, stream, clips, ents, pk_base, (const uint32_t*)u32(w.np), st,
+                       (const float*)f32(w.vbuf), (const uint32_t*)u32(w.cand_cnt), (const uint32_t*)u32(w.cand_t),
+                       (const uint32_t*)u32(w.cand_k), (const float*)f32(w.cand_p), (const uint32_t*)u32(w.pt),
+                       (const float*)f32(w.pp), pcm, reinterpret_cast<const WangStreamRsEntry*>(ws + w.rs), rs);
 }
 
 // Launches: the front end, pair count, scan (1 or 3), pair emit, [ring,] offsets, save.  With a ring (rg.cap != 0)
 // every entry's new hashes join its stream's window (A20).
-int launch_wang_streams_push(const float* pcm, const WangStreamsDev& st, const WangRingsDev& rg, uint32_t fan_out,
+int launch_wang_streams_push(const float* pcm, const WangStreamsDev& st, const WangStreamsRsDev& rs,
+                             const WangRingsDev& rg, uint32_t fan_out,
                              uint32_t zone_t, uint32_t zone_f, uint32_t pps, float floor_power, uint8_t* ws,
                              const WangPushWs& w, uint32_t* out, size_t cap, uint64_t* d_out_off, hipStream_t stream) {
     const uint32_t n = (uint32_t)w.n;
@@ -2097,7 +2157,7 @@ int launch_wang_streams_push(const float* pcm, const WangStreamsDev& st, const W
         (void)hipMemsetAsync(d_out_off, 0, 8, stream);
         return 0;
     }
-    launch_wang_streams_front(pcm, st, pps, ws, w, stream);
+    launch_wang_streams_front(pcm, st, rs, pps, ws, w, stream);
     auto f32 = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
     auto u32 = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
     const WangStreamEntry* ents = reinterpret_cast<const WangStreamEntry*>(ws + w.ents);
@@ -2114,14 +2174,15 @@ int launch_wang_streams_push(const float* pcm, const WangStreamsDev& st, const W
     if (rg.cap)
         hipLaunchKernelGGL(streams_ring_kernel<uint2>, dim3(n), dim3(256), 0, stream, ents, pk_base,
                            (const uint32_t*)u32(w.pair_off), reinterpret_cast<const uint2*>(out), rg);
-    launch_wang_streams_back(st, ws, w, d_out_off, stream);
+    launch_wang_streams_back(pcm, st, rs, ws, w, d_out_off, stream);
     return 0;
 }
 
 // ---- streaming Panako orchestration (A19) -----------------------------------------------------------
 // As launch_wang_streams_push with triplets in the middle (out: 16-byte records, 16-byte aligned); with a ring
 // (rg.cap != 0) every entry's new records then join its stream's window.
-int launch_panako_streams_push(const float* pcm, const WangStreamsDev& st, const PanakoRingsDev& rg, uint32_t fan_out,
+int launch_panako_streams_push(const float* pcm, const WangStreamsDev& st, const WangStreamsRsDev& rs,
+                               const PanakoRingsDev& rg, uint32_t fan_out,
                                uint32_t zone_t, uint32_t zone_f, uint32_t pps, float floor_power, uint8_t* ws,
                                const WangPushWs& w, uint32_t* out, size_t cap, uint64_t* d_out_off, hipStream_t stream) {
     const uint32_t n = (uint32_t)w.n;
@@ -2129,7 +2190,7 @@ int launch_panako_streams_push(const float* pcm, const WangStreamsDev& st, const
         (void)hipMemsetAsync(d_out_off, 0, 8, stream);
         return 0;
     }
-    launch_wang_streams_front(pcm, st, pps, ws, w, stream);
+    launch_wang_streams_front(pcm, st, rs, pps, ws, w, stream);
     auto f32 = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
     auto u32 = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
     const WangStreamEntry* ents = reinterpret_cast<const WangStreamEntry*>(ws + w.ents);
@@ -2147,7 +2208,7 @@ int launch_panako_streams_push(const float* pcm, const WangStreamsDev& st, const
     if (rg.cap)
         hipLaunchKernelGGL(streams_ring_kernel<uint4>, dim3(n), dim3(256), 0, stream, ents, pk_base,
                            (const uint32_t*)u32(w.pair_off), reinterpret_cast<const uint4*>(out), rg);
-    launch_wang_streams_back(st, ws, w, d_out_off, stream);
+    launch_wang_streams_back(pcm, st, rs, ws, w, d_out_off, stream);
     return 0;
 }
 

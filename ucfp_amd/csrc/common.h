@@ -400,6 +400,25 @@ struct WangStreamEntry {
     uint32_t ret_from;    // peaks with t >= ret_from are retained (non-final)
     uint32_t fresh;       // first push of the stream: its state holds nothing yet
 };
+// A21: what an entry of a push adds on a set whose input rate is not 8 kHz.  The virtual clip is then assembled from the
+// stream's carried inputs and its chunk: the carried 8 kHz samples, then the samples that became final in this push,
+// each resampled (A1) at its ABSOLUTE 8 kHz index.  The first fields bear the names of HaitsmaStreamEntry's: the two
+// sets share the input lookup and the resampled sample (audio.hip, stream_input / stream_resampled).
+struct WangStreamRsEntry {
+    uint64_t s0;          // 8 kHz index of the first new sample of the virtual clip: S before the push
+    uint64_t n0, n1;      // input samples before / after the push
+    uint64_t c_in;        // the state's carried inputs are samples [c_in, n0)
+    uint64_t c_out;       // ... and [c_out, n1) after the push
+    uint64_t chunk_off;   // the entry's chunk in the caller's buffer
+    uint32_t slot;
+    uint32_t fin;         // final push: idx + 1 clamps to n1 - 1 (A1), nothing is saved
+};
+// ... and the set's state for it, per slot
+struct WangStreamsRsDev {
+    float* carry;         // [slots][carry_cap] input samples the next output still needs
+    uint32_t carry_cap;   // ceil(sr / 8000) + 1
+    uint32_t sr;          // the set's input rate (8000: nothing is resampled and carry is NULL)
+};
 // device state of a stream set, per slot (sized at creation)
 struct WangStreamsDev {
     float* smp;           // [slots][kWangCarry]
@@ -414,15 +433,16 @@ struct WangStreamsDev {
     uint32_t ret_cap;
 };
 // one push in the context's workspace; [tab, tab + tab_bytes) is the host-built table:
-// clips[n], ents[n], v_base[n + 1] (virtual clips in vbuf), seg_base[n + 1], pk_base[n + 1] (peak lists), n_closed
+// clips[n], ents[n], v_base[n + 1] (virtual clips in vbuf), seg_base[n + 1], pk_base[n + 1] (peak lists), n_closed and,
+// on a resampling set (A21), rs[n]
 struct WangPushWs {
     size_t n = 0, n_slots = 0, n_closed = 0, total_v = 0, total_cap = 0, n_seg = 0;
     uint32_t seg = 0;
-    size_t clips, ents, v_base, seg_base, pk_base, n_closed_w, tab_bytes, vbuf, cand_cnt, cand_t, cand_k, cand_p,
+    size_t clips, ents, v_base, seg_base, pk_base, n_closed_w, rs, tab_bytes, vbuf, cand_cnt, cand_t, cand_k, cand_p,
         sel_cnt, sel_t, sel_k, sel_p, pt, pp, np, pair_cnt, pair_off, scan_tmp, total = 0;
 };
 WangPushWs wang_push_layout(size_t n, size_t n_slots, size_t n_closed, size_t total_v, size_t total_cap,
-                            size_t judged, uint32_t pps);
+                            size_t judged, uint32_t pps, bool resample);
 // ---- live windows (A19 Panako, A20 Wang): a ring per stream that holds the latest window of emitted records.  Rec is
 // the record of the set: uint4 (hash, t_a, t_b, t_c) for Panako, uint2 (hash, t_anchor) for Wang ----
 template <class Rec>
@@ -453,14 +473,16 @@ int launch_streams_windows(const PanakoRingsDev& rg, uint8_t* ws, const StreamWi
 int launch_streams_windows(const WangRingsDev& rg, uint8_t* ws, const StreamWindowsWs& w, uint8_t* out, size_t cap,
                            uint64_t* d_offsets, uint32_t* d_origins, hipStream_t stream);
 
-// with a ring (rg.cap != 0) every entry's new hashes then join its stream's window (A20)
-int launch_wang_streams_push(const float* pcm, const WangStreamsDev& st, const WangRingsDev& rg, uint32_t fan_out,
+// with a ring (rg.cap != 0) every entry's new hashes then join its stream's window (A20); pcm is at rs.sr (A21)
+int launch_wang_streams_push(const float* pcm, const WangStreamsDev& st, const WangStreamsRsDev& rs,
+                             const WangRingsDev& rg, uint32_t fan_out,
                              uint32_t zone_t, uint32_t zone_f, uint32_t pps, float floor_power, uint8_t* ws,
                              const WangPushWs& w, uint32_t* out, size_t cap, uint64_t* d_out_off, hipStream_t stream);
 
 // ---- streaming Panako (A19): the Wang push with triplets behind it (panako_streams.hip plans it with the shared
 // wang_streams_core.h, audio.hip runs it) ----
-int launch_panako_streams_push(const float* pcm, const WangStreamsDev& st, const PanakoRingsDev& rg, uint32_t fan_out,
+int launch_panako_streams_push(const float* pcm, const WangStreamsDev& st, const WangStreamsRsDev& rs,
+                               const PanakoRingsDev& rg, uint32_t fan_out,
                                uint32_t zone_t, uint32_t zone_f, uint32_t pps, float floor_power, uint8_t* ws,
                                const WangPushWs& w, uint32_t* out, size_t cap, uint64_t* d_out_off, hipStream_t stream);
 

@@ -5,7 +5,7 @@
 // push, the carried state) sized with the Panako config; a push ends in triplets instead of pairs (audio.hip,
 // launch_panako_streams_push).  On top comes one ring of records per stream: the emitted records with t_a >= w0 =
 // max(0, F(n) - W), which ucfp_panako_streams_windows_dev hands out rebased to w0 in the ragged shape
-// ucfp_panako_index_query_dev takes.
+// ucfp_panako_index_query_dev takes.  A set from ucfp_panako_streams_create_sr resamples its feed on the device (A21).
 #include "wang_streams_core.h"
 
 #define fail ucfp::capi_fail
@@ -33,7 +33,7 @@ struct Panako {
     static void launch(set* s, const float* d_pcm, const ucfp::WangPushWs& w, uint8_t* d_out, size_t cap_hashes,
                        uint64_t* d_out_offsets, hipStream_t st) {
         const Cfg& c = s->cfg;
-        ucfp::launch_panako_streams_push(d_pcm, s->dev, s->rings, c.fan_out, c.target_zone_t, c.target_zone_f,
+        ucfp::launch_panako_streams_push(d_pcm, s->dev, s->rs, s->rings, c.fan_out, c.target_zone_t, c.target_zone_f,
                                          c.peaks_per_sec, s->floor_p, s->ctx->audio_ws, w,
                                          reinterpret_cast<uint32_t*>(d_out), cap_hashes, d_out_offsets, st);
     }
@@ -56,9 +56,18 @@ size_t ucfp_panako_streams_state_bytes(const ucfp_panako_config* cfg, uint32_t w
     return entry_state_bytes<Panako>(cfg, window_frames);
 }
 
+size_t ucfp_panako_streams_state_bytes_sr(const ucfp_panako_config* cfg, uint32_t window_frames, uint32_t sample_rate) {
+    return entry_state_bytes<Panako>(cfg, window_frames, sample_rate);
+}
+
 int ucfp_panako_streams_create(ucfp_ctx* ctx, uint32_t sample_rate, const ucfp_panako_config* cfg, uint32_t max_streams,
                                uint32_t window_frames, ucfp_panako_streams** out) {
     return entry_create<Panako>(ctx, sample_rate, cfg, max_streams, window_frames, out);
+}
+
+int ucfp_panako_streams_create_sr(ucfp_ctx* ctx, uint32_t sample_rate, const ucfp_panako_config* cfg,
+                                  uint32_t max_streams, uint32_t window_frames, ucfp_panako_streams** out) {
+    return entry_create<Panako>(ctx, sample_rate, cfg, max_streams, window_frames, out, true);
 }
 
 void ucfp_panako_streams_destroy(ucfp_panako_streams* s) {

@@ -7,6 +7,8 @@
 // keeps the data (carried samples, the open second's candidates, the retained peaks).  A set created with window_frames
 // = W > 0 also keeps one ring of hashes per stream (A20): the emitted hashes with t_anchor >= w0 = max(0, F(n) - W),
 // which ucfp_wang_streams_windows_dev hands out rebased to w0 in the ragged shape ucfp_landmark_index_query_dev takes.
+// A set from ucfp_wang_streams_create_sr takes its feed at any rate from 1 to 384 kHz (A21): the slot also carries the
+// few input samples the next 8 kHz sample needs, and n above becomes S(n), the 8 kHz samples that are final.
 #include "wang_streams_core.h"
 
 #define fail ucfp::capi_fail
@@ -33,7 +35,7 @@ struct Wang {
     static void launch(set* s, const float* d_pcm, const ucfp::WangPushWs& w, uint8_t* d_out, size_t cap_hashes,
                        uint64_t* d_out_offsets, hipStream_t st) {
         const Cfg& c = s->cfg;
-        ucfp::launch_wang_streams_push(d_pcm, s->dev, s->rings, c.fan_out, c.target_zone_t, c.target_zone_f,
+        ucfp::launch_wang_streams_push(d_pcm, s->dev, s->rs, s->rings, c.fan_out, c.target_zone_t, c.target_zone_f,
                                        c.peaks_per_sec, s->floor_p, s->ctx->audio_ws, w,
                                        reinterpret_cast<uint32_t*>(d_out), cap_hashes, d_out_offsets, st);
     }
@@ -48,10 +50,18 @@ uint64_t ucfp_wang_stream_frontier(uint64_t n_samples, const ucfp_wang_config* c
     return frontier_of(judged_of(n_samples), c.target_zone_t);
 }
 
+uint64_t ucfp_wang_stream_samples(uint64_t n_samples, uint32_t sample_rate, int final) {
+    return sr_ok(sample_rate) ? samples_of(n_samples, sample_rate, final != 0) : 0;
+}
+
 size_t ucfp_wang_streams_state_bytes(const ucfp_wang_config* cfg) { return entry_state_bytes<Wang>(cfg, 0); }
 
 size_t ucfp_wang_streams_state_bytes_ex(const ucfp_wang_config* cfg, uint32_t window_frames) {
     return entry_state_bytes<Wang>(cfg, window_frames);
+}
+
+size_t ucfp_wang_streams_state_bytes_sr(const ucfp_wang_config* cfg, uint32_t window_frames, uint32_t sample_rate) {
+    return entry_state_bytes<Wang>(cfg, window_frames, sample_rate);
 }
 
 size_t ucfp_wang_streams_window_cap(const ucfp_wang_config* cfg, uint32_t window_frames) {
@@ -66,6 +76,11 @@ int ucfp_wang_streams_create(ucfp_ctx* ctx, uint32_t sample_rate, const ucfp_wan
 int ucfp_wang_streams_create_ex(ucfp_ctx* ctx, uint32_t sample_rate, const ucfp_wang_config* cfg, uint32_t max_streams,
                                 uint32_t window_frames, ucfp_wang_streams** out) {
     return entry_create<Wang>(ctx, sample_rate, cfg, max_streams, window_frames, out);
+}
+
+int ucfp_wang_streams_create_sr(ucfp_ctx* ctx, uint32_t sample_rate, const ucfp_wang_config* cfg, uint32_t max_streams,
+                                uint32_t window_frames, ucfp_wang_streams** out) {
+    return entry_create<Wang>(ctx, sample_rate, cfg, max_streams, window_frames, out, true);
 }
 
 void ucfp_wang_streams_destroy(ucfp_wang_streams* s) {

@@ -15,6 +15,7 @@
 #include "../../include/ucfp_hip.h"
 #include "common.h"
 #include "ctx.h"
+#include "stream_resample.h"
 #include "stream_set.h"
 
 namespace ucfp {
@@ -51,13 +52,17 @@ inline uint64_t f0_of(uint64_t s) { return (125 * s + 1) / 2; }                 
 inline uint64_t closed_of(uint64_t j) { return f0_of(sec_of(j)); }     // C = f0(S), S = the second holding frame J
 inline uint64_t frontier_of(uint64_t j, uint32_t zone_t) { const uint64_t c = closed_of(j); return c > zone_t ? c - zone_t : 0; }
 
+// A21 (stream_resample.h): a set takes its feed at `sr`, 1 .. 384 kHz; every quantity of A9 above is then taken at
+// S(n) = samples_of(n, sr, final), the 8 kHz samples that are final after n input samples.
+
 // retained peaks: the selected peaks of [F, C), zone_t frames wide
 inline uint32_t ret_cap_of(const Cfg& c) { return c.peaks_per_sec * ((c.target_zone_t * 2 + 124) / 125 + 2); }
 
 // one entry of a push, planned on the host
 struct Plan {
     uint32_t slot;
-    uint64_t m, n0, n1;
+    uint64_t m, n0, n1;                   // 8 kHz samples: S before and after the push, m = n1 - n0
+    RsSpan rs;                            // the same in input samples, and the carried inputs (A21)
     bool fin;
     uint64_t vbase, o, j0, j1, s0, n_closed, f_lo, f_hi, cap, bound;
 };
@@ -69,6 +74,7 @@ struct Set : streams::Slots, streams::Tables {
     float floor_p = 0.0f;
     std::vector<Plan> plan;
     WangStreamsDev dev{};
+    WangStreamsRsDev rs{nullptr, 0, kSr8k};   // A21: the input rate and the carried inputs
     uint8_t* dev_mem = nullptr;
     uint32_t window = 0;                  // W in frames (0: the set keeps no windows)
     uint8_t* ring_mem = nullptr;          // the rings of the including file's record type
@@ -84,20 +90,23 @@ inline size_t state_bytes_per_stream(uint32_t ret_cap) {
     return (size_t)kWangCarry * 4 + 4 + (size_t)kWangCandCap * 12 + 4 + (size_t)ret_cap * 12;
 }
 
-inline size_t tab_bytes_max(uint32_t max_streams) {
-    return (size_t)max_streams * (sizeof(WangStreamClip) + sizeof(WangStreamEntry)) + 3 * ((size_t)max_streams + 1) * 4 +
-           4 + 256;
+inline size_t tab_bytes_max(uint32_t max_streams, bool resample) {
+    return (size_t)max_streams * (sizeof(WangStreamClip) + sizeof(WangStreamEntry) +
+                                  (resample ? sizeof(WangStreamRsEntry) : 0)) +
+           3 * ((size_t)max_streams + 1) * 4 + 4 + 256;
 }
 
 // host state, device state and the pinned tables of a set; on failure the caller releases what exists
-inline hipError_t set_init(Set* s, ucfp_ctx* ctx, const Cfg& c, uint32_t max_streams) {
+inline hipError_t set_init(Set* s, ucfp_ctx* ctx, const Cfg& c, uint32_t max_streams, uint32_t sr) {
     s->ctx = ctx;
+    s->rs.sr = sr;
+    s->rs.carry_cap = carry_cap_of(sr);
     s->cfg = c;
     s->floor_p = (float)(65536.0 * pow(10.0, (double)c.min_anchor_mag_db / 10.0));
     s->init(max_streams);
     const uint32_t rc = ret_cap_of(c);
     const size_t ms = max_streams;
-    const size_t bytes = ms * state_bytes_per_stream(rc) + 16 * 256;
+    const size_t bytes = ms * (state_bytes_per_stream(rc) + (size_t)s->rs.carry_cap * 4) + 17 * 256;
     hipError_t e = hipMalloc((void**)&s->dev_mem, bytes);
     if (e == hipSuccess) {
         size_t off = 0;
@@ -112,8 +121,9 @@ inline hipError_t set_init(Set* s, ucfp_ctx* ctx, const Cfg& c, uint32_t max_str
         s->dev.ret_k = reinterpret_cast<uint32_t*>(take(ms * rc * 4));
         s->dev.ret_p = reinterpret_cast<float*>(take(ms * rc * 4));
         s->dev.ret_cap = rc;
+        if (s->rs.carry_cap) s->rs.carry = reinterpret_cast<float*>(take(ms * s->rs.carry_cap * 4));
     }
-    return e == hipSuccess ? s->setup(tab_bytes_max(max_streams)) : e;
+    return e == hipSuccess ? s->setup(tab_bytes_max(max_streams, sr != kSr8k)) : e;
 }
 
 // one ring of window_cap records per slot behind set_init (window_frames != 0)
@@ -154,6 +164,7 @@ inline int plan_push(Set* s, const uint32_t* slots, const uint64_t* n_samples, c
     int rc = s->fits(n, "entries", "push");
     if (rc) return rc;
     const Cfg& c = s->cfg;
+    const uint32_t sr = s->rs.sr;
     s->plan.resize(n);
     size_t total = 0;
     uint64_t total_v = 0;
@@ -161,17 +172,23 @@ inline int plan_push(Set* s, const uint32_t* slots, const uint64_t* n_samples, c
         const uint32_t slot = slots[i];
         rc = s->mark(slot, "push");
         if (rc) break;
-        if (n_samples[i] > kMaxChunk)
+        if (n_samples[i] > kMaxChunk) {
             rc = capi_fail(UCFP_E_INVALID, "a chunk of %llu samples exceeds 2^29: split it", (unsigned long long)n_samples[i]);
-        else if (frames_of(s->n[slot] + n_samples[i]) > kMaxFrames)
-            rc = capi_fail(UCFP_E_INVALID, "slot %u would pass 2^32 frames", slot);
-        if (rc) break;
+            break;
+        }
+        // the slot table counts input samples; A9 runs on the final 8 kHz samples (A21)
         Plan& p = s->plan[i];
         p.slot = slot;
-        p.m = n_samples[i];
-        p.n0 = s->n[slot];
-        p.n1 = p.n0 + p.m;
         p.fin = fin && fin[i];
+        p.rs = rs_span(s->n[slot], n_samples[i], sr, p.fin);
+        p.n0 = p.rs.s0;
+        p.n1 = p.rs.s1;
+        p.m = p.n1 - p.n0;
+        if (p.m > kMaxChunk)
+            rc = capi_fail(UCFP_E_INVALID, "a chunk of %llu samples at 8 kHz exceeds 2^29: split it", (unsigned long long)p.m);
+        else if (frames_of(p.n1) > kMaxFrames)
+            rc = capi_fail(UCFP_E_INVALID, "slot %u would pass 2^32 frames", slot);
+        if (rc) break;
         p.j0 = judged_of(p.n0);
         p.s0 = sec_of(p.j0);
         p.f_lo = frontier_of(p.j0, c.target_zone_t);
@@ -219,7 +236,8 @@ inline int push_begin(Set* s, size_t n, hipStream_t st, WangPushWs* out_w) {
         total_cap += p.cap;
         judged += p.j1 - p.j0;
     }
-    WangPushWs w = wang_push_layout(n, n_closed + n_open, n_closed, total_v, total_cap, judged, c.peaks_per_sec);
+    const bool resample = s->rs.sr != kSr8k;
+    WangPushWs w = wang_push_layout(n, n_closed + n_open, n_closed, total_v, total_cap, judged, c.peaks_per_sec, resample);
     if (total_cap >= 0x7fffffffu || (n_closed + n_open) * kWangCandCap >= ((size_t)1 << 30))
         return capi_fail(UCFP_E_INVALID, "push too large for one call: split it");
     HIP_TRY(hipSetDevice(ctx->device));
@@ -235,6 +253,7 @@ inline int push_begin(Set* s, size_t n, hipStream_t st, WangPushWs* out_w) {
     auto* v_base = reinterpret_cast<uint32_t*>(tab + w.v_base);
     auto* seg_base = reinterpret_cast<uint32_t*>(tab + w.seg_base);
     auto* pk_base = reinterpret_cast<uint32_t*>(tab + w.pk_base);
+    auto* rs_ents = reinterpret_cast<WangStreamRsEntry*>(tab + w.rs);     // filled on a resampling set only
     uint32_t vb = 0, sb = 0, pb = 0, closed_base = 0, open_slot = (uint32_t)n_closed;
     for (size_t i = 0; i < n; i++) {
         const Plan& p = s->plan[i];
@@ -276,8 +295,22 @@ inline int push_begin(Set* s, size_t n, hipStream_t st, WangPushWs* out_w) {
     }
     uint64_t chunk = 0;
     for (size_t i = 0; i < n; i++) {
+        const Plan& p = s->plan[i];
         ents[i].chunk_off = chunk;
-        chunk += s->plan[i].m;
+        if (resample) {
+            // between pushes the state holds the inputs from floor(S sr / 8000) on, S the non-final count: the final
+            // push of a stream carries nothing out
+            WangStreamRsEntry& r = rs_ents[i];
+            r.s0 = p.rs.s0;
+            r.n0 = p.rs.n0;
+            r.n1 = p.rs.n1;
+            r.c_in = p.rs.c_in;
+            r.c_out = p.rs.c_out;
+            r.chunk_off = chunk;
+            r.slot = p.slot;
+            r.fin = p.fin ? 1u : 0u;
+        }
+        chunk += p.rs.n1 - p.rs.n0;
     }
     v_base[n] = vb;
     seg_base[n] = sb;
@@ -300,7 +333,7 @@ inline int push_end(Set* s, size_t n, hipStream_t st) {
     HIP_TRY(hipEventRecord(s->done, st));
     for (size_t i = 0; i < n; i++) {
         const Plan& p = s->plan[i];
-        s->n[p.slot] = p.fin ? 0 : p.n1;
+        s->n[p.slot] = p.fin ? 0 : p.rs.n1;
         if (p.fin) s->open[p.slot] = 0;
     }
     return UCFP_OK;
@@ -394,10 +427,15 @@ int entry_push(typename K::set* s, uint32_t slot, const float* pcm, size_t n, in
 
 // Creation, for either back end: K also names the algorithm `name`, its default config `defaults()` and the set's rings
 // `rings(s)`.  The rate and the config are judged first (UCFP_E_MODALITY), whatever else is wrong.
+// `any_rate` (the _sr entries, A21): the set resamples its feed on the device; otherwise only 8 kHz is taken, as the
+// reference does.
 template <class K, class C>
 int entry_create(ucfp_ctx* ctx, uint32_t sample_rate, const C* cfg, uint32_t max_streams, uint32_t window_frames,
-                 typename K::set** out) {
-    if (sample_rate != 8000)
+                 typename K::set** out, bool any_rate = false) {
+    if (any_rate && !sr_ok(sample_rate))
+        return capi_fail(UCFP_E_MODALITY, "%s streams: sample rate %u Hz outside [%u, %u]", K::name, sample_rate, kMinSr,
+                         kMaxSr);
+    if (!any_rate && sample_rate != kSr8k)
         return capi_fail(UCFP_E_MODALITY, "%s requires 8 kHz mono input (got %u Hz); resample upstream", K::name, sample_rate);
     const Cfg c = cfg ? cfg_of(*cfg) : K::defaults();
     if (!cfg_ok(c)) return capi_fail(UCFP_E_MODALITY, "%sConfig outside the ranges of /v1/algorithms", K::name);
@@ -410,7 +448,7 @@ int entry_create(ucfp_ctx* ctx, uint32_t sample_rate, const C* cfg, uint32_t max
     HIP_TRY(hipSetDevice(ctx->device));
     typename K::set* s = new (std::nothrow) typename K::set();
     if (!s) return capi_fail(UCFP_E_INDEX, "out of host memory");
-    hipError_t e = set_init(s, ctx, c, max_streams);
+    hipError_t e = set_init(s, ctx, c, max_streams, sample_rate);
     s->window = window_frames;
     if (e == hipSuccess && window_frames) e = rings_init(s, window_frames, &K::rings(s));
     if (e != hipSuccess) {
@@ -430,11 +468,11 @@ size_t entry_window_cap(const C* cfg, uint32_t window_frames) {
 }
 
 template <class K, class C>
-size_t entry_state_bytes(const C* cfg, uint32_t window_frames) {
+size_t entry_state_bytes(const C* cfg, uint32_t window_frames, uint32_t sample_rate = kSr8k) {
     const Cfg c = cfg ? cfg_of(*cfg) : K::defaults();
-    if (!cfg_ok(c) || window_frames > kMaxWindowFrames) return 0;
+    if (!cfg_ok(c) || window_frames > kMaxWindowFrames || !sr_ok(sample_rate)) return 0;
     const size_t ring = window_frames ? kRingHeader + K::rec_bytes * window_cap_of(c, window_frames) : 0;
-    return state_bytes_per_stream(ret_cap_of(c)) + ring;
+    return state_bytes_per_stream(ret_cap_of(c)) + ring + (size_t)carry_cap_of(sample_rate) * 4;
 }
 
 // The live windows of n distinct open slots in the ragged shape of the back end's index, rebased to their origins; K
@@ -467,7 +505,8 @@ int entry_windows_dev(typename K::set* s, const uint32_t* slots, size_t n, uint8
     if (rc) return rc;
     auto* items = reinterpret_cast<StreamWindowItem*>(s->tab_h[k]);
     for (size_t i = 0; i < n; i++) {
-        const uint64_t ns = s->n[slots[i]], f = frontier_of(judged_of(ns), s->cfg.target_zone_t);
+        const uint64_t ns = s->n[slots[i]];
+        const uint64_t f = frontier_of(judged_of(samples_of(ns, s->rs.sr, false)), s->cfg.target_zone_t);
         items[i].slot = slots[i];
         items[i].w0 = (uint32_t)(f > s->window ? f - s->window : 0);
         items[i].live = ns ? 1u : 0u;

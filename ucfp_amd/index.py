@@ -1106,8 +1106,9 @@ class GpuIndex:
         device (`windows_dev` -> `LandmarkIndex.query_dev` / `PanakoIndex.query_dev`, one stream); only the answers
         come back.  The hits of a slot are those of `identify` (Wang) / `identify_stretched` (Panako, with `match`) on
         the host copy of its window, [] for an empty window; `offset` = frame `origin` of the stream in the record.  A
-        set without windows raises InvalidArgument.  Haitsma sets are left out on purpose: `blocks_dev` reports no
-        origin, so a hit's offset could not be placed in the stream."""
+        set that resamples its feed (`resample=True`, DESIGN A21) needs nothing else: its windows and origins are in
+        8 kHz frames like any other's.  A set without windows raises InvalidArgument.  Haitsma sets are left out on
+        purpose: `blocks_dev` reports no origin, so a hit's offset could not be placed in the stream."""
         import torch
         if isinstance(streams, WangStreams):
             if match:

@@ -853,17 +853,53 @@ size_t ucfp_text_streams_state_bytes(void);
 size_t ucfp_text_streams_state_bytes_ex(uint32_t flags);
 /* text.rs:645-730, handlers.rs:590-626.  slots / n_bytes / final: host arrays of n entries (distinct open slots; final may
  * be NULL = none; a chunk of 0 bytes is legal, final or not); d_bytes: the n chunks concatenated in that order on the
- * device (any alignment).  d_out: n x 1032 bytes, entry i is written only when final[i] is set (NULL allowed when no
- * entry is final); a final entry frees its slot.  d_status: n x int32, see above.  UCFP_E_INVALID before ANY state
- * changes: a slot out of range, not open or listed twice, a stream that would pass 2^63 bytes, RAW_UTF8 chunks of more
- * than the set's max_push_bytes in all.  One launch whatever n is; no host synchronisation (the host waits only for the
- * table copy of the push two back). */
+ * device (any alignment).  d_out: n x 1032 bytes (n x ucfp_text_streams_record_bytes: 8 for a SimHash set), entry i is
+ * written only when final[i] is set (NULL allowed when no entry is final); a final entry frees its slot.  d_status:
+ * n x int32, see above.  UCFP_E_INVALID before ANY state changes: a slot out of range, not open or listed twice, a stream
+ * that would pass 2^63 bytes (a SimHash stream: reach UCFP_TEXT_SIMHASH_STREAM_LIMIT_BYTES), RAW_UTF8 chunks of more than
+ * the set's max_push_bytes in all, a SimHash set's table that is not final.  One launch whatever n is; no host
+ * synchronisation (the host waits only for the table copy of the push two back). */
 int ucfp_text_streams_push_dev(ucfp_text_streams* s, const uint32_t* slots, const uint64_t* n_bytes, const uint8_t* final,
                                size_t n, const uint8_t* d_bytes, uint8_t* d_out, int32_t* d_status, void* stream);
 /* text.rs:645-730, handlers.rs:590-626.  Host-pointer convenience for one slot (the per-request shape of the reference
- * route); synchronous.  out (1032 bytes) may be NULL unless final is set; status may be NULL. */
+ * route); synchronous.  out (1032 bytes; ucfp_text_streams_record_bytes) may be NULL unless final is set; status may be NULL. */
 int ucfp_text_streams_push(ucfp_text_streams* s, uint32_t slot, const uint8_t* bytes, size_t n, int final, uint8_t* out,
                            int32_t* status);
+
+/* STREAMING SimHash: the other record a text request can ask for (text::fingerprint_simhash_tf,
+ * src/modality/text.rs:328-343, and fingerprint_simhash_idf, text.rs:344-362, whose record body is text.rs:364-421)
+ * behind the session shape of text.rs:645-730.  The reference has no such session; a set made by
+ * ucfp_text_streams_create_sim is a ucfp_text_streams whose streams end in the 8-byte SimHash record instead of the
+ * MinHash one.  open, close, push_dev, push and destroy are the entries above.  A stream keeps 64 counters, the total
+ * weight, the one unfinished token and the held-back byte on the device (ucfp_text_streams_state_bytes_sim, about 2 KiB).
+ * CONTRACT.  Let B be the concatenation of a stream's chunks, however they are cut.  The final record and status equal
+ * those of ucfp_text_simhash_batch(mode) -- with a table, of ucfp_text_simhash_idf_batch(table, mode, UCFP_TEXT_TOK_WORD)
+ * -- on the one document B, byte for byte, whenever every token of B has at most UCFP_TEXT_MAX_WINDOW_BYTES canonical
+ * bytes; above that limit, what the MinHash streams promise (the window is the single token, text.rs:277-280: SimHash
+ * hashes tokens, not shingles).  The held-back byte, d_status, the sticky statuses (UCFP_TEXT_NEEDS_HOST, which wins, and
+ * UCFP_E_UNSUPPORTED), UCFP_E_MODALITY on a final entry only, locking, ordering and everything said of UTF-8 STREAMS are
+ * those of the MinHash streams.  With a table UCFP_E_MODALITY also ends a stream whose tokens weigh 0 in all (T9.3).
+ *   - BYTE LIMIT.  A SimHash stream carries fewer than UCFP_TEXT_SIMHASH_STREAM_LIMIT_BYTES bytes: the record compares
+ *     2 x a 32-bit count, and the weighted sums hold 2^31 weights.  n bytes make at most 4 n canonical bytes
+ *     (ucfp_text_canon_bound) and a token costs two of them, its separator included, so fewer than 2^30 bytes keep the
+ *     token count below 2^31.  A push that would reach the limit fails with UCFP_E_INVALID and changes no state.
+ *   - TABLE.  The set reads the table at every push and does not own it: the table must outlive the set.  A push while
+ *     the table is not final (T9.6) fails with UCFP_E_INVALID and changes no state.  Changing a table's weights in the
+ *     middle of a stream gives a record that no offline call gives: tokens are weighed when their push runs. */
+#define UCFP_TEXT_SIMHASH_STREAM_LIMIT_BYTES 0x40000000ull
+/* text.rs:328-421 behind text.rs:645-730.  flags: 0 or UCFP_TEXT_STREAMS_UTF8, then max_push_bytes in [1, 2^28], as
+ * ucfp_text_streams_create_ex; unknown flags -> UCFP_E_INVALID.  table == NULL: TF records (text.rs:328-343); a table on
+ * the context's device: the weighted records of T9 (text.rs:344-362).  max_streams in [1, 2^20].  Fails with
+ * UCFP_E_INDEX without a gfx950 device (no CPU fallback). */
+int ucfp_text_streams_create_sim(ucfp_ctx* ctx, uint32_t max_streams, uint32_t flags, uint64_t max_push_bytes,
+                                 const ucfp_idf_table* table, ucfp_text_streams** out);
+/* text.rs:277-280, :645-730.  Host-only: bytes of a final record of this set, UCFP_MINHASH_BYTES or UCFP_SIMHASH_BYTES
+ * (0 for NULL).  ucfp_text_streams_push_dev writes d_out with this stride (n x this many bytes) and
+ * ucfp_text_streams_push copies this many bytes to `out`. */
+size_t ucfp_text_streams_record_bytes(const ucfp_text_streams* s);
+/* text.rs:328-421, :645-730.  Host-only: device bytes a SimHash set holds per stream; weighted != 0: a set with a table
+ * (64-bit sums). */
+size_t ucfp_text_streams_state_bytes_sim(uint32_t flags, int weighted);
 
 /* ---- the first half of UCFP_TEXT_RAW_UTF8 on its own: documents -> canonical token strings ----
  * What the Rust host otherwise does with txtfp's canonicaliser and tokeniser before text::fingerprint_minhash_with

@@ -177,6 +177,10 @@ SIGNATURES = {
     "ucfp_text_streams_create_ex": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
                                               C.POINTER(C.c_void_p)]),
     "ucfp_text_streams_state_bytes_ex": (C.c_size_t, [C.c_uint32]),
+    "ucfp_text_streams_create_sim": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p,
+                                               C.POINTER(C.c_void_p)]),
+    "ucfp_text_streams_record_bytes": (C.c_size_t, [C.c_void_p]),
+    "ucfp_text_streams_state_bytes_sim": (C.c_size_t, [C.c_uint32, C.c_int]),
     "ucfp_text_streams_destroy": (None, [C.c_void_p]),
     "ucfp_text_streams_open": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint32)]),
     "ucfp_text_streams_close": (C.c_int, [C.c_void_p, C.c_uint32]),

@@ -1,5 +1,5 @@
 """What the device-resident stream sets share on the host side of the C ABI: audio.WangStreams, audio.HaitsmaStreams,
-audio.PanakoStreams and text.MinHashStreams (the slot rules themselves live once in csrc/stream_slots.h).
+audio.PanakoStreams and text.MinHashStreams / text.SimHashStreams (the slot rules themselves live once in csrc/stream_slots.h).
 
 A set's entries are `<_abi>_create*`, `_open`, `_close`, `_push_dev`, `_push`, `_destroy`.  The three audio kinds also
 share the shape of a push -- float32 chunks in, ragged int32 rows out -- and differ in the capacity entry and the

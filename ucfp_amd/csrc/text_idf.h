@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 struct ucfp_ctx;
+struct ucfp_idf_table;
 
 namespace ucfp {
 
@@ -29,6 +30,11 @@ struct TextIdfAux {
     uint32_t ord = 0;         // (set per wave) the document's ordinal in the piece
 };
 constexpr uint64_t kIdfMul = 0x9E3779B97F4A7C15ull;
+
+// text_idf.hip: the T_IDF arguments of a table as it stands now (a kernel launched with them must not outlive a change of
+// the table); *is_final: its weights are set (T9.6), *device: where it lives.  Either pointer may be NULL.  A stream set
+// (text_streams.hip) calls this at every push.
+TextIdfAux idf_table_aux(const ucfp_idf_table* t, bool* is_final, int* device);
 
 // text.hip: the word tokeniser (modes RAW_ASCII and PRETOKENIZED); idf = true the weighted record, false the keys
 int launch_text_idf_words(bool idf, const TextIdfAux& aux, const uint8_t* utf8, const uint64_t* offsets, size_t n, int mode,

@@ -191,6 +191,18 @@ struct ucfp_idf_table {
 
 namespace ucfp {
 
+TextIdfAux idf_table_aux(const ucfp_idf_table* t, bool* is_final, int* device) {
+    TextIdfAux a;
+    a.tab_keys = t->keys;
+    a.tab_wts = t->wts;
+    a.shift = t->shift();
+    a.mask = (uint32_t)(t->cap - 1);
+    a.default_w = t->default_w;
+    if (is_final) *is_final = t->is_final;
+    if (device) *device = t->device;
+    return a;
+}
+
 namespace {
 
 int idf_alloc(size_t cap, uint64_t** k, uint32_t** d, uint32_t** w) {
@@ -236,15 +248,7 @@ int idf_reserve(ucfp_idf_table* t, size_t extra, hipStream_t st) {
     return UCFP_OK;
 }
 
-TextIdfAux idf_aux(const ucfp_idf_table* t) {
-    TextIdfAux a;
-    a.tab_keys = t->keys;
-    a.tab_wts = t->wts;
-    a.shift = t->shift();
-    a.mask = (uint32_t)(t->cap - 1);
-    a.default_w = t->default_w;
-    return a;
-}
+TextIdfAux idf_aux(const ucfp_idf_table* t) { return idf_table_aux(t, nullptr, nullptr); }
 
 int idf_counters(ucfp_idf_table* t, uint32_t* h, hipStream_t st) {
     HIP_TRY(hipMemcpyAsync(h, t->cnt, C_WORDS * 4, hipMemcpyDeviceToHost, st));

@@ -1,4 +1,5 @@
-// text_streams.hip -- streaming MinHash-128: device-resident text sessions, batched pushes, for gfx950.
+// text_streams.hip -- streaming MinHash-128 and streaming SimHash, TF and TF.IDF:
+// device-resident text sessions, batched pushes, for gfx950.
 //
 // Counterpart of text::StreamingMinHashSession::new / push / finalize (src/modality/text.rs:645-730) behind the stream
 // ingest route (src/server/handlers.rs:590-626).  The reference buffers the whole document and hashes it at the end; a
@@ -30,7 +31,14 @@
 //          taken back into the state (at most UCFP_TEXT_STREAM_OPEN_SEGMENT_BYTES, more is NEEDS_HOST) and restored to
 //          the front of the next push's slice
 // The step body is text_canon_kernel's, the same code (canon_place and canon_decide of text_canon_core.h), as the hash
-// stage's is text_hash_kernel's.  text_stream_kernel<false> is what sets without the flag launch.
+// stage's is text_hash_kernel's.  text_stream_kernel<false, ..> is what sets without the flag launch.
+//
+// SIMHASH STREAMS (sets made by ucfp_text_streams_create_sim).  The kernel's second template parameter is
+// the MODE of text_core.h: T_MIN above, T_SIM (text.rs:328-343) and T_IDF (text.rs:344-362; the table of text_idf.hip).
+// A SimHash item is one token and is final as soon as the token closes, so what survives flush(false) is at most the
+// unfinished token, at canon[0]: a slot (SimStreamState) keeps 64 counters -- `ones` of bit `lane`, or T_IDF's `pos` --
+// the total weight, that token's bytes, and the tokeniser words a MinHash slot keeps.  Bytes, steps, the held-back byte,
+// the canon stage and the statuses are the ones above, the same code; the record is text_emit<MODE>'s 8 bytes.
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
@@ -66,6 +74,28 @@ struct TextStreamState {
 };
 static_assert(sizeof(TextStreamState) <= 4096 && sizeof(TextStreamState) % 8 == 0, "about 3 KiB per stream");
 static_assert(offsetof(TextStreamState, canon) % 4 == 0 && offsetof(WaveLds, canon) % 4 == 0, "canon moves as dwords");
+
+// one slot of a SimHash set: CNT = uint32_t for T_SIM (`ones`), uint64_t for T_IDF (`pos`)
+template <typename CNT>
+struct SimStreamState {
+    CNT cnt[64];                    // lane b: tokens (T_SIM) or weight of the tokens (T_IDF) with bit b set
+    uint64_t tot;                   // T_IDF: weight of all tokens
+    uint64_t total_bytes;
+    uint32_t ntok, cbase;           // 0 or 1 kept token, the unfinished one, which begins at canon[0]; its bytes
+    uint32_t carry, prev_last;
+    uint32_t total_tok;
+    uint32_t flags;
+    uint32_t pending;
+    uint32_t mode;
+    uint8_t canon[kCanonCap];
+};
+static_assert(sizeof(SimStreamState<uint32_t>) == 1840 && sizeof(SimStreamState<uint64_t>) == 2096, "about 2 KiB per stream");
+static_assert(offsetof(SimStreamState<uint32_t>, canon) % 4 == 0 && offsetof(SimStreamState<uint64_t>, canon) % 4 == 0,
+              "canon moves as dwords");
+
+template <int MODE> struct StreamStateOf { using type = TextStreamState; };
+template <> struct StreamStateOf<T_SIM> { using type = SimStreamState<uint32_t>; };
+template <> struct StreamStateOf<T_IDF> { using type = SimStreamState<uint64_t>; };
 
 enum : uint32_t { kAnyShingle = 1, kNonAscii = 2, kTooLong = 4, kPendValid = 0x100 };
 enum : uint32_t { kEntFinal = 1, kEntFresh = 2, kEntModeShift = 2 };
@@ -232,10 +262,15 @@ __device__ __forceinline__ uint32_t canon_stream_push(CanonLds& L, const CanonAr
 
 }  // namespace
 
-template <bool UTF8>
+// MODE: T_MIN, T_SIM or T_IDF (never T_KEYS); `k` is 1 and `aux` the table of this push for the SimHash modes
+template <bool UTF8, int MODE>
 __global__ __launch_bounds__(64 * kWavesPerBlock) void text_stream_kernel(
-    TextStreamState* __restrict__ states, const TextStreamEntry* __restrict__ ents, size_t n,
-    const uint8_t* __restrict__ bytes, uint32_t k, uint8_t* __restrict__ out, int32_t* __restrict__ status, CanonArgs ca) {
+    typename StreamStateOf<MODE>::type* __restrict__ states, const TextStreamEntry* __restrict__ ents, size_t n,
+    const uint8_t* __restrict__ bytes, uint32_t k, uint8_t* __restrict__ out, int32_t* __restrict__ status, CanonArgs ca,
+    TextIdfAux aux) {
+    static_assert(MODE == T_MIN || MODE == T_SIM || MODE == T_IDF, "T_KEYS is never a stream mode");
+    constexpr size_t kRecBytes = MODE == T_MIN ? UCFP_MINHASH_BYTES : UCFP_SIMHASH_BYTES;
+    const TextIdfAux* A = MODE == T_IDF ? &aux : nullptr;
     __shared__ WaveLds lds[kWavesPerBlock];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const size_t ei = (size_t)blockIdx.x * kWavesPerBlock + wave;
@@ -244,7 +279,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void text_stream_kernel(
     const TextStreamEntry ent = ents[ei];
     const uint32_t eflags = uni(ent.flags);
     const bool fin = eflags & kEntFinal, fresh = eflags & kEntFresh;
-    TextStreamState& S = states[uni(ent.slot)];
+    typename StreamStateOf<MODE>::type& S = states[uni(ent.slot)];
 
     TextWave W;
     bool nonascii = false, too_long = false;
@@ -255,8 +290,15 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void text_stream_kernel(
 
     // ---- load ----
     if (!fresh) {
-        W.m0 = S.m0[lane];
-        W.m1 = S.m1[lane];
+        if constexpr (MODE == T_MIN) {
+            W.m0 = S.m0[lane];
+            W.m1 = S.m1[lane];
+        } else if constexpr (MODE == T_SIM) {
+            W.ones = S.cnt[lane];
+        } else {
+            W.pos = S.cnt[lane];
+            W.tot = S.tot;
+        }
         total_bytes = S.total_bytes;
         W.ntok = uni(S.ntok);
         W.cbase = uni(S.cbase);
@@ -270,15 +312,19 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void text_stream_kernel(
         dead = nonascii || too_long;
         pend = uni(S.pending);
         mode = uni(S.mode);
-        if (W.ntok > 64u) W.ntok = 64u;                               // a stored state never has more: keeps every index in range
+        if (W.ntok > (MODE == T_MIN ? 64u : 1u)) W.ntok = MODE == T_MIN ? 64u : 0u;   // a stored state never has more: keeps every index in range
         if (W.cbase + W.ntok > (uint32_t)kCanonCap) W.cbase = 0, W.ntok = 0;
         const uint32_t used = W.cbase + (W.ntok ? W.ntok - 1 : 0);
         const uint32_t* src = reinterpret_cast<const uint32_t*>(S.canon);
         uint32_t* dst = reinterpret_cast<uint32_t*>(L.canon);
         for (uint32_t i = lane; 4 * i < used; i += 64) dst[i] = src[i];
-        if ((uint32_t)lane < W.ntok) {
-            L.cstart[lane] = S.cstart[lane];
-            L.cend[lane] = S.cend[lane];
+        if constexpr (MODE == T_MIN) {
+            if ((uint32_t)lane < W.ntok) {
+                L.cstart[lane] = S.cstart[lane];
+                L.cend[lane] = S.cend[lane];
+            }
+        } else {
+            if (lane == 0 && W.ntok) L.cstart[0] = 0;   // the unfinished token: a flush left it at the front, its end is not known yet
         }
     }
     const bool pretok = UTF8 ? mode != UCFP_TEXT_RAW_ASCII : mode == UCFP_TEXT_PRETOKENIZED;   // a canon piece is pre-tokenised
@@ -332,7 +378,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void text_stream_kernel(
             const size_t pos = base + 64 * sub + lane;
             if (base + 64 * sub >= proc) break;
             if (text_batch_full(W)) {   // make room
-                text_flush<false>(L, W, k, lane, false);
+                text_flush<MODE>(L, W, k, lane, false, A);
                 if (text_batch_full(W)) too_long = true;
                 if (too_long) break;
             }
@@ -356,19 +402,28 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void text_stream_kernel(
     total_bytes += clen;
 
     if (!fin) {
-        // ---- store: what survives flush(false) is a prefix of one k-token window ----
-        if (!too_long && !dead) text_flush<false>(L, W, k, lane, false);
+        // ---- store: what survives flush(false) is a prefix of one k-token window (SimHash: of the unfinished token) ----
+        if (!too_long && !dead) text_flush<MODE>(L, W, k, lane, false, A);
         if (too_long) W.ntok = 0, W.cbase = 0, W.carry = false;
         wave_sync();
-        S.m0[lane] = W.m0;
-        S.m1[lane] = W.m1;
+        if constexpr (MODE == T_MIN) {
+            S.m0[lane] = W.m0;
+            S.m1[lane] = W.m1;
+        } else if constexpr (MODE == T_SIM) {
+            S.cnt[lane] = W.ones;
+        } else {
+            S.cnt[lane] = W.pos;
+            if (lane == 0) S.tot = W.tot;
+        }
         const uint32_t used = W.cbase + (W.ntok ? W.ntok - 1 : 0);
         const uint32_t* src = reinterpret_cast<const uint32_t*>(L.canon);
         uint32_t* dst = reinterpret_cast<uint32_t*>(S.canon);
         for (uint32_t i = lane; 4 * i < used; i += 64) dst[i] = src[i];
-        if ((uint32_t)lane < W.ntok) {   // ntok <= k <= 64 after the flush
-            S.cstart[lane] = L.cstart[lane];
-            S.cend[lane] = L.cend[lane];
+        if constexpr (MODE == T_MIN) {
+            if ((uint32_t)lane < W.ntok) {   // ntok <= k <= 64 after the flush
+                S.cstart[lane] = L.cstart[lane];
+                S.cend[lane] = L.cend[lane];
+            }
         }
         if (lane == 0) {
             S.total_bytes = total_bytes;
@@ -387,8 +442,8 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void text_stream_kernel(
 
     // ---- final: close a token that runs to the end of the stream, the final flush, emit as text_hash_kernel does ----
     if (W.carry && W.ntok > 0 && lane == 0) L.cend[W.ntok - 1] = (uint16_t)(W.cbase + W.ntok - 1);
-    if (!too_long && !dead) text_flush<false>(L, W, k, lane, true);
-    const int32_t stv = text_emit<false>(out + ei * 1032, W, na, too_long, lane);
+    if (!too_long && !dead) text_flush<MODE>(L, W, k, lane, true, A);
+    const int32_t stv = text_emit<MODE>(out + ei * kRecBytes, W, na, too_long, lane);
     if (lane == 0) status[ei] = stv;
 }
 
@@ -402,9 +457,11 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void text_stream_kernel(
 struct ucfp_text_streams : ucfp::streams::Slots, ucfp::streams::Tables {
     ucfp_ctx* ctx = nullptr;
     uint32_t k = 0;
+    int kind = ucfp::T_MIN;               // the kernel's MODE: T_MIN, or T_SIM / T_IDF for a set of create_sim
+    const ucfp_idf_table* table = nullptr;   // T_IDF: read at every push, not owned
     std::vector<uint8_t> fresh;           // opened, not pushed yet: the device state is not read
     std::vector<uint8_t> mode;
-    ucfp::TextStreamState* states = nullptr;
+    void* states = nullptr;               // TextStreamState or SimStreamState<..> per slot, by `kind`
     ucfp::TextStreamEntry* tab_d = nullptr;           // the push table on the device; the next push waits for `done`
     // UTF-8 sets (UCFP_TEXT_STREAMS_UTF8); the push tables then carry a CanonSlice per entry behind the entries
     bool utf8 = false;
@@ -415,6 +472,14 @@ struct ucfp_text_streams : ucfp::streams::Slots, ucfp::streams::Tables {
 namespace {
 
 constexpr uint64_t kMaxStreamBytes = (uint64_t)1 << 63;
+// A SimHash stream carries FEWER than this many bytes, so that no counter of any mode wraps.  text_emit<T_SIM> compares
+// 2u * ones with total_tok in 32 bits and ones <= total_tok; T_IDF adds weights below 2^32 into 64-bit sums, which hold
+// 2^31 of them (pos <= tot < 2^63, and 2 pos is compared).  Both are safe while total_tok < 2^31.  A token costs at least
+// two canonical bytes, its separator included, and only the last token has none: c canonical bytes hold at most
+// (c + 1) / 2 tokens.  A RAW_UTF8 stream of n bytes makes at most ucfp_text_canon_bound(n) = 4 n canonical bytes (the
+// other modes at most n), so total_tok <= (4 n + 1) / 2 <= 2 n, and n < 2^30 gives total_tok <= 2^31 - 2.
+constexpr uint64_t kSimStreamLimit = UCFP_TEXT_SIMHASH_STREAM_LIMIT_BYTES;
+static_assert(2 * (kSimStreamLimit - 1) < ((uint64_t)1 << 31), "total_tok stays below 2^31 in a SimHash stream");
 constexpr uint64_t kMaxPushBytes = (uint64_t)1 << 28;   // 4 x this, and a slice's cap, stay below 2^32
 
 // the scratch slice of a RAW_UTF8 entry with a chunk of `len` bytes
@@ -427,12 +492,24 @@ int check_push(ucfp_text_streams* s, const uint32_t* slots, const uint64_t* n_by
     if (n && (!slots || !n_bytes)) return fail(UCFP_E_INVALID, "slots / n_bytes is NULL");
     int rc = s->fits(n, "entries", "push");
     if (rc) return rc;
+    const bool sim = s->kind != ucfp::T_MIN;
     for (size_t i = 0; i < n && rc == UCFP_OK; i++) {
         const uint32_t slot = slots[i];
         rc = s->mark(slot, "push");
-        if (!rc && n_bytes[i] > kMaxStreamBytes - s->n[slot]) rc = fail(UCFP_E_INVALID, "slot %u would pass 2^63 bytes", slot);
+        if (rc) break;
+        if (sim) {   // s->n[slot] < kSimStreamLimit
+            if (n_bytes[i] >= kSimStreamLimit - s->n[slot])
+                rc = fail(UCFP_E_INVALID, "slot %u would reach 2^30 bytes: a SimHash stream carries fewer (UCFP_TEXT_SIMHASH_STREAM_LIMIT_BYTES)", slot);
+        } else if (n_bytes[i] > kMaxStreamBytes - s->n[slot]) {
+            rc = fail(UCFP_E_INVALID, "slot %u would pass 2^63 bytes", slot);
+        }
     }
     s->unmark(slots, n);
+    if (rc == UCFP_OK && s->table) {
+        bool is_final = false;
+        (void)ucfp::idf_table_aux(s->table, &is_final, nullptr);
+        if (!is_final) rc = fail(UCFP_E_INVALID, "the IDF table is not final: call ucfp_idf_table_finalize or _set_weights");
+    }
     if (rc == UCFP_OK && s->utf8) {
         uint64_t total = 0;
         for (size_t i = 0; i < n; i++)
@@ -477,15 +554,23 @@ int push_impl(ucfp_text_streams* s, const uint32_t* slots, const uint64_t* n_byt
     HIP_TRY(hipMemcpyAsync(s->tab_d, tab, tab_bytes, hipMemcpyHostToDevice, st));
     HIP_TRY(hipEventRecord(s->tab_copied[t], st));
     const unsigned grid = (unsigned)((n + ucfp::kWavesPerBlock - 1) / ucfp::kWavesPerBlock);
-    if (s->utf8) {
-        ucfp::CanonArgs ca = s->ca;
-        ca.slices = reinterpret_cast<const ucfp::CanonSlice*>(s->tab_d + n);
-        hipLaunchKernelGGL(ucfp::text_stream_kernel<true>, dim3(grid), dim3(64 * ucfp::kWavesPerBlock), 0, st, s->states, s->tab_d,
-                           n, d_bytes, s->k, d_out, d_status, ca);
-    } else {
-        hipLaunchKernelGGL(ucfp::text_stream_kernel<false>, dim3(grid), dim3(64 * ucfp::kWavesPerBlock), 0, st, s->states, s->tab_d,
-                           n, d_bytes, s->k, d_out, d_status, ucfp::CanonArgs{});
+    ucfp::CanonArgs ca = s->utf8 ? s->ca : ucfp::CanonArgs{};
+    if (s->utf8) ca.slices = reinterpret_cast<const ucfp::CanonSlice*>(s->tab_d + n);
+    const ucfp::TextIdfAux aux = s->table ? ucfp::idf_table_aux(s->table, nullptr, nullptr) : ucfp::TextIdfAux{};   // check_push saw it final
+#define UCFP_STREAM_LAUNCH(UTF8, MODE)                                                                                              \
+    hipLaunchKernelGGL((ucfp::text_stream_kernel<UTF8, ucfp::MODE>), dim3(grid), dim3(64 * ucfp::kWavesPerBlock), 0, st,            \
+                       static_cast<ucfp::StreamStateOf<ucfp::MODE>::type*>(s->states), s->tab_d, n, d_bytes, s->k, d_out, d_status, \
+                       ca, aux)
+    switch (s->kind * 2 + (s->utf8 ? 1 : 0)) {
+        case ucfp::T_MIN * 2: UCFP_STREAM_LAUNCH(false, T_MIN); break;
+        case ucfp::T_MIN * 2 + 1: UCFP_STREAM_LAUNCH(true, T_MIN); break;
+        case ucfp::T_SIM * 2: UCFP_STREAM_LAUNCH(false, T_SIM); break;
+        case ucfp::T_SIM * 2 + 1: UCFP_STREAM_LAUNCH(true, T_SIM); break;
+        case ucfp::T_IDF * 2: UCFP_STREAM_LAUNCH(false, T_IDF); break;
+        case ucfp::T_IDF * 2 + 1: UCFP_STREAM_LAUNCH(true, T_IDF); break;
+        default: return fail(UCFP_E_INVALID, "stream set of unknown kind %d", s->kind);   // a missing kernel is an error
     }
+#undef UCFP_STREAM_LAUNCH
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(s->done, st));
     for (size_t i = 0; i < n; i++) {
@@ -497,6 +582,18 @@ int push_impl(ucfp_text_streams* s, const uint32_t* slots, const uint64_t* n_byt
     return UCFP_OK;
 }
 
+size_t hash_state_bytes(int kind) {
+    return kind == ucfp::T_MIN ? sizeof(ucfp::TextStreamState)
+           : kind == ucfp::T_SIM ? sizeof(ucfp::SimStreamState<uint32_t>)
+                                 : sizeof(ucfp::SimStreamState<uint64_t>);
+}
+
+size_t record_bytes(int kind) { return kind == ucfp::T_MIN ? (size_t)UCFP_MINHASH_BYTES : (size_t)UCFP_SIMHASH_BYTES; }
+
+// a set of `kind` (shingle_k: 1 for the SimHash kinds); `table` only for T_IDF
+int create_set(ucfp_ctx* ctx, int kind, const ucfp_idf_table* table, uint32_t shingle_k, uint32_t max_streams, uint32_t flags,
+               uint64_t max_push_bytes, ucfp_text_streams** out);
+
 }  // namespace
 
 extern "C" {
@@ -507,6 +604,12 @@ size_t ucfp_text_streams_state_bytes_ex(uint32_t flags) {
     return sizeof(ucfp::TextStreamState) + ((flags & UCFP_TEXT_STREAMS_UTF8) ? sizeof(ucfp::CanonStreamState) : 0);
 }
 
+size_t ucfp_text_streams_state_bytes_sim(uint32_t flags, int weighted) {
+    return hash_state_bytes(weighted ? ucfp::T_IDF : ucfp::T_SIM) + ((flags & UCFP_TEXT_STREAMS_UTF8) ? sizeof(ucfp::CanonStreamState) : 0);
+}
+
+size_t ucfp_text_streams_record_bytes(const ucfp_text_streams* s) { return s ? record_bytes(s->kind) : 0; }
+
 int ucfp_text_streams_create(ucfp_ctx* ctx, uint32_t shingle_k, uint32_t max_streams, ucfp_text_streams** out) {
     return ucfp_text_streams_create_ex(ctx, shingle_k, max_streams, 0, 0, out);
 }
@@ -514,6 +617,20 @@ int ucfp_text_streams_create(ucfp_ctx* ctx, uint32_t shingle_k, uint32_t max_str
 int ucfp_text_streams_create_ex(ucfp_ctx* ctx, uint32_t shingle_k, uint32_t max_streams, uint32_t flags, uint64_t max_push_bytes,
                                 ucfp_text_streams** out) {
     if (shingle_k == 0 || shingle_k > 64) return fail(UCFP_E_MODALITY, "shingle k must be in [1, 64] (got %u)", shingle_k);
+    return create_set(ctx, ucfp::T_MIN, nullptr, shingle_k, max_streams, flags, max_push_bytes, out);
+}
+
+int ucfp_text_streams_create_sim(ucfp_ctx* ctx, uint32_t max_streams, uint32_t flags, uint64_t max_push_bytes,
+                                 const ucfp_idf_table* table, ucfp_text_streams** out) {
+    return create_set(ctx, table ? ucfp::T_IDF : ucfp::T_SIM, table, 1, max_streams, flags, max_push_bytes, out);
+}
+
+}  // extern "C"
+
+namespace {
+
+int create_set(ucfp_ctx* ctx, int kind, const ucfp_idf_table* table, uint32_t shingle_k, uint32_t max_streams, uint32_t flags,
+               uint64_t max_push_bytes, ucfp_text_streams** out) {
     if (!out) return fail(UCFP_E_INVALID, "out is NULL");
     *out = nullptr;
     if (flags & ~(uint32_t)UCFP_TEXT_STREAMS_UTF8) return fail(UCFP_E_INVALID, "unknown flags 0x%x", flags);
@@ -525,18 +642,25 @@ int ucfp_text_streams_create_ex(ucfp_ctx* ctx, uint32_t shingle_k, uint32_t max_
         return fail(UCFP_E_INVALID, "ctx is NULL");
     }
     if (max_streams == 0 || max_streams > (1u << 20)) return fail(UCFP_E_INVALID, "max_streams %u outside [1, 2^20]", max_streams);
+    if (table) {
+        int tdev = 0;
+        (void)ucfp::idf_table_aux(table, nullptr, &tdev);
+        if (tdev != ctx->device) return fail(UCFP_E_INVALID, "the IDF table lives on device %d, the context on %d", tdev, ctx->device);
+    }
     HIP_TRY(hipSetDevice(ctx->device));
     ucfp_text_streams* s = new (std::nothrow) ucfp_text_streams();
     if (!s) return fail(UCFP_E_INDEX, "out of host memory");
     s->ctx = ctx;
     s->k = shingle_k;
+    s->kind = kind;
+    s->table = table;
     s->init(max_streams);
     s->fresh.assign(max_streams, 0);
     s->mode.assign(max_streams, 0);
     s->utf8 = utf8;
     s->max_push_bytes = utf8 ? max_push_bytes : 0;
     const size_t tab_bytes = (size_t)max_streams * (sizeof(ucfp::TextStreamEntry) + (utf8 ? sizeof(ucfp::CanonSlice) : 0));
-    hipError_t e = hipMalloc((void**)&s->states, (size_t)max_streams * sizeof(ucfp::TextStreamState));
+    hipError_t e = hipMalloc(&s->states, (size_t)max_streams * hash_state_bytes(kind));
     if (utf8) {
         // every slice of a push at once: 4 x the chunk bytes, and per entry the slack and the rounding to a line
         const size_t scratch = (size_t)ucfp_text_canon_bound((size_t)max_push_bytes) +
@@ -554,6 +678,10 @@ int ucfp_text_streams_create_ex(ucfp_ctx* ctx, uint32_t shingle_k, uint32_t max_
     *out = s;
     return UCFP_OK;
 }
+
+}  // namespace
+
+extern "C" {
 
 void ucfp_text_streams_destroy(ucfp_text_streams* s) {
     if (!s) return;
@@ -615,7 +743,8 @@ int ucfp_text_streams_push(ucfp_text_streams* s, uint32_t slot, const uint8_t* b
     std::lock_guard<std::mutex> lk2(ctx->mu);
     HIP_TRY(hipSetDevice(ctx->device));
     rc = ucfp::grow(&ctx->stage_in, &ctx->stage_in_cap, n ? n : 1);
-    if (!rc) rc = ucfp::grow(&ctx->stage_out, &ctx->stage_out_cap, 256 + UCFP_MINHASH_BYTES);
+    const size_t rec = record_bytes(s->kind);
+    if (!rc) rc = ucfp::grow(&ctx->stage_out, &ctx->stage_out_cap, 256 + rec);
     if (rc) return rc;
     hipStream_t st = ctx->host_stream;
     int32_t* d_st = reinterpret_cast<int32_t*>(ctx->stage_out);
@@ -625,7 +754,7 @@ int ucfp_text_streams_push(ucfp_text_streams* s, uint32_t slot, const uint8_t* b
     if (rc) return rc;
     int32_t stv = 0;
     HIP_TRY(hipMemcpyAsync(&stv, d_st, 4, hipMemcpyDeviceToHost, st));
-    if (final) HIP_TRY(hipMemcpyAsync(out, d_out, UCFP_MINHASH_BYTES, hipMemcpyDeviceToHost, st));
+    if (final) HIP_TRY(hipMemcpyAsync(out, d_out, rec, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (status) *status = stv;
     return UCFP_OK;

@@ -7,9 +7,11 @@
     fingerprint_tlsh                                                text.rs:452-484  (TLSH 128/1, DESIGN A15)
 
     StreamingMinHashSession(opts, tenant_id, record_id)             text.rs:645-730  (DESIGN T7)
+    StreamingSimHashSession(opts, tenant_id, record_id, idf=)       text.rs:328-421 as a session (DESIGN T11)
     ingest_stream_ndjson(body, opts, tenant_id, record_id)          handlers.rs:590-626
 
-plus the batched form (`minhash_batch` / `simhash_batch` / `tlsh_batch`) and the stream set (`MinHashStreams`).  Hashing runs in the HIP library.
+plus the batched form (`minhash_batch` / `simhash_batch` / `tlsh_batch`) and the stream sets (`MinHashStreams`,
+`SimHashStreams`).  Hashing runs in the HIP library.
 ASCII documents go to the GPU raw (it lower-cases and segments them).  A document with non-ASCII characters goes
 to the GPU as UTF-8 (mode RAW_UTF8: the default canonicaliser -- NFKC + case fold + Bidi/Cf stripping,
 text.rs:112-114 -- and the UAX#29 word tokeniser as tables).  Only what the device hands back
@@ -26,7 +28,8 @@ itself (the reference's cjk-jp / cjk-ko).  Streams and the micro-batcher are bui
 
 `IdfTable` is the table `fingerprint_simhash_idf` takes: token key -> Q16.16 weight in device memory,
 supplied (`from_weights`, `load`) or fitted to a corpus on the GPU (`fit`), applied by `simhash_batch(.., idf=)` and
-`simhash_tokens(.., idf=)` through the same routes.  Streams and the micro-batcher take no table.
+`simhash_tokens(.., idf=)` through the same routes, and by `SimHashStreams(.., idf=)` chunk by chunk.
+The micro-batcher takes no table.
 """
 import ctypes as C
 import math
@@ -72,6 +75,9 @@ STREAMS_UTF8 = 1                     # UCFP_TEXT_STREAMS_UTF8: the set also open
 # UCFP_TEXT_STREAM_OPEN_SEGMENT_BYTES: canonical bytes of a segment without an alphanumeric a RAW_UTF8 stream can carry
 # from one push to the next; more at a push boundary and the stream is handed back (NEEDS_HOST).
 STREAM_OPEN_SEGMENT_BYTES = 256
+# UCFP_TEXT_SIMHASH_STREAM_LIMIT_BYTES (derived in include/ucfp_hip.h): a SimHash stream carries FEWER bytes than this,
+# which keeps its token count below 2^31 on every route; a push that would reach it is refused.
+SIMHASH_STREAM_LIMIT_BYTES = 1 << 30
 
 # txtfp::config_hash is not available offline and could not be reconstructed (DESIGN section 2 lists what was
 # tried).  The ONE value the reference's tests show (src/server/tests.rs:1158-1161: default canonicalizer,
@@ -605,26 +611,24 @@ class IdfTable:
             pass
 
 
-class MinHashStreams(StreamSet):
-    """A set of live MinHash streams on the device (DESIGN.md T7; ucfp_text_streams_*): `push` advances any subset of
-    them by one chunk each with one launch.  A stream's final record and status are those of `ucfp_text_minhash_batch`
-    on the concatenation of its chunks, however they were cut.  Modes: RAW_ASCII and PRETOKENIZED; with `utf8=True`
-    also RAW_UTF8 (the device canonicalises and tokenises, cuts inside a UTF-8 sequence included), and the RAW_UTF8
-    chunks of one push may then have `max_push_bytes` bytes in all (the set's scratch is sized for them once)."""
+class _TextStreams(StreamSet):
+    """What the text stream sets share (ucfp_text_streams_*): `open`, and a push whose final entries emit one record of
+    `record_bytes` bytes each (ucfp_text_streams_record_bytes)."""
     _abi = "ucfp_text_streams"
+    record_bytes = MINHASH_BYTES
 
-    def __init__(self, max_streams: int, k: int = DEFAULT_K, ctx=None, utf8: bool = False, max_push_bytes: int = 1 << 20):
-        self._create(ctx, "create_ex", k, max_streams, STREAMS_UTF8 if utf8 else 0, max_push_bytes if utf8 else 0)
-        self.max_streams, self.k = max_streams, k
+    def _created(self, max_streams: int, utf8: bool, max_push_bytes: int) -> None:
+        self.max_streams = max_streams
         self.utf8, self.max_push_bytes = bool(utf8), int(max_push_bytes) if utf8 else 0
+        self.record_bytes = int(self._lib.ucfp_text_streams_record_bytes(self.handle))
 
     def open(self, mode: int = RAW_ASCII) -> int:
         return super().open(mode)
 
     def push_dev(self, slots, counts, d_bytes, d_out, d_status, final=(), stream: int = 0) -> None:
         """Device variant (no sync): `d_bytes` the chunks of `slots` concatenated (uint8 tensor, any alignment), `d_out` a
-        uint8 [len(slots), 1032] tensor (row i is written only when slots[i] is in `final`; None when nothing is final),
-        `d_status` an int32 [len(slots)] tensor."""
+        uint8 [len(slots), record_bytes] tensor -- 1032 for MinHash, 8 for SimHash -- (row i is written only when slots[i]
+        is in `final`; None when nothing is final), `d_status` an int32 [len(slots)] tensor."""
         sl, ns, fi = slot_arrays(slots, counts, final)
         _lib.check(self._lib.ucfp_text_streams_push_dev(
             self.handle, sl.ctypes.data, ns.ctypes.data, fi.ctypes.data, sl.size,
@@ -634,7 +638,7 @@ class MinHashStreams(StreamSet):
 
     def push(self, chunks: dict, final=()) -> dict:
         """{slot: bytes} -> {slot: (record bytes or None, status)}; slots in `final` end (and free their slot) and
-        return their 1032-byte record."""
+        return their record (1032 bytes for MinHash, 8 for SimHash)."""
         import torch
         final = set(final)
         slots = list(chunks)
@@ -644,13 +648,43 @@ class MinHashStreams(StreamSet):
         dev = f"cuda:{self.ctx.device}"
         blob = b"".join(blobs)
         d_bytes = torch.from_numpy(np.frombuffer(blob, np.uint8).copy()).to(dev) if blob else None
-        d_out = torch.zeros((len(slots), MINHASH_BYTES), dtype=torch.uint8, device=dev) if final else None
+        d_out = torch.zeros((len(slots), self.record_bytes), dtype=torch.uint8, device=dev) if final else None
         d_st = torch.zeros(len(slots), dtype=torch.int32, device=dev)
         self.push_dev(slots, [len(b) for b in blobs], d_bytes, d_out, d_st, final,
                       torch.cuda.current_stream().cuda_stream)
         st = d_st.cpu().numpy()
         out = d_out.cpu().numpy() if final else None
         return {s: (out[i].tobytes() if s in final else None, int(st[i])) for i, s in enumerate(slots)}
+
+
+class MinHashStreams(_TextStreams):
+    """A set of live MinHash streams on the device (DESIGN.md T7; ucfp_text_streams_*): `push` advances any subset of
+    them by one chunk each with one launch.  A stream's final record and status are those of `ucfp_text_minhash_batch`
+    on the concatenation of its chunks, however they were cut.  Modes: RAW_ASCII and PRETOKENIZED; with `utf8=True`
+    also RAW_UTF8 (the device canonicalises and tokenises, cuts inside a UTF-8 sequence included), and the RAW_UTF8
+    chunks of one push may then have `max_push_bytes` bytes in all (the set's scratch is sized for them once)."""
+
+    def __init__(self, max_streams: int, k: int = DEFAULT_K, ctx=None, utf8: bool = False, max_push_bytes: int = 1 << 20):
+        self._create(ctx, "create_ex", k, max_streams, STREAMS_UTF8 if utf8 else 0, max_push_bytes if utf8 else 0)
+        self.k = k
+        self._created(max_streams, utf8, max_push_bytes)
+
+
+class SimHashStreams(_TextStreams):
+    """A set of live SimHash streams on the device (ucfp_text_streams_create_sim): the `open`, `push_dev`
+    and `push` of `MinHashStreams`, with 8-byte records.  A stream's final record and status are those of
+    `ucfp_text_simhash_batch` -- with `idf`, a final `IdfTable`, of `ucfp_text_simhash_idf_batch` -- on the concatenation
+    of its chunks, however they were cut.  A falsy `idf` gives TF records.  The set reads the table at every push and
+    keeps a reference to it; a push while the table is not final is refused.  A stream carries fewer than
+    SIMHASH_STREAM_LIMIT_BYTES bytes."""
+
+    def __init__(self, max_streams: int, ctx=None, utf8: bool = False, max_push_bytes: int = 1 << 20, idf=None):
+        if idf and not isinstance(idf, IdfTable):
+            raise UnsupportedError("only a ucfp_amd.text.IdfTable is built into the HIP path")
+        self.idf = idf if idf else None           # held: the device reads the table until the set is destroyed
+        self._create(ctx, "create_sim", max_streams, STREAMS_UTF8 if utf8 else 0, max_push_bytes if utf8 else 0,
+                     self.idf.handle if self.idf is not None else None)
+        self._created(max_streams, utf8, max_push_bytes)
 
 
 _CUT_AT = " \n\t\r"
@@ -667,11 +701,9 @@ def _stream_cut(s: str) -> Tuple[str, str]:
     return (s[:at], s[at:]) if at > 0 else ("", s)
 
 
-class StreamingMinHashSession:
-    """Push/finalize wrapper (text.rs:655-730) on a one-slot MinHashStreams.  The reference's session buffers the whole
-    document; here every chunk advances the stream on the device.  `push` returns no records (as the reference's);
-    `finalize` returns the one record, equal to `minhash_batch([whole text], opts)` however the text was cut into
-    chunks, cuts inside a UTF-8 sequence included.  Routing follows `_prepare`:
+class _StreamingSession:
+    """The routing that `StreamingMinHashSession` and `StreamingSimHashSession` share, on a one-slot stream set that
+    `_make_set(utf8)` creates; `_record(fingerprint)` makes the record `finalize` returns.  Routing follows `_prepare`:
       - while every byte so far is ASCII and the canonicaliser folds case, chunks go raw to a RAW_ASCII stream; the
         session keeps these ASCII bytes on the host (no more than the reference buffers), because
       - at the first byte >= 0x80 the document is one the DEVICE canonicalises when the canonicaliser is the default
@@ -690,13 +722,11 @@ class StreamingMinHashSession:
         self.opts = opts or TextOpts()
         if self.opts.tokenizer != "word":
             raise UnsupportedError(f"tokenizer `{self.opts.tokenizer}` is not built into the HIP path")
-        if self.opts.h != DEFAULT_H:
-            raise UnsupportedError(f"streaming MinHash is built for H = {DEFAULT_H} only, as the reference's session is (got "
-                                   f"H = {self.opts.h}); minhash_batch takes any H")
+        self._check_opts()
         self.tenant_id, self.record_id = tenant_id, record_id
         self._config_hash_value = config_hash_value
         self._utf8_ok = self.opts.canonicalizer.is_default()
-        self._set = MinHashStreams(1, self.opts.k, utf8=self._utf8_ok, max_push_bytes=_SESSION_PUSH_BYTES)
+        self._set = self._make_set(self._utf8_ok)
         self._dec = codecs.getincrementaldecoder("utf-8")("strict")
         self._tail = ""
         self._bad = None                  # the first UTF-8 error: reported by finalize
@@ -705,8 +735,17 @@ class StreamingMinHashSession:
         self._kept = bytearray()          # ASCII and UTF-8 routes: the bytes so far, for the replay
         self._slot = self._set.open(RAW_ASCII if self.route == "ascii" else PRETOKENIZED)
 
+    def _check_opts(self) -> None:
+        pass
+
+    def _make_set(self, utf8: bool) -> "_TextStreams":
+        raise NotImplementedError
+
+    def _record(self, fingerprint: bytes) -> Record:
+        raise NotImplementedError
+
     def _dev_push(self, data: bytes, final: bool):
-        out = (C.c_uint8 * MINHASH_BYTES)()
+        out = (C.c_uint8 * self._set.record_bytes)()
         st = C.c_int32(0)
         _lib.check(self._set._lib.ucfp_text_streams_push(self._set.handle, self._slot, data if data else None, len(data),
                                                          1 if final else 0, out if final else None, C.byref(st)))
@@ -782,11 +821,59 @@ class StreamingMinHashSession:
                 self._kept = bytearray()
                 self._set.destroy()
         _raise_for(status)
+        return [self._record(rec)]
+
+
+class StreamingMinHashSession(_StreamingSession):
+    """Push/finalize wrapper (text.rs:655-730) on a one-slot MinHashStreams.  The reference's session buffers the whole
+    document; here every chunk advances the stream on the device.  `push` returns no records (as the reference's);
+    `finalize` returns the one record, equal to `minhash_batch([whole text], opts)` however the text was cut into
+    chunks, cuts inside a UTF-8 sequence included.  The routing ("ascii", "utf8", "host") is `_StreamingSession`'s."""
+
+    def _check_opts(self) -> None:
+        if self.opts.h != DEFAULT_H:
+            raise UnsupportedError(f"streaming MinHash is built for H = {DEFAULT_H} only, as the reference's session is (got "
+                                   f"H = {self.opts.h}); minhash_batch takes any H")
+
+    def _make_set(self, utf8: bool) -> MinHashStreams:
+        return MinHashStreams(1, self.opts.k, utf8=utf8, max_push_bytes=_SESSION_PUSH_BYTES)
+
+    def _record(self, fingerprint: bytes) -> Record:
         o = self.opts
-        return [Record(tenant_id=self.tenant_id, record_id=self.record_id, modality=Modality.Text,
-                       format_version=FORMAT_VERSION_MINHASH_HIP, algorithm=ALGORITHM_MINHASH_128,
-                       config_hash=_record_config_hash(o, o.tokenizer_tag(), ALGORITHM_MINHASH_128, self._config_hash_value),
-                       fingerprint=rec, embedding=None, model_id=None, metadata=b"", text=None)]
+        return Record(tenant_id=self.tenant_id, record_id=self.record_id, modality=Modality.Text,
+                      format_version=FORMAT_VERSION_MINHASH_HIP, algorithm=ALGORITHM_MINHASH_128,
+                      config_hash=_record_config_hash(o, o.tokenizer_tag(), ALGORITHM_MINHASH_128, self._config_hash_value),
+                      fingerprint=fingerprint, embedding=None, model_id=None, metadata=b"", text=None)
+
+
+class StreamingSimHashSession(_StreamingSession):
+    """The session of `StreamingMinHashSession` on a one-slot SimHashStreams: `finalize` returns the one
+    record that `fingerprint_simhash_tf(whole text, opts, ..)` builds -- with `idf`, a final `IdfTable`, and
+    `algorithm=ALGORITHM_SIMHASH_IDF`, the one `fingerprint_simhash_idf(whole text, opts, idf, ..)` builds -- however the
+    text was cut into chunks (`text` is None, as in the MinHash session).  A falsy `idf` weighs every token 1.0 under
+    either tag, as `fingerprint_simhash_idf` does.  The reference has no SimHash session; the routing is the shared one."""
+
+    def __init__(self, opts: Optional[TextOpts], tenant_id: int, record_id: int, idf=None,
+                 algorithm: str = ALGORITHM_SIMHASH_TF, config_hash_value: Optional[int] = None):
+        if algorithm not in (ALGORITHM_SIMHASH_TF, ALGORITHM_SIMHASH_IDF):
+            raise UnsupportedError(f"a SimHash session makes `{ALGORITHM_SIMHASH_TF}` or `{ALGORITHM_SIMHASH_IDF}` records "
+                                   f"(got `{algorithm}`)")
+        if idf and not isinstance(idf, IdfTable):
+            raise UnsupportedError("only a ucfp_amd.text.IdfTable is built into the HIP path")
+        if idf and algorithm != ALGORITHM_SIMHASH_IDF:
+            raise InvalidArgument(f"a table makes `{ALGORITHM_SIMHASH_IDF}` records: pass algorithm=ALGORITHM_SIMHASH_IDF")
+        self.algorithm = algorithm
+        self._idf = idf if idf else None
+        super().__init__(opts, tenant_id, record_id, config_hash_value)
+
+    def _make_set(self, utf8: bool) -> SimHashStreams:
+        return SimHashStreams(1, utf8=utf8, max_push_bytes=_SESSION_PUSH_BYTES, idf=self._idf)
+
+    def _record(self, fingerprint: bytes) -> Record:
+        return Record(tenant_id=self.tenant_id, record_id=self.record_id, modality=Modality.Text,
+                      format_version=FORMAT_VERSION, algorithm=self.algorithm,
+                      config_hash=_record_config_hash(self.opts, "word-uax29", self.algorithm, self._config_hash_value),
+                      fingerprint=fingerprint, embedding=None, model_id=None, metadata=b"", text=None)
 
 
 def _ndjson_chunks(body: bytes) -> List[bytes]:
@@ -809,13 +896,22 @@ def _ndjson_chunks(body: bytes) -> List[bytes]:
     return chunks
 
 
-def ingest_stream_ndjson(body: bytes, opts: Optional[TextOpts], tenant_id: int, record_id: int) -> Record:
+def ingest_stream_ndjson(body: bytes, opts: Optional[TextOpts], tenant_id: int, record_id: int,
+                         algorithm: Optional[str] = None, idf=None) -> Record:
     """The body loop of POST /v1/ingest/text/{tid}/{rid}/stream (handlers.rs:603-617): every line is a JSON string
-    carrying a chunk; push each, finalise, return the record.  The body is parsed before any device work."""
+    carrying a chunk; push each, finalise, return the record.  The body is parsed before any device work.
+    `algorithm` is this library's own (the reference's route only knows MinHash): None gives the MinHash record,
+    "simhash-tf" / "simhash-idf" the record of a `StreamingSimHashSession`, the latter weighted by `idf`."""
+    if algorithm not in (None, "simhash-tf", "simhash-idf"):
+        raise UnsupportedError(f"stream ingest makes MinHash (None), `simhash-tf` or `simhash-idf` records (got `{algorithm}`)")
     chunks = _ndjson_chunks(body)
     if not chunks:
         raise ModalityError("streaming session produced no record")
-    session = StreamingMinHashSession(opts, tenant_id, record_id)
+    if algorithm is None:
+        session = StreamingMinHashSession(opts, tenant_id, record_id)
+    else:
+        session = StreamingSimHashSession(opts, tenant_id, record_id, idf=idf if algorithm == "simhash-idf" else None,
+                                          algorithm=ALGORITHM_SIMHASH_TF if algorithm == "simhash-tf" else ALGORITHM_SIMHASH_IDF)
     try:
         for c in chunks:
             session.push(c)

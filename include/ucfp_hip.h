@@ -1231,6 +1231,41 @@ int ucfp_panako_index_query_dev(ucfp_panako_index* ix, uint32_t tenant, const ui
                                 uint64_t* d_out_ids, uint32_t* d_out_votes, int32_t* d_out_offsets, uint32_t* d_out_scales,
                                 float* d_out_scores, uint32_t* d_out_n, void* stream);
 
+/* ---- The same vote for RESAMPLED copies: the bins follow the scale ----
+ * A copy played at another speed through a resampler (a tape off speed, a sped-up upload) has its times divided by the
+ * speed and every frequency multiplied by it, so the three 9-bit bins of its hashes (h = k_a << 23 | k_b << 14 |
+ * k_c << 5 | r) move and the probes above meet nothing.  Two more match parameters: bins (0 = kept, the vote above;
+ * 1 = scaled) and f_slack in 0 ... 3, which must be 0 when bins = 0.  Everything of A14 that is not named here is
+ * unchanged; all arithmetic is in signed integers.
+ *   bin map     of hypothesis s (record frames per query frame = the speed the query was played at, in 1/256):
+ *               B_s(k) = (512 k + s) / (2 s) in integer division = round(256 k / s); non-increasing in s; B_256(k) = k.
+ *   votes       with bins = 1 a match is a pair (query triple (h, a, d) with bins k_a, k_b, k_c and ratio r, posting
+ *               (record, h', a', d') with bins k_a', k_b', k_c' and ratio r') whose h' is not ignored (P(h') <=
+ *               max_postings, as above).  It supports s iff |k_x' - B_s(k_x)| <= f_slack for x = a, b, c and
+ *               |r' - r| <= r_slack and |256 d' - s d| <= 256 slack; its offset under s is a' - ((s a + 128) >> 8).
+ *               Every (match, supported s) is one vote; count, votes, (scale, offset), hits, score, |Q| and the limits
+ *               on expanded votes are those above, word for word.
+ *   intervals   for 64 <= s <= 1024, |k' - B_s(k)| <= f holds iff 512 k / (2 k' + 2 f + 1) + 1 <= s and, when
+ *               k' - f >= 1, s <= 512 k / (2 (k' - f) - 1): the hypotheses of a match are one interval, as above.
+ * With bins = 1, f_slack = 0 and the single hypothesis 256 the answers are those of bins = 0.  config NULL = 204, 320,
+ * 4, 16, 2, 1 with bins = 0.  UCFP_E_INVALID before anything runs: bins > 1, f_slack > 3, f_slack != 0 with bins = 0.
+ * ucfp_panako_index_query and _query_dev forward here with bins = 0; their struct keeps its layout.  Independent
+ * changes of pitch and tempo are not covered: a caller who does not know which change a copy went through asks with
+ * bins = 0 and with bins = 1. */
+typedef struct ucfp_panako_match_config_ex {
+    uint32_t scale_min, scale_max, scale_step, window, slack, r_slack; /* as ucfp_panako_match_config */
+    uint32_t bins;                                                     /* 0 = kept, 1 = scaled */
+    uint32_t f_slack;                                                  /* 0 ... 3 bins; 0 when bins = 0 */
+} ucfp_panako_match_config_ex;
+int ucfp_panako_index_query_ex(ucfp_panako_index* ix, uint32_t tenant, const uint8_t* records, const uint64_t* offsets,
+                               size_t nq, uint32_t k, uint32_t min_votes, const ucfp_panako_match_config_ex* cfg,
+                               uint64_t* out_ids, uint32_t* out_votes, int32_t* out_offsets, uint32_t* out_scales,
+                               float* out_scores, uint32_t* out_n);
+int ucfp_panako_index_query_ex_dev(ucfp_panako_index* ix, uint32_t tenant, const uint8_t* d_records, const uint64_t* d_offsets,
+                                   size_t nq, uint32_t k, uint32_t min_votes, const ucfp_panako_match_config_ex* cfg,
+                                   uint64_t* d_out_ids, uint32_t* d_out_votes, int32_t* d_out_offsets, uint32_t* d_out_scales,
+                                   float* d_out_scores, uint32_t* d_out_n, void* stream);
+
 /* ---- Haitsma-Kalker sub-fingerprint index (the reference has no audio matcher) ----
  * A record r is a sequence F_r[0 .. n_r) of u32 sub-fingerprints (the bytes of an audiofp-haitsma-v1 record, 4 per
  * frame, little endian); a query is a sequence Q[0 .. m), m <= UCFP_HAITSMA_MAX_QUERY_FRAMES.  Item i of a batch is

@@ -2,12 +2,14 @@
 projection of the same records (DESIGN A13 P7, the code path of the parent commit): queries/s at batch sizes 1, 64 and
 1024 for unstretched 8 s excerpts through both, and for excerpts re-rendered at speeds 0.85 ... 1.2 through the new one,
 with the share of queries whose expanded votes exceed ucfp_panako_index_lds_votes() (the global path), counted in numpy
-over a sample.  Prints one JSON line per measurement.
+over a sample.  A third set, `resampled`, is the same excerpts played at those speeds through a resampler (frequencies
+multiplied by the speed) and answered with bins="scaled" (DESIGN A22, ucfp_panako_index_query_ex).  Prints one JSON
+line per measurement.
 
-    python tools/bench_panako_index.py [--tracks 500] [--seconds 60]
+    python tools/bench_panako_index.py [--tracks 500] [--seconds 60] [--sets unstretched stretched resampled]
 
-Every unstretched excerpt's first hit must be its source track through both indexes, and every stretched one through
-the new index: the tool exits with an error otherwise.  The corpus is synthetic (tone bursts at seeded onsets, the
+Every unstretched excerpt's first hit must be its source track through both indexes, every stretched one through the new
+index and every resampled one through its scaled mode: the tool exits with an error otherwise.  The corpus is synthetic (tone bursts at seeded onsets, the
 generator of tests/panako_match_ref.py restated): its hash distribution is not music's."""
 import argparse
 import json
@@ -33,11 +35,12 @@ def make_score(seed, seconds, per_second=9.0):
                      rng.integers(40, 440, n) * (SR / 1024.0), rng.uniform(0.08, 0.25, n)], axis=1)
 
 
-def render(score, t0, t1, speed=1.0):
-    """The excerpt [t0, t1) of the score at `speed`: onsets and durations divided by it, frequencies kept."""
+def render(score, t0, t1, speed=1.0, pitch=1.0):
+    """The excerpt [t0, t1) of the score at `speed`: onsets and durations divided by it, frequencies multiplied by `pitch`
+    (1.0: a time stretch; `speed`: a resampled copy, whose tones past SR / 2 alias and are left in)."""
     n = int(round((t1 - t0) / speed * SR))
     x = np.zeros(n)
-    for onset, dur, freq, amp in score[(score[:, 0] + score[:, 1] > t0) & (score[:, 0] < t1)]:
+    for onset, dur, freq, amp in score[(score[:, 0] + score[:, 1] > t0) & (score[:, 0] < t1)] * np.array([1.0, 1.0, pitch, 1.0]):
         a, m = int(round((onset - t0) / speed * SR)), int(round(dur / speed * SR))
         lo, hi = max(a, 0), min(a + m, n)
         if hi > lo and m >= 2:
@@ -81,6 +84,8 @@ def main():
     ap.add_argument("--seconds", type=int, default=60)
     ap.add_argument("--queries", type=int, default=1024)
     ap.add_argument("--batches", type=int, nargs="+", default=[1, 64, 1024])
+    ap.add_argument("--sets", nargs="+", default=["unstretched", "stretched", "resampled"],
+                    choices=["unstretched", "stretched", "resampled"])
     ap.add_argument("--path-sample", type=int, default=128)
     ap.add_argument("--reps", type=int, default=0, help="timed repetitions per case (0: 256 / batch, at least 3)")
     a = ap.parse_args()
@@ -110,10 +115,13 @@ def main():
     start = rng.integers(0, int(a.seconds - EXCERPT_S - 1), a.queries).astype(float)
     speed = np.array(SPEEDS)[rng.integers(0, len(SPEEDS), a.queries)]
     sets = {}
-    for name, sp in (("unstretched", np.ones(a.queries)), ("stretched", speed)):
+    for name, sp, pitch in (("unstretched", np.ones(a.queries), np.ones(a.queries)), ("stretched", speed, np.ones(a.queries)),
+                            ("resampled", speed, speed)):
+        if name not in a.sets:
+            continue
         qs = []
         for c0 in range(0, a.queries, 64):
-            qs += audio.panako_hashes_batch([render(scores[src[i]], start[i], start[i] + EXCERPT_S, sp[i])
+            qs += audio.panako_hashes_batch([render(scores[src[i]], start[i], start[i] + EXCERPT_S, sp[i], pitch[i])
                                              for i in range(c0, min(a.queries, c0 + 64))], SR, ctx=ctx)
         sets[name] = qs
     # the share of queries on the global path, from a sample
@@ -123,14 +131,19 @@ def main():
     lds = PanakoIndex.lds_votes()
     bad = 0
     for name, qs_all in sets.items():
-        v = np.array([expanded_votes(ph, pa, pd, q, PANAKO_MATCH_DEFAULTS) for q in qs_all[: a.path_sample]])
-        share = float((v > lds).mean())
+        if name == "resampled":                  # the kept-bins count says nothing about scaled mode: not sampled
+            v_mean = share = None
+        else:
+            v = np.array([expanded_votes(ph, pa, pd, q, PANAKO_MATCH_DEFAULTS) for q in qs_all[: a.path_sample]])
+            v_mean, share = round(float(v.mean()), 1), round(float((v > lds).mean()), 3)
         for nq in a.batches:
             if nq > a.queries:
                 continue
             qs = qs_all[:nq]
             reps = a.reps or max(3, 256 // nq)
             legs = [("a14_scale_offset_vote", lambda: new.query(0, qs, 10))]
+            if name == "resampled":
+                legs = [("a22_scaled_bins_vote", lambda: new.query(0, qs, 10, bins="scaled"))]
             if name == "unstretched":
                 lm = [audio.panako_landmarks(q.tobytes()) for q in qs]
                 legs.append(("a10_projection_baseline", lambda: old.query(0, lm, 10)))
@@ -142,8 +155,8 @@ def main():
                                   "ms_per_batch": round(dt * 1e3, 3), "ms_min": round(lo * 1e3, 3), "ms_max": round(hi * 1e3, 3),
                                   "queries_per_s": round(nq / dt, 1), "top1_correct": float(np.mean(ok)),
                                   "triples_per_query": round(float(np.mean([q.shape[0] for q in qs])), 1),
-                                  "expanded_votes_per_query_sampled": round(float(v.mean()), 1),
-                                  "global_path_share_sampled": round(share, 3)}), flush=True)
+                                  "expanded_votes_per_query_sampled": v_mean, "global_path_share_sampled": share}),
+                      flush=True)
     new.close()
     old.close()
     if bad:

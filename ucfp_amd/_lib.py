@@ -28,6 +28,11 @@ class PanakoMatchConfig(C.Structure):
                 ("slack", C.c_uint32), ("r_slack", C.c_uint32)]
 
 
+class PanakoMatchConfigEx(C.Structure):
+    """ucfp_panako_match_config_ex: the same, then bins (0 kept, 1 scaled) and f_slack (DESIGN A22)."""
+    _fields_ = PanakoMatchConfig._fields_ + [("bins", C.c_uint32), ("f_slack", C.c_uint32)]
+
+
 class WangConfig(C.Structure):
     """ucfp_wang_config (audiofp WangConfig; defaults src/server/algorithms_manifest.rs:553-592)."""
     _fields_ = [("fan_out", C.c_uint32), ("target_zone_t", C.c_uint32), ("target_zone_f", C.c_uint32),
@@ -277,6 +282,12 @@ SIGNATURES = {
     "ucfp_panako_index_query_dev": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32,
                                               C.c_uint32, C.POINTER(PanakoMatchConfig), C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ucfp_panako_index_query_ex": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32,
+                                             C.c_uint32, C.POINTER(PanakoMatchConfigEx), C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ucfp_panako_index_query_ex_dev": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32,
+                                                 C.c_uint32, C.POINTER(PanakoMatchConfigEx), C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ucfp_haitsma_index_probes": (C.c_size_t, [C.c_uint32]),
     "ucfp_haitsma_index_create": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
     "ucfp_haitsma_index_destroy": (None, [C.c_void_p]),

@@ -78,7 +78,9 @@ FORMAT_VERSION = 1  # src/lib.rs:62
 # (the reference's `?explain=1`, handlers.rs:133-140): terms alone give a BM25 query, vector + terms the hybrid one.
 # `triplets` (DESIGN A14) are whole Panako records, 16 bytes per triplet or a list of [hash, t_a, t_b, t_c], and with
 # `algorithm` = "audiofp-panako-v1" go to the (scale, offset) vote, which also finds a time-stretched copy; its hits carry
-# `scale`.
+# `scale`.  `resampled`: true next to `triplets` (DESIGN A22) asks the same vote with the bins following the scale, which
+# finds a copy played at another speed through a resampler (times and frequencies both change); it is a JSON bool, left
+# out when false, and valid only with `triplets`.
 # Identification by bit-error rate adds `subfingerprints` (DESIGN A12): Haitsma frames as bytes (4 per frame, u32 LE) or a
 # list of integers.
 # TLSH-distance search adds `tlsh` (DESIGN A15): the digest string a `tlsh-128-1` record stores ("T1" + 70 hex digits; the
@@ -106,6 +108,7 @@ class QueryRequest:
     landmarks: Optional[bytes] = None   # 8 bytes per landmark: u32 LE hash, u32 LE t
     subfingerprints: Optional[bytes] = None   # 4 bytes per frame: u32 LE (an audiofp-haitsma-v1 block)
     triplets: Optional[bytes] = None    # 16 bytes per Panako triplet: u32 LE hash, t_a, t_b, t_c (DESIGN A14)
+    resampled: bool = False             # a `triplets` query whose bins follow the scale (DESIGN A22)
     tlsh: Optional[bytes] = None        # the 35 bytes of a TLSH digest (DESIGN A15)
     image_record: Optional[bytes] = None   # a whole image record, 168 or 536 bytes (DESIGN A16)
     multi_hash: Optional[dict] = None   # MultiHashConfigDto of an `image_record` query (dto.rs:462-480)
@@ -155,6 +158,11 @@ class QueryRequest:
             tl = _tlsh_bytes(tl)
             if body.get("algorithm") not in (None, "tlsh-128-1"):
                 raise InvalidArgument("`tlsh` goes with `algorithm` = \"tlsh-128-1\" or none")
+        resampled = body.get("resampled", False)
+        if not isinstance(resampled, bool):
+            raise InvalidArgument("`resampled` must be true or false")
+        if resampled and tri is None:
+            raise InvalidArgument("`resampled` goes with `triplets`")
         if tri is not None:
             tri = _triplet_bytes(tri)
         if sub is not None:
@@ -170,7 +178,7 @@ class QueryRequest:
         return cls(tenant_id=tenant_id, modality=modality, k=max(k, 1),       # handlers.rs:153: k.max(1)
                    vector=[float(x) for x in vector] if vector is not None else None,
                    hash=int(h) if h is not None else None, algorithm=body.get("algorithm"), landmarks=lm, subfingerprints=sub,
-                   triplets=tri, tlsh=tl, image_record=img, multi_hash=dict(mh) if mh is not None else None,
+                   triplets=tri, resampled=resampled, tlsh=tl, image_record=img, multi_hash=dict(mh) if mh is not None else None,
                    min_score=float(ms) if ms is not None else None,
                    minhash=mhr, min_similarity=float(sim) if sim is not None else None,
                    terms=list(terms), explain=_flag(body.get("explain", False)))

@@ -34,6 +34,12 @@
 //                         into an LDS top-k (topk_offer).
 // Both paths sort the same keys and fold the same values, so they agree bit for bit.  The host reads three small arrays
 // per query batch (the checked sizes, the input flags, V per query) to size the sorts and the spill buffers.
+//
+// Scaled mode (bins = 1 in ucfp_panako_match_config_ex) finds resampled copies, whose bins moved with
+// their speed: pk_qruns and pk_vote are templates over the mode, and only the walk from a query triple to its matches
+// differs (for_each_match).  A triple visits the buckets (k_a', k_b') that some scale hypothesis allows instead of three
+// probes, and a posting is tested against the ratio bits, three bin intervals and the d interval (pk_interval_scaled);
+// a stopped hash is known by one byte per posting (pk_mark_stopped).  The bins = 0 instantiation is A14's code.
 
 #include <hip/hip_runtime.h>
 
@@ -62,6 +68,7 @@ struct Postings {
     const uint64_t* entries;
     const uint32_t* dir;
     uint32_t max_postings;
+    const uint8_t* stop;   // scaled mode with max_postings > 0: stop[i] = posting i belongs to a stopped hash
 };
 
 struct Outputs {
@@ -156,10 +163,99 @@ __device__ __forceinline__ uint64_t window_end(const uint64_t* votes, uint64_t i
 // f(valid, ordinal, a', a, jlo, jhi) is called by all threads together (it may hold barriers), valid on the lanes that
 // carry a match; [jlo, jhi] is the interval of hypotheses the match supports (empty when jlo > jhi).  n_distinct counts
 // this lane's distinct triples.
-template <class F>
+//
+// Scaled mode (kBins = 1, A22) has no fixed number of slots per triple: the distinct triples are taken one after the
+// other, and a slot is one k_a' that some hypothesis allows, 256 of them at a time.  The hypotheses of that k_a' bound
+// k_b' and k_c'; hash >> 14 = k_a' << 9 | k_b' keys the directory, so the buckets of the slot are neighbours and the
+// run is everything from (k_a', first k_b', first k_c') to (k_a', last k_b', last k_c', r = 31): every posting at most
+// once per triple.  The slots are computed, not stored; most are empty, which two directory reads show, and a chunk
+// of empty slots costs one barrier.  The ratio bits, the three bin intervals, the d interval and the stop flag are
+// tested per posting (pk_interval_scaled).
+template <int kBins, class F>
 __device__ __forceinline__ void for_each_match(const uint64_t* __restrict__ qh, const uint64_t* __restrict__ qad, uint64_t a,
                                                uint64_t e, const Postings& P, const PkMatch& m, uint64_t* s_inc,
                                                uint32_t* s_lo, uint64_t* s_qad, uint64_t* s_w, uint64_t& n_distinct, F f) {
+    if constexpr (kBins != 0) {
+        const uint32_t nt = (uint32_t)(e - a);   // a batch holds fewer than 2^32 / 3 triples
+        uint32_t hq = 0;
+        uint64_t ad = 0;
+        for (uint32_t i = 0; i < nt; i++) {
+            const uint32_t hprev = hq;
+            const uint64_t adprev = ad;
+            hq = (uint32_t)qh[a + i];   // the upper half is the query
+            ad = qad[a + i];
+            if (i && hprev == hq && adprev == ad) continue;
+            if (threadIdx.x == 0) n_distinct++;
+            const int32_t ka = (int32_t)(hq >> 23), kb = (int32_t)((hq >> 14) & 511u), kc = (int32_t)((hq >> 5) & 511u);
+            int32_t alo, ahi;
+            ucfp::pk_bin_range(m, ka, 0, m.nh - 1, &alo, &ahi);
+            for (int32_t c = alo; c <= ahi; c += kThreads) {
+                const int32_t kap = c + (int32_t)threadIdx.x;
+                uint32_t lo = 0, len = 0;
+                if (kap <= ahi) {
+                    int32_t jlo, jhi, blo, bhi, clo, chi;
+                    ucfp::pk_bin_interval(m, ka, kap, m.f_slack, &jlo, &jhi);
+                    if (jlo <= jhi) {
+                        ucfp::pk_bin_range(m, kb, jlo, jhi, &blo, &bhi);
+                        ucfp::pk_bin_range(m, kc, jlo, jhi, &clo, &chi);
+                        if (blo <= bhi && clo <= chi) {
+                            const uint32_t b0 = ((uint32_t)kap << 9) | (uint32_t)blo, b1 = ((uint32_t)kap << 9) | (uint32_t)bhi;
+                            const uint32_t pa = P.dir[b0], pe = P.dir[b1 + 1];   // b1 + 1 <= kDirSize
+                            if (pa < pe) {
+                                const uint32_t h0 = (b0 << kDirBits) | ((uint32_t)clo << 5);
+                                const uint32_t h1 = (b1 << kDirBits) | ((uint32_t)chi << 5) | 31u;
+                                uint32_t l = pa, r = pe;
+                                while (l < r) {   // first >= h0
+                                    const uint32_t mid = (l + r) >> 1;
+                                    if (P.hashes[mid] < h0) l = mid + 1;
+                                    else r = mid;
+                                }
+                                uint32_t u = l, r2 = pe;
+                                while (u < r2) {  // first > h1
+                                    const uint32_t mid = (u + r2) >> 1;
+                                    if (P.hashes[mid] <= h1) u = mid + 1;
+                                    else r2 = mid;
+                                }
+                                lo = l;
+                                len = u - l;
+                            }
+                        }
+                    }
+                }
+                if (__syncthreads_count(len != 0) == 0) continue;
+                s_inc[threadIdx.x] = block_scan_incl(len, s_w);
+                s_lo[threadIdx.x] = lo;
+                __syncthreads();
+                const uint32_t total = (uint32_t)s_inc[kThreads - 1];   // the runs of a triple are disjoint: below 2^32
+                for (uint32_t mb = 0; mb < total; mb += kThreads) {
+                    const uint32_t j = mb + threadIdx.x;
+                    const bool valid = j < total;
+                    uint32_t ord = 0, ap = 0;
+                    int32_t jlo = 0, jhi = -1;
+                    if (valid) {
+                        uint32_t l = 0, r = kThreads - 1;   // first slot x with s_inc[x] > j
+                        while (l < r) {
+                            const uint32_t mid = (l + r) >> 1;
+                            if ((uint32_t)s_inc[mid] > j) r = mid;
+                            else l = mid + 1;
+                        }
+                        const uint32_t excl = l ? (uint32_t)s_inc[l - 1] : 0u;
+                        const size_t at = (size_t)s_lo[l] + (j - excl);
+                        if (!(P.stop && P.stop[at])) {
+                            const uint64_t ent = P.entries[at];
+                            ord = ucfp::pk_entry_ord(ent);
+                            ap = ucfp::pk_entry_a(ent);
+                            ucfp::pk_interval_scaled(m, hq, (int32_t)(ad & 1023u), P.hashes[at], (int32_t)ucfp::pk_entry_d(ent),
+                                                     &jlo, &jhi);
+                        }
+                    }
+                    f(valid, ord, ap, (uint32_t)(ad >> 10), jlo, jhi);
+                }
+                __syncthreads();
+            }
+        }
+        return;
+    }
     const uint64_t nslots = 3 * (e - a);
     for (uint64_t c = 0; c < nslots; c += kThreads) {
         const uint64_t s = c + threadIdx.x;
@@ -232,6 +328,22 @@ struct PkEmit {
     }
 };
 
+// stop[i] = the hash of posting i has more than max_postings postings: the posting max_postings places after the first
+// of its hash still carries it (scaled mode meets a posting without looking its hash up, so the flag travels with it)
+__global__ void pk_mark_stopped(const uint32_t* __restrict__ hashes, size_t n, uint32_t max_postings, uint8_t* __restrict__ stop) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t h = hashes[i];
+    size_t l = 0, r = i;   // first posting of h
+    while (l < r) {
+        const size_t mid = (l + r) >> 1;
+        if (hashes[mid] < h) l = mid + 1;
+        else r = mid;
+    }
+    const size_t far = l + max_postings;
+    stop[i] = far < n && hashes[far] == h ? 1 : 0;
+}
+
 // ---------------------------------------------------------------- query
 
 // one block: offsets (bytes) -> triple offsets; info[0] = triples in the batch
@@ -270,16 +382,34 @@ __global__ void pk_qkeys(const uint32_t* __restrict__ rec, size_t n, const uint6
     qh[i] = ((uint64_t)l << 32) | h;
 }
 
+// The plan as the kernel uses it.  Kept mode reads the kernel argument.  Scaled mode takes it through LDS, which moves
+// its eight words and the constants the compiler derives from them (the reciprocal of the step) from scalar to vector
+// registers: the kernels sit at the scalar register limit and have vector registers to spare, LDS bounding their
+// occupancy.  Ends with a barrier in scaled mode.
+template <int kBins>
+__device__ __forceinline__ PkMatch plan_for(const PkMatch& m) {
+    if constexpr (kBins == 0) {
+        return m;
+    } else {
+        __shared__ PkMatch s_m;
+        if (threadIdx.x == 0) s_m = m;
+        __syncthreads();
+        return s_m;
+    }
+}
+
 // one block per query: qn[q] = |Q|, votes[q] = V (expanded votes)
+template <int kBins>
 __global__ __launch_bounds__(kThreads) void pk_qruns(const uint64_t* __restrict__ qh, const uint64_t* __restrict__ qad,
-                                                      const uint64_t* __restrict__ toff, Postings P, PkMatch m,
+                                                      const uint64_t* __restrict__ toff, Postings P, PkMatch m_arg,
                                                       uint32_t* __restrict__ qn, uint64_t* __restrict__ votes) {
     __shared__ uint64_t s_inc[kThreads], s_qad[kThreads];
     __shared__ uint32_t s_lo[kThreads];
     __shared__ uint64_t s_w[4];
     const uint32_t q = blockIdx.x;
+    const PkMatch m = plan_for<kBins>(m_arg);
     uint64_t n_local = 0, v_local = 0;
-    for_each_match(qh, qad, toff[q], toff[q + 1], P, m, s_inc, s_lo, s_qad, s_w, n_local,
+    for_each_match<kBins>(qh, qad, toff[q], toff[q + 1], P, m, s_inc, s_lo, s_qad, s_w, n_local,
                    [&](bool valid, uint32_t, uint32_t, uint32_t, int32_t jlo, int32_t jhi) {
                        if (valid && jhi >= jlo) v_local += (uint64_t)(jhi - jlo + 1);
                    });
@@ -292,8 +422,9 @@ __global__ __launch_bounds__(kThreads) void pk_qruns(const uint64_t* __restrict_
 }
 
 // one block per query
+template <int kBins>
 __global__ __launch_bounds__(kThreads) void pk_vote(const uint64_t* __restrict__ qh, const uint64_t* __restrict__ qad,
-                                                     const uint64_t* __restrict__ toff, Postings P, PkMatch m,
+                                                     const uint64_t* __restrict__ toff, Postings P, PkMatch m_arg,
                                                      const uint32_t* __restrict__ qn, const uint64_t* __restrict__ votes,
                                                      const uint64_t* __restrict__ spill_base,
                                                      const uint64_t* __restrict__ ids, uint32_t k, uint32_t min_votes,
@@ -308,6 +439,7 @@ __global__ __launch_bounds__(kThreads) void pk_vote(const uint64_t* __restrict__
     __shared__ uint32_t s_rank[ucfp::kPkMaxHyp], s_jof[ucfp::kPkMaxHyp];
     __shared__ uint32_t s_cnt;
     const uint32_t q = blockIdx.x;
+    const PkMatch m = plan_for<kBins>(m_arg);
     const uint64_t base = spill_base[q];
     const bool spilling = base != kNoSpill;
     const uint64_t nv = votes[q];
@@ -319,7 +451,7 @@ __global__ __launch_bounds__(kThreads) void pk_vote(const uint64_t* __restrict__
     // the votes, in match order
     const uint64_t limit = spilling ? nv : (nv < kLdsVotes ? nv : kLdsVotes);
     uint64_t done = 0, unused = 0;
-    for_each_match(qh, qad, toff[q], toff[q + 1], P, m, s_inc, s_lo, s_qad, s_w, unused,
+    for_each_match<kBins>(qh, qad, toff[q], toff[q + 1], P, m, s_inc, s_lo, s_qad, s_w, unused,
                    [&](bool valid, uint32_t ord, uint32_t ap, uint32_t qa, int32_t jlo, int32_t jhi) {
                        const uint32_t cnt = valid && jhi >= jlo ? (uint32_t)(jhi - jlo + 1) : 0u;
                        const uint64_t incl = block_scan_incl(cnt, s_w);
@@ -456,7 +588,8 @@ struct Tenant {
     std::map<uint64_t, Record> recs;   // ascending id = ordinal order
     bool dirty = true;
     size_t postings = 0;               // deduplicated, valid when !dirty
-    DevArr hashes, entries, dir, ids;
+    bool stop_valid = false;           // `stop` follows the postings (made by the first scaled query after a rebuild)
+    DevArr hashes, entries, dir, ids, stop;
 };
 
 }  // namespace
@@ -496,15 +629,23 @@ int check_batch_host(const uint8_t* records, const uint64_t* offsets, size_t n, 
     return UCFP_OK;
 }
 
-int plan_match(const ucfp_panako_match_config* cfg, PkMatch* m) {
-    static const ucfp_panako_match_config dflt = {204, 320, 4, 16, 2, 1};
+int plan_match(const ucfp_panako_match_config_ex* cfg, PkMatch* m) {
+    static const ucfp_panako_match_config_ex dflt = {204, 320, 4, 16, 2, 1, 0, 0};
     if (!cfg) cfg = &dflt;
-    if (!ucfp::pk_plan(cfg->scale_min, cfg->scale_max, cfg->scale_step, cfg->window, cfg->slack, cfg->r_slack, m))
+    if (!ucfp::pk_plan_ex(cfg->scale_min, cfg->scale_max, cfg->scale_step, cfg->window, cfg->slack, cfg->r_slack, cfg->bins,
+                          cfg->f_slack, m))
         return capi_fail(UCFP_E_INVALID,
                          "match config out of range: scales 64 <= min <= max <= 1024 in at most %u steps >= 1, window 1 ... 256, "
-                         "slack 0 ... 8, r_slack 0 or 1",
-                         ucfp::kPkMaxHyp);
+                         "slack 0 ... 8, r_slack 0 or 1, bins 0 or 1, f_slack 0 ... %u and 0 with bins = 0",
+                         ucfp::kPkMaxHyp, ucfp::kPkMaxFSlack);
     return UCFP_OK;
+}
+
+// the old struct as the new one: the bins are kept
+const ucfp_panako_match_config_ex* widen(const ucfp_panako_match_config* cfg, ucfp_panako_match_config_ex* ex) {
+    if (!cfg) return nullptr;
+    *ex = {cfg->scale_min, cfg->scale_max, cfg->scale_step, cfg->window, cfg->slack, cfg->r_slack, 0, 0};
+    return ex;
 }
 
 int rebuild(ucfp_panako_index* ix, Tenant& T, hipStream_t st) {
@@ -553,6 +694,7 @@ int rebuild(ucfp_panako_index* ix, Tenant& T, hipStream_t st) {
     HIP_TRY(hipStreamSynchronize(st));   // the host vectors above go out of scope
     T.postings = p;
     T.dirty = false;
+    T.stop_valid = false;
     return UCFP_OK;
 }
 
@@ -623,7 +765,17 @@ int query_impl(ucfp_panako_index* ix, uint32_t tenant, const uint8_t* d_rec, con
     }
     Tenant& T = it->second;
     if (T.dirty && (rc = rebuild(ix, T, st))) return rc;
-    const Postings P{T.hashes.as<uint32_t>(), T.entries.as<uint64_t>(), T.dir.as<uint32_t>(), ix->max_postings};
+    Postings P{T.hashes.as<uint32_t>(), T.entries.as<uint64_t>(), T.dir.as<uint32_t>(), ix->max_postings, nullptr};
+    if (m.bins && ix->max_postings && T.postings) {
+        if (!T.stop_valid) {
+            if ((rc = T.stop.ensure(T.postings))) return rc;
+            hipLaunchKernelGGL(pk_mark_stopped, dim3((unsigned)((T.postings + 255) / 256)), dim3(256), 0, st, P.hashes,
+                               T.postings, ix->max_postings, T.stop.as<uint8_t>());
+            HIP_TRY(hipGetLastError());
+            T.stop_valid = true;
+        }
+        P.stop = T.stop.as<uint8_t>();
+    }
     // 2. equal triples of a query next to each other: stable sorts by (a, d), then by (query, hash); |Q| and V
     int qbits = 1;
     while (qbits < 32 && ((size_t)1 << qbits) < nq) qbits++;
@@ -631,7 +783,7 @@ int query_impl(ucfp_panako_index* ix, uint32_t tenant, const uint8_t* d_rec, con
         (rc = sort_pairs(ix->q_tmp, qh_b, qh_a, ad_b, ad_a, total, 32 + qbits, st)))
         return rc;
     if ((rc = ix->q_qn.ensure(nq * 4)) || (rc = ix->q_votes.ensure(nq * 8)) || (rc = ix->q_sbase.ensure(nq * 8))) return rc;
-    hipLaunchKernelGGL(pk_qruns, dim3((unsigned)nq), dim3(kThreads), 0, st, qh_a, ad_a, toff, P, m, ix->q_qn.as<uint32_t>(),
+    hipLaunchKernelGGL(m.bins ? pk_qruns<1> : pk_qruns<0>, dim3((unsigned)nq), dim3(kThreads), 0, st, qh_a, ad_a, toff, P, m, ix->q_qn.as<uint32_t>(),
                        ix->q_votes.as<uint64_t>());
     HIP_TRY(hipGetLastError());
     ix->h_votes.resize(nq);
@@ -666,7 +818,7 @@ int query_impl(ucfp_panako_index* ix, uint32_t tenant, const uint8_t* d_rec, con
         HIP_TRY(hipMemcpyAsync(ix->q_sq.p, ix->h_sq.data(), n_spill * 4, hipMemcpyHostToDevice, st));
     }
     // 4. votes: in LDS, or to the spill buffer
-    hipLaunchKernelGGL(pk_vote, dim3((unsigned)nq), dim3(kThreads), 0, st, qh_a, ad_a, toff, P, m, ix->q_qn.as<uint32_t>(),
+    hipLaunchKernelGGL(m.bins ? pk_vote<1> : pk_vote<0>, dim3((unsigned)nq), dim3(kThreads), 0, st, qh_a, ad_a, toff, P, m, ix->q_qn.as<uint32_t>(),
                        ix->q_votes.as<uint64_t>(), ix->q_sbase.as<uint64_t>(), T.ids.as<uint64_t>(), k, min_votes,
                        n_spill ? ix->q_spill_a.as<uint64_t>() : nullptr, out);
     HIP_TRY(hipGetLastError());
@@ -690,7 +842,7 @@ int query_impl(ucfp_panako_index* ix, uint32_t tenant, const uint8_t* d_rec, con
     return UCFP_OK;
 }
 
-int query_args(ucfp_panako_index* ix, const uint64_t* offsets, size_t nq, uint32_t k, const ucfp_panako_match_config* cfg,
+int query_args(ucfp_panako_index* ix, const uint64_t* offsets, size_t nq, uint32_t k, const ucfp_panako_match_config_ex* cfg,
                PkMatch* m, const Outputs& out) {
     if (!ix) return capi_fail(UCFP_E_INVALID, "index is NULL");
     if (k > UCFP_INDEX_MAX_K) return capi_fail(UCFP_E_INVALID, "k = %u exceeds UCFP_INDEX_MAX_K = %u", k, UCFP_INDEX_MAX_K);
@@ -722,7 +874,7 @@ void ucfp_panako_index_destroy(ucfp_panako_index* ix) {
     if (!ix) return;
     ix->quiesce();
     for (auto& kv : ix->tenants)
-        for (DevArr* a : {&kv.second.hashes, &kv.second.entries, &kv.second.dir, &kv.second.ids}) a->release();
+        for (DevArr* a : {&kv.second.hashes, &kv.second.entries, &kv.second.dir, &kv.second.ids, &kv.second.stop}) a->release();
     for (DevArr* a : {&ix->b_ent_a, &ix->b_ent_b, &ix->b_hash_a, &ix->b_hash_b, &ix->b_cnt, &ix->b_off, &ix->b_tmp, &ix->q_rec,
                       &ix->q_off, &ix->q_toff, &ix->q_info, &ix->q_ad_a, &ix->q_ad_b, &ix->q_qh_a, &ix->q_qh_b, &ix->q_tmp,
                       &ix->q_qn, &ix->q_votes, &ix->q_sbase, &ix->q_soff, &ix->q_sq, &ix->q_spill_a, &ix->q_spill_b,
@@ -796,10 +948,10 @@ int ucfp_panako_index_size(ucfp_panako_index* ix, uint32_t tenant, size_t* recor
 
 int ucfp_panako_index_flush(ucfp_panako_index* ix) { return ucfp::flush_dirty(ix, rebuild); }
 
-int ucfp_panako_index_query_dev(ucfp_panako_index* ix, uint32_t tenant, const uint8_t* d_records, const uint64_t* d_offsets,
-                                size_t nq, uint32_t k, uint32_t min_votes, const ucfp_panako_match_config* cfg,
-                                uint64_t* d_out_ids, uint32_t* d_out_votes, int32_t* d_out_offsets, uint32_t* d_out_scales,
-                                float* d_out_scores, uint32_t* d_out_n, void* stream) {
+int ucfp_panako_index_query_ex_dev(ucfp_panako_index* ix, uint32_t tenant, const uint8_t* d_records, const uint64_t* d_offsets,
+                                   size_t nq, uint32_t k, uint32_t min_votes, const ucfp_panako_match_config_ex* cfg,
+                                   uint64_t* d_out_ids, uint32_t* d_out_votes, int32_t* d_out_offsets, uint32_t* d_out_scales,
+                                   float* d_out_scores, uint32_t* d_out_n, void* stream) {
     const Outputs out{d_out_ids, d_out_votes, d_out_offsets, d_out_scales, d_out_scores, d_out_n};
     PkMatch m;
     int rc = query_args(ix, d_offsets, nq, k, cfg, &m, out);
@@ -811,10 +963,10 @@ int ucfp_panako_index_query_dev(ucfp_panako_index* ix, uint32_t tenant, const ui
     return ix->end(st, rc);
 }
 
-int ucfp_panako_index_query(ucfp_panako_index* ix, uint32_t tenant, const uint8_t* records, const uint64_t* offsets, size_t nq,
-                            uint32_t k, uint32_t min_votes, const ucfp_panako_match_config* cfg, uint64_t* out_ids,
-                            uint32_t* out_votes, int32_t* out_offsets, uint32_t* out_scales, float* out_scores,
-                            uint32_t* out_n) {
+int ucfp_panako_index_query_ex(ucfp_panako_index* ix, uint32_t tenant, const uint8_t* records, const uint64_t* offsets,
+                               size_t nq, uint32_t k, uint32_t min_votes, const ucfp_panako_match_config_ex* cfg,
+                               uint64_t* out_ids, uint32_t* out_votes, int32_t* out_offsets, uint32_t* out_scales,
+                               float* out_scores, uint32_t* out_n) {
     PkMatch m;
     int rc = query_args(ix, offsets, nq, k, cfg, &m, Outputs{out_ids, out_votes, out_offsets, out_scales, out_scores, out_n});
     if (rc || nq == 0) return rc;
@@ -842,6 +994,24 @@ int ucfp_panako_index_query(ucfp_panako_index* ix, uint32_t tenant, const uint8_
     }
     HIP_TRY(hipMemcpyAsync(out_n, dev.n, nq * 4, hipMemcpyDeviceToHost, st));
     return ix->end_sync(UCFP_OK);
+}
+
+int ucfp_panako_index_query_dev(ucfp_panako_index* ix, uint32_t tenant, const uint8_t* d_records, const uint64_t* d_offsets,
+                                size_t nq, uint32_t k, uint32_t min_votes, const ucfp_panako_match_config* cfg,
+                                uint64_t* d_out_ids, uint32_t* d_out_votes, int32_t* d_out_offsets, uint32_t* d_out_scales,
+                                float* d_out_scores, uint32_t* d_out_n, void* stream) {
+    ucfp_panako_match_config_ex ex;
+    return ucfp_panako_index_query_ex_dev(ix, tenant, d_records, d_offsets, nq, k, min_votes, widen(cfg, &ex), d_out_ids,
+                                          d_out_votes, d_out_offsets, d_out_scales, d_out_scores, d_out_n, stream);
+}
+
+int ucfp_panako_index_query(ucfp_panako_index* ix, uint32_t tenant, const uint8_t* records, const uint64_t* offsets, size_t nq,
+                            uint32_t k, uint32_t min_votes, const ucfp_panako_match_config* cfg, uint64_t* out_ids,
+                            uint32_t* out_votes, int32_t* out_offsets, uint32_t* out_scales, float* out_scores,
+                            uint32_t* out_n) {
+    ucfp_panako_match_config_ex ex;
+    return ucfp_panako_index_query_ex(ix, tenant, records, offsets, nq, k, min_votes, widen(cfg, &ex), out_ids, out_votes,
+                                      out_offsets, out_scales, out_scores, out_n);
 }
 
 }  // extern "C"

@@ -1,7 +1,8 @@
-// panako_match.h -- the integer arithmetic of the Panako scale/offset vote, shared by the kernels of
-// panako_index.hip and by a plain C++ check on the CPU (tests/native/panako_match_check.cpp): the probes of a query
-// hash, the hypotheses a match supports, its offset under a hypothesis, the preference rank of a hypothesis and the
-// packed keys the vote sorts and folds.  No HIP types: it compiles with g++.
+// panako_match.h -- the integer arithmetic of the Panako scale/offset vote, shared by the kernels
+// of panako_index.hip and by plain C++ checks on the CPU (tests/native/panako_match_check.cpp, panako_pitch_check.cpp):
+// the probes of a query hash, the hypotheses a match supports, its offset under a hypothesis, the preference rank of a
+// hypothesis, the packed keys the vote sorts and folds and, for A22, the bin map of a hypothesis and the hypotheses
+// under which a posting's bin follows a query's.  No HIP types: it compiles with g++.
 #pragma once
 #include <stdint.h>
 
@@ -18,6 +19,8 @@ constexpr uint32_t kPkMaxD = 1023;           // d = t_c - t_a of a triple: 1 ...
 constexpr uint32_t kPkOrdBits = 23;          // ordinal bits of a posting entry: a' (31) | d' (10) | ordinal (23)
 constexpr uint32_t kPkCountBits = 26;        // count bits of the packed best: count (26) | preference (6) | ~offset (32)
 constexpr uint32_t kPkBias = 0x80000000u;    // an offset is stored as offset + 2^31 (monotone)
+constexpr int32_t kPkMaxBin = 511;           // the three bins of a hash are 9 bits each: k_a << 23 | k_b << 14 | k_c << 5 | r
+constexpr uint32_t kPkMaxFSlack = 3;
 
 // a checked ucfp_panako_match_config; scales in units of 1/256
 struct PkMatch {
@@ -27,6 +30,8 @@ struct PkMatch {
     int32_t window;   // W
     int32_t slack;
     int32_t r_slack;
+    int32_t bins;     // 0 = the bins are kept (A14), 1 = they follow the scale (A22)
+    int32_t f_slack;  // 0 ... 3 bins, 0 when bins = 0
 };
 
 // false when a field is out of range or the hypotheses exceed kPkMaxHyp
@@ -42,6 +47,18 @@ UCFP_PKM bool pk_plan(uint32_t scale_min, uint32_t scale_max, uint32_t scale_ste
     m->window = (int32_t)window;
     m->slack = (int32_t)slack;
     m->r_slack = (int32_t)r_slack;
+    m->bins = 0;
+    m->f_slack = 0;
+    return true;
+}
+
+// the same with the two parameters of A22: bins 0 or 1, f_slack 0 ... 3 and 0 when the bins are kept
+UCFP_PKM bool pk_plan_ex(uint32_t scale_min, uint32_t scale_max, uint32_t scale_step, uint32_t window, uint32_t slack,
+                         uint32_t r_slack, uint32_t bins, uint32_t f_slack, PkMatch* m) {
+    if (bins > 1 || f_slack > kPkMaxFSlack || (bins == 0 && f_slack != 0)) return false;
+    if (!pk_plan(scale_min, scale_max, scale_step, window, slack, r_slack, m)) return false;
+    m->bins = (int32_t)bins;
+    m->f_slack = (int32_t)f_slack;
     return true;
 }
 
@@ -62,6 +79,54 @@ UCFP_PKM void pk_interval(const PkMatch& m, int32_t d, int32_t dp, int32_t* jlo,
     *jlo = lo <= 0 ? 0 : (lo + sd - 1) / sd;
     const int32_t h = hi < 0 ? -1 : hi / sd;
     *jhi = h > m.nh - 1 ? m.nh - 1 : h;
+}
+
+// A22: the bin of the record that bin k of a query played at speed s / 256 came from: round(256 k / s), halves up.
+// k <= 511 and 64 <= s <= 1024: non-increasing in s, at most 2048, and pk_bin(256, k) = k.
+UCFP_PKM int32_t pk_bin(int32_t s, int32_t k) { return (512 * k + s) / (2 * s); }
+
+// A22: the hypotheses j with |k' - pk_bin(s_j, k)| <= f.  Over 64 <= s <= 1024 they are the s of one interval,
+//   k' - f <= (512 k + s) / (2 s)  <=>  s (2 (k' - f) - 1) <= 512 k       (no upper end when k' - f < 1)
+//   (512 k + s) / (2 s) <= k' + f  <=>  s (2 (k' + f) + 1) >  512 k,
+// so s_lo = 512 k / (2 k' + 2 f + 1) + 1 and s_hi = 512 k / (2 (k' - f) - 1); on the grid, clamped to [0, nh - 1].
+// Empty when *jlo > *jhi.
+UCFP_PKM void pk_bin_interval(const PkMatch& m, int32_t k, int32_t kp, int32_t f, int32_t* jlo, int32_t* jhi) {
+    const int32_t s_lo = (512 * k) / (2 * kp + 2 * f + 1) + 1;
+    *jlo = s_lo <= m.smin ? 0 : (s_lo - m.smin + m.step - 1) / m.step;
+    int32_t h = m.nh - 1;
+    if (kp - f >= 1) {
+        const int32_t s_hi = (512 * k) / (2 * (kp - f) - 1);
+        const int32_t t = s_hi < m.smin ? -1 : (s_hi - m.smin) / m.step;
+        h = t < h ? t : h;
+    }
+    *jhi = h;
+}
+
+// A22: the hypotheses a (query triple, posting) pair supports in scaled mode -- the intersection of pk_interval's with
+// the three bin intervals -- or none when the ratio bits differ by more than r_slack.  hq, hp = the two hashes.
+UCFP_PKM void pk_interval_scaled(const PkMatch& m, uint32_t hq, int32_t d, uint32_t hp, int32_t dp, int32_t* jlo,
+                                 int32_t* jhi) {
+    const int32_t dr = (int32_t)(hp & 31u) - (int32_t)(hq & 31u);
+    int32_t lo = 0, hi = -1;
+    if (dr >= -m.r_slack && dr <= m.r_slack) {
+        pk_interval(m, d, dp, &lo, &hi);
+        for (uint32_t sh = 5; sh <= 23 && lo <= hi; sh += 9) {
+            int32_t l, h;
+            pk_bin_interval(m, (int32_t)((hq >> sh) & 511u), (int32_t)((hp >> sh) & 511u), m.f_slack, &l, &h);
+            lo = l > lo ? l : lo;
+            hi = h < hi ? h : hi;
+        }
+    }
+    *jlo = lo;
+    *jhi = hi;
+}
+
+// A22: the bins k' that bin k of a query can meet under the hypotheses jlo ... jhi, clamped to 0 ... 511 (a clamped bin
+// never carries into the neighbouring field of the hash)
+UCFP_PKM void pk_bin_range(const PkMatch& m, int32_t k, int32_t jlo, int32_t jhi, int32_t* klo, int32_t* khi) {
+    const int32_t lo = pk_bin(m.smin + jhi * m.step, k) - m.f_slack, hi = pk_bin(m.smin + jlo * m.step, k) + m.f_slack;
+    *klo = lo < 0 ? 0 : lo;
+    *khi = hi > kPkMaxBin ? kPkMaxBin : hi;
 }
 
 // the offset of a match under scale s: a' - ((s a + 128) >> 8); a < 2^28, s <= 1024, a' < 2^31, so it fits an int32

@@ -9,7 +9,8 @@ path, backed by the GPU-resident shard behind the C ABI (ucfp_index_*).
     GpuIndex.identify(tenant, lm, k)  audio identification over Wang landmarks (DESIGN A10; LandmarkIndex), or with
                                       algorithm=ALGORITHM_PANAKO over Panako (hash, t_anchor) pairs (DESIGN A13)
     GpuIndex.identify_stretched(tenant, records, k)  the same over whole Panako triplets, by a (scale, offset) vote that
-                                      survives a change of tempo (DESIGN A14; PanakoIndex)
+                                      survives a change of tempo (DESIGN A14; PanakoIndex) or, with bins="scaled",
+                                      a resampled copy whose pitch moved with its speed (DESIGN A22)
     GpuIndex.identify_live(tenant, streams, slots, k)  identify / identify_stretched over the live windows of a WangStreams
                                       / PanakoStreams, windows and queries on the device (DESIGN A20)
     GpuIndex.identify_frames(tenant, frames, k)  the same over Haitsma sub-fingerprints (DESIGN A12; HaitsmaIndex)
@@ -291,15 +292,29 @@ def _pack_triplets(items):
 PANAKO_MATCH_DEFAULTS = dict(scale_min=204, scale_max=320, scale_step=4, window=16, slack=2, r_slack=1)
 
 
-def panako_match_config(**match) -> "_lib.PanakoMatchConfig":
-    """ucfp_panako_match_config from keyword arguments over PANAKO_MATCH_DEFAULTS (scales in units of 1/256)."""
-    unknown = set(match) - set(PANAKO_MATCH_DEFAULTS)
+PANAKO_BINS = {"kept": 0, "scaled": 1}
+# what bins="scaled" changes in the defaults: measured on resampled tone-burst excerpts at speeds 0.85 ... 1.2
+# (DESIGN A22): a 4/256 scale grid is up to 3.5 bins off at bin 440 and needs f_slack = 3 for the votes that a 2/256
+# grid gets with f_slack = 1, from three times the buckets
+PANAKO_SCALED_DEFAULTS = dict(scale_step=2, f_slack=1)
+
+
+def panako_match_config(**match) -> "_lib.PanakoMatchConfigEx":
+    """ucfp_panako_match_config_ex from keyword arguments over PANAKO_MATCH_DEFAULTS (scales in units of 1/256), plus
+    bins = "kept" (the default: the vote of DESIGN A14, for time-stretched copies) or "scaled" (A22, for resampled
+    copies, whose frequencies move with the speed) and f_slack (0 ... 3 bins, scaled mode only).  With bins="scaled"
+    the defaults become scale_step = 2 and f_slack = 1; these were measured, not derived (PANAKO_SCALED_DEFAULTS)."""
+    match = dict(match)
+    bins = match.pop("bins", "kept")
+    if not isinstance(bins, str) or bins not in PANAKO_BINS:
+        raise InvalidArgument(f"bins is one of {sorted(PANAKO_BINS)}, not {bins!r}")
+    unknown = set(match) - set(PANAKO_MATCH_DEFAULTS) - {"f_slack"}
     if unknown:
         raise InvalidArgument(f"unknown match parameters: {sorted(unknown)}")
-    v = {**PANAKO_MATCH_DEFAULTS, **match}
+    v = {**PANAKO_MATCH_DEFAULTS, "f_slack": 0, **(PANAKO_SCALED_DEFAULTS if bins == "scaled" else {}), **match}
     if not all(isinstance(x, (int, np.integer)) and 0 <= int(x) < 1 << 32 for x in v.values()):
         raise InvalidArgument("match parameters are integers in 0 ... 2^32 - 1")
-    return _lib.PanakoMatchConfig(*(int(v[name]) for name in PANAKO_MATCH_DEFAULTS))
+    return _lib.PanakoMatchConfigEx(*(int(v[name]) for name in PANAKO_MATCH_DEFAULTS), PANAKO_BINS[bins], int(v["f_slack"]))
 
 
 class PanakoIndex:
@@ -360,7 +375,8 @@ class PanakoIndex:
         _lib.check(self._lib.ucfp_panako_index_flush(self.handle))
 
     def query(self, tenant: int, queries, k: int, min_votes: int = 1, **match):
-        """queries: Panako records (bytes or uint32 [m, 4]); match: fields of PANAKO_MATCH_DEFAULTS.  -> (ids [nq,k] u64,
+        """queries: Panako records (bytes or uint32 [m, 4]); match: fields of PANAKO_MATCH_DEFAULTS, bins="kept" |
+        "scaled" and f_slack (panako_match_config).  -> (ids [nq,k] u64,
         votes [nq,k] u32, offsets [nq,k] i32, scales [nq,k] u32 in 1/256, scores [nq,k] f32, counts [nq] u32)."""
         cfg = panako_match_config(**match)
         blob, offs = _pack_triplets(list(queries))
@@ -372,7 +388,7 @@ class PanakoIndex:
         scales = np.zeros((nq, kk), np.uint32)
         scores = np.zeros((nq, kk), np.float32)
         counts = np.zeros(nq, np.uint32)
-        _lib.check(self._lib.ucfp_panako_index_query(self.handle, tenant, blob.ctypes.data, offs.ctypes.data, nq, int(k),
+        _lib.check(self._lib.ucfp_panako_index_query_ex(self.handle, tenant, blob.ctypes.data, offs.ctypes.data, nq, int(k),
                                                      int(min_votes), C.byref(cfg), ids.ctypes.data, votes.ctypes.data,
                                                      offsets.ctypes.data, scales.ctypes.data, scores.ctypes.data,
                                                      counts.ctypes.data))
@@ -382,7 +398,7 @@ class PanakoIndex:
                   out_votes_ptr: int, out_offsets_ptr: int, out_scales_ptr: int, out_scores_ptr: int, out_n_ptr: int,
                   stream: int = 0, **match) -> None:
         cfg = panako_match_config(**match)
-        _lib.check(self._lib.ucfp_panako_index_query_dev(self.handle, tenant, records_ptr or None, offsets_ptr, nq, k,
+        _lib.check(self._lib.ucfp_panako_index_query_ex_dev(self.handle, tenant, records_ptr or None, offsets_ptr, nq, k,
                                                          min_votes, C.byref(cfg), out_ids_ptr or None, out_votes_ptr or None,
                                                          out_offsets_ptr or None, out_scales_ptr or None,
                                                          out_scores_ptr or None, out_n_ptr, stream or None))
@@ -1091,7 +1107,9 @@ class GpuIndex:
         """Which recording is this clip, where in it and at what tempo: records = Panako records as bytes (16 per
         triplet) or uint32 [n, 4] of (hash, t_a, t_b, t_c).  Hits by votes that agree on a scale and an offset window
         (DESIGN A14; `match` overrides PANAKO_MATCH_DEFAULTS): `offset` = the clip's frame 0 in the record, `scale` =
-        the record's frames per frame of the clip."""
+        the record's frames per frame of the clip.  bins="scaled" in `match` (DESIGN A22, panako_match_config) finds a
+        resampled copy, whose frequencies moved with its speed, instead of a time-stretched one; a caller who does not
+        know which change a copy went through asks both ways."""
         if self._ps is None:
             panako_match_config(**match)
             return []
@@ -1105,7 +1123,8 @@ class GpuIndex:
         `PanakoStreams` created with window_frames > 0 (DESIGN A20).  The windows go from the set to the index on the
         device (`windows_dev` -> `LandmarkIndex.query_dev` / `PanakoIndex.query_dev`, one stream); only the answers
         come back.  The hits of a slot are those of `identify` (Wang) / `identify_stretched` (Panako, with `match`) on
-        the host copy of its window, [] for an empty window; `offset` = frame `origin` of the stream in the record.  A
+        the host copy of its window, [] for an empty window; `offset` = frame `origin` of the stream in the record.
+        bins="scaled" in `match` finds a feed that runs fast or slow (DESIGN A22), still without a host trip.  A
         set that resamples its feed (`resample=True`, DESIGN A21) needs nothing else: its windows and origins are in
         8 kHz frames like any other's.  A set without windows raises InvalidArgument.  Haitsma sets are left out on
         purpose: `blocks_dev` reports no origin, so a hit's offset could not be placed in the stream."""
@@ -1250,7 +1269,8 @@ class GpuIndex:
     def query(self, req) -> List[Hit]:
         """POST /v1/query (handlers.rs:143-187) with the additive `hash` field: a vector goes to the cosine kNN,
         a hash to the Hamming space `algorithm` (default: the only hash space present), `landmarks` to identify (the Panako
-        index when `algorithm` is "audiofp-panako-v1", the Wang one otherwise), `triplets` to identify_stretched,
+        index when `algorithm` is "audiofp-panako-v1", the Wang one otherwise), `triplets` to identify_stretched (with
+        bins="scaled" when `resampled` is true),
         `subfingerprints` to identify_frames, `tlsh` to nearest_tlsh, `image_record` to similar_images,
         `minhash` to similar_text;
         `terms` go through the matcher (BM25, or vector + BM25 fused by RRF: src/matcher/mod.rs:140-207)."""
@@ -1279,7 +1299,8 @@ class GpuIndex:
         elif getattr(req, "triplets", None) is not None:
             if getattr(req, "algorithm", None) != ALGORITHM_PANAKO:
                 raise InvalidArgument(f"`triplets` need `algorithm` = {ALGORITHM_PANAKO!r}")
-            hits = self.identify_stretched(req.tenant_id, req.triplets, req.k)
+            match = dict(bins="scaled") if getattr(req, "resampled", False) else {}
+            hits = self.identify_stretched(req.tenant_id, req.triplets, req.k, **match)
         elif getattr(req, "landmarks", None) is not None:
             panako = getattr(req, "algorithm", None) == ALGORITHM_PANAKO
             hits = self.identify(req.tenant_id, req.landmarks, req.k,

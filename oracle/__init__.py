@@ -309,6 +309,16 @@ def haitsma(x, sample_rate: int, fmin: float = 300.0, fmax: float = 2000.0) -> n
     return out
 
 
+def haitsma_edges(fmin: float = 300.0, fmax: float = 2000.0) -> np.ndarray:
+    """u32 [34]: band b of `haitsma` sums the bins [edges[b], edges[b + 1])."""
+    out = np.zeros(34, np.uint32)
+    f = lib().ucfp_oracle_haitsma_edges
+    f.restype = None
+    f.argtypes = [C.c_float, C.c_float, C.c_void_p]
+    f(fmin, fmax, out.ctypes.data)
+    return out
+
+
 def num_threads() -> int:
     return int(lib().ucfp_oracle_num_threads())
 

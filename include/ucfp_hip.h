@@ -1403,6 +1403,44 @@ int ucfp_bm25_index_query_dev(ucfp_bm25_index* ix, uint32_t tenant, const uint64
                               size_t nq, uint32_t k, uint64_t* d_out_ids, float* d_out_scores, uint32_t* d_out_n,
                               float* d_out_idf, uint32_t* d_out_tf, float* d_out_contrib, void* stream);
 
+/* ---- BM25 terms: tokenise, hash and count on the device (bm25.rs:88-97 `tokenize`, :343) ----
+ * Document i of a batch is utf8[offsets[i] .. offsets[i+1]) (BYTE offsets, n + 1 entries).  A token is a maximal run of
+ * bytes in [0-9A-Za-z] with A-Z mapped to a-z; every other byte separates ('_', '\'', '.', ':', ',' and ';' included:
+ * this is not the word rule of the MinHash / SimHash entries).  Its key is XXH3_64 of the lower-cased bytes, seed 0 =
+ * ucfp_text_token_key.  Every u64 is a legal key; two terms whose keys collide are one term.
+ *   form UCFP_BM25_TERMS_COUNTS    the distinct keys of each document in ascending order, each with its count tf: what
+ *                                  ucfp_bm25_index_upsert(_dev) takes (a key never twice in one document);
+ *        UCFP_BM25_TERMS_SEQUENCE  one key per token in text order, duplicates kept: what ucfp_bm25_index_query(_dev)
+ *                                  takes.  tfs is not written and may be NULL.
+ * Document i's pairs are keys/tfs[pair_offsets[i] .. pair_offsets[i+1]): ELEMENT offsets, n + 1 entries, non-decreasing,
+ * pair_offsets[0] = 0.  status[i]:
+ *   0                     every ASCII document; one of length 0 or without a letter or digit has no pairs (it still
+ *                         counts in N of the index);
+ *   UCFP_TEXT_NEEDS_HOST  a byte >= 0x80 anywhere in the document: no pairs, and this status wins.  Unicode
+ *                         is_alphanumeric and to_lowercase (Final_Sigma, U+0130) stay on the host;
+ *   UCFP_E_UNSUPPORTED    only for a document holding a token of more than UCFP_TEXT_MAX_WINDOW_BYTES bytes: no pairs.
+ *                         Tokens up to that length are never refused; above it the document gets either status 0 and the
+ *                         right pairs or this status;
+ *   UCFP_E_INVALID        offsets[i+1] < offsets[i], offsets[i+1] > n_bytes, offsets[i] below an earlier offset of the
+ *                         table (the document would share bytes with an earlier one) or 2^31 bytes and more: no pairs.
+ *                         No byte outside [0, n_bytes) is read.
+ * A document whose status is not 0 has an empty range.  cap_pairs >= ucfp_bm25_terms_max_pairs(n_bytes, n) = (n_bytes +
+ * n) / 2 (host-only): a token takes a byte and two tokens a separator between them.  The host form takes n_bytes =
+ * offsets[n].  UCFP_E_INVALID before anything runs or is written: ctx NULL (checked first), an unknown form, a NULL
+ * buffer (tfs in form COUNTS; utf8 when n_bytes > 0), n >= 2^31, n_bytes + n >= 2^33, cap_pairs below the bound.
+ * The scratch (6 bytes per input byte, 28 per token in form COUNTS) belongs to the context and grows on demand; calls
+ * on different streams are ordered on the device.  HOST SYNCHRONISATIONS of the _dev form: SEQUENCE none; COUNTS one of
+ * `stream`, to read the batch's token count back (it sizes the sort).  A call that grows the scratch frees the old
+ * buffers, which waits for the device. */
+#define UCFP_BM25_TERMS_COUNTS 0
+#define UCFP_BM25_TERMS_SEQUENCE 1
+size_t ucfp_bm25_terms_max_pairs(size_t n_bytes, size_t n);
+int ucfp_bm25_terms_batch_dev(ucfp_ctx* ctx, const uint8_t* d_utf8, const uint64_t* d_offsets, size_t n, size_t n_bytes,
+                              int form, uint64_t* d_keys, uint32_t* d_tfs, size_t cap_pairs, uint64_t* d_pair_offsets,
+                              int32_t* d_status, void* stream);
+int ucfp_bm25_terms_batch(ucfp_ctx* ctx, const uint8_t* utf8, const uint64_t* offsets, size_t n, int form, uint64_t* keys,
+                          uint32_t* tfs, size_t cap_pairs, uint64_t* pair_offsets, int32_t* status);
+
 /* =============================== INDEX ========================================
  * Replaces `trait IndexBackend` kNN (src/index/mod.rs:29-35) as implemented by
  * EmbeddedBackend::knn (src/index/embedded/mod.rs:268-360): exact brute-force top-k inside

@@ -317,6 +317,11 @@ SIGNATURES = {
     "ucfp_bm25_index_query_dev": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p]),
+    "ucfp_bm25_terms_max_pairs": (C.c_size_t, [C.c_size_t, C.c_size_t]),
+    "ucfp_bm25_terms_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p,
+                                            C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ucfp_bm25_terms_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p,
+                                        C.c_size_t, C.c_void_p, C.c_void_p]),
     "ucfp_image_record_codes_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p,
                                               C.c_void_p]),
     "ucfp_index_save": (C.c_int, [C.c_void_p, C.c_char_p]),

@@ -168,6 +168,7 @@ void ucfp_ctx_destroy(ucfp_ctx* c) {
     if (c->geo) (void)hipFree(c->geo);
     if (c->canon_ws) (void)hipFree(c->canon_ws);
     if (c->canon_done) (void)hipEventDestroy(c->canon_done);
+    ucfp::bm25_terms_ws_free(c->terms_ws);
     for (int i = 0; i < 2; i++) {
         if (c->item_h[i]) (void)hipHostFree(c->item_h[i]);
         if (c->item_d[i]) (void)hipFree(c->item_d[i]);

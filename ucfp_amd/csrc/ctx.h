@@ -7,6 +7,11 @@
 #include "../../include/ucfp_hip.h"
 #include "common.h"
 
+namespace ucfp {
+struct Bm25TermsWs;                          // bm25_terms.hip: the scratch of the BM25 terms entries
+void bm25_terms_ws_free(Bm25TermsWs* w);     // (NULL is fine)
+}  // namespace ucfp
+
 struct ucfp_ctx {
     int device = 0;
     uint8_t* norm_ws = nullptr;  // kNormWsFrames x 65536: ONE scratch area shared by every generic-geometry launch,
@@ -53,6 +58,10 @@ struct ucfp_ctx {
     std::mutex geo_mu;
     uint32_t* geo = nullptr;
     uint64_t geo_have[2049 / 64 + 1] = {0};
+    // BM25 terms: slots, counts and sort scratch, made at the first call; its users are ordered across
+    // streams by the event it holds, enqueued under terms_mu
+    std::mutex terms_mu;
+    ucfp::Bm25TermsWs* terms_ws = nullptr;
 };
 
 

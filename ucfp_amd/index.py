@@ -37,7 +37,7 @@ from .core import Hit, HitSource, Record, TermHit
 from .errors import InvalidArgument, UnsupportedError
 from .image import MultiHashConfig, match_algo
 from .image import _TAG as _IMAGE_TAG
-from .terms import query_terms, tokenize
+from .terms import query_terms, term_key, terms_batch, tokenize
 from .text import ALGORITHM_LSH, ALGORITHM_MINHASH_128, ALGORITHM_TLSH, DEFAULT_H, MINHASH_BYTES, _check_h, minhash_slots
 
 HAMMING64, COSINE_F32 = 1, 2
@@ -709,12 +709,17 @@ class ImageMatchIndex(_ScanIndex):
 class Bm25Index:
     """Thin RAII wrapper over one ucfp_bm25_index (DESIGN A11): BM25 over documents of (key, tf) pairs.  It keeps the
     term -> key dictionary of the index (keys number the terms in order of first sight); query terms it has never
-    seen are dropped on the host."""
+    seen are dropped on the host.  With keys="hashed" (DESIGN A23) a term's key is its hash (terms.term_key): the device
+    tokenises, hashes and counts the texts (terms.terms_batch), the dictionary stays empty, and an unseen query term is a
+    key that matches nothing."""
 
-    def __init__(self, flags: int = 0, ctx=None):
+    def __init__(self, flags: int = 0, ctx=None, keys: str = "numbered"):
+        if keys not in ("numbered", "hashed"):
+            raise InvalidArgument(f"unknown BM25 key mode {keys!r}: 'numbered' or 'hashed'")
+        self.hashed = keys == "hashed"
         self._lib = _lib.load()
         self.ctx = ctx or _lib.current_context()
-        self.keys = {}     # term -> key
+        self.keys = {}     # term -> key (numbered mode)
         h = C.c_void_p()
         _lib.check(self._lib.ucfp_bm25_index_create(self.ctx.handle, flags, C.byref(h)))
         self.handle = h
@@ -755,6 +760,10 @@ class Bm25Index:
         texts = list(texts)
         if len(texts) != ids.size:
             raise InvalidArgument("ids and texts disagree on the number of documents")
+        if self.hashed:
+            keys, tfs, offs, _ = terms_batch(texts, "counts", self.ctx)
+            self.upsert_pairs(tenant, ids, keys, tfs, offs)
+            return
         keys, tfs, offs = [], [], [0]
         for t in texts:
             counts = {}
@@ -816,24 +825,49 @@ class Bm25Index:
     def search(self, tenant: int, terms: Sequence[str], k: int, explain: bool = False) -> List[Hit]:
         """bm25.rs `search_explain`: the query terms are re-tokenized and flattened; each hit explains at most 16
         matched positions, sorted stably by contribution, descending."""
-        toks = [t for t in query_terms(terms) if t in self.keys]
+        toks = query_terms(terms)
+        if not self.hashed:
+            toks = [t for t in toks if t in self.keys]
         if k == 0 or not toks:
             return []
         k = min(k, MAX_K)
-        res = self.query_keys(tenant, [[self.keys[t] for t in toks]], k, explain)
+        res = self.query_keys(tenant, [[term_key(t) if self.hashed else self.keys[t] for t in toks]], k, explain)
+        return self._hits(tenant, res, 0, 0, toks, k, explain)
+
+    def _hits(self, tenant: int, res, q: int, base: int, toks, k: int, explain: bool) -> List[Hit]:
+        """The hits of query q of a query_keys result; its m = len(toks) positions begin at `base` of the explain arrays."""
         ids, scores, counts = res[:3]
         hits = []
         m = len(toks)
-        for h in range(int(counts[0])):
+        for h in range(int(counts[q])):
             th = []
             if explain:
                 idf, tf, con = res[3:]
-                th = [TermHit(term=toks[j], idf=float(idf[j]), tf=int(tf[h * m + j]), contribution=float(con[h * m + j]))
-                      for j in range(m) if tf[h * m + j]]
+                o = k * base + h * m
+                th = [TermHit(term=toks[j], idf=float(idf[base + j]), tf=int(tf[o + j]), contribution=float(con[o + j]))
+                      for j in range(m) if tf[o + j]]
                 th = sorted(th, key=lambda t: t.contribution, reverse=True)[:TERM_HITS_PER_DOC]
-            hits.append(Hit(tenant_id=tenant, record_id=int(ids[0, h]), score=float(scores[0, h]), source=HitSource.Bm25,
+            hits.append(Hit(tenant_id=tenant, record_id=int(ids[q, h]), score=float(scores[q, h]), source=HitSource.Bm25,
                             term_hits=th))
         return hits
+
+    def search_texts(self, tenant: int, texts: Sequence[str], k: int, explain: bool = False) -> List[List[Hit]]:
+        """A batch of query strings (hashed mode): the device tokenises and hashes them (the SEQUENCE form of
+        terms.terms_batch), one query_keys call scores them.  -> one hit list per text, each what
+        search(tenant, [text], k, explain) returns."""
+        if not self.hashed:
+            raise InvalidArgument("search_texts needs keys='hashed'")
+        texts = list(texts)
+        if k == 0 or not texts:
+            return [[] for _ in texts]
+        k = min(k, MAX_K)
+        keys, _, offs, _ = terms_batch(texts, "sequence", self.ctx)
+        res = self.query_keys(tenant, [keys[int(offs[i]):int(offs[i + 1])] for i in range(len(texts))], k, explain)
+        out = []
+        for i, t in enumerate(texts):
+            toks = tokenize(t) if explain else [None] * int(offs[i + 1] - offs[i])
+            out.append(self._hits(tenant, res, i, int(offs[i]), toks, k, explain))
+        return out
 
 
 def topk_merge_dev(kind: int, part_ids_ptr: int, part_keys_ptr: int, parts: int, nq: int, k: int,
@@ -851,7 +885,10 @@ class GpuIndex:
     like the reference skips rows whose stored length differs from the query's
     (src/index/embedded/mod.rs:307-309)."""
 
-    def __init__(self, ctx=None, sidecar=None):
+    def __init__(self, ctx=None, sidecar=None, bm25_keys: str = "numbered"):
+        if bm25_keys not in ("numbered", "hashed"):
+            raise InvalidArgument(f"unknown BM25 key mode {bm25_keys!r}: 'numbered' or 'hashed'")
+        self._bm25_keys = bm25_keys   # how the Bm25Index keys its terms (DESIGN A23)
         self.ctx = ctx or _lib.current_context()
         self._cos = {}        # dim -> DeviceIndex
         self._ham = {}        # hash space name -> DeviceIndex
@@ -929,7 +966,7 @@ class GpuIndex:
 
     def _bm25(self) -> Bm25Index:
         if self._bm is None:
-            self._bm = Bm25Index(0, self.ctx)
+            self._bm = Bm25Index(0, self.ctx, self._bm25_keys)
         return self._bm
 
     def _all(self):

@@ -924,6 +924,35 @@ int ucfp_text_canon_batch(ucfp_ctx* ctx, const uint8_t* utf8, const uint64_t* of
 int ucfp_text_utab_lookup(uint32_t cp, uint32_t out_cps[8], uint32_t* n, uint32_t* cls_flags);
 const char* ucfp_text_utab_versions(void);
 
+/* ---- HTML pages -> text: the `preprocess = html` stage of the text route on its own (rules M1-M8) ----
+ * What the Rust host otherwise does with txtfp::html_to_text before it fingerprints a page (TextOpts.preprocess,
+ * src/modality/text.rs:85-96,751-767, behind POST /v1/ingest/text/{tid}/{rid}/preprocess/html,
+ * src/server/handlers.rs:628-699).  txtfp is not available, so the rules are this library's own (parity unpinned): tags,
+ * comments, declarations and script / style bodies are dropped, a tag outside the inline set leaves a space, the 252
+ * named references of HTML 4, `apos` and the numeric ones are decoded, runs of white space become one space.  A total
+ * function from bytes to bytes: no status, no hand-back; bytes >= 0x80 pass through (UTF-8 is validated by whatever
+ * consumes the text).  Same blob + n + 1 byte offsets shape as the MinHash calls; text_offsets has n + 1 entries
+ * (text_offsets[0] = 0) and document i's text is text[text_offsets[i] .. text_offsets[i + 1]), so the output feeds
+ * ucfp_text_minhash_batch_dev and its kin as it is.  flags[i] (may be NULL): bit 0 (UCFP_TEXT_HTML_NON_ASCII) the text holds
+ * a byte >= 0x80; bit 1 (UCFP_TEXT_HTML_OPEN_MARKUP) the document ended inside markup, which was dropped to the end.  The
+ * text is never longer than the page. */
+#define UCFP_TEXT_HTML_NON_ASCII 1u
+#define UCFP_TEXT_HTML_OPEN_MARKUP 2u
+/* src/modality/text.rs:751-767, src/server/handlers.rs:628-699; host code, no device: returns n_bytes */
+size_t ucfp_text_html_bound(size_t n_bytes);
+/* src/modality/text.rs:751-767, src/server/handlers.rs:628-699; device pointers; d_text holds
+ * ucfp_text_html_bound(d_offsets[n] - d_offsets[0]) bytes; no workspace, no synchronisation: three launches on `stream`;
+ * n = 0 launches one and writes d_text_offsets[0] = 0 */
+int ucfp_text_html_batch_dev(ucfp_ctx* ctx, const uint8_t* d_html, const uint64_t* d_offsets, size_t n, uint8_t* d_text,
+                             uint64_t* d_text_offsets, uint32_t* d_flags, void* stream);
+/* src/modality/text.rs:751-767, src/server/handlers.rs:628-699; host pointers; UCFP_E_INVALID when the text is larger
+ * than text_cap */
+int ucfp_text_html_batch(ucfp_ctx* ctx, const uint8_t* html, const uint64_t* offsets, size_t n, uint8_t* text, size_t text_cap,
+                         uint64_t* text_offsets, uint32_t* flags);
+/* src/modality/text.rs:751-767, src/server/handlers.rs:628-699; host code, no device: the compiled table of named
+ * references (include/ucfp_text_html_tab.h).  Returns 1 and *cp when name[0 .. len) is one of them (case-sensitive), else 0. */
+int ucfp_text_html_entity(const char* name, size_t len, uint32_t* cp);
+
 /* ---- TLSH 128/1 (the `tlsh` arm of the text route, src/modality/text.rs:452-484, tag "tlsh-128-1") ----
  * The digest of a BYTE STRING: for a text record the UTF-8 of the canonicalised, preprocessed text (the reference's
  * tokenizer tag "tlsh-bytes"); there is no `mode`, bytes are bytes, 0x00 and 0xff included.  Same blob + n + 1 byte

@@ -199,6 +199,12 @@ SIGNATURES = {
                                             C.c_void_p]),
     "ucfp_text_canon_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
                                         C.c_void_p]),
+    "ucfp_text_html_bound": (C.c_size_t, [C.c_size_t]),
+    "ucfp_text_html_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]),
+    "ucfp_text_html_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                       C.c_void_p]),
+    "ucfp_text_html_entity": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32)]),
     "ucfp_text_utab_lookup": (C.c_int, [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "ucfp_text_utab_versions": (C.c_char_p, []),
     "ucfp_text_tlsh_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),

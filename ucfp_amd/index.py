@@ -754,8 +754,13 @@ class Bm25Index:
         _lib.check(self._lib.ucfp_bm25_index_upsert(self.handle, tenant, ids.ctypes.data, keys.ctypes.data,
                                                     tfs.ctypes.data, offsets.ctypes.data, ids.size))
 
-    def upsert(self, tenant: int, ids, texts: Sequence[str]) -> None:
-        """Tokenize each text (terms.tokenize) and store its term counts; a text without tokens is an empty document."""
+    def upsert(self, tenant: int, ids, texts: Sequence[str], preprocess=None) -> None:
+        """Tokenize each text (terms.tokenize) and store its term counts; a text without tokens is an empty document.
+        `preprocess` (TextOpts.preprocess) is not built into this entry and is refused: strip pages first with
+        text.html_to_text_batch."""
+        if preprocess is not None:
+            raise UnsupportedError(f"preprocess `{preprocess}` is not built into the BM25 index: strip the pages first "
+                                   "(text.html_to_text_batch)")
         ids = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
         texts = list(texts)
         if len(texts) != ids.size:

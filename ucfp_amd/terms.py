@@ -68,19 +68,23 @@ def host_pairs(text: str, form: int):
     return ks, [counts[k] for k in ks]
 
 
-def terms_batch(texts, form: str = "counts", ctx=None):
+def terms_batch(texts, form: str = "counts", ctx=None, preprocess=None):
     """-> (keys u64, tfs u32, pair_offsets u64 [n + 1], status i32 [n]): document i's terms are
     (keys, tfs)[pair_offsets[i] .. pair_offsets[i + 1]) -- "counts": its distinct keys ascending, each with its count;
     "sequence": one key per token in text order, tfs empty.  The batch runs through ucfp_bm25_terms_batch; a document the
     device hands back (status 1: a byte >= 0x80; -2: a token too long for it) is tokenised on the host and spliced in,
     so the pairs are the same whatever the route.  `status` is the device's: its non-zero entries say which documents
-    took the host route."""
+    took the host route.  `preprocess` (TextOpts.preprocess: html | markdown | pdf) is not built into this entry and is
+    refused: strip pages first with text.html_to_text_batch."""
     import ctypes as C
 
     import numpy as np
 
     from . import _lib
-    from .errors import InvalidArgument
+    from .errors import InvalidArgument, UnsupportedError
+    if preprocess is not None:
+        raise UnsupportedError(f"preprocess `{preprocess}` is not built into the BM25 ingest: strip the pages first "
+                               "(text.html_to_text_batch)")
     if form not in _FORMS:
         raise InvalidArgument(f"unknown terms form {form!r}: 'counts' or 'sequence'")
     f = _FORMS[form]

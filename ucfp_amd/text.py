@@ -30,12 +30,17 @@ itself (the reference's cjk-jp / cjk-ko).  Streams and the micro-batcher are bui
 supplied (`from_weights`, `load`) or fitted to a corpus on the GPU (`fit`), applied by `simhash_batch(.., idf=)` and
 `simhash_tokens(.., idf=)` through the same routes, and by `SimHashStreams(.., idf=)` chunk by chunk.
 The micro-batcher takes no table.
+
+`TextOpts(preprocess="html")` (text.rs:85-96, 751-767 behind handlers.rs:628-699) makes the texts of the
+batch entries and the `fingerprint_*` builders HTML pages: `html_to_text_batch` strips them on the device
+(ucfp_text_html_batch) and the routing above runs on the stripped text, which is also what a record's `text` holds.
+`markdown` and `pdf` are not built and are refused; streams, the micro-batcher and the IDF fit take no `preprocess` yet.
 """
 import ctypes as C
 import math
 import threading
 import unicodedata
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -118,7 +123,7 @@ class TextOpts:
     tokenizer: str = "word"          # word | grapheme | cjk-jp | cjk-ko (text.rs:71-82)
     k: int = DEFAULT_K
     h: int = DEFAULT_H
-    preprocess: Optional[str] = None  # html | markdown | pdf: not on the hot path
+    preprocess: Optional[str] = None  # "html": stripped on the device; markdown | pdf: not built
 
     def tokenizer_tag(self) -> str:   # text.rs:152-159
         return {"word": f"shingle-k={self.k}/word-uax29", "grapheme": f"shingle-k={self.k}/grapheme-uax29",
@@ -308,7 +313,7 @@ def simhash_tokens(docs: Sequence[Sequence[bytes]], ctx=None, idf: Optional["Idf
     return _run_tokens("simhash", docs, 1, ctx)
 
 
-def _batch_grapheme(kind: str, texts: Sequence[str], opts: TextOpts, ctx=None):
+def _batch_grapheme(kind: str, texts: Sequence[str], opts: TextOpts, ctx=None, is_ascii=None):
     """The `grapheme` tokeniser: ASCII documents go raw (RAW_ASCII, when the canonicaliser folds case),
     other documents as UTF-8 when the canonicaliser is the default one (RAW_UTF8); what the device hands back and every
     other canonicaliser is canonicalised and cut into clusters here (`Canonicalizer.apply`, then \\X) and goes to the
@@ -320,9 +325,10 @@ def _batch_grapheme(kind: str, texts: Sequence[str], opts: TextOpts, ctx=None):
     host = []
     groups = {RAW_ASCII: [], RAW_UTF8: []}
     for i, t in enumerate(texts):
-        if t.isascii() and c.case_fold:
+        asc = is_ascii[i] if is_ascii is not None else t.isascii()
+        if asc and c.case_fold:
             groups[RAW_ASCII].append(i)
-        elif not t.isascii() and c.is_default():
+        elif not asc and c.is_default():
             groups[RAW_UTF8].append(i)
         else:
             host.append(i)
@@ -342,15 +348,19 @@ def _batch_grapheme(kind: str, texts: Sequence[str], opts: TextOpts, ctx=None):
     return out, status
 
 
-def _batch(kind: str, texts: Sequence[str], opts: TextOpts, ctx=None):
+def _batch(kind: str, texts: Sequence[str], opts: TextOpts, ctx=None, is_ascii=None):
     """Split into the raw-ASCII, the raw-UTF-8 and the host-pretokenised group, one launch each; the documents the
-    UTF-8 launch hands back join the host group."""
+    UTF-8 launch hands back join the host group.  `is_ascii` (per text, from the HTML strip's flags) picks the UTF-8 group
+    under the default canonicaliser without `_device_utf8`'s look at each text; `_prepare` still looks at the rest."""
     if opts.tokenizer == "grapheme":
-        return _batch_grapheme(kind, texts, opts, ctx)
+        return _batch_grapheme(kind, texts, opts, ctx, is_ascii)
     h = _check_h(opts.h) if kind == "minhash" else DEFAULT_H
     out = np.zeros((len(texts), _rec_bytes(kind, h)), np.uint8)
     status = np.zeros(len(texts), np.int32)
-    dev = [i for i, t in enumerate(texts) if _device_utf8(t, opts)]
+    if is_ascii is not None and opts.tokenizer == "word" and opts.canonicalizer.is_default():
+        dev = [i for i, a in enumerate(is_ascii) if not a]
+    else:
+        dev = [i for i, t in enumerate(texts) if _device_utf8(t, opts)]
     if dev:
         o, s = _run(kind, [texts[i].encode("utf-8", "surrogatepass") for i in dev], RAW_UTF8, opts.k, ctx, h)
         out[dev] = o
@@ -367,20 +377,79 @@ def _batch(kind: str, texts: Sequence[str], opts: TextOpts, ctx=None):
     return out, status
 
 
+HTML_NON_ASCII, HTML_OPEN_MARKUP = 1, 2      # UCFP_TEXT_HTML_*: the flag bits of html_to_text_batch
+
+
+def html_to_text_batch(docs: Sequence, ctx=None) -> Tuple[List[bytes], np.ndarray]:
+    """HTML pages -> (their text, flags uint32 [n]) on the GPU (ucfp_text_html_batch; DESIGN.md T12, rules M1-M8): markup,
+    comments and script / style bodies dropped, character references decoded, white space folded.  `docs` are `bytes` or
+    `str` (encoded as UTF-8).  Every page has a text -- there is no status and no hand-back; flag bit 0
+    (HTML_NON_ASCII): the text holds a byte >= 0x80; bit 1 (HTML_OPEN_MARKUP): the page ended inside markup."""
+    docs = [d.encode("utf-8", "surrogatepass") if isinstance(d, str) else bytes(d) for d in docs]
+    n = len(docs)
+    flags = np.zeros(n, np.uint32)
+    if n == 0:
+        return [], flags
+    ctx = ctx or _lib.current_context()
+    lib = _lib.load()
+    blob, offs = _pack(docs)
+    cap = int(lib.ucfp_text_html_bound(int(offs[n])))
+    text = np.zeros(max(cap, 1), np.uint8)
+    toff = np.zeros(n + 1, np.uint64)
+    _lib.check(lib.ucfp_text_html_batch(ctx.handle, blob.ctypes.data, offs.ctypes.data, n, text.ctypes.data, cap,
+                                        toff.ctypes.data, flags.ctypes.data))
+    return [text[int(toff[i]):int(toff[i + 1])].tobytes() for i in range(n)], flags
+
+
+def _no_preprocess(opts: Optional[TextOpts], what: str) -> None:
+    """The entries that take no `preprocess` yet refuse it: ignoring it would fingerprint the markup."""
+    if opts is not None and opts.preprocess is not None:
+        raise UnsupportedError(f"preprocess `{opts.preprocess}` is not built into {what}: strip the pages first "
+                               "(text.html_to_text_batch), or use the batch entries, which take preprocess=\"html\"")
+
+
+def _check_preprocess(opts: Optional[TextOpts]) -> None:
+    """The batch entries build `preprocess="html"` alone: markdown, pdf and anything unknown are refused."""
+    if opts is not None and opts.preprocess not in (None, "html"):
+        raise UnsupportedError(f"preprocess `{opts.preprocess}` is not built into the HIP path (only `html` is)")
+
+
+def _preprocessed(texts: Sequence[str], opts: TextOpts, ctx=None):
+    """TextOpts.preprocess (text.rs:85-96, 751-767) in front of the batch entries.  -> (texts, opts, is_ascii): with
+    preprocess="html" the pages stripped on the device and decoded, the options with `preprocess` cleared, and per text
+    whether it is ASCII (flag bit 0 of the strip: the routing needs no look at the text); without, everything as it came
+    and is_ascii None.  Any other value is refused: markdown and pdf are not built.  The pages are `str`; a `bytes` page
+    is taken too when what the strip leaves of it is UTF-8, and refused with InvalidArgument otherwise (markup between the
+    bytes of one character: `\xc3<p>\xa9`) -- `html_to_text_batch` and `tlsh_batch` take any bytes."""
+    _check_preprocess(opts)
+    if opts.preprocess is None:
+        return texts, opts, None
+    stripped, flags = html_to_text_batch(texts, ctx)
+    try:
+        decoded = [b.decode("utf-8", "surrogatepass") for b in stripped]
+    except UnicodeDecodeError as e:
+        raise InvalidArgument(f"the text of a page is not UTF-8 after the markup is stripped ({e}): pass `str` pages, or strip "
+                              "with text.html_to_text_batch and decode as you see fit") from None
+    return decoded, replace(opts, preprocess=None), [not f & HTML_NON_ASCII for f in flags.tolist()]
+
+
 def minhash_batch(texts: Sequence[str], opts: Optional[TextOpts] = None, ctx=None):
     """-> (records uint8 [n, 8 + 8 opts.h], status int32 [n]); opts.h is the slot count (1032 bytes at the
-    default 128)."""
-    return _batch("minhash", texts, opts or TextOpts(), ctx)
+    default 128).  With opts.preprocess = "html" the texts are pages, stripped on the device first."""
+    texts, opts, is_ascii = _preprocessed(texts, opts or TextOpts(), ctx)
+    return _batch("minhash", texts, opts, ctx, is_ascii)
 
 
 def simhash_batch(texts: Sequence[str], opts: Optional[TextOpts] = None, ctx=None, idf: Optional["IdfTable"] = None):
-    """-> (records uint8 [n, 8], status int32 [n]).  With `idf` (a final `IdfTable`) the TF.IDF record of DESIGN.md T9."""
+    """-> (records uint8 [n, 8], status int32 [n]).  With `idf` (a final `IdfTable`) the TF.IDF record of DESIGN.md T9.
+    With opts.preprocess = "html" the texts are pages, stripped on the device first."""
+    texts, opts, is_ascii = _preprocessed(texts, opts or TextOpts(), ctx)
     if idf is not None:
-        return idf._simhash(texts, opts or TextOpts(), ctx)
-    return _batch("simhash", texts, opts or TextOpts(), ctx)
+        return idf._simhash(texts, opts, ctx, is_ascii)
+    return _batch("simhash", texts, opts, ctx, is_ascii)
 
 
-def _route(texts: Sequence[str], opts: TextOpts, run, run_tokens, rec_bytes: int):
+def _route(texts: Sequence[str], opts: TextOpts, run, run_tokens, rec_bytes: int, is_ascii=None):
     """The routing of `_batch` / `_batch_grapheme` around other runners (the IDF table's): ASCII documents raw, other
     documents as UTF-8 under the default canonicaliser, what the device hands back and every other canonicaliser through
     the host (PRETOKENIZED for `word`, the token form for `grapheme`).  run(docs, mode, tokenizer) and run_tokens(docs)
@@ -395,9 +464,10 @@ def _route(texts: Sequence[str], opts: TextOpts, run, run_tokens, rec_bytes: int
     host = []
     groups = {RAW_ASCII: [], RAW_UTF8: []}
     for i, t in enumerate(texts):
-        if t.isascii() and c.case_fold:
+        asc = is_ascii[i] if is_ascii is not None else t.isascii()
+        if asc and c.case_fold:
             groups[RAW_ASCII].append(i)
-        elif not t.isascii() and c.is_default():
+        elif not asc and c.is_default():
             groups[RAW_UTF8].append(i)
         else:
             host.append(i)
@@ -467,6 +537,7 @@ class IdfTable:
         """Count the documents' tokens (routed as `simhash_batch` routes them: raw ASCII, UTF-8 on the device, the host's
         tokens for what the device hands back; `cjk-*` has no segmenter here -- pass its tokens to `add_tokens`).
         -> status int32 [n]; a document whose final status is not 0 adds nothing.  The table is not final afterwards."""
+        _no_preprocess(self.opts, "the IDF table's fit")
         return _route(texts, self.opts, self._add_docs, self._add_tokens, 0)[1]
 
     def add_tokens(self, docs: Sequence[Sequence[bytes]]) -> np.ndarray:
@@ -594,10 +665,10 @@ class IdfTable:
                                                                 doc_toks.ctypes.data, len(docs), out.ctypes.data, status.ctypes.data))
         return out, status
 
-    def _simhash(self, texts: Sequence[str], opts: TextOpts, ctx=None):
+    def _simhash(self, texts: Sequence[str], opts: TextOpts, ctx=None, is_ascii=None):
         ctx = ctx or self.ctx
         return _route(texts, opts, lambda d, m, t: self._simhash_docs(ctx, d, m, t), lambda d: self._simhash_tokens(d, ctx),
-                      SIMHASH_BYTES)
+                      SIMHASH_BYTES, is_ascii)
 
     def close(self):
         if getattr(self, "handle", None):
@@ -722,6 +793,7 @@ class _StreamingSession:
         self.opts = opts or TextOpts()
         if self.opts.tokenizer != "word":
             raise UnsupportedError(f"tokenizer `{self.opts.tokenizer}` is not built into the HIP path")
+        _no_preprocess(self.opts, "the text streams")
         self._check_opts()
         self.tenant_id, self.record_id = tenant_id, record_id
         self._config_hash_value = config_hash_value
@@ -940,6 +1012,7 @@ class TextBatcher:
         self._lib = _lib.load()
         self.ctx = ctx or _lib.current_context()
         self.opts = opts or TextOpts()
+        _no_preprocess(self.opts, "the text micro-batcher")
         if kind == "minhash" and self.opts.h != DEFAULT_H:
             raise UnsupportedError(f"the text micro-batcher is built for H = {DEFAULT_H} only (got H = {self.opts.h}); "
                                    "minhash_batch takes any H")
@@ -1024,7 +1097,9 @@ def fingerprint_minhash(text: str, tenant_id: int, record_id: int) -> Record:
 def fingerprint_minhash_with(text: str, opts: TextOpts, tenant_id: int, record_id: int,
                              config_hash_value: Optional[int] = None) -> Record:
     """text.rs:182-236 at any slot count opts.h.  Every H carries the tag `minhash-h128`, as in the
-    reference (text.rs:221-228): the fingerprint's length, 8 + 8 h, tells H."""
+    reference (text.rs:221-228): the fingerprint's length, 8 + 8 h, tells H.  With opts.preprocess = "html" `text` is a
+    page; the record's `text` is the stripped text (text.rs:751-767)."""
+    (text,), opts, _ = _preprocessed([text], opts)
     recs, status = minhash_batch([text], opts)
     _raise_for(int(status[0]))
     return Record(tenant_id=tenant_id, record_id=record_id, modality=Modality.Text,
@@ -1035,6 +1110,7 @@ def fingerprint_minhash_with(text: str, opts: TextOpts, tenant_id: int, record_i
 
 def _simhash(text: str, opts: TextOpts, tag: str, tenant_id: int, record_id: int,
              config_hash_value: Optional[int] = None) -> Record:
+    (text,), opts, _ = _preprocessed([text], opts)
     recs, status = simhash_batch([text], opts)
     _raise_for(int(status[0]))
     tok_tag = {"word": "word-uax29", "grapheme": "grapheme-uax29", "cjk-jp": "cjk-jp", "cjk-ko": "cjk-ko"}[opts.tokenizer]
@@ -1058,6 +1134,7 @@ def fingerprint_simhash_idf(text: str, opts: TextOpts, idf, tenant_id: int, reco
         return _simhash(text, opts, ALGORITHM_SIMHASH_IDF, tenant_id, record_id, config_hash_value)
     if not isinstance(idf, IdfTable):
         raise UnsupportedError("only a ucfp_amd.text.IdfTable is built into the HIP path")
+    (text,), opts, _ = _preprocessed([text], opts)
     recs, status = simhash_batch([text], opts, idf=idf)
     _raise_for(int(status[0]))
     tok_tag = {"word": "word-uax29", "grapheme": "grapheme-uax29", "cjk-jp": "cjk-jp", "cjk-ko": "cjk-ko"}[opts.tokenizer]
@@ -1078,8 +1155,6 @@ def _tlsh_input(doc, opts: TextOpts) -> bytes:
     "tlsh-bytes": no tokens, so non-ASCII text needs no host segmentation)."""
     if isinstance(doc, (bytes, bytearray, memoryview)):
         return bytes(doc)
-    if opts.preprocess is not None:
-        raise UnsupportedError(f"preprocess `{opts.preprocess}` is not built into the HIP path")
     return opts.canonicalizer.apply(doc).encode("utf-8")
 
 
@@ -1088,6 +1163,14 @@ def tlsh_batch(texts_or_bytes: Sequence, opts: Optional[TextOpts] = None, ctx=No
     -> (digests uint8 [n, 35], status int32 [n]): status -1 and a zero digest for a document TLSH refuses (shorter than
     50 bytes, or at most 64 of its 128 buckets non-zero)."""
     opts = opts or TextOpts()
+    if opts.preprocess is not None:
+        # pages: stripped on the device (DESIGN.md T12); a `bytes` page stays bytes, a `str` page is canonicalised after
+        _check_preprocess(opts)
+        texts_or_bytes = list(texts_or_bytes)
+        stripped, _ = html_to_text_batch(texts_or_bytes, ctx)
+        texts_or_bytes = [b.decode("utf-8", "surrogatepass") if isinstance(d, str) else b
+                          for d, b in zip(texts_or_bytes, stripped)]
+        opts = replace(opts, preprocess=None)
     docs = [_tlsh_input(d, opts) for d in texts_or_bytes]
     n = len(docs)
     out = np.zeros((n, TLSH_BYTES), np.uint8)
@@ -1138,7 +1221,9 @@ def tlsh_distance(a, b) -> int:
 
 def fingerprint_tlsh(text: str, opts: TextOpts, tenant_id: int, record_id: int,
                      config_hash_value: Optional[int] = None) -> Record:
-    """text.rs:452-484: `fingerprint` = the digest string, `text` = the prepared text."""
+    """text.rs:452-484: `fingerprint` = the digest string, `text` = the prepared text (with opts.preprocess = "html" the
+    text of the page, stripped on the device)."""
+    (text,), opts, _ = _preprocessed([text], opts)
     digs, status = tlsh_batch([text], opts)
     if int(status[0]) != 0:
         raise ModalityError(f"TLSH refuses the document: fewer than {TLSH_MIN_BYTES} bytes after canonicalisation, or too "
@@ -1312,6 +1397,7 @@ def dedup_corpus(texts: Sequence[str], threshold: float = 0.8, opts: Optional[Te
     A document whose status is not 0 (no tokens, oversized token) is its own cluster: kept, its own label, never
     the representative of another."""
     min_agree = min_agree_for(threshold)
+    _check_preprocess(opts)                  # whatever the corpus, an empty one included
     if opts is not None and opts.h != DEFAULT_H:
         raise UnsupportedError(f"de-duplication runs on the LSH index, which is built for H = {DEFAULT_H} only (got H = {opts.h})")
     n = len(texts)

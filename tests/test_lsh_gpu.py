@@ -58,7 +58,9 @@ def test_query_matches_checker(gpu_ctx, oracle, bands, rows, k, keep):
     assert np.array_equal(g_ct, o_ct)
     assert np.array_equal(g_ids, o_ids)
     assert np.array_equal(g_sc, o_sc)
-    assert g_ct.max() == min(k, 6) or g_ct.max() > 1   # the planted clusters are found
+    # the planted clusters are found: by the checker first, then by the kernel
+    assert (o_ct >= 1).sum() >= 0.9 * bases.shape[0]
+    assert (g_ct >= 1).sum() >= 0.9 * bases.shape[0]
     idx.close()
 
 

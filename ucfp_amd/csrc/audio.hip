@@ -747,7 +747,10 @@ __global__ __launch_bounds__(kSW * 64) void wang_stream_kernel(const float* __re
             if (st < 0) st += kRing;
             // The whole wave pays for every instruction here, so the test is kept short: v is the row maximum of its
             // own row at k, hence "v equals the window maximum and no earlier row reaches it" is
-            //   max(7 earlier rows at k) < v  and  max(7 later rows at k) <= v.
+            //   not max(7 earlier rows at k) >= v  and  not max(7 later rows at k) > v.
+            // The negated form is the oracle's rule for a NaN (a row that holds a NaN or Inf sample is all NaN): such
+            // a cell blocks nothing.  fmaxf drops a NaN beside a number, and where all 7 rows are NaN the maximum is
+            // NaN and both tests pass (v itself is a row-local candidate, never NaN).
             // All reads are unconditional (lanes past the list read a stale entry and are masked at the end).
             const uint32_t n = L.pl_cnt[st];
             const uint32_t pk_raw = L.pl_k[st][lane & (kPl - 1)] & (uint32_t)(kWangBins - 1);
@@ -783,7 +786,7 @@ __global__ __launch_bounds__(kSW * 64) void wang_stream_kernel(const float* __re
                 mb = fmaxf(mb, rr[d]);
                 ma = fmaxf(ma, rr[kRT + 1 + d]);
             }
-            const bool is_peak = (uint32_t)lane < n && mb < pv && ma <= pv;
+            const bool is_peak = (uint32_t)lane < n && !(mb >= pv) && !(ma > pv);
             // one counter bump per wave (all its peaks share the frame, hence the second); the returned base is
             // consumed a round later by flush_take(), so the L2 round trip overlaps the next FFT.  The address is hidden
             // from the compiler: for a uniform address it aggregates by itself and reads the result back at once

@@ -1534,6 +1534,47 @@ int ucfp_index_search_dev(ucfp_index* idx, uint32_t tenant, const void* d_querie
                           uint64_t* d_out_ids, float* d_out_scores, uint32_t* d_out_dist,
                           uint32_t* d_out_counts, void* stream);
 
+/* Filtered search (DESIGN F1 - F6): `Query.filter` (src/core/mod.rs:165-167), a set of record ids as the portable
+ * serialization of a 64-bit Roaring treemap (what RoaringTreemap::serialize_into writes).  A filter becomes a VIEW of one
+ * (index, tenant): a compact sub-shard of the allowed rows, in the shard's row order, that the Hamming and cosine searches
+ * read exactly as they read a shard -- a filtered search answers, bit for bit, what an index holding only the allowed rows
+ * answers.  Malformed bytes are UCFP_E_INVALID with the byte offset in ucfp_last_error().
+ *
+ * ucfp_roaring_validate: host only, no context; `cardinality` (may be NULL) = ids in the set.
+ * ucfp_index_filter_create: one call, one host synchronisation (the allowed-row count sizes the view).  An unknown tenant or
+ *   an empty filter gives a view of 0 rows.  The view keeps a copy of the bytes.
+ * ucfp_index_filter_stale: 1 once the tenant's shard changed since the view was built (upsert, append_dev, delete, load),
+ *   0 while it is current, UCFP_E_INVALID for a NULL or detached view.  ucfp_index_filter_refresh rebuilds it.
+ * ucfp_index_filter_stats: rows in the view, rows of the shard it was built from, containers of the filter, device bytes
+ *   it holds (any pointer may be NULL).
+ * Destroying the index first detaches its views: every later call on them but destroy returns UCFP_E_INVALID.
+ * Refreshing a view that holds rows and destroying a view synchronise the whole device (a search on any stream may still
+ * read the buffers they free).
+ * A view lives in device memory (rows_allowed x (8 + row bytes [+ 4 cosine]) + the filter's image + 16 bytes per 64 shard
+ * rows) until it is destroyed; views are not part of ucfp_index_save. */
+typedef struct ucfp_index_filter ucfp_index_filter;
+int ucfp_roaring_validate(const uint8_t* bytes, size_t len, uint64_t* cardinality);
+int ucfp_index_filter_create(ucfp_index* idx, uint32_t tenant, const uint8_t* bytes, size_t len, ucfp_index_filter** out);
+void ucfp_index_filter_destroy(ucfp_index_filter* f);
+int ucfp_index_filter_stats(ucfp_index_filter* f, size_t* rows_allowed, size_t* rows_seen, size_t* containers,
+                            size_t* device_bytes);
+/* Milliseconds of the view's last build on the device (0 for a view of 0 rows; any pointer may be NULL): the probe, the scan
+ * of the tile counts, from the end of the scan to the start of the gather (the read-back of the row count, the host's
+ * wake-up and the allocation of the view), and the gather with the ids-ascend pass. */
+int ucfp_index_filter_build_ms(ucfp_index_filter* f, float* probe_ms, float* scan_ms, float* readback_ms, float* gather_ms);
+/* Self-check for tests: every buffer of a view lies between 256-byte guard patterns (its mask / count scratch has one
+ * behind it); synchronises the device and returns UCFP_E_INDEX, naming the buffer, if a guard was overwritten. */
+int ucfp_index_filter_check(ucfp_index_filter* f);
+int ucfp_index_filter_stale(ucfp_index_filter* f);
+int ucfp_index_filter_refresh(ucfp_index_filter* f);
+/* ucfp_index_search_dev / ucfp_index_search over a view: same arguments, checks, outputs and stream protocol.  A view of
+ * another index is UCFP_E_INVALID.  The _dev entry refuses a stale view (UCFP_E_INVALID); the host entry refreshes it. */
+int ucfp_index_search_filtered_dev(ucfp_index* idx, ucfp_index_filter* f, const void* d_queries, size_t nq, uint32_t k,
+                                   uint64_t* d_out_ids, float* d_out_scores, uint32_t* d_out_dist,
+                                   uint32_t* d_out_counts, void* stream);
+int ucfp_index_search_filtered(ucfp_index* idx, ucfp_index_filter* f, const void* queries, size_t nq, uint32_t k,
+                               uint64_t* out_ids, float* out_scores, uint32_t* out_dist, uint32_t* out_counts);
+
 /* Host micro-batcher for the QUERY route: /v1/query is one query per request (src/server/handlers.rs:143-187),
  * up to 512 requests in flight (src/bin/ucfp.rs:267).  submit() is BLOCKING and thread-safe: concurrent calls -- each with
  * ITS OWN query (a u64 hash, or dim floats) and ITS OWN k (QueryRequest.k, src/server/dto.rs:74-87) -- become ONE copy of the

@@ -343,6 +343,20 @@ SIGNATURES = {
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     "ucfp_index_search_dev": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ucfp_roaring_validate": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
+    "ucfp_index_filter_create": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
+    "ucfp_index_filter_destroy": (None, [C.c_void_p]),
+    "ucfp_index_filter_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
+                                          C.POINTER(C.c_size_t)]),
+    "ucfp_index_filter_build_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                             C.POINTER(C.c_float)]),
+    "ucfp_index_filter_check": (C.c_int, [C.c_void_p]),
+    "ucfp_index_filter_stale": (C.c_int, [C.c_void_p]),
+    "ucfp_index_filter_refresh": (C.c_int, [C.c_void_p]),
+    "ucfp_index_search_filtered": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ucfp_index_search_filtered_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ucfp_index_search_batcher_create": (C.c_int, [C.c_void_p, C.c_uint32, C.c_size_t, C.c_uint32, C.POINTER(C.c_void_p)]),
     "ucfp_index_search_batcher_destroy": (None, [C.c_void_p]),
     "ucfp_index_search_batcher_submit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,

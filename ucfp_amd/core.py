@@ -117,6 +117,7 @@ class QueryRequest:
     min_similarity: Optional[float] = None   # hits of a `minhash` query need agree / H >= this, in (0, 1]
     terms: List[str] = field(default_factory=list)
     explain: bool = False
+    filter: Optional[bytes] = None      # Query.filter (src/core/mod.rs:165-167): a serialized Roaring treemap of record ids (DESIGN F1)
 
     @classmethod
     def from_json(cls, body: dict) -> "QueryRequest":
@@ -158,6 +159,9 @@ class QueryRequest:
             tl = _tlsh_bytes(tl)
             if body.get("algorithm") not in (None, "tlsh-128-1"):
                 raise InvalidArgument("`tlsh` goes with `algorithm` = \"tlsh-128-1\" or none")
+        filt = body.get("filter")
+        if filt is not None:
+            filt = _filter_bytes(filt)
         resampled = body.get("resampled", False)
         if not isinstance(resampled, bool):
             raise InvalidArgument("`resampled` must be true or false")
@@ -181,7 +185,22 @@ class QueryRequest:
                    triplets=tri, resampled=resampled, tlsh=tl, image_record=img, multi_hash=dict(mh) if mh is not None else None,
                    min_score=float(ms) if ms is not None else None,
                    minhash=mhr, min_similarity=float(sim) if sim is not None else None,
-                   terms=list(terms), explain=_flag(body.get("explain", False)))
+                   terms=list(terms), explain=_flag(body.get("explain", False)), filter=filt)
+
+
+def _filter_bytes(f) -> bytes:
+    """`filter` of a query body: standard base64 of the filter bytes (or the bytes themselves)."""
+    from .errors import InvalidArgument
+    if isinstance(f, (bytes, bytearray)):
+        return bytes(f)
+    if not isinstance(f, str):
+        raise InvalidArgument("`filter` must be a base64 string")
+    import base64
+    import binascii
+    try:
+        return base64.b64decode(f, validate=True)
+    except (binascii.Error, ValueError):
+        raise InvalidArgument("`filter` is not standard base64") from None
 
 
 def _flag(v) -> bool:

@@ -209,6 +209,17 @@ int launch_hamming_search(const uint64_t* codes, const uint64_t* ids, size_t n,
 int launch_ids_order_update(const uint64_t* ids, size_t n, bool first, uint32_t* state, hipStream_t stream);
 int launch_hamming_scores(const uint32_t* dist, size_t total, float* scores, hipStream_t stream);
 
+// index_filter.hip: a Roaring filter (roaring_parse.h: keys / ents / image) against a shard's ids, in tiles of 64 rows.
+// probe: mask[t] = allowed rows of tile t, cnt[1 + t] = their number (scan cnt with launch_text_canon_scan: cnt[t] is then
+// the first output row of tile t, cnt[tiles] the total); gather: the allowed rows, in row order, into buffers of n_out rows.
+void launch_filter_probe(const uint64_t* ids, size_t n, const uint64_t* keys, const void* ents, uint32_t nc, const uint8_t* image,
+                         uint64_t* mask, uint64_t* cnt, hipStream_t stream);
+void launch_filter_gather_hamming(const uint64_t* ids, const uint64_t* rows, size_t n, const uint64_t* mask, const uint64_t* base,
+                                  size_t n_out, uint64_t* out_ids, uint64_t* out_rows, hipStream_t stream);
+void launch_filter_gather_cosine(const uint64_t* ids, const float* rows, const float* norms, size_t n, uint32_t dim,
+                                 const uint64_t* mask, const uint64_t* base, size_t n_out, uint64_t* out_ids, float* out_rows,
+                                 float* out_norms, hipStream_t stream);
+
 // hamming_direct.hip: 1..8 queries, k <= 32, ONE launch (the request shape of /v1/query).  `state` =
 // hamming_direct_state_bytes() of device memory whose first kHammingDirectZeroBytes were zeroed once (the kernel leaves
 // them zero).

@@ -23,6 +23,7 @@
 
 #include "../../include/ucfp_hip.h"
 #include "common.h"
+#include "roaring_parse.h"
 
 using ucfp::capi_fail;
 
@@ -56,6 +57,7 @@ struct Shard {
     std::unordered_map<uint64_t, size_t> pos;  // id -> row (unless APPEND_ONLY)
     std::vector<uint64_t> host_ids;            // row -> id (unless APPEND_ONLY)
     uint32_t* order = nullptr;                 // APPEND_ONLY Hamming shards: [0] = 1 while ids ascend with the row, [2..3] = last id
+    uint64_t epoch = 0;                        // bumped by every mutation: a filter view built at another epoch is stale
 };
 
 __global__ void scatter_rows_kernel(const uint64_t* __restrict__ src_ids, const uint8_t* __restrict__ src_rows,
@@ -110,6 +112,24 @@ struct ucfp_index {
     // behind; a search waits for `data_ready` (rows appended on another stream have landed).
     hipEvent_t data_ready = nullptr;
     DevBuf stage;                  // host<->device staging
+    std::vector<ucfp_index_filter*> views;   // the filter views of this index (detached when it is destroyed)
+};
+
+// A filter view (DESIGN F5): the allowed rows of one tenant's shard as a compact sub-shard, built by filter_build.
+struct ucfp_index_filter {
+    ucfp_index* ix = nullptr;      // NULL once the index is gone
+    uint32_t tenant = 0;
+    std::vector<uint8_t> bytes;    // the filter, kept for a refresh
+    uint64_t epoch = 0;            // the shard's epoch at build time (0: no shard); ~0 while the view is not built
+    uint64_t* ids = nullptr;
+    uint8_t* rows = nullptr;
+    float* norms = nullptr;
+    uint32_t* order = nullptr;
+    size_t n = 0, seen = 0, containers = 0, view_bytes = 0;
+    DevBuf scratch;                // directory | payload image | tile masks | tile counts, kept for a refresh
+    size_t scratch_used = 0;       // bytes of `scratch` the last build laid out; a guard follows them
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // the last build: before probe, after probe, after scan, before gather, after gather
+    bool timed = false;            // ev[] belong to a complete build
 };
 
 namespace ucfp {
@@ -466,6 +486,186 @@ int check_search_args(ucfp_index* ix, const void* q, size_t nq, uint32_t k, cons
     return 0;
 }
 
+// ---- filter views (DESIGN F1 - F6) -------------------------------------------------------------------------------------
+std::mutex g_views_mu;   // guards every view's `ix` link and every index's view list; taken before an index's own mutex
+
+// Every buffer of a view lies between two guards of kViewGuard bytes of 0xA5 (its scratch has one behind it):
+// ucfp_index_filter_check reads them back, so that a gather that writes outside its buffer is seen by a test.
+constexpr size_t kViewGuard = 256;
+
+hipError_t view_alloc(void** out, size_t bytes, hipStream_t st) {
+    uint8_t* base = nullptr;
+    hipError_t e = hipMalloc((void**)&base, bytes + 2 * kViewGuard);
+    if (e != hipSuccess) return e;
+    e = hipMemsetAsync(base, 0xA5, kViewGuard, st);
+    if (e == hipSuccess) e = hipMemsetAsync(base + kViewGuard + bytes, 0xA5, kViewGuard, st);
+    if (e != hipSuccess) {
+        (void)hipFree(base);
+        return e;
+    }
+    *out = base + kViewGuard;
+    return hipSuccess;
+}
+
+void view_free(void* p) {
+    if (p) (void)hipFree(static_cast<uint8_t*>(p) - kViewGuard);
+}
+
+// 0: the kViewGuard bytes at `at` still hold the pattern; 1: they do not; -1: the copy failed
+int guard_state(const void* at) {
+    uint8_t h[kViewGuard];
+    if (hipMemcpy(h, at, kViewGuard, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    for (size_t i = 0; i < kViewGuard; i++)
+        if (h[i] != 0xA5) return 1;
+    return 0;
+}
+
+void filter_free_view(ucfp_index_filter* f) {
+    view_free(f->ids);
+    view_free(f->rows);
+    view_free(f->norms);
+    view_free(f->order);
+    f->ids = nullptr;
+    f->rows = nullptr;
+    f->norms = nullptr;
+    f->order = nullptr;
+    f->n = 0;
+    f->view_bytes = 0;
+    f->timed = false;
+}
+
+// everything a view holds on the device (the handle itself stays)
+void filter_release(ucfp_index_filter* f) {
+    filter_free_view(f);
+    f->scratch.release();
+    f->scratch_used = 0;
+    for (hipEvent_t& ev : f->ev) {
+        if (ev) (void)hipEventDestroy(ev);
+        ev = nullptr;
+    }
+}
+
+bool filter_is_stale(ucfp_index* ix, const ucfp_index_filter* f) {
+    auto it = ix->shards.find(f->tenant);
+    return (it == ix->shards.end() ? 0ull : it->second.epoch) != f->epoch;
+}
+
+// (Re)build the view from its bytes and the tenant's shard as it is now: probe, scan, ONE read-back of the allowed-row count,
+// gather.  Both mutexes are held.  Everything runs on the index's own stream and ends in `data_ready`, like a mutation: a
+// search waits for it, and a later mutation of the shard waits until the gather has read the rows.
+int filter_build_impl(ucfp_index* ix, ucfp_index_filter* f) {
+    ucfp::roaring::Parsed p;
+    char msg[160];
+    msg[0] = 0;
+    if (ucfp::roaring::parse(f->bytes.data(), f->bytes.size(), &p, nullptr, msg, sizeof msg) != 0)
+        return capi_fail(UCFP_E_INVALID, "%s", msg);
+    HIP_TRY(hipSetDevice(ix->device));
+    if (f->ids) HIP_TRY(hipDeviceSynchronize());   // searches still reading the old view
+    filter_free_view(f);
+    f->epoch = ~0ull;
+    auto it = ix->shards.find(f->tenant);
+    const Shard* s = it == ix->shards.end() ? nullptr : &it->second;
+    const uint64_t epoch = s ? s->epoch : 0ull;
+    f->seen = s ? s->n : 0;
+    f->containers = p.keys.size();
+    if (!s || s->n == 0 || p.keys.empty()) {
+        f->epoch = epoch;
+        return UCFP_OK;
+    }
+    const size_t n = s->n, tiles = (n + 63) / 64, nc = p.keys.size();
+    const size_t o_keys = 0, o_ents = align256(nc * 8), o_img = align256(o_ents + nc * sizeof(ucfp::roaring::Entry));
+    const size_t o_mask = align256(o_img + p.image.size()), o_cnt = align256(o_mask + tiles * 8);
+    const size_t used = o_cnt + (tiles + 1) * 8;
+    f->scratch_used = 0;
+    int rc = f->scratch.ensure(used + kViewGuard);
+    if (rc) return rc;
+    uint8_t* w = f->scratch.p;
+    hipStream_t st = ix->stream;
+    for (hipEvent_t& ev : f->ev)
+        if (!ev) HIP_TRY(hipEventCreate(&ev));
+    HIP_TRY(hipStreamWaitEvent(st, ix->data_ready, 0));
+    HIP_TRY(hipMemsetAsync(w + used, 0xA5, kViewGuard, st));
+    f->scratch_used = used;
+    HIP_TRY(hipMemcpyAsync(w + o_keys, p.keys.data(), nc * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(w + o_ents, p.ents.data(), nc * sizeof(ucfp::roaring::Entry), hipMemcpyHostToDevice, st));
+    if (!p.image.empty()) HIP_TRY(hipMemcpyAsync(w + o_img, p.image.data(), p.image.size(), hipMemcpyHostToDevice, st));
+    uint64_t* mask = reinterpret_cast<uint64_t*>(w + o_mask);
+    uint64_t* cnt = reinterpret_cast<uint64_t*>(w + o_cnt);
+    HIP_TRY(hipEventRecord(f->ev[0], st));
+    ucfp::launch_filter_probe(s->ids, n, reinterpret_cast<const uint64_t*>(w + o_keys), w + o_ents, (uint32_t)nc, w + o_img, mask,
+                              cnt, st);
+    HIP_TRY(hipEventRecord(f->ev[1], st));
+    ucfp::launch_text_canon_scan(cnt, tiles, st);
+    HIP_TRY(hipEventRecord(f->ev[2], st));
+    uint64_t allowed = 0;
+    HIP_TRY(hipMemcpyAsync(&allowed, cnt + tiles, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));   // the one host synchronisation: the search plans need the row count (the host vectors end here too)
+    if (allowed > n) return capi_fail(UCFP_E_INDEX, "filter probe counted %llu of %zu rows", (unsigned long long)allowed, n);
+    if (allowed == 0) {
+        f->epoch = epoch;
+        return UCFP_OK;
+    }
+    const bool cosine = ix->kind == UCFP_INDEX_COSINE_F32;
+    hipError_t e = view_alloc((void**)&f->ids, allowed * 8, st);
+    if (e == hipSuccess) e = view_alloc((void**)&f->rows, allowed * ix->row_bytes, st);
+    if (e == hipSuccess && cosine) e = view_alloc((void**)&f->norms, allowed * 4, st);
+    const bool ordered = ix->kind == UCFP_INDEX_HAMMING64 && (ix->flags & UCFP_INDEX_APPEND_ONLY);
+    if (e == hipSuccess && ordered) e = view_alloc((void**)&f->order, 16, st);
+    if (e == hipSuccess) e = hipEventRecord(f->ev[3], st);
+    if (e != hipSuccess) {
+        filter_free_view(f);
+        return capi_fail(UCFP_E_INDEX, "out of device memory for a view of %llu rows: %s", (unsigned long long)allowed,
+                         hipGetErrorString(e));
+    }
+    if (cosine)
+        ucfp::launch_filter_gather_cosine(s->ids, reinterpret_cast<const float*>(s->rows), s->norms, n, ix->dim, mask, cnt,
+                                          (size_t)allowed, f->ids, reinterpret_cast<float*>(f->rows), f->norms, st);
+    else
+        ucfp::launch_filter_gather_hamming(s->ids, reinterpret_cast<const uint64_t*>(s->rows), n, mask, cnt, (size_t)allowed, f->ids,
+                                           reinterpret_cast<uint64_t*>(f->rows), st);
+    if (ordered) {   // a stable compaction of ascending ids ascends: the staged search keeps its strict thresholds on the view
+        static const uint32_t init[4] = {1u, 0u, 0u, 0u};
+        e = hipMemcpyAsync(f->order, init, 16, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) ucfp::launch_ids_order_update(f->ids, (size_t)allowed, true, f->order, st);
+    }
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e == hipSuccess) e = hipEventRecord(f->ev[4], st);
+    if (e == hipSuccess) e = hipEventRecord(ix->data_ready, st);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(st);
+        filter_free_view(f);
+        return capi_fail(UCFP_E_INDEX, "filter gather failed: %s", hipGetErrorString(e));
+    }
+    f->n = (size_t)allowed;
+    f->view_bytes = (size_t)allowed * (8 + ix->row_bytes + (cosine ? 4 : 0)) + (ordered ? 16 : 0) +
+                    (2 + (cosine ? 1 : 0) + (ordered ? 1 : 0)) * 2 * kViewGuard;
+    f->epoch = epoch;
+    f->timed = true;
+    return UCFP_OK;
+}
+
+// (the parser's vectors grow with the filter: an allocation failure is a status, not an exception through the C ABI)
+int filter_build(ucfp_index* ix, ucfp_index_filter* f) {
+    try {
+        return filter_build_impl(ix, f);
+    } catch (const std::bad_alloc&) {
+        f->epoch = ~0ull;
+        return capi_fail(UCFP_E_INDEX, "out of host memory while parsing a filter of %zu bytes", f->bytes.size());
+    }
+}
+
+// The view is this index's and current (refreshed when `refresh`); both mutexes are held.
+int filter_check(ucfp_index* ix, ucfp_index_filter* f, bool refresh) {
+    if (f->ix != ix)
+        return capi_fail(UCFP_E_INVALID, f->ix ? "the filter view belongs to another index" : "the filter view's index was destroyed");
+    if (!filter_is_stale(ix, f)) return UCFP_OK;
+    if (!refresh)
+        return capi_fail(UCFP_E_INVALID, "the filter view is stale: tenant %u changed since it was built (ucfp_index_filter_refresh)",
+                         f->tenant);
+    return filter_build(ix, f);
+}
+
 }  // namespace
 
 extern "C" {
@@ -501,6 +701,14 @@ void ucfp_index_destroy(ucfp_index* ix) {
     if (!ix) return;
     (void)hipSetDevice(ix->device);
     (void)hipDeviceSynchronize();
+    {   // views outlive the index detached: their buffers go now, their handles stay valid for destroy
+        std::lock_guard<std::mutex> g(g_views_mu);
+        for (ucfp_index_filter* f : ix->views) {
+            filter_release(f);
+            f->ix = nullptr;
+        }
+        ix->views.clear();
+    }
     for (auto& kv : ix->shards) {
         if (kv.second.ids) (void)hipFree(kv.second.ids);
         if (kv.second.rows) (void)hipFree(kv.second.rows);
@@ -524,6 +732,7 @@ int ucfp_index_upsert(ucfp_index* ix, uint32_t tenant, const uint64_t* ids, cons
     std::lock_guard<std::mutex> lk(ix->mu);
     HIP_TRY(hipSetDevice(ix->device));
     Shard& s = ix->shards[tenant];
+    s.epoch++;
     hipStream_t st = ix->stream;
     for (hipEvent_t ev : ix->ws_done) HIP_TRY(hipStreamWaitEvent(st, ev, 0));
     HIP_TRY(hipStreamWaitEvent(st, ix->data_ready, 0));
@@ -609,6 +818,7 @@ int ucfp_index_append_dev(ucfp_index* ix, uint32_t tenant, const uint64_t* d_ids
     std::lock_guard<std::mutex> lk(ix->mu);
     HIP_TRY(hipSetDevice(ix->device));
     Shard& s = ix->shards[tenant];
+    s.epoch++;
     hipStream_t st = (hipStream_t)stream;
     for (hipEvent_t ev : ix->ws_done) HIP_TRY(hipStreamWaitEvent(st, ev, 0));
     HIP_TRY(hipStreamWaitEvent(st, ix->data_ready, 0));   // an earlier mutation on another stream (growth copies the rows)
@@ -641,6 +851,7 @@ int ucfp_index_delete(ucfp_index* ix, uint32_t tenant, const uint64_t* ids, size
     auto sit = ix->shards.find(tenant);
     if (sit == ix->shards.end()) return UCFP_OK;  // deleting from an unknown tenant is a no-op
     Shard& s = sit->second;
+    s.epoch++;
     HIP_TRY(hipSetDevice(ix->device));
     hipStream_t st = ix->stream;
     for (hipEvent_t ev : ix->ws_done) HIP_TRY(hipStreamWaitEvent(st, ev, 0));
@@ -822,6 +1033,219 @@ int ucfp_index_search(ucfp_index* ix, uint32_t tenant, const void* queries, size
         rc = ucfp_index_search_dev(ix, tenant, buf + o_q, nq, k, reinterpret_cast<uint64_t*>(buf + o_ids),
                                    reinterpret_cast<float*>(buf + o_sc), reinterpret_cast<uint32_t*>(buf + o_d),
                                    reinterpret_cast<uint32_t*>(buf + o_c), st);
+        if (rc == 0) {
+            e = hipMemcpyAsync(out_ids, buf + o_ids, nq * k * 8, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess && out_scores)
+                e = hipMemcpyAsync(out_scores, buf + o_sc, nq * k * 4, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess && out_dist)
+                e = hipMemcpyAsync(out_dist, buf + o_d, nq * k * 4, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipMemcpyAsync(out_counts, buf + o_c, nq * 4, hipMemcpyDeviceToHost, st);
+        }
+    }
+    hipError_t e2 = hipStreamSynchronize(st);
+    (void)hipFree(buf);
+    if (rc) return rc;
+    if (e != hipSuccess) return capi_fail(UCFP_E_INDEX, "search copy failed: %s", hipGetErrorString(e));
+    if (e2 != hipSuccess) return capi_fail(UCFP_E_INDEX, "search failed: %s", hipGetErrorString(e2));
+    return UCFP_OK;
+}
+
+int ucfp_index_filter_create(ucfp_index* ix, uint32_t tenant, const uint8_t* bytes, size_t len, ucfp_index_filter** out) {
+    if (!ix || !out) return capi_fail(UCFP_E_INVALID, "index/out is NULL");
+    *out = nullptr;
+    if (!bytes) return capi_fail(UCFP_E_INVALID, "filter bytes is NULL");
+    ucfp_index_filter* f = new (std::nothrow) ucfp_index_filter();
+    if (!f) return capi_fail(UCFP_E_INDEX, "out of host memory");
+    f->ix = ix;
+    f->tenant = tenant;
+    try {
+        f->bytes.assign(bytes, bytes + len);
+    } catch (const std::bad_alloc&) {
+        delete f;
+        return capi_fail(UCFP_E_INDEX, "out of host memory for a filter of %zu bytes", len);
+    }
+    std::lock_guard<std::mutex> g(g_views_mu);
+    std::lock_guard<std::mutex> lk(ix->mu);
+    const int rc = filter_build(ix, f);
+    if (rc) {
+        filter_release(f);
+        delete f;
+        return rc;
+    }
+    ix->views.push_back(f);
+    *out = f;
+    return UCFP_OK;
+}
+
+void ucfp_index_filter_destroy(ucfp_index_filter* f) {
+    if (!f) return;
+    {
+        std::lock_guard<std::mutex> g(g_views_mu);
+        if (ucfp_index* ix = f->ix) {
+            std::lock_guard<std::mutex> lk(ix->mu);
+            (void)hipSetDevice(ix->device);
+            (void)hipDeviceSynchronize();   // searches still reading the view
+            filter_release(f);
+            for (size_t i = 0; i < ix->views.size(); i++)
+                if (ix->views[i] == f) {
+                    ix->views.erase(ix->views.begin() + (long)i);
+                    break;
+                }
+        }
+    }
+    delete f;
+}
+
+int ucfp_index_filter_stats(ucfp_index_filter* f, size_t* rows_allowed, size_t* rows_seen, size_t* containers,
+                            size_t* device_bytes) {
+    if (!f) return capi_fail(UCFP_E_INVALID, "filter view is NULL");
+    std::lock_guard<std::mutex> g(g_views_mu);
+    if (!f->ix) return capi_fail(UCFP_E_INVALID, "the filter view's index was destroyed");
+    std::lock_guard<std::mutex> lk(f->ix->mu);
+    if (rows_allowed) *rows_allowed = f->n;
+    if (rows_seen) *rows_seen = f->seen;
+    if (containers) *containers = f->containers;
+    if (device_bytes) *device_bytes = f->view_bytes + f->scratch.cap;
+    return UCFP_OK;
+}
+
+int ucfp_index_filter_build_ms(ucfp_index_filter* f, float* probe_ms, float* scan_ms, float* readback_ms, float* gather_ms) {
+    if (!f) return capi_fail(UCFP_E_INVALID, "filter view is NULL");
+    std::lock_guard<std::mutex> g(g_views_mu);
+    if (!f->ix) return capi_fail(UCFP_E_INVALID, "the filter view's index was destroyed");
+    std::lock_guard<std::mutex> lk(f->ix->mu);
+    float ms[4] = {0.f, 0.f, 0.f, 0.f};
+    if (f->timed) {   // (a view of 0 rows ran no complete build: zeros)
+        HIP_TRY(hipSetDevice(f->ix->device));
+        HIP_TRY(hipEventSynchronize(f->ev[4]));
+        for (int i = 0; i < 4; i++) HIP_TRY(hipEventElapsedTime(&ms[i], f->ev[i], f->ev[i + 1]));
+    }
+    if (probe_ms) *probe_ms = ms[0];
+    if (scan_ms) *scan_ms = ms[1];
+    if (readback_ms) *readback_ms = ms[2];
+    if (gather_ms) *gather_ms = ms[3];
+    return UCFP_OK;
+}
+
+int ucfp_index_filter_check(ucfp_index_filter* f) {
+    if (!f) return capi_fail(UCFP_E_INVALID, "filter view is NULL");
+    std::lock_guard<std::mutex> g(g_views_mu);
+    if (!f->ix) return capi_fail(UCFP_E_INVALID, "the filter view's index was destroyed");
+    ucfp_index* ix = f->ix;
+    std::lock_guard<std::mutex> lk(ix->mu);
+    HIP_TRY(hipSetDevice(ix->device));
+    HIP_TRY(hipDeviceSynchronize());
+    const bool cosine = ix->kind == UCFP_INDEX_COSINE_F32;
+    struct {
+        const char* name;
+        const uint8_t* p;
+        size_t bytes;
+    } bufs[4] = {{"ids", reinterpret_cast<const uint8_t*>(f->ids), f->n * 8},
+                 {"rows", f->rows, f->n * ix->row_bytes},
+                 {"norms", reinterpret_cast<const uint8_t*>(f->norms), cosine ? f->n * 4 : 0},
+                 {"order", reinterpret_cast<const uint8_t*>(f->order), 16}};
+    for (const auto& b : bufs) {
+        if (!b.p) continue;
+        const int front = guard_state(b.p - kViewGuard), back = guard_state(b.p + b.bytes);
+        if (front < 0 || back < 0) return capi_fail(UCFP_E_INDEX, "could not read the guards of the view's %s", b.name);
+        if (front || back)
+            return capi_fail(UCFP_E_INDEX, "the bytes %s the view's %s buffer (%zu bytes) were overwritten", front ? "in front of" : "behind",
+                             b.name, b.bytes);
+    }
+    if (f->scratch.p && f->scratch_used) {
+        const int back = guard_state(f->scratch.p + f->scratch_used);
+        if (back < 0) return capi_fail(UCFP_E_INDEX, "could not read the guard of the view's scratch");
+        if (back) return capi_fail(UCFP_E_INDEX, "the bytes behind the view's masks and counts (%zu bytes) were overwritten", f->scratch_used);
+    }
+    return UCFP_OK;
+}
+
+int ucfp_index_filter_stale(ucfp_index_filter* f) {
+    if (!f) return capi_fail(UCFP_E_INVALID, "filter view is NULL");
+    std::lock_guard<std::mutex> g(g_views_mu);
+    if (!f->ix) return capi_fail(UCFP_E_INVALID, "the filter view's index was destroyed");
+    std::lock_guard<std::mutex> lk(f->ix->mu);
+    return filter_is_stale(f->ix, f) ? 1 : 0;
+}
+
+int ucfp_index_filter_refresh(ucfp_index_filter* f) {
+    if (!f) return capi_fail(UCFP_E_INVALID, "filter view is NULL");
+    std::lock_guard<std::mutex> g(g_views_mu);
+    if (!f->ix) return capi_fail(UCFP_E_INVALID, "the filter view's index was destroyed");
+    std::lock_guard<std::mutex> lk(f->ix->mu);
+    return filter_build(f->ix, f);
+}
+
+// ucfp_index_search_dev over a view: the same slot and event protocol, a Shard value over the view's buffers
+static int search_filtered_dev(ucfp_index* ix, ucfp_index_filter* f, bool refresh, const void* d_queries, size_t nq, uint32_t k,
+                               uint64_t* d_out_ids, float* d_out_scores, uint32_t* d_out_dist, uint32_t* d_out_counts,
+                               hipStream_t st) {
+    std::lock_guard<std::mutex> g(g_views_mu);
+    std::lock_guard<std::mutex> lk(ix->mu);
+    HIP_TRY(hipSetDevice(ix->device));
+    int rc = filter_check(ix, f, refresh);
+    if (rc) return rc;
+    if (nq == 0) return UCFP_OK;
+    if (k == 0) {
+        HIP_TRY(hipMemsetAsync(d_out_counts, 0, nq * 4, st));
+        return UCFP_OK;
+    }
+    Shard v;
+    v.ids = f->ids;
+    v.rows = f->rows;
+    v.norms = f->norms;
+    v.order = f->order;
+    v.n = v.cap = f->n;
+    ix->ws_cur = ix->kind == UCFP_INDEX_HAMMING64 ? (ix->ws_next++ & 1u) : 0u;
+    HIP_TRY(hipStreamWaitEvent(st, ix->ws_done[ix->ws_cur], 0));
+    HIP_TRY(hipStreamWaitEvent(st, ix->data_ready, 0));
+    rc = search_shard_dev(ix, f->n ? &v : nullptr, d_queries, nq, k, d_out_ids, d_out_scores, d_out_dist, d_out_counts, st);
+    HIP_TRY(hipEventRecord(ix->ws_done[ix->ws_cur], st));
+    return rc;
+}
+
+int ucfp_index_search_filtered_dev(ucfp_index* ix, ucfp_index_filter* f, const void* d_queries, size_t nq, uint32_t k,
+                                   uint64_t* d_out_ids, float* d_out_scores, uint32_t* d_out_dist, uint32_t* d_out_counts,
+                                   void* stream) {
+    int rc = check_search_args(ix, d_queries, nq, k, d_out_ids, d_out_counts);
+    if (rc) return rc;
+    if (!f) return capi_fail(UCFP_E_INVALID, "filter view is NULL");
+    return search_filtered_dev(ix, f, false, d_queries, nq, k, d_out_ids, d_out_scores, d_out_dist, d_out_counts,
+                               (hipStream_t)stream);
+}
+
+int ucfp_index_search_filtered(ucfp_index* ix, ucfp_index_filter* f, const void* queries, size_t nq, uint32_t k,
+                               uint64_t* out_ids, float* out_scores, uint32_t* out_dist, uint32_t* out_counts) {
+    int rc = check_search_args(ix, queries, nq, k, out_ids, out_counts);
+    if (rc) return rc;
+    if (!f) return capi_fail(UCFP_E_INVALID, "filter view is NULL");
+    if (nq == 0 || k == 0) {   // nothing to search: the view is still checked (and refreshed)
+        {
+            std::lock_guard<std::mutex> g(g_views_mu);
+            std::lock_guard<std::mutex> lk(ix->mu);
+            HIP_TRY(hipSetDevice(ix->device));
+            rc = filter_check(ix, f, true);
+        }
+        if (rc == 0 && nq) memset(out_counts, 0, nq * 4);
+        return rc;
+    }
+    const size_t qbytes = nq * ix->row_bytes;
+    const size_t o_q = 0, o_ids = align256(qbytes), o_sc = align256(o_ids + nq * k * 8);
+    const size_t o_d = align256(o_sc + nq * k * 4), o_c = align256(o_d + nq * k * 4);
+    const size_t total = align256(o_c + nq * 4);
+    hipStream_t st;
+    uint8_t* buf = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(ix->mu);
+        HIP_TRY(hipSetDevice(ix->device));
+        st = ix->stream;
+        HIP_TRY(hipMalloc((void**)&buf, total));
+    }
+    hipError_t e = hipMemcpyAsync(buf + o_q, queries, qbytes, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        rc = search_filtered_dev(ix, f, true, buf + o_q, nq, k, reinterpret_cast<uint64_t*>(buf + o_ids),
+                                 reinterpret_cast<float*>(buf + o_sc), reinterpret_cast<uint32_t*>(buf + o_d),
+                                 reinterpret_cast<uint32_t*>(buf + o_c), st);
         if (rc == 0) {
             e = hipMemcpyAsync(out_ids, buf + o_ids, nq * k * 8, hipMemcpyDeviceToHost, st);
             if (e == hipSuccess && out_scores)

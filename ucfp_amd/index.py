@@ -27,6 +27,8 @@ The reference keeps redb as the source of truth; this object is the device mirro
 node and merges per-shard top-k after an RCCL all-gather.
 """
 import ctypes as C
+import hashlib
+from collections import OrderedDict
 from typing import Iterable, List, Optional, Sequence
 
 import numpy as np
@@ -43,6 +45,7 @@ from .text import ALGORITHM_LSH, ALGORITHM_MINHASH_128, ALGORITHM_TLSH, DEFAULT_
 HAMMING64, COSINE_F32 = 1, 2
 APPEND_ONLY = 1
 MAX_K = 128
+MAX_VIEWS = 4              # filter views a GpuIndex keeps (DESIGN F5)
 INVALID_ID = 0xFFFFFFFFFFFFFFFF
 BM25_LDS_POSTINGS = 6144   # UCFP_BM25_LDS_POSTINGS: a query with more postings is scored by ordinal ranges
 TERM_HITS_PER_DOC = 16     # bm25.rs:503
@@ -85,6 +88,132 @@ class SearchBatcher:
     def close(self):
         if getattr(self, "handle", None):
             self._lib.ucfp_index_search_batcher_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _filter_ids(ids) -> np.ndarray:
+    """Any iterable of ints in [0, 2^64), in any order, duplicates allowed -> sorted unique uint64."""
+    if isinstance(ids, np.ndarray):
+        if ids.dtype.kind not in "iu":
+            raise InvalidArgument("filter ids must be integers")
+        if ids.dtype.kind == "i" and ids.size and int(ids.min()) < 0:
+            raise InvalidArgument("filter ids must lie in [0, 2^64)")
+        a = ids.astype(np.uint64).reshape(-1)
+    else:
+        items = list(ids)
+        if not all(isinstance(x, (int, np.integer)) and not isinstance(x, bool) and 0 <= int(x) < 1 << 64 for x in items):
+            raise InvalidArgument("filter ids must be integers in [0, 2^64)")
+        a = np.array([int(x) for x in items], dtype=np.uint64)
+    return np.unique(a)
+
+
+def _bitmap32_bytes(low: np.ndarray, runs: bool) -> bytes:
+    """One 32-bit Roaring bitmap (DESIGN F1) over sorted unique uint32 values."""
+    uk, first = np.unique(low >> np.uint32(16), return_index=True)
+    n = int(uk.size)
+    bounds = np.append(first, low.size)
+    bodies, cards, flags = [], [], []
+    for i in range(n):
+        vals = (low[bounds[i]:bounds[i + 1]] & np.uint32(0xFFFF)).astype("<u2")
+        card = int(vals.size)
+        body, is_run = None, False
+        if runs:
+            brk = np.flatnonzero(np.diff(vals.astype(np.int32)) != 1)
+            starts, ends = vals[np.r_[0, brk + 1]], vals[np.r_[brk, card - 1]]
+            if 2 + 4 * starts.size < (2 * card if card <= 4096 else 8192):
+                pairs = np.empty((starts.size, 2), "<u2")
+                pairs[:, 0], pairs[:, 1] = starts, ends - starts
+                body, is_run = np.array([starts.size], "<u2").tobytes() + pairs.tobytes(), True
+        if body is None and card <= 4096:
+            body = vals.tobytes()
+        elif body is None:
+            bits = np.zeros(65536, np.uint8)
+            bits[vals] = 1
+            body = np.packbits(bits, bitorder="little").tobytes()
+        bodies.append(body)
+        cards.append(card)
+        flags.append(is_run)
+    if any(flags):
+        head = np.array([12347 | (n - 1) << 16], "<u4").tobytes() + np.packbits(np.array(flags, np.uint8), bitorder="little").tobytes()
+    else:
+        head = np.array([12346, n], "<u4").tobytes()
+    desc = np.empty((n, 2), "<u2")
+    desc[:, 0], desc[:, 1] = uk, np.array(cards, np.int64) - 1
+    head += desc.tobytes()
+    if not any(flags) or n >= 4:
+        sizes = np.array([len(b) for b in bodies], np.int64)
+        head += (len(head) + 4 * n + np.concatenate(([0], np.cumsum(sizes)[:-1]))).astype("<u4").tobytes()
+    return head + b"".join(bodies)
+
+
+def filter_bytes(ids, runs: bool = False) -> bytes:
+    """A query filter (DESIGN F1): the portable serialization of the 64-bit Roaring treemap of `ids` -- what
+    RoaringTreemap::serialize_into writes.  Containers of up to 4096 values are arrays, larger ones bitmaps; with `runs`
+    a container is written as runs where that is smaller."""
+    a = _filter_ids(ids)
+    uh, first = np.unique(a >> np.uint64(32), return_index=True)
+    bounds = np.append(first, a.size)
+    out = [np.array([uh.size], "<u8").tobytes()]
+    for i in range(int(uh.size)):
+        out.append(np.array([uh[i]], "<u4").tobytes())
+        out.append(_bitmap32_bytes((a[bounds[i]:bounds[i + 1]] & np.uint64(0xFFFFFFFF)).astype(np.uint32), runs))
+    return b"".join(out)
+
+
+def roaring_cardinality(data: bytes) -> int:
+    """ucfp_roaring_validate: the number of ids in a filter; InvalidArgument (with the byte offset) for malformed bytes."""
+    card = C.c_uint64(0)
+    data = bytes(data)
+    _lib.check(_lib.load().ucfp_roaring_validate(data, len(data), C.byref(card)))
+    return int(card.value)
+
+
+class IndexFilter:
+    """A filter view (ucfp_index_filter_*, DESIGN F5): the rows of one tenant that a filter allows, as a compact sub-shard
+    on the device.  Made by DeviceIndex.filter; pass it to DeviceIndex.search / search_dev."""
+
+    def __init__(self, index: "DeviceIndex", tenant: int, data):
+        self._lib = _lib.load()
+        self.index, self.tenant = index, int(tenant)
+        data = bytes(data) if isinstance(data, (bytes, bytearray, memoryview)) else filter_bytes(data)
+        h = C.c_void_p()
+        _lib.check(self._lib.ucfp_index_filter_create(index.handle, self.tenant, data, len(data), C.byref(h)))
+        self.handle = h
+
+    def stats(self) -> dict:
+        v = [C.c_size_t(0) for _ in range(4)]
+        _lib.check(self._lib.ucfp_index_filter_stats(self.handle, *[C.byref(x) for x in v]))
+        return dict(zip(("rows_allowed", "rows_seen", "containers", "device_bytes"), (int(x.value) for x in v)))
+
+    def build_ms(self) -> dict:
+        """Device milliseconds of the last build: probe, scan, read-back (+ allocation), gather."""
+        v = [C.c_float(0) for _ in range(4)]
+        _lib.check(self._lib.ucfp_index_filter_build_ms(self.handle, *[C.byref(x) for x in v]))
+        return dict(zip(("probe", "scan", "readback", "gather"), (float(x.value) for x in v)))
+
+    def check_guards(self) -> None:
+        """Raises if anything wrote outside the view's own device buffers (ucfp_index_filter_check)."""
+        _lib.check(self._lib.ucfp_index_filter_check(self.handle))
+
+    @property
+    def stale(self) -> bool:
+        rc = self._lib.ucfp_index_filter_stale(self.handle)
+        if rc < 0:
+            _lib.check(rc)
+        return bool(rc)
+
+    def refresh(self) -> None:
+        _lib.check(self._lib.ucfp_index_filter_refresh(self.handle))
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self._lib.ucfp_index_filter_destroy(self.handle)
             self.handle = None
 
     def __del__(self):
@@ -159,9 +288,21 @@ class DeviceIndex:
         _lib.check(self._lib.ucfp_index_flush(self.handle))
 
     # ---- search ----
-    def search(self, tenant: int, queries, k: int):
+    def filter(self, tenant: int, filter_bytes_or_ids) -> IndexFilter:
+        """The view of `tenant` that a filter allows: bytes (DESIGN F1, e.g. `filter_bytes`) or an iterable of record ids."""
+        return IndexFilter(self, tenant, filter_bytes_or_ids)
+
+    def _view(self, tenant: int, filter) -> IndexFilter:
+        if not isinstance(filter, IndexFilter):
+            raise InvalidArgument("`filter` must be an IndexFilter (DeviceIndex.filter)")
+        if filter.tenant != tenant:
+            raise InvalidArgument(f"the filter view was made for tenant {filter.tenant}, not {tenant}")
+        return filter
+
+    def search(self, tenant: int, queries, k: int, filter: Optional[IndexFilter] = None):
         """Host-memory batch search. Returns (ids [nq,k] u64, scores [nq,k] f32, keys [nq,k] u32,
-        counts [nq] u32); keys = Hamming distance, or the inverted order image of the cosine score."""
+        counts [nq] u32); keys = Hamming distance, or the inverted order image of the cosine score.
+        With `filter` (a view of this index and tenant) only the rows it allows answer; a stale view is refreshed."""
         q = self._rows(queries)
         nq = q.shape[0]
         kk = max(k, 1)
@@ -169,12 +310,23 @@ class DeviceIndex:
         scores = np.zeros((nq, kk), np.float32)
         keys = np.full((nq, kk), 0xFFFFFFFF, np.uint32)
         counts = np.zeros(nq, np.uint32)
+        if filter is not None:
+            _lib.check(self._lib.ucfp_index_search_filtered(self.handle, self._view(tenant, filter).handle, q.ctypes.data, nq, k,
+                                                            ids.ctypes.data, scores.ctypes.data, keys.ctypes.data,
+                                                            counts.ctypes.data))
+            return ids[:, :k], scores[:, :k], keys[:, :k], counts
         _lib.check(self._lib.ucfp_index_search(self.handle, tenant, q.ctypes.data, nq, k, ids.ctypes.data,
                                                scores.ctypes.data, keys.ctypes.data, counts.ctypes.data))
         return ids[:, :k], scores[:, :k], keys[:, :k], counts
 
     def search_dev(self, tenant: int, queries_ptr: int, nq: int, k: int, out_ids_ptr: int,
-                   out_scores_ptr: int, out_keys_ptr: int, out_counts_ptr: int, stream: int = 0) -> None:
+                   out_scores_ptr: int, out_keys_ptr: int, out_counts_ptr: int, stream: int = 0,
+                   filter: Optional[IndexFilter] = None) -> None:
+        if filter is not None:   # (a stale view is refused here: refresh it, or search through the host entry)
+            _lib.check(self._lib.ucfp_index_search_filtered_dev(self.handle, self._view(tenant, filter).handle, queries_ptr, nq, k,
+                                                                out_ids_ptr, out_scores_ptr or None, out_keys_ptr or None,
+                                                                out_counts_ptr, stream or None))
+            return
         _lib.check(self._lib.ucfp_index_search_dev(self.handle, tenant, queries_ptr, nq, k, out_ids_ptr,
                                                    out_scores_ptr or None, out_keys_ptr or None,
                                                    out_counts_ptr, stream or None))
@@ -907,6 +1059,23 @@ class GpuIndex:
         self._mh = {}         # MinHash algorithm tag -> MinHashIndex of its 1032-byte records (DESIGN A17)
         self._mh_h = {}       # (tag, H) -> MinHashIndex of the tag's records of H != 128 slots (DESIGN T10): one index per (tag, H)
         self._sidecar = sidecar   # ucfp_amd.store.Sidecar: the stored-table mirror written at upsert
+        self._views = OrderedDict()   # (id of the DeviceIndex, tenant, digest of the filter bytes) -> IndexFilter, at most MAX_VIEWS
+
+    def _view(self, ix: DeviceIndex, tenant_id: int, filter) -> IndexFilter:
+        """The cached view of a query's filter bytes (DESIGN F5): least recently used out at MAX_VIEWS; a stale one is
+        refreshed by the search itself."""
+        if not isinstance(filter, (bytes, bytearray, memoryview)):
+            raise InvalidArgument("`filter` must be bytes (a serialized Roaring treemap: index.filter_bytes)")
+        data = bytes(filter)
+        key = (id(ix), int(tenant_id), hashlib.blake2b(data, digest_size=16).digest())
+        view = self._views.get(key)
+        if view is None:
+            view = self._views[key] = ix.filter(tenant_id, data)
+            while len(self._views) > MAX_VIEWS:
+                self._views.popitem(last=False)[1].close()
+        else:
+            self._views.move_to_end(key)
+        return view
 
     def attach_sidecar(self, sidecar) -> None:
         self._sidecar = sidecar
@@ -1119,15 +1288,18 @@ class GpuIndex:
         ix = self._cos.get(q.size)
         if ix is None:
             return []
-        ids, scores, _, counts = ix.search(tenant_id, q[None, :], min(k, MAX_K))
+        view = self._view(ix, tenant_id, _filter) if _filter is not None else None
+        ids, scores, _, counts = ix.search(tenant_id, q[None, :], min(k, MAX_K), view)
         return [Hit(tenant_id=tenant_id, record_id=int(ids[0, i]), score=float(scores[0, i]),
                     source=HitSource.Vector) for i in range(int(counts[0]))]
 
-    def hamming(self, tenant_id: int, space: str, query_hash: int, k: int) -> List[Hit]:
+    def hamming(self, tenant_id: int, space: str, query_hash: int, k: int, filter: Optional[bytes] = None) -> List[Hit]:
         if k == 0 or space not in self._ham:
             return []
-        ids, scores, dist, counts = self._ham[space].search(
-            tenant_id, np.array([query_hash], np.uint64), min(k, MAX_K))
+        ix = self._ham[space]
+        view = self._view(ix, tenant_id, filter) if filter is not None else None
+        ids, scores, dist, counts = ix.search(
+            tenant_id, np.array([query_hash], np.uint64), min(k, MAX_K), view)
         return [Hit(tenant_id=tenant_id, record_id=int(ids[0, i]), score=float(scores[0, i]),
                     source=HitSource.Hamming, distance=int(dist[0, i])) for i in range(int(counts[0]))]
 
@@ -1326,6 +1498,10 @@ class GpuIndex:
                 if h.source == HitSource.Bm25:
                     h.bm25_score, h.bm25_rank = h.score, rank + 1
             return hits
+        filt = getattr(req, "filter", None)
+        if filt is not None and any(getattr(req, a, None) is not None for a in
+                                    ("landmarks", "subfingerprints", "triplets", "tlsh", "image_record", "minhash")):
+            raise UnsupportedError("`filter` goes with a `vector` or a `hash` query; the other indexes take no filter yet")
         if getattr(req, "image_record", None) is not None:
             cfg = MultiHashConfig.from_dto(getattr(req, "multi_hash", None))
             if getattr(req, "min_score", None) is not None:
@@ -1355,9 +1531,9 @@ class GpuIndex:
                 if len(self._ham) != 1:
                     raise InvalidArgument("`algorithm` is required when several hash spaces exist")
                 space = next(iter(self._ham))
-            hits = self.hamming(req.tenant_id, space, req.hash, req.k)
+            hits = self.hamming(req.tenant_id, space, req.hash, req.k, filt)
         else:
-            hits = self.knn(req.tenant_id, req.vector or [], req.k)
+            hits = self.knn(req.tenant_id, req.vector or [], req.k, filt)
         for rank, h in enumerate(hits):   # Matcher::search fills the rank of the only list it fused (matcher/mod.rs:140-207)
             if h.source == HitSource.Vector:
                 h.vector_score, h.vector_rank = h.score, rank + 1

@@ -1575,6 +1575,36 @@ int ucfp_index_search_filtered_dev(ucfp_index* idx, ucfp_index_filter* f, const 
 int ucfp_index_search_filtered(ucfp_index* idx, ucfp_index_filter* f, const void* queries, size_t nq, uint32_t k,
                                uint64_t* out_ids, float* out_scores, uint32_t* out_dist, uint32_t* out_counts);
 
+/* Multi-tenant search (DESIGN M1 - M6): one batch for the queries of many tenants.  Every shape of the reference carries a
+ * tenant_id (src/core/mod.rs) and the requests in flight belong to whatever tenants are calling; the entries above take one
+ * tenant per call, so the queries of ten thousand small tenants are ten thousand chains of launches.  Here query i searches
+ * tenant tenants[i]; the number of launches does not depend on the tenants of the batch (hamming_multi.hip).
+ *   tenants     nq tenant ids, HOST memory in both forms (the host owns the tenant -> shard map); read before the call returns
+ *   outputs     the layout of ucfp_index_search[_dev]: nq x k (d_out_scores / d_out_dist may be NULL), counts nq
+ * Row i of every output is, bit for bit, what ucfp_index_search_dev(idx, tenants[i], &query_i, 1, k, ...) writes: ids, score
+ * bits, distances, the count and the padding past it, in (distance, record id) order.  An unknown tenant or one without
+ * rows gives count 0 and a padded row; k = 0 zeroes the counts and writes nothing else; nq = 0 is UCFP_OK.  Tenants may
+ * repeat, come in any order, and all be the same; a query's answer does not depend on the rest of the batch.
+ * Checks: those of ucfp_index_search, and tenants == NULL with nq > 0 -> UCFP_E_INVALID.  HAMMING64 only: a COSINE_F32
+ * index is UCFP_E_UNSUPPORTED, and filter views are not accepted.  A batch runs in chunks of 16 384 queries; a chunk whose
+ * work items (ucfp_index_search_multi_limits: tiles of tile_rows rows x chunks of query_chunk queries, per tenant) number
+ * more than (2^32 - 1) / 256, or a batch that names a tenant of more than 2^32 - 1 rows, is UCFP_E_UNSUPPORTED before
+ * anything runs.  Nothing is written on a refusal.
+ * Each tenant's rows are read twice: a tenant with many rows AND many queries is better served by ucfp_index_search_dev.
+ * The _dev form follows the stream protocol of ucfp_index_search_dev (a workspace slot, ordered against mutations) and has
+ * ONE host wait: the pinned staging of the slot's plan tables is rewritten by the host, which first waits for the search
+ * that used the slot last -- the search two calls back; none in the first two calls.  It synchronises nothing else.  That
+ * wait is taken with the index's mutex held (the plan holds shard pointers that a mutation may free): while it lasts, other
+ * threads' searches and mutations of this index queue behind it, as they do behind the synchronising mutations.
+ * ucfp_index_search_multi_limits: host only; the constants of the implementation -- rows per work item, queries per work
+ * item, ids of a query's tie list (more ties at the k-th distance take a gated exact pass); any pointer may be NULL. */
+int ucfp_index_search_multi_dev(ucfp_index* idx, const uint32_t* tenants, const void* d_queries, size_t nq, uint32_t k,
+                                uint64_t* d_out_ids, float* d_out_scores, uint32_t* d_out_dist, uint32_t* d_out_counts,
+                                void* stream);
+int ucfp_index_search_multi(ucfp_index* idx, const uint32_t* tenants, const void* queries, size_t nq, uint32_t k,
+                            uint64_t* out_ids, float* out_scores, uint32_t* out_dist, uint32_t* out_counts);
+int ucfp_index_search_multi_limits(uint32_t* tile_rows, uint32_t* query_chunk, uint32_t* tie_cap);
+
 /* Host micro-batcher for the QUERY route: /v1/query is one query per request (src/server/handlers.rs:143-187),
  * up to 512 requests in flight (src/bin/ucfp.rs:267).  submit() is BLOCKING and thread-safe: concurrent calls -- each with
  * ITS OWN query (a u64 hash, or dim floats) and ITS OWN k (QueryRequest.k, src/server/dto.rs:74-87) -- become ONE copy of the
@@ -1593,6 +1623,13 @@ void ucfp_index_search_batcher_destroy(ucfp_search_batcher* b);
 int ucfp_index_search_batcher_submit(ucfp_search_batcher* b, const void* query, uint32_t k, uint64_t* out_ids, float* out_scores,
                                      uint32_t* out_dist, uint32_t* out_count);
 int ucfp_index_search_batcher_stats(ucfp_search_batcher* b, uint64_t* batches, uint64_t* items);
+/* The same object for the requests of MANY tenants (DESIGN M5): one batcher per index, every submit names its tenant, one
+ * flush is ONE ucfp_index_search_multi_dev with the largest k of the batch.  Limits, flush rules, stats and destroy as above.
+ * ucfp_index_search_batcher_submit on a multi batcher and ucfp_index_search_batcher_submit_tenant on a per-tenant one are
+ * UCFP_E_INVALID; create_multi on a COSINE_F32 index is UCFP_E_UNSUPPORTED. */
+int ucfp_index_search_batcher_create_multi(ucfp_index* idx, size_t max_batch, uint32_t max_delay_us, ucfp_search_batcher** out);
+int ucfp_index_search_batcher_submit_tenant(ucfp_search_batcher* b, uint32_t tenant, const void* query, uint32_t k,
+                                            uint64_t* out_ids, float* out_scores, uint32_t* out_dist, uint32_t* out_count);
 
 /* Final step of a sharded search: merge `parts` per-shard top-k lists -- the
  * all-gathered [parts][nq][k] ids + keys -- into one. Keys: Hamming distance (kind

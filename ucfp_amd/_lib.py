@@ -357,6 +357,14 @@ SIGNATURES = {
                                              C.c_void_p, C.c_void_p, C.c_void_p]),
     "ucfp_index_search_filtered_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ucfp_index_search_multi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ucfp_index_search_multi_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ucfp_index_search_multi_limits": (C.c_int, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "ucfp_index_search_batcher_create_multi": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "ucfp_index_search_batcher_submit_tenant": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                          C.c_void_p, C.POINTER(C.c_uint32)]),
     "ucfp_index_search_batcher_create": (C.c_int, [C.c_void_p, C.c_uint32, C.c_size_t, C.c_uint32, C.POINTER(C.c_void_p)]),
     "ucfp_index_search_batcher_destroy": (None, [C.c_void_p]),
     "ucfp_index_search_batcher_submit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,

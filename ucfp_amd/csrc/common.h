@@ -230,6 +230,16 @@ int launch_hamming_direct(const uint64_t* codes, const uint64_t* ids, size_t n, 
                           uint32_t k, uint8_t* state, uint64_t* out_ids, uint32_t* out_dist, float* out_scores,
                           uint32_t* out_cnt, hipStream_t stream, const uint32_t* ids_ascending = nullptr);
 
+// hamming_multi.hip: one planned chunk (multi_plan.h) of a batch in which every query names its own tenant
+namespace multi {
+struct Seg;
+struct Item;
+}  // namespace multi
+size_t hamming_multi_ws_bytes(uint32_t cn, uint32_t k);
+int launch_hamming_multi(uint8_t* ws, const uint32_t* perm, const uint32_t* pos_seg, const multi::Seg* segs,
+                         const multi::Item* items, uint32_t n_items, const uint64_t* queries, uint32_t cn, uint32_t k,
+                         uint64_t* out_ids, float* out_scores, uint32_t* out_dist, uint32_t* out_counts, hipStream_t stream);
+
 // topk.hip
 struct SelectPlan {
     uint32_t slices = 0;

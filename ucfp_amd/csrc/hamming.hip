@@ -32,6 +32,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "hamming64.h"
 
 namespace ucfp {
 
@@ -41,12 +42,6 @@ constexpr int kWave = 64;
 // are 80 atomics with return on ONE address otherwise, a dependent chain in the memory-side atomic unit (19 of the first
 // rescan's 38 us at 12.5 M x 4096).  (A 128-byte line per counter, by itself, measured no change.)
 constexpr uint32_t kSub = 8;
-
-__device__ __forceinline__ uint32_t hamming64(uint64_t q, uint64_t x) {
-    const uint32_t lo = (uint32_t)q ^ (uint32_t)x;
-    const uint32_t hi = (uint32_t)(q >> 32) ^ (uint32_t)(x >> 32);
-    return __builtin_popcount(hi) + __builtin_popcount(lo);
-}
 
 // ---- sample pre-pass --------------------------------------------------------------------
 // hist layout: [q][65] u32 (global, zeroed by the launcher).

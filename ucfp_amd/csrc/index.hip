@@ -23,6 +23,7 @@
 
 #include "../../include/ucfp_hip.h"
 #include "common.h"
+#include "multi_plan.h"
 #include "roaring_parse.h"
 
 using ucfp::capi_fail;
@@ -112,6 +113,10 @@ struct ucfp_index {
     // behind; a search waits for `data_ready` (rows appended on another stream have landed).
     hipEvent_t data_ready = nullptr;
     DevBuf stage;                  // host<->device staging
+    // multi-tenant search (DESIGN M4): per workspace slot, the pinned staging its plan tables are copied up from.  The host
+    // rewrites it on the slot's next multi search, after waiting for the slot's ws_done.
+    uint8_t* multi_stage[2] = {nullptr, nullptr};
+    size_t multi_stage_cap[2] = {0, 0};
     std::vector<ucfp_index_filter*> views;   // the filter views of this index (detached when it is destroyed)
 };
 
@@ -718,6 +723,8 @@ void ucfp_index_destroy(ucfp_index* ix) {
     for (auto& w : ix->ws_slot) w.release();
     for (auto& w : ix->direct_state) w.release();
     ix->stage.release();
+    for (uint8_t* h : ix->multi_stage)
+        if (h) (void)hipHostFree(h);
     if (ix->stream) (void)hipStreamDestroy(ix->stream);
     for (hipEvent_t ev : ix->ws_done)
         if (ev) (void)hipEventDestroy(ev);
@@ -1262,6 +1269,189 @@ int ucfp_index_search_filtered(ucfp_index* ix, ucfp_index_filter* f, const void*
     if (e2 != hipSuccess) return capi_fail(UCFP_E_INDEX, "search failed: %s", hipGetErrorString(e2));
     return UCFP_OK;
 }
+
+}  // extern "C"
+
+// ---- multi-tenant search (DESIGN M1 - M4) --------------------------------------------------------------------------------
+namespace {
+
+int check_multi_args(ucfp_index* ix, const uint32_t* tenants, const void* q, size_t nq, uint32_t k, const void* ids,
+                     const void* cnt) {
+    int rc = check_search_args(ix, q, nq, k, ids, cnt);
+    if (rc) return rc;
+    if (nq && !tenants) return capi_fail(UCFP_E_INVALID, "tenants is NULL");
+    if (ix->kind != UCFP_INDEX_HAMMING64)
+        return capi_fail(UCFP_E_UNSUPPORTED, "multi-tenant search is not supported on a COSINE_F32 index (HAMMING64 only)");
+    return 0;
+}
+
+struct MultiChunk {
+    ucfp::multi::Plan plan;
+    size_t o_perm = 0, o_pseg = 0, o_segs = 0, o_items = 0;   // in the table image
+};
+
+// ix->mu is held.  Plans first (a refusal changes nothing), then the slot protocol of ucfp_index_search_dev.
+int search_multi_locked(ucfp_index* ix, const uint32_t* tenants, const uint8_t* d_queries, size_t nq, uint32_t k,
+                        uint64_t* d_out_ids, float* d_out_scores, uint32_t* d_out_dist, uint32_t* d_out_counts,
+                        hipStream_t st) {
+    namespace m = ucfp::multi;
+    const size_t nchunks = (nq + m::kMaxBatch - 1) / m::kMaxBatch;
+    std::vector<MultiChunk> chunks(nchunks);
+    auto lookup = [ix](uint32_t tenant) {
+        m::ShardRef r;
+        auto it = ix->shards.find(tenant);
+        if (it != ix->shards.end() && it->second.n) {
+            r.rows = reinterpret_cast<const uint64_t*>(it->second.rows);
+            r.ids = it->second.ids;
+            r.n = it->second.n;
+        }
+        return r;
+    };
+    size_t tbytes = 0;
+    for (size_t c = 0; c < nchunks; c++) {
+        const size_t c0 = c * m::kMaxBatch, cn = nq - c0 < m::kMaxBatch ? nq - c0 : m::kMaxBatch;
+        MultiChunk& ch = chunks[c];
+        const int prc = m::plan(tenants + c0, cn, lookup, &ch.plan);
+        if (prc == m::kPlanTooManyItems)      // (every chunk is a grid of its own: only its own count has to fit)
+            return capi_fail(UCFP_E_UNSUPPORTED, "multi-tenant batch needs more than %llu work items (tiles of %u rows x chunks of %u "
+                             "queries): they do not fit a 32-bit grid; search the large tenants one tenant per call",
+                             (unsigned long long)m::kMaxItems, m::kTileRows, m::kQueryChunk);
+        if (prc == m::kPlanTooManyRows)
+            return capi_fail(UCFP_E_UNSUPPORTED, "multi-tenant search counts a tenant's rows in 32 bits: a tenant of the batch has more");
+        ch.o_perm = tbytes;
+        tbytes = align256(tbytes + cn * 4);
+        ch.o_pseg = tbytes;
+        tbytes = align256(tbytes + cn * 4);
+        ch.o_segs = tbytes;
+        tbytes = align256(tbytes + ch.plan.segs.size() * sizeof(m::Seg));
+        ch.o_items = tbytes;
+        tbytes = align256(tbytes + ch.plan.items.size() * sizeof(m::Item));
+    }
+    const unsigned cur = ix->ws_next++ & 1u;
+    ix->ws_cur = cur;
+    // the ONE host wait: the staging of this slot may still be read by the copy of the slot's previous search
+    HIP_TRY(hipEventSynchronize(ix->ws_done[cur]));
+    if (ix->multi_stage_cap[cur] < tbytes) {
+        if (ix->multi_stage[cur]) (void)hipHostFree(ix->multi_stage[cur]);
+        ix->multi_stage[cur] = nullptr;
+        ix->multi_stage_cap[cur] = 0;
+        const size_t want = tbytes + tbytes / 4 + 4096;
+        HIP_TRY(hipHostMalloc((void**)&ix->multi_stage[cur], want, hipHostMallocDefault));
+        ix->multi_stage_cap[cur] = want;
+    }
+    uint8_t* hs = ix->multi_stage[cur];
+    for (size_t c = 0; c < nchunks; c++) {
+        const MultiChunk& ch = chunks[c];
+        const m::Plan& p = ch.plan;
+        memcpy(hs + ch.o_perm, p.perm.data(), p.perm.size() * 4);
+        memcpy(hs + ch.o_pseg, p.pos_seg.data(), p.pos_seg.size() * 4);
+        memcpy(hs + ch.o_segs, p.segs.data(), p.segs.size() * sizeof(m::Seg));
+        if (!p.items.empty()) memcpy(hs + ch.o_items, p.items.data(), p.items.size() * sizeof(m::Item));
+    }
+    HIP_TRY(hipStreamWaitEvent(st, ix->ws_done[cur], 0));
+    HIP_TRY(hipStreamWaitEvent(st, ix->data_ready, 0));
+    const uint32_t cmax = (uint32_t)(nq < m::kMaxBatch ? nq : m::kMaxBatch);
+    const size_t o_tab = align256(ucfp::hamming_multi_ws_bytes(cmax, k));
+    int rc = ix->ws_slot[cur].ensure(o_tab + tbytes);
+    if (rc) return rc;
+    uint8_t* w = ix->ws_slot[cur].p;
+    hipError_t e = hipMemcpyAsync(w + o_tab, hs, tbytes, hipMemcpyHostToDevice, st);
+    for (size_t c = 0; c < nchunks && e == hipSuccess; c++) {
+        const MultiChunk& ch = chunks[c];
+        const size_t c0 = c * m::kMaxBatch;
+        const uint8_t* t = w + o_tab;
+        if (ucfp::launch_hamming_multi(w, reinterpret_cast<const uint32_t*>(t + ch.o_perm), reinterpret_cast<const uint32_t*>(t + ch.o_pseg),
+                                       reinterpret_cast<const m::Seg*>(t + ch.o_segs), reinterpret_cast<const m::Item*>(t + ch.o_items),
+                                       (uint32_t)ch.plan.items.size(), reinterpret_cast<const uint64_t*>(d_queries) + c0,
+                                       (uint32_t)ch.plan.perm.size(), k, d_out_ids + c0 * k, d_out_scores ? d_out_scores + c0 * k : nullptr,
+                                       d_out_dist ? d_out_dist + c0 * k : nullptr, d_out_counts + c0, st))
+            e = hipErrorUnknown;
+    }
+    if (e == hipSuccess) e = hipGetLastError();
+    const hipError_t e2 = hipEventRecord(ix->ws_done[cur], st);   // whatever was enqueued reads the shards and the staging
+    if (e != hipSuccess) return capi_fail(UCFP_E_INDEX, "multi-tenant search failed: %s", hipGetErrorString(e));
+    HIP_TRY(e2);
+    return UCFP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ucfp_index_search_multi_limits(uint32_t* tile_rows, uint32_t* query_chunk, uint32_t* tie_cap) {
+    if (tile_rows) *tile_rows = ucfp::multi::kTileRows;
+    if (query_chunk) *query_chunk = ucfp::multi::kQueryChunk;
+    if (tie_cap) *tie_cap = ucfp::multi::kTieCap;
+    return UCFP_OK;
+}
+
+int ucfp_index_search_multi_dev(ucfp_index* ix, const uint32_t* tenants, const void* d_queries, size_t nq, uint32_t k,
+                                uint64_t* d_out_ids, float* d_out_scores, uint32_t* d_out_dist, uint32_t* d_out_counts,
+                                void* stream) {
+    int rc = check_multi_args(ix, tenants, d_queries, nq, k, d_out_ids, d_out_counts);
+    if (rc) return rc;
+    if (nq == 0) return UCFP_OK;
+    std::lock_guard<std::mutex> lk(ix->mu);
+    HIP_TRY(hipSetDevice(ix->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (k == 0) {
+        HIP_TRY(hipMemsetAsync(d_out_counts, 0, nq * 4, st));
+        return UCFP_OK;
+    }
+    try {
+        return search_multi_locked(ix, tenants, static_cast<const uint8_t*>(d_queries), nq, k, d_out_ids, d_out_scores, d_out_dist,
+                                   d_out_counts, st);
+    } catch (const std::bad_alloc&) {
+        return capi_fail(UCFP_E_INDEX, "out of host memory while planning a multi-tenant batch of %zu queries", nq);
+    }
+}
+
+int ucfp_index_search_multi(ucfp_index* ix, const uint32_t* tenants, const void* queries, size_t nq, uint32_t k,
+                            uint64_t* out_ids, float* out_scores, uint32_t* out_dist, uint32_t* out_counts) {
+    int rc = check_multi_args(ix, tenants, queries, nq, k, out_ids, out_counts);
+    if (rc) return rc;
+    if (nq == 0) return UCFP_OK;
+    if (k == 0) {
+        memset(out_counts, 0, nq * 4);
+        return UCFP_OK;
+    }
+    const size_t qbytes = nq * 8;
+    const size_t o_q = 0, o_ids = align256(qbytes), o_sc = align256(o_ids + nq * k * 8);
+    const size_t o_d = align256(o_sc + nq * k * 4), o_c = align256(o_d + nq * k * 4);
+    const size_t total = align256(o_c + nq * 4);
+    hipStream_t st;
+    uint8_t* buf = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(ix->mu);
+        HIP_TRY(hipSetDevice(ix->device));
+        st = ix->stream;
+        HIP_TRY(hipMalloc((void**)&buf, total));
+    }
+    hipError_t e = hipMemcpyAsync(buf + o_q, queries, qbytes, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        rc = ucfp_index_search_multi_dev(ix, tenants, buf + o_q, nq, k, reinterpret_cast<uint64_t*>(buf + o_ids),
+                                         reinterpret_cast<float*>(buf + o_sc), reinterpret_cast<uint32_t*>(buf + o_d),
+                                         reinterpret_cast<uint32_t*>(buf + o_c), st);
+        if (rc == 0) {
+            e = hipMemcpyAsync(out_ids, buf + o_ids, nq * k * 8, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess && out_scores)
+                e = hipMemcpyAsync(out_scores, buf + o_sc, nq * k * 4, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess && out_dist)
+                e = hipMemcpyAsync(out_dist, buf + o_d, nq * k * 4, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipMemcpyAsync(out_counts, buf + o_c, nq * 4, hipMemcpyDeviceToHost, st);
+        }
+    }
+    hipError_t e2 = hipStreamSynchronize(st);
+    (void)hipFree(buf);
+    if (rc) return rc;
+    if (e != hipSuccess) return capi_fail(UCFP_E_INDEX, "search copy failed: %s", hipGetErrorString(e));
+    if (e2 != hipSuccess) return capi_fail(UCFP_E_INDEX, "search failed: %s", hipGetErrorString(e2));
+    return UCFP_OK;
+}
+
+}  // extern "C"
+
+extern "C" {
 
 int ucfp_topk_merge_dev(ucfp_ctx* ctx, int kind, const uint64_t* d_part_ids, const uint32_t* d_part_keys,
                         uint32_t parts, size_t nq, uint32_t k, uint64_t* d_out_ids, float* d_out_scores,

@@ -97,6 +97,38 @@ class SearchBatcher:
             pass
 
 
+class MultiSearchBatcher(SearchBatcher):
+    """The micro-batcher for the requests of MANY tenants (DESIGN M5): one per HAMMING64 index; `submit(tenant, query, k)`; one
+    flush is one multi-tenant search (ucfp_index_search_multi_dev) whatever tenants its requests name."""
+
+    def __init__(self, index: "DeviceIndex", *, max_batch: int = 256, max_delay_us: int = 0):
+        self._lib = _lib.load()
+        self.index = index
+        h = C.c_void_p()
+        _lib.check(self._lib.ucfp_index_search_batcher_create_multi(index.handle, max_batch, max_delay_us, C.byref(h)))
+        self.handle = h
+
+    def submit(self, tenant: int, query: int, k: int):
+        """query: int (64-bit hash).  -> (ids u64 [n], scores f32 [n], dist u32 [n]) with n <= k hits."""
+        q = np.array([query], dtype=np.uint64)
+        kk = max(int(k), 1)
+        ids = np.empty(kk, np.uint64)
+        sc = np.empty(kk, np.float32)
+        d = np.empty(kk, np.uint32)
+        cnt = C.c_uint32(0)
+        _lib.check(self._lib.ucfp_index_search_batcher_submit_tenant(self.handle, int(tenant), q.ctypes.data, int(k), ids.ctypes.data,
+                                                                     sc.ctypes.data, d.ctypes.data, C.byref(cnt)))
+        n = int(cnt.value)
+        return ids[:n], sc[:n], d[:n]
+
+
+def search_multi_limits():
+    """-> (rows per work item, queries per work item, tie-list capacity) of the multi-tenant search (host only)."""
+    t, q, c = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    _lib.check(_lib.load().ucfp_index_search_multi_limits(C.byref(t), C.byref(q), C.byref(c)))
+    return int(t.value), int(q.value), int(c.value)
+
+
 def _filter_ids(ids) -> np.ndarray:
     """Any iterable of ints in [0, 2^64), in any order, duplicates allowed -> sorted unique uint64."""
     if isinstance(ids, np.ndarray):
@@ -330,6 +362,35 @@ class DeviceIndex:
         _lib.check(self._lib.ucfp_index_search_dev(self.handle, tenant, queries_ptr, nq, k, out_ids_ptr,
                                                    out_scores_ptr or None, out_keys_ptr or None,
                                                    out_counts_ptr, stream or None))
+
+    def search_multi(self, tenants, queries, k: int):
+        """`search` for a batch in which query i names its own tenant, tenants[i] (HAMMING64; DESIGN M1 - M6): one call and a
+        number of launches that does not depend on the tenants.  Row i is what search(tenants[i], queries[i:i + 1], k) returns."""
+        q = self._rows(queries)
+        t = np.ascontiguousarray(tenants, dtype=np.uint32).reshape(-1)
+        nq = q.shape[0]
+        if t.shape[0] != nq:
+            raise InvalidArgument("tenants and queries disagree on the number of queries")
+        kk = max(k, 1)
+        ids = np.full((nq, kk), INVALID_ID, np.uint64)
+        scores = np.zeros((nq, kk), np.float32)
+        keys = np.full((nq, kk), 0xFFFFFFFF, np.uint32)
+        counts = np.zeros(nq, np.uint32)
+        _lib.check(self._lib.ucfp_index_search_multi(self.handle, t.ctypes.data, q.ctypes.data, nq, k, ids.ctypes.data,
+                                                     scores.ctypes.data, keys.ctypes.data, counts.ctypes.data))
+        return ids[:, :k], scores[:, :k], keys[:, :k], counts
+
+    def search_multi_dev(self, tenants, queries_ptr: int, nq: int, k: int, out_ids_ptr: int, out_scores_ptr: int,
+                         out_keys_ptr: int, out_counts_ptr: int, stream: int = 0) -> None:
+        """`tenants`: host array of nq tenant ids (read before the call returns); everything else as `search_dev`."""
+        t = None
+        if tenants is not None:
+            t = np.ascontiguousarray(tenants, dtype=np.uint32).reshape(-1)
+            if t.shape[0] != nq:
+                raise InvalidArgument("tenants and nq disagree on the number of queries")
+        _lib.check(self._lib.ucfp_index_search_multi_dev(self.handle, t.ctypes.data if t is not None and nq else None, queries_ptr,
+                                                         nq, k, out_ids_ptr, out_scores_ptr or None, out_keys_ptr or None,
+                                                         out_counts_ptr, stream or None))
 
 
 def _pack_landmarks(items):
@@ -1302,6 +1363,17 @@ class GpuIndex:
             tenant_id, np.array([query_hash], np.uint64), min(k, MAX_K), view)
         return [Hit(tenant_id=tenant_id, record_id=int(ids[0, i]), score=float(scores[0, i]),
                     source=HitSource.Hamming, distance=int(dist[0, i])) for i in range(int(counts[0]))]
+
+    def hamming_many(self, space: str, requests, k: int) -> List[List[Hit]]:
+        """[hamming(t, space, h, k) for t, h in requests] through ONE multi-tenant search (DESIGN M6): `requests` is an
+        iterable of (tenant_id, query_hash)."""
+        reqs = [(int(t), int(h)) for t, h in requests]
+        if k == 0 or space not in self._ham or not reqs:
+            return [[] for _ in reqs]
+        ids, scores, dist, counts = self._ham[space].search_multi(
+            np.array([t for t, _ in reqs], np.uint32), np.array([h for _, h in reqs], np.uint64), min(k, MAX_K))
+        return [[Hit(tenant_id=t, record_id=int(ids[q, i]), score=float(scores[q, i]), source=HitSource.Hamming,
+                     distance=int(dist[q, i])) for i in range(int(counts[q]))] for q, (t, _) in enumerate(reqs)]
 
     def identify(self, tenant_id: int, landmarks, k: int, min_votes: int = 1, algorithm: str = ALGORITHM_WANG) -> List[Hit]:
         """Which recording is this clip, and where in it: landmarks = bytes (8 per landmark) or uint32 [n, 2] of
